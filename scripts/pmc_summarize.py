@@ -7,7 +7,7 @@ from collections import defaultdict
 R = sys.argv[1] if len(sys.argv) > 1 else "r02"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 base = os.path.join(ROOT, "gpurun_out", f"pmc_{R}")
-STEPS = 3          # 1 warm-up + 2 timed + (bench.py's serialized roofline pass: 1 + 2) = 6 steps in the process
+STEPS = 3          # 1 warm-up + 2 timed + (bench.py --full: serialized roofline pass, 1 + 2) = 6 steps in the process
 CALLS_PER_STEP = 76        # conv forward + input-gradient calls of the 64..512-channel layers (the stem runs on its own kernels since round 3)
 
 
@@ -55,7 +55,7 @@ for math, kname in (("f32", ("igemm_kernel",)), ("split", ("igemm_split_kernel",
         # SQ_VALU_MFMA_BUSY_CYCLES is summed over the SIMDs (4 per CU x 256 CUs); GRBM_GUI_ACTIVE is summed over the 8 XCDs
         rows[short(k)] = {"dispatches": len(v), "mfma_busy_frac": busy / (act / 8.0 * 1024.0)}
     util[math] = dict(sorted(rows.items(), key=lambda kv: -kv[1]["mfma_busy_frac"]))
-traffic["method"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 2 --warmup 1 --no-cpu-baseline "
+traffic["method"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "
                      "--no-alt --no-overlap --math {f32,split}`; bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 (gfx950: FETCH_SIZE counts 64 B per "
                      "128-B request, MI355X_MICROARCH.md HBM section), averaged over all launches of the kernel")
 traffic["note"] = ("a conv forward / input-gradient CALL (what bench.py's roofline counts: 40 + 38 per step) is one kernel launch, except a "

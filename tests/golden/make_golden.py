@@ -492,7 +492,19 @@ def run_ogm_kat(seed=81, B=6, spec_hw=(96, 64), T=2, img_hw=(64, 64)):
     print(f"  wrote {path} ({os.path.getsize(path) / 1024:.1f} KiB)")
 
 
-if __name__ == "__main__":
+if __name__ == "__main__" and sys.argv[1:] == ["m3ae_pinned"]:
+    # m3ae_small_pinned.npz: the M3AE case again under one host-independent CPU arithmetic (tests/util.py), for the
+    # CPU oracle test: its projected head gradients are ill-conditioned, so their fp32 bits follow the CPU code path
+    #   env MKL_CBWR=COMPATIBLE ATEN_CPU_CAPABILITY=default OMP_NUM_THREADS=1 MKL_NUM_THREADS=1 \
+    #       python tests/golden/make_golden.py m3ae_pinned
+    sys.path.insert(0, os.path.dirname(HERE))
+    from util import PINNED_CPU_ENV
+    assert all(os.environ.get(k) == v for k, v in PINNED_CPU_ENV.items()), f"needs the environment {PINNED_CPU_ENV}"
+    assert torch.backends.cpu.get_cpu_capability() == "DEFAULT"
+    torch.backends.mkldnn.enabled = False
+    torch.set_num_threads(1)
+    run_m3ae_case("small_pinned", 3, 2, 1000, 11, 2, seed=61)
+elif __name__ == "__main__":
     torch.set_num_threads(8)
     keep = ("conv1.weight", "bn1.weight", "bn1.bias", "layer1.0.conv1.weight", "layer2.0.downsample.0.weight",
             "layer2.0.conv1.weight", "layer4.1.conv2.weight", "layer4.1.bn2.weight")

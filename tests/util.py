@@ -1,6 +1,12 @@
 """Shared comparison helpers for the parity tests (tolerances are stated where they are used)."""
 import torch
 
+# One CPU arithmetic for every x86-64 host: MKL's conditional-numerical-reproducibility baseline, ATen's baseline
+# (non-vectorised-dispatch) kernels, one thread.  Read at library load, so it goes into the environment of a FRESH
+# process; that process also switches oneDNN off (torch.backends.mkldnn.enabled = False).  Used where a fixture pins
+# an ill-conditioned fp32 quantity whose last bits otherwise depend on the CPU (tests/golden/m3ae_small_pinned.npz).
+PINNED_CPU_ENV = {"MKL_CBWR": "COMPATIBLE", "ATEN_CPU_CAPABILITY": "default", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
+
 
 def max_abs_err(got, want):
     return (torch.as_tensor(got).double().cpu() - torch.as_tensor(want).double().cpu()).abs().max().item()
