@@ -244,6 +244,30 @@ int mla_head_bwd(const float* X, const float* W, const float* dlogits, float* dW
                  int B, int D, int C, float scale, void* stream);
 int mla_scale_by_device_scalar(float* x, const float* scalar, size_t n, void* stream);
 
+/* ---- concatenated fusion head of the joint step (fusion_modules.py:16-35; main.py:164-168, 232-237, 273-311) ----------
+ * ConcatFusion.fc_out = nn.Linear(M*D, C) on cat(x_0 .. x_{M-1}) without materialising the concatenation: x_m [B][D]
+ * (x2 / dx2 NULL when M = 2), W [C][M*D] (the reference's row-major layout, column block m = W_m), M = 2 or 3, C <= 128.
+ *   out = sum_m x_m W_m^T + b                    [B][C]    (fusion_modules.py:22-23, 32-34)
+ *   out_m = x_m W_m^T + b / M                    [M][B][C] (the half / third-head logits of main.py:283-302)
+ * mla_concat_head_ce_fwd_bwd: the training head of main.py:305-310 in two launches: `out`, `out_m`,
+ *   loss = -sum_i log softmax(out_i)[label_i] * inv_batch (rank-local part), loss_m[M] = the same for out_m (the reported
+ *   losses of main.py:307-309, never differentiated), dlogits = (softmax - onehot) * inv_batch, dW = dlogits^T cat(x)
+ *   (into W's column blocks), db = sum dlogits, dx_m = dlogits W_m.  A label outside [0, C) yields NaN losses and a zero
+ *   dlogits row.  ws: mla_concat_head_ws_elems(B, C, M) floats.
+ * mla_concat_head_fwd: out and out_m only (valid(), main.py:539-619, 653-679; the autograd forward), one launch.
+ * mla_concat_head_bwd: autograd of the concatenated Linear for a given dlogits: dW = s dlogits^T cat(x), db = s sum dlogits,
+ *   dx_m = s dlogits W_m (s = 1/world under data parallel, else 1), two launches.
+ * No atomics; every reduction in a fixed order (bitwise reproducible). */
+size_t mla_concat_head_ws_elems(int B, int C, int M);
+int mla_concat_head_ce_fwd_bwd(const float* x0, const float* x1, const float* x2, const float* W, const float* b,
+                               const int64_t* labels, float* out, float* out_m, float* loss, float* loss_m, float* dW,
+                               float* db, float* dx0, float* dx1, float* dx2, float* ws, int M, int B, int D, int C,
+                               float inv_batch, void* stream);
+int mla_concat_head_fwd(const float* x0, const float* x1, const float* x2, const float* W, const float* b, float* out,
+                        float* out_m, int M, int B, int D, int C, void* stream);
+int mla_concat_head_bwd(const float* x0, const float* x1, const float* x2, const float* W, const float* dlogits, float* dW,
+                        float* db, float* dx0, float* dx1, float* dx2, int M, int B, int D, int C, float scale, void* stream);
+
 /* ---- GSPlugin.before_update (utils/utils.py:24-41) ------------------------------------------- */
 /* r[j] = scale * sum_i X[i][j]   (column mean with scale = 1/B; rank-local column sum otherwise) */
 int mla_colsum(const float* X, float* r, int B, int D, float scale, void* stream);

@@ -80,6 +80,10 @@ PROTOTYPES = {
     "mla_ce_fwd_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _P]),
     "mla_head_bwd": (_I, [_P] * 6 + [_I, _I, _I, _F, _P]),
     "mla_scale_by_device_scalar": (_I, [_P, _P, _Z, _P]),
+    "mla_concat_head_ws_elems": (_Z, [_I, _I, _I]),
+    "mla_concat_head_ce_fwd_bwd": (_I, [_P] * 16 + [_I, _I, _I, _I, _F, _P]),
+    "mla_concat_head_fwd": (_I, [_P] * 7 + [_I, _I, _I, _I, _P]),
+    "mla_concat_head_bwd": (_I, [_P] * 10 + [_I, _I, _I, _I, _F, _P]),
     "mla_ogm_coeff": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
     "mla_ogm_chunk_elems": (_I, []),
     "mla_ogm_ws_bytes": (_Z, [_I, _I]),

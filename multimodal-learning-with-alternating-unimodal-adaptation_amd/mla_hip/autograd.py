@@ -7,6 +7,7 @@ head and on ONE encoder.  Each Function below is a thin shell over the same laun
   EncoderFeature   forward  = encoder forward + global pooling  -> (B, D) feature (fresh tensor)
                    backward = encoder.backward_from_pooled(d feature) -> flat gradient buffer -> p.grad views
   HeadLinear       forward  = mla_head_logits; backward = mla_head_bwd (dW, db, dX in one launch pair)
+  ConcatHeadLinear forward  = mla_concat_head_fwd; backward = mla_concat_head_bwd (dW, db, every dX_m; joint step)
   SoftmaxCE        forward  = mla_ce_fwd_bwd (loss + d logits in one launch); backward = scale by the incoming grad
 
 Graph recording is triggered by a private 1-element `anchor` tensor (requires_grad, not a Parameter): the encoder's
@@ -79,6 +80,36 @@ class HeadLinear(torch.autograd.Function):
             comm.allreduce_small(head.grad)                          # critical path: packed dW|db, one message
         head.publish_grads(pending)
         return None, None, dX
+
+
+class ConcatHeadLinear(torch.autograd.Function):
+    """fc_out(cat(x_1 .. x_M)) of the joint step (fusion_modules.py:22-23, 32-34) on the concatenated-head kernels: the
+    concatenation is never formed; backward hands each modality its own dX_m, so ONE `loss.backward()` (main.py:310)
+    reaches every encoder's EncoderFeature node."""
+
+    @staticmethod
+    def forward(ctx, anchor, head, *xs):
+        xd = [x.detach().contiguous() for x in xs]
+        B = xd[0].shape[0]
+        out = torch.empty((B, head.out_features), device=xd[0].device, dtype=torch.float32)
+        out_m = torch.empty((len(xd), B, head.out_features), device=xd[0].device, dtype=torch.float32)
+        ops.concat_head_fwd(xd, head.weight.detach(), head.bias.detach(), out, out_m)
+        ctx.head, ctx.xs = head, xd
+        return out
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        head, xs = ctx.head, ctx.xs
+        comm = head.comm
+        active = comm is not None and comm.active
+        pending = head.grads_pending()
+        dxs = [torch.empty_like(x) for x in xs]
+        ops.concat_head_bwd(xs, head.weight.detach(), dlogits.contiguous(), head.weight_grad, head.bias_grad, dxs,
+                            (1.0 / comm.world) if active else 1.0)
+        if active:
+            comm.allreduce_small(head.grad)                          # critical path: packed dW|db, one message
+        head.publish_grads(pending)
+        return (None, None) + tuple(dxs)
 
 
 class SoftmaxCE(torch.autograd.Function):

@@ -1,0 +1,238 @@
+"""The joint concat-fusion training step (gs_flag false) that MLA is measured against, fused driver, and its evaluator.
+
+    optimizer.zero_grad()                                            main.py:164
+    a, v[, t], out = model(...)  /  fusion_module(a, v[, t])         :164-168, 232-237, 273
+    out_a, out_v[, out_t] = half / third-head logits                 :283-302
+    loss = CE(out, label); loss_m = CE(out_m, label) (reported)      :305-309
+    loss.backward()                                                  :310
+    OGM / OGM-GE: coefficients from out_m, conv-gradient modulation  :312-410
+    optimizer.step()                                                 :416
+
+Orchestration only: every arithmetic step is a libmla_hip.so kernel.  Order of work per step:
+
+  1. every encoder's forward on its own stream (as in MLATrainer: no forward depends on another encoder or on the head);
+  2. the concatenated head (mla_concat_head_ce_fwd_bwd: out, out_m, losses, dW, db, every dX_m) once, on the calling stream;
+     data parallel: (dW|db|losses) packed into one all-reduce;
+  3. OGM / OGM-GE: the coefficients (mla_ogm_coeff) from out_m -- of the GLOBAL batch under data parallelism (the rows of
+     every rank gathered in rank order, as torch.nn.DataParallel computes them on the gathered outputs);
+  4. each encoder's chain on its own stream: backward from dX_m -> gradient all-reduce -> modulation (inside
+     [modulation_starts, modulation_ends]; after the all-reduce, so OGM-GE's std is that of the reduced gradient, as the
+     reference reads it after DataParallel's reduction) -> its SGD step;
+  5. the head's SGD step on the calling stream.
+
+Unlike MLA no modality waits for another's head update: the M encoder backwards run concurrently.  `set_overlap(False)`
+puts every kernel on the calling stream in program order (A/B runs).
+"""
+from __future__ import annotations
+
+import contextlib
+from typing import Optional
+
+import torch
+
+from . import ops
+from ._lib import MLAHipError
+from .dist import Comm
+from .modulation import OGM
+from .optim import FusedSGD
+from .streams import distinct_streams
+
+MODULATIONS = ("Normal", "OGM", "OGM_GE")
+
+
+def _joint_fusion(model):
+    fusion = model.fusion_module
+    if not getattr(fusion, "joint", False):
+        raise MLAHipError("the joint step needs a classifier built with gs_flag false (ConcatFusion on cat(a, v[, t]))")
+    return fusion
+
+
+def _prep_inputs(inputs):
+    if len(inputs) == 2:                                                  # ResNet audio + visual
+        spec, image = inputs
+        if spec.dim() == 3:
+            spec = spec.unsqueeze(1)                                      # main.py:273
+        return (spec.float(), image.float())
+    return tuple(inputs)
+
+
+class JointTrainer:
+    def __init__(self, model, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 1e-4, modulation: str = "Normal",
+                 alpha: float = 0.3, modulation_starts: int = 0, modulation_ends: int = 50, seed: int = 0,
+                 comm: Optional[Comm] = None):
+        """`model`: AVClassifier / M3AEClassifier / Modal3Classifier built with gs_flag false.  `modulation`, `alpha`,
+        `modulation_starts`, `modulation_ends`: args.* of main.py:312-410; `seed` keys OGM-GE's noise."""
+        if modulation not in MODULATIONS:
+            raise NotImplementedError(f"JointTrainer implements --modulation {' | '.join(MODULATIONS)}, not {modulation!r}")
+        _joint_fusion(model)
+        self.model = model
+        self.head = model.fusion_module.fc_out
+        self.encoders = model.mla_encoders()                              # [(tag, group, encoder)] in concatenation order
+        self.M = len(self.encoders)
+        groups = {grp: enc for _t, grp, enc in self.encoders}
+        groups["head"] = self.head
+        self.optimizer = FusedSGD(groups, lr, momentum, weight_decay)
+        self.modulation = modulation
+        self.modulation_starts, self.modulation_ends = modulation_starts, modulation_ends
+        self.comm = comm if comm is not None else Comm()
+        dev = model.device
+        self.ogm = OGM(alpha, modulation, seed, dev) if modulation != "Normal" else None
+        self._msg = torch.empty(self.head.numel + 1 + self.M, device=dev, dtype=torch.float32)
+        self.losses = {k: torch.zeros(1, device=dev, dtype=torch.float32) for k in ["loss"] + ["loss_" + t for t, _g, _e in self.encoders]}
+        self.last = {}
+        # one stream per encoder chain (forward, backward, all-reduce, modulation, SGD) plus its weight-gradient side stream,
+        # drawn as in MLATrainer (streams.py: encoder chains on hardware queues of their own first)
+        self._can_overlap = dev.type == "cuda" and hasattr(model, "forward_split")
+        pool = distinct_streams(2 * self.M, dev) if self._can_overlap else []
+        self._estreams, self._wstreams = pool[:self.M], pool[self.M:]
+        self.overlap = False
+        self.set_overlap(self._can_overlap)
+
+    def join(self) -> None:
+        """Make the current stream wait for every encoder chain (see MLATrainer.join)."""
+        if self._estreams and torch.cuda.is_available():
+            cur = torch.cuda.current_stream()
+            for es in self._estreams:
+                cur.wait_stream(es)
+
+    def set_overlap(self, on: bool) -> None:
+        """Per-encoder streams on / off (off: every kernel of the step on the current stream, in program order)."""
+        self.join()
+        self.overlap = bool(on) and self._can_overlap
+        for k, (_t, _g, enc) in enumerate(self.encoders):
+            if hasattr(enc, "wgrad_stream"):
+                enc.wgrad_stream = self._wstreams[k] if self.overlap else None
+            enc.tail_stream = self._estreams[k] if self.overlap else None
+
+    def _on(self, stream):
+        return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+
+    def _modulating(self, epoch: int) -> bool:
+        return self.ogm is not None and self.modulation_starts <= epoch <= self.modulation_ends
+
+    def train_step(self, *batch):
+        """AVClassifier:     train_step(spec, image, label, epoch)
+        M3AEClassifier:   train_step(token, padding_mask, image, label, epoch)
+        Modal3Classifier: train_step(token, padding_mask, image, spec, label, epoch)
+        Returns device scalars {'loss', 'loss_a', 'loss_v'[, 'loss_t']} (no host sync).  `self.last`: features, `out`,
+        `out_m` (M, B, C) and, with OGM / OGM-GE, `coeff`, `scores`, `ratios` (device tensors)."""
+        *inputs, label, epoch = batch
+        m, opt = self.model, self.optimizer
+        if not getattr(m, "training", True):
+            m.train()
+        inputs = _prep_inputs(inputs)
+        B = label.shape[0]
+        inv_batch = 1.0 / (B * self.comm.world)
+        opt.zero_grad()                                                                   # main.py:164
+        main = torch.cuda.current_stream() if self.overlap else None
+        # 1. forwards (main.py:273), one stream per encoder
+        if self.overlap:
+            fwds, feats, done = m.forward_split(*inputs), [], []
+            for es, f in zip(self._estreams, fwds):
+                es.wait_stream(main)          # inputs ready; the previous step's head has read this encoder's features
+                with torch.cuda.stream(es):
+                    feats.append(f())
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    done.append(ev)
+            for ev in done:
+                main.wait_event(ev)
+        else:
+            feats = m.forward_raw(*inputs)
+        for (tag, _g, _e), f in zip(self.encoders, feats):
+            self.last[tag] = f
+        # 2. the concatenated head (main.py:273-310)
+        out, out_m, L, dX = self.head.concat_forward_backward(list(feats), label, inv_batch)
+        if self.comm.active:                                  # (dW|db) and the rank-local losses: one message
+            n = self.head.numel
+            self._msg[:n].copy_(self.head.grad)
+            self._msg[n:].copy_(L)
+            self.comm.allreduce_small(self._msg)
+            self.head.grad.copy_(self._msg[:n])
+            L.copy_(self._msg[n:])
+        self.last["out"], self.last["out_m"] = out, out_m
+        self.losses["loss"].copy_(L[:1])
+        for k, (tag, _g, _e) in enumerate(self.encoders):
+            self.losses["loss_" + tag].copy_(L[1 + k:2 + k])
+        # 3. OGM coefficients (main.py:314-337 / 373-384), from the global batch
+        modulate = self._modulating(epoch)
+        if self.ogm is not None:
+            outs = [out_m[k] for k in range(self.M)]
+            if self.comm.active:
+                outs = [self.comm.allgather_rows(o) for o in outs]
+                lab = self.comm.allgather_rows(label.contiguous())
+            else:
+                lab = label
+            coeff = self.ogm.coefficients(outs, lab)
+            self.last["coeff"] = coeff
+            self.last["scores"], self.last["ratios"] = self.ogm.info[:self.M], self.ogm.info[3:3 + self.M]
+        # 4. encoder chains: backward (loss.backward()) -> all-reduce -> modulation (main.py:392-408) -> SGD (main.py:416)
+        for k, (_tag, grp, enc) in enumerate(self.encoders):
+            es = self._estreams[k] if self.overlap else None
+            if es is not None:
+                es.wait_stream(main)                          # dX_m (and the coefficients) are ready
+            with self._on(es):
+                enc.backward_from_pooled(dX[k], enc._pa)
+                self.comm.wait(self.comm.allreduce_flat_async(enc.grad))
+                if modulate:
+                    self.ogm.modulate_one(enc, k)
+                opt.mark_ready(grp)
+                opt.step_group(grp)
+        if modulate:
+            self.ogm.step += 1
+        # 5. the head's SGD step
+        opt.mark_ready("head")
+        opt.step_group("head")
+        opt.drop_grads()
+        return self.losses
+
+
+class JointEvaluator:
+    """`valid()` of the joint model (main.py:539-619, 653-679): eval-mode encoders, out = fc_out(cat(...)) and the half /
+    third-head logits out_m, arg-max predictions (first maximum, like np.argmax) and per-class counters kept on the device.
+    Data parallel: every rank all-gathers out / out_m / labels of all ranks in rank order and counts the global batch, as
+    `Evaluator` does.
+
+    The counters come from the existing fusion / accuracy kernel (mla_eval_fuse) fed with (out, out_a, out_v) and the fixed
+    weights (1, 0, 0): its fused prediction is then exactly arg-max(out); with three modalities a second call counts out_t."""
+
+    def __init__(self, model, comm: Optional[Comm] = None):
+        _joint_fusion(model)
+        self.model = model
+        self.comm = comm if comm is not None else Comm()
+        self.head = model.fusion_module.fc_out
+        self.M = len(model.mla_encoders())
+        self.C = self.head.out_features
+        dev = model.device
+        self.counts = torch.zeros(self.C * 5, device=dev, dtype=torch.int32)       # [num, argmax(out), out, out_a, out_v]
+        self.counts_t = torch.zeros(self.C * 4, device=dev, dtype=torch.int32)     # [num, out_t, out_t, out_t]
+        self.weights = torch.zeros(3, device=dev, dtype=torch.float32)
+        model.eval()                                                                # main.py:519
+
+    def reset(self) -> None:
+        self.counts.zero_()
+        self.counts_t.zero_()
+
+    def update(self, *batch):
+        """update(spec, image, label) | update(token, padding_mask, image, label) | update(token, pm, image, spec, label).
+        Returns (out, out_m) of the local batch."""
+        *inputs, label = batch
+        feats = self.model.forward_raw(*_prep_inputs(inputs))
+        out, out_m = self.head.concat_logits(list(feats), slot="eval")
+        outs = [out] + [out_m[k] for k in range(self.M)]
+        if self.comm.active:
+            outs = [self.comm.allgather_rows(o) for o in outs]
+            label = self.comm.allgather_rows(label.contiguous())
+        ops.eval_fuse(outs[:3], label, self.counts, self.weights, False, [1.0, 0.0, 0.0])
+        if self.M == 3:
+            ops.eval_fuse([outs[3], outs[3]], label, self.counts_t, self.weights, False, [1.0, 0.0])
+        return out, out_m
+
+    def result(self):
+        """(acc, acc_a, acc_v[, acc_t]) = sum(acc) / sum(num) (main.py:677-679; one host sync)."""
+        c = self.counts.view(5, self.C).sum(dim=1).cpu().tolist()
+        num = max(c[0], 1)
+        res = [c[1] / num, c[3] / num, c[4] / num]
+        if self.M == 3:
+            res.append(self.counts_t.view(4, self.C).sum(dim=1)[1].item() / num)
+        return tuple(res)

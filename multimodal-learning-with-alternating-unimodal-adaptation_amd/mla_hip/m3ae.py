@@ -23,7 +23,7 @@ import torch.nn as nn
 from . import ops
 from ._lib import MLAHipError
 from .encoder import DEFAULT_CONV_MATH
-from .model import ConcatFusion, N_CLASSES, SharedHead, _Classifier
+from .model import ConcatFusion, N_CLASSES, SharedHead, _Classifier, check_joint_args, concat_fusion_forward
 from .module import FlatModule, Holder
 
 
@@ -489,11 +489,14 @@ class M3AEClassifier(_Classifier):
             raise NotImplementedError("Incorrect dataset name {}".format(dataset))
         if fusion != "concat":                                                      # basic_model.py:146-163
             raise NotImplementedError("Incorrect fusion method: {}!".format(fusion))
-        if not getattr(args, "gs_flag", False):
-            raise NotImplementedError("mla_hip implements the --gs_flag (MLA) path only")
+        self.gs_flag = bool(getattr(args, "gs_flag", False))
+        if not self.gs_flag:
+            check_joint_args(args)
         self.args, self.device = args, torch.device(device)
         s = (lambda k: None if seed is None else seed + k)
-        self.fusion_module = ConcatFusion(768, N_CLASSES[dataset], device, s(2))   # basic_model.py:149
+        # basic_model.py:149-152: Linear(768, C) shared (--gs_flag) or Linear(1536, C) on cat(a, v); either way forward returns
+        # (a, v) and the reference loop calls fusion_module(a, v) itself (main.py:236-237)
+        self.fusion_module = ConcatFusion(768 if self.gs_flag else 1536, N_CLASSES[dataset], device, s(2), joint=not self.gs_flag)
         self.mae_a = M3AEEncoder("text", device, depth=depth, text_vocab_size=text_vocab_size, seed=s(0), conv_math=conv_math)    # :166
         self.mae_v = M3AEEncoder("image", device, depth=depth, text_vocab_size=text_vocab_size, seed=s(1), conv_math=conv_math)   # :167
 
@@ -517,14 +520,17 @@ class M3AEClassifier(_Classifier):
 
 
 class ConcatFusion3(nn.Module):
-    """models/fusion_modules.py:26-35; under --gs_flag only `fc_out` is touched (main.py:432, 444, 456)."""
+    """models/fusion_modules.py:26-35.  Under --gs_flag (joint=False) only `fc_out` is touched (main.py:432, 444, 456) and
+    forward raises; the joint step calls forward(x, y, z) -> (x, y, z, fc_out(cat(x, y, z))) (main.py:232-233)."""
 
-    def __init__(self, input_dim: int = 768, output_dim: int = 4, device="cuda", seed: Optional[int] = None):
+    def __init__(self, input_dim: int = 768, output_dim: int = 4, device="cuda", seed: Optional[int] = None,
+                 joint: bool = False):
         super().__init__()
+        self.joint = bool(joint)
         self.fc_out = SharedHead(input_dim, output_dim, device, seed)
 
     def forward(self, x, y, z):
-        raise NotImplementedError("mla_hip implements the --gs_flag (MLA) path only: fc_out is applied per modality")
+        return concat_fusion_forward(self, (x, y, z))
 
 
 class Modal3Classifier(_Classifier):
@@ -540,11 +546,13 @@ class Modal3Classifier(_Classifier):
             raise NotImplementedError("Incorrect dataset name {}".format(dataset))
         if fusion != "concat":                                                      # basic_model.py:213-229
             raise NotImplementedError("Incorrect fusion method: {}!".format(fusion))
-        if not getattr(args, "gs_flag", False):
-            raise NotImplementedError("mla_hip implements the --gs_flag (MLA) path only")
+        self.gs_flag = bool(getattr(args, "gs_flag", False))
+        if not self.gs_flag:
+            check_joint_args(args)
         self.args, self.device = args, torch.device(device)
         s = (lambda k: None if seed is None else seed + k)
-        self.fusion_module = ConcatFusion3(768, N_CLASSES[dataset], device, s(3))  # basic_model.py:218
+        # basic_model.py:218-221: Linear(768, C) shared (--gs_flag) or Linear(2304, C) on cat(a, v, t)
+        self.fusion_module = ConcatFusion3(768 if self.gs_flag else 2304, N_CLASSES[dataset], device, s(3), joint=not self.gs_flag)
         self.mae_a = M3AEEncoder("audio", device, depth=depth, seed=s(0), conv_math=conv_math)                                     # :231 CAVMAEFT
         self.mae_v = M3AEEncoder("image", device, depth=depth, text_vocab_size=text_vocab_size, seed=s(1), conv_math=conv_math)   # :232
         self.mae_t = M3AEEncoder("text", device, depth=depth, text_vocab_size=text_vocab_size, seed=s(2), conv_math=conv_math)    # :233

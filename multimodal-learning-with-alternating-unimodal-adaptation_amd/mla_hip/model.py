@@ -1,8 +1,10 @@
-"""Drop-in model objects for the --gs_flag path of the reference.
+"""Drop-in model objects for the --gs_flag path of the reference and for the joint concat-fusion step it is measured
+against (gs_flag false, main.py:164-168, 232-237, 273-417).
 
   AVClassifier   models/basic_model.py:14-77   (attribute paths audio_net / visual_net / fusion_module.fc_out)
-  ConcatFusion   models/fusion_modules.py:16-24 (only fc_out is used by MLA; main.py:432, 444)
-  SharedHead     the nn.Linear(D, C) behind fc_out
+  ConcatFusion   models/fusion_modules.py:16-24 (--gs_flag: only fc_out is used, main.py:432, 444; joint: forward(x, y)
+                 returns (x, y, fc_out(cat(x, y))) on the concatenated-head kernels)
+  SharedHead     the nn.Linear(D, C) (joint: nn.Linear(M*D, C)) behind fc_out
 
 state_dict()/load_state_dict() speak the reference's keys and layouts (OIHW conv weights,
 `audio_net.conv1.weight`, `fusion_module.fc_out.weight`, optional `module.` prefix,
@@ -20,7 +22,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import MLAHipError
-from .autograd import EncoderFeature, HeadLinear, make_anchor
+from .autograd import ConcatHeadLinear, EncoderFeature, HeadLinear, make_anchor
 from .encoder import ResNet18Encoder
 from .module import FlatModule
 
@@ -77,6 +79,36 @@ class SharedHead(FlatModule, nn.Linear):
         ops.head_logits(X, self.weight.detach(), self.bias.detach(), buf["logits"])
         return buf["logits"]
 
+    def _joint_bufs(self, B: int, M: int, slot: str) -> dict:
+        key = (B, "joint", M, slot)
+        if key not in self._ws:
+            f32 = dict(device=self.device, dtype=torch.float32)
+            D = self.in_features // M
+            self._ws[key] = {"out": torch.empty((B, self.out_features), **f32),
+                             "out_m": torch.empty((M, B, self.out_features), **f32),
+                             "loss": torch.empty(1 + M, **f32),
+                             "dX": [torch.empty((B, D), **f32) for _ in range(M)],
+                             "ws": torch.empty(ops.concat_head_ws_elems(B, self.out_features, M), **f32)}
+        return self._ws[key]
+
+    def concat_forward_backward(self, xs, labels: torch.Tensor, inv_batch: Optional[float] = None, slot: str = ""):
+        """Fused joint-step head (main.py:273-310): out = fc_out(cat(xs)), out_m (the half / third-head logits), the CE
+        loss and the reported per-modality losses, and every gradient, in two launches.  Gradients land in
+        self.weight_grad / self.bias_grad; returns (out, out_m (M, B, C), losses [loss, loss_m...], [dX_m])."""
+        B, M = xs[0].shape[0], len(xs)
+        buf = self._joint_bufs(B, M, slot)
+        L = buf["loss"]
+        ops.concat_head_ce_fwd_bwd(xs, self.weight.detach(), self.bias.detach(), labels, buf["out"], buf["out_m"], L[:1], L[1:],
+                                   self.weight_grad, self.bias_grad, buf["dX"], buf["ws"],
+                                   (1.0 / B) if inv_batch is None else inv_batch)
+        return buf["out"], buf["out_m"], L, buf["dX"]
+
+    def concat_logits(self, xs, slot: str = "eval"):
+        """(out, out_m) of the concatenated head into reused buffers, no gradients (JointEvaluator, main.py:539-619)."""
+        buf = self._joint_bufs(xs[0].shape[0], len(xs), slot)
+        ops.concat_head_fwd(xs, self.weight.detach(), self.bias.detach(), buf["out"], buf["out_m"])
+        return buf["out"], buf["out_m"]
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """out = fc_out(x)  (main.py:432, 444, 456, 636-639): differentiable when x carries history."""
         if x.dim() != 2 or x.shape[1] != self.in_features:
@@ -84,15 +116,51 @@ class SharedHead(FlatModule, nn.Linear):
         return HeadLinear.apply(self._anchor, self, x)
 
 
-class ConcatFusion(nn.Module):
-    """models/fusion_modules.py:16-24; under --gs_flag only `fc_out` is touched."""
+def concat_fusion_forward(fusion, xs):
+    """`output = fc_out(torch.cat(xs, dim=1))` (fusion_modules.py:22-23, 32-34) on the concatenated-head kernels; returns
+    (*xs, output).  Differentiable when the features carry history (ConcatHeadLinear)."""
+    if not fusion.joint:
+        raise NotImplementedError("this fusion module was built for the --gs_flag (MLA) path, where fc_out is applied per "
+                                  "modality; construct it with joint=True (gs_flag false) for the concatenated head")
+    head = fusion.fc_out
+    if len({tuple(x.shape) for x in xs}) != 1 or xs[0].dim() != 2 or xs[0].shape[1] * len(xs) != head.in_features:
+        raise MLAHipError(f"{type(fusion).__name__}: expects {len(xs)} x (B, {head.in_features // len(xs)}), "
+                          f"got {[tuple(x.shape) for x in xs]}")
+    if any(x.requires_grad for x in xs) and torch.is_grad_enabled():
+        out = ConcatHeadLinear.apply(head._anchor, head, *xs)
+    else:
+        out = torch.empty((xs[0].shape[0], head.out_features), device=head.device, dtype=torch.float32)
+        out_m = torch.empty((len(xs), xs[0].shape[0], head.out_features), device=head.device, dtype=torch.float32)
+        ops.concat_head_fwd([x.detach().contiguous() for x in xs], head.weight.detach(), head.bias.detach(), out, out_m)
+    return tuple(xs) + (out,)
 
-    def __init__(self, input_dim: int = 512, output_dim: int = 100, device="cuda", seed: Optional[int] = None):
+
+class ConcatFusion(nn.Module):
+    """models/fusion_modules.py:16-24.  Under --gs_flag (joint=False) only `fc_out` is touched and forward raises; the joint
+    step (gs_flag false, joint=True) calls forward(x, y) -> (x, y, fc_out(cat(x, y)))."""
+
+    def __init__(self, input_dim: int = 512, output_dim: int = 100, device="cuda", seed: Optional[int] = None,
+                 joint: bool = False):
         super().__init__()
+        self.joint = bool(joint)
         self.fc_out = SharedHead(input_dim, output_dim, device, seed)
 
     def forward(self, x, y):
-        raise NotImplementedError("mla_hip implements the --gs_flag (MLA) path only: fc_out is applied per modality")
+        return concat_fusion_forward(self, (x, y))
+
+
+def check_joint_args(args) -> None:
+    """What the joint (gs_flag false) classifiers support: `--modulation Normal | OGM | OGM_GE` with concat fusion."""
+    mod = getattr(args, "modulation", "Normal")
+    if mod == "QMF":
+        raise NotImplementedError("mla_hip does not implement --modulation QMF (main.py:170-268): it needs the per-modality "
+                                  "audio_fc / visual_fc heads and the History ranking loss")
+    if mod not in ("Normal", "OGM", "OGM_GE"):
+        raise NotImplementedError(f"Incorrect modulation: {mod}")
+    if getattr(args, "lorb", "base") == "large":
+        raise NotImplementedError("mla_hip does not implement --lorb large")
+    if getattr(args, "clip", False):
+        raise NotImplementedError("mla_hip does not implement --clip")
 
 
 class _Classifier(nn.Module):
@@ -145,12 +213,14 @@ class AVClassifier(_Classifier):
         n_classes = N_CLASSES[dataset]
         if fusion != "concat":                                              # basic_model.py:28-40
             raise NotImplementedError("Incorrect fusion method: {}!".format(fusion))
-        if not getattr(args, "gs_flag", False):
-            raise NotImplementedError("mla_hip implements the --gs_flag (MLA) path only")
+        self.gs_flag = bool(getattr(args, "gs_flag", False))
+        if not self.gs_flag:
+            check_joint_args(args)
         self.args = args
         self.device = torch.device(device)
         s = (lambda k: None if seed is None else seed + k)
-        self.fusion_module = ConcatFusion(512, n_classes, device, s(2))    # basic_model.py:31-32
+        # basic_model.py:31-34: Linear(512, C) shared by both modalities (--gs_flag) or Linear(1024, C) on cat(a, v)
+        self.fusion_module = ConcatFusion(512 if self.gs_flag else 1024, n_classes, device, s(2), joint=not self.gs_flag)
         self.audio_net = ResNet18Encoder("audio", device, s(0), conv_math)     # basic_model.py:42
         self.visual_net = ResNet18Encoder("visual", device, s(1), conv_math)   # basic_model.py:43
         self._feat: Dict[int, dict] = {}
@@ -193,12 +263,15 @@ class AVClassifier(_Classifier):
 
     def forward(self, audio: torch.Tensor, visual: torch.Tensor):
         """a, v = model(spec.unsqueeze(1).float(), image.float())  (main.py:431; basic_model.py:52-77): fresh (B,512)
-        tensors that carry autograd history to their encoder when grad mode is on and the model is training."""
+        tensors that carry autograd history to their encoder when grad mode is on and the model is training.
+        gs_flag false: a, v, out = model(...) (main.py:273; basic_model.py:72-74)."""
         if visual.shape[0] != audio.shape[0]:
             raise MLAHipError("audio/visual batch mismatch")
         B = audio.shape[0]
         a = self._feature(self.audio_net, lambda out: self.forward_audio(audio, out), B, 512)
         v = self._feature(self.visual_net, lambda out: self.forward_visual(visual, out), B, 512)
+        if not self.gs_flag:
+            return self.fusion_module(a, v)                                  # basic_model.py:72-74: a, v, out
         return a, v
 
     def forward_split(self, audio: torch.Tensor, visual: torch.Tensor):

@@ -79,19 +79,24 @@ class OGM:
         if not (modulation_starts <= epoch <= modulation_ends):
             return
         for m, enc in enumerate(encoders):
-            plan = self._plans.get(id(enc))
-            if plan is None:
-                plan = self._plans[id(enc)] = _Plan(enc, self.device)
-            if plan.n_seg == 0:
-                continue
-            if hasattr(enc, "_await_tail"):
-                enc._await_tail()
-            works = getattr(enc, "_grad_works", None)
-            if works:                       # data-parallel protocol path: the encoder-gradient all-reduce is still in flight
-                enc.comm.wait(works)        # (autograd.py leaves it to FusedSGD.step()); modulate the REDUCED gradient
-                enc._grad_works = []
-            # Philox stream = (call counter, modality, tensor): the reference draws a fresh normal_() per tensor (main.py:399-407),
-            # so conv k of the audio and of the visual ResNet-18 must not share a noise sequence
-            ops.ogm_modulate(enc.grad, plan.seg, plan.first, plan.n_seg, plan.total_chunks, self.coeff[m:m + 1],
-                             self.mode == "OGM_GE", self.seed, self.step * 8 + m, plan.ws if self.mode == "OGM_GE" else None)
+            self.modulate_one(enc, m)
         self.step += 1
+
+    def modulate_one(self, enc, m: int) -> None:
+        """The body of `modulate` for ONE encoder (modality index m) on the current stream, without advancing the call
+        counter: JointTrainer runs it on each encoder's own stream and advances `step` once per training step."""
+        plan = self._plans.get(id(enc))
+        if plan is None:
+            plan = self._plans[id(enc)] = _Plan(enc, self.device)
+        if plan.n_seg == 0:
+            return
+        if hasattr(enc, "_await_tail"):
+            enc._await_tail()
+        works = getattr(enc, "_grad_works", None)
+        if works:                       # data-parallel protocol path: the encoder-gradient all-reduce is still in flight
+            enc.comm.wait(works)        # (autograd.py leaves it to FusedSGD.step()); modulate the REDUCED gradient
+            enc._grad_works = []
+        # Philox stream = (call counter, modality, tensor): the reference draws a fresh normal_() per tensor (main.py:399-407),
+        # so conv k of the audio and of the visual ResNet-18 must not share a noise sequence
+        ops.ogm_modulate(enc.grad, plan.seg, plan.first, plan.n_seg, plan.total_chunks, self.coeff[m:m + 1],
+                         self.mode == "OGM_GE", self.seed, self.step * 8 + m, plan.ws if self.mode == "OGM_GE" else None)

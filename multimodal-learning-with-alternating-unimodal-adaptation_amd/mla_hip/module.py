@@ -36,6 +36,18 @@ class Holder(nn.Module):
         raise MLAHipError("this submodule only carries parameter names; call the owning encoder / classifier")
 
 
+def _alias(view: torch.Tensor) -> torch.Tensor:
+    """A tensor on the same memory as `view` that autograd sees as a LEAF, not as a view of the flat gradient buffer.
+    The reference modulates gradients in place (`parms.grad *= coeff_a`, main.py:402), and coeff_a carries autograd history
+    because it is computed from out_a, which reads fc_out.weight.  On a view of the flat buffer, that in-place op puts the
+    whole buffer into the graph, and the next parameter's view then fails as an in-place op on a leaf that requires grad.
+    On an independent leaf it behaves as on the reference's own gradient tensors."""
+    t = torch.empty(0, device=view.device, dtype=view.dtype)
+    with torch.no_grad():
+        t.set_(view.untyped_storage(), view.storage_offset(), view.shape, view.stride())
+    return t
+
+
 def _bare_init(self) -> None:
     nn.Module.__init__(self)
 
@@ -93,7 +105,7 @@ class FlatModule(nn.Module):
         p = nn.Parameter(v, requires_grad=True)
         p._mla_owner = self
         p._mla_index = len(self._entries)
-        self._entries.append((name, p, to_ref(grad_internal)))
+        self._entries.append((name, p, _alias(to_ref(grad_internal))))
         return p
 
     @staticmethod
@@ -140,7 +152,10 @@ class FlatModule(nn.Module):
                 if g is not None:                                         # a gradient tensor somebody else assigned
                     self._entries[i][2].add_(g)
         pub = []
-        for _n, p, gv in self._entries:
+        for i, (n, p, gv) in enumerate(self._entries):
+            if gv.requires_grad:          # the reference's `p.grad *= coeff` (main.py:402) with a coefficient that carries history
+                gv = _alias(gv.detach())  # made the published view part of that graph: publish a fresh alias instead
+                self._entries[i] = (n, p, gv)
             p.grad = gv
             pub.append(gv)
         self._published = pub

@@ -548,6 +548,55 @@ def head_bwd(X, W, dlogits, dW, db, dX, scale: float = 1.0, stream: Optional[int
           "mla_head_bwd")
 
 
+def _concat_ptrs(xs, who: str):
+    M = len(xs)
+    if M not in (2, 3):
+        raise MLAHipError(f"{who}: needs 2 or 3 feature tensors, got {M}")
+    B, D = xs[0].shape
+    for x in xs[1:]:
+        if tuple(x.shape) != (B, D):
+            raise MLAHipError(f"{who}: every modality must have the same (B, D); got {[tuple(t.shape) for t in xs]}")
+    return [_p(x) for x in xs] + [None] * (3 - M), M, B, D
+
+
+def concat_head_ws_elems(B: int, C: int, M: int) -> int:
+    return int(_lib.load().mla_concat_head_ws_elems(B, C, M))
+
+
+def concat_head_ce_fwd_bwd(xs, W, b, labels, out, out_m, loss, loss_m, dW, db, dxs, ws, inv_batch: float,
+                           stream: Optional[int] = None) -> None:
+    """Joint head (main.py:273-311): out = fc_out(cat(xs)), out_m (M, B, C), CE loss / per-modality losses and all gradients."""
+    x, M, B, D = _concat_ptrs(xs, "concat_head_ce_fwd_bwd")
+    C = W.shape[0]
+    if tuple(W.shape) != (C, M * D) or len(dxs) != M:
+        raise MLAHipError(f"concat_head_ce_fwd_bwd: W {tuple(W.shape)} does not match {M} x (B, {D})")
+    dx = [_p(t) for t in dxs] + [None] * (3 - M)
+    check(_lib.load().mla_concat_head_ce_fwd_bwd(x[0], x[1], x[2], _p(W), _p(b), _p(labels, torch.int64), _p(out), _p(out_m),
+                                                 _p(loss), _p(loss_m), _p(dW), _p(db), dx[0], dx[1], dx[2], _p(ws), M, B, D, C,
+                                                 inv_batch, stream or cur_stream()), "mla_concat_head_ce_fwd_bwd")
+
+
+def concat_head_fwd(xs, W, b, out, out_m, stream: Optional[int] = None) -> None:
+    """out = fc_out(cat(xs)) and out_m = xs[m] W_m^T + b / M, no gradients (valid(); the autograd forward)."""
+    x, M, B, D = _concat_ptrs(xs, "concat_head_fwd")
+    C = W.shape[0]
+    if tuple(W.shape) != (C, M * D):
+        raise MLAHipError(f"concat_head_fwd: W {tuple(W.shape)} does not match {M} x (B, {D})")
+    check(_lib.load().mla_concat_head_fwd(x[0], x[1], x[2], _p(W), _p(b), _p(out), _p(out_m), M, B, D, C, stream or cur_stream()),
+          "mla_concat_head_fwd")
+
+
+def concat_head_bwd(xs, W, dlogits, dW, db, dxs, scale: float = 1.0, stream: Optional[int] = None) -> None:
+    """autograd of the concatenated fc_out for a given d out: dW, db, dX_m (all times `scale`)."""
+    x, M, B, D = _concat_ptrs(xs, "concat_head_bwd")
+    C = W.shape[0]
+    if tuple(W.shape) != (C, M * D) or tuple(dlogits.shape) != (B, C) or len(dxs) != M:
+        raise MLAHipError(f"concat_head_bwd: W {tuple(W.shape)} / dlogits {tuple(dlogits.shape)} do not match {M} x ({B}, {D})")
+    dx = [_p(t) for t in dxs] + [None] * (3 - M)
+    check(_lib.load().mla_concat_head_bwd(x[0], x[1], x[2], _p(W), _p(dlogits), _p(dW), _p(db), dx[0], dx[1], dx[2], M, B, D, C,
+                                          scale, stream or cur_stream()), "mla_concat_head_bwd")
+
+
 def scale_by_device_scalar(x, scalar, stream: Optional[int] = None) -> None:
     check(_lib.load().mla_scale_by_device_scalar(_p(x), _p(scalar), x.numel(), stream or cur_stream()),
           "mla_scale_by_device_scalar")

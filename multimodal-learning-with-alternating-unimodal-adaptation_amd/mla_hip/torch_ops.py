@@ -184,6 +184,37 @@ def head_ce_fwd_bwd(X, W, b, labels, inv_batch):
     return logits, loss, dW, db, dX
 
 
+@_op("concat_head_ce_fwd_bwd(Tensor[] xs, Tensor W, Tensor b, Tensor labels, float inv_batch) -> "
+     "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor[])")
+def concat_head_ce_fwd_bwd(xs, W, b, labels, inv_batch):
+    """Joint head (main.py:273-311): (out, out_m (M, B, C), loss[1], loss_m[M], dW, db, [dX_m])"""
+    M, (B, D), C = len(xs), xs[0].shape, W.shape[0]
+    x0 = xs[0]
+    out, out_m, loss, loss_m = _f32((B, C), x0), _f32((M, B, C), x0), _f32(1, x0), _f32(M, x0)
+    dW, db, dxs = _f32((C, M * D), x0), _f32(C, x0), [_f32((B, D), x0) for _ in range(M)]
+    ops.concat_head_ce_fwd_bwd(list(xs), W, b, labels, out, out_m, loss, loss_m, dW, db, dxs,
+                               _f32(ops.concat_head_ws_elems(B, C, M), x0), inv_batch)
+    return out, out_m, loss, loss_m, dW, db, dxs
+
+
+@_op("concat_head_fwd(Tensor[] xs, Tensor W, Tensor b) -> (Tensor, Tensor)")
+def concat_head_fwd(xs, W, b):
+    """(out, out_m (M, B, C)) = fc_out(cat(xs)) and the per-modality block products + b / M"""
+    M, (B, _D), C = len(xs), xs[0].shape, W.shape[0]
+    out, out_m = _f32((B, C), xs[0]), _f32((M, B, C), xs[0])
+    ops.concat_head_fwd(list(xs), W, b, out, out_m)
+    return out, out_m
+
+
+@_op("concat_head_bwd(Tensor[] xs, Tensor W, Tensor dlogits, float scale=1.0) -> (Tensor, Tensor, Tensor[])")
+def concat_head_bwd(xs, W, dlogits, scale=1.0):
+    """(dW, db, [dX_m]) of the concatenated fc_out for a given d out, times `scale`"""
+    M, (B, D), C = len(xs), xs[0].shape, W.shape[0]
+    dW, db, dxs = _f32((C, M * D), xs[0]), _f32(C, xs[0]), [_f32((B, D), xs[0]) for _ in range(M)]
+    ops.concat_head_bwd(list(xs), W, dlogits, dW, db, dxs, scale)
+    return dW, db, dxs
+
+
 @_op("gs_project(Tensor(a!) Pl, Tensor X, Tensor(b!) G, float alpha) -> ()")
 def gs_project(Pl, X, G, alpha):
     """GSPlugin.before_update body (utils/utils.py:34-41) on the batch features X (B, D): Pl and G updated in place."""
