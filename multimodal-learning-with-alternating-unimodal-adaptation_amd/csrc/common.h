@@ -31,6 +31,17 @@ void mla_set_error(const char* fmt, ...);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// CU count of the device current at the first call (the persistent grids and the tile-round models of every planner).  256 -- the
+// MI355X's -- when no device answers, so the host-side size and support queries stay usable without a GPU.
+inline int mla_cu_count() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    return n;
+  }();
+  return cus;
+}
+
 // wave-level reductions (64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

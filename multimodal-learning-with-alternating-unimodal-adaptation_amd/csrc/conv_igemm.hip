@@ -11,7 +11,7 @@
 // parity class (no MFMA work on structurally-zero taps), one launch per class.
 //
 // Tiling: 256 threads = 4 waves; block tile BMxBN (128x128, 256x64, 128x64 or 64x64, picked per problem to
-// minimise the tail on 256 CUs), K step 32 channels of one tap; A (pixels x channels) and B
+// minimise the tail on the CUs), K step 32 channels of one tap; A (pixels x channels) and B
 // (channels x cout) staged through LDS with register prefetch of the next K step; every wave owns a
 // (BM/WM)x(BN/WN) sub-tile as 32x32 MFMA tiles.  fp32 MFMA moves 512 B of LDS per 64-cycle
 // instruction, so the kernel is MFMA-issue bound; >= 2 workgroups per CU hide each other's barriers.
@@ -517,10 +517,10 @@ static void wgrad_plan(long M, int Cin, int Cout, int T, int* span, int* splits)
   const int BI = scalar ? 64 : (Cin % 128 == 0 && Cout % 128 == 0 ? 128 : 64);
   const int BJ = scalar ? 64 : BI;
   const long tiles = (long)(scalar ? cdiv((long)T * Cin, BI) : (Cin / BI) * T) * (Cout / BJ);
-  // workgroup budget: 3 rounds of 256 for the 128x128 tile (134 VGPRs: 3 resident per CU), 8 rounds for the
-  // 64x64 tile (60 VGPRs).  Measured on the layer shapes: 64x64 layers gain 4-8 % from 768 -> 2048.
-  // stem (scalar gathers, 60 VGPRs: 6 workgroups per CU): one round of 1536 (-4 % against 2048 = 1.33 rounds, same-box sweep)
-  long want = (scalar ? 1536 : (BI == 64 ? 2048 : 768)) / tiles;
+  // workgroup budget in rounds of the CUs: 3 for the 128x128 tile (134 VGPRs: 3 resident per CU), 8 for the 64x64 tile
+  // (60 VGPRs).  Measured on the layer shapes: 64x64 layers gain 4-8 % from 3 -> 8 rounds.
+  // stem (scalar gathers, 60 VGPRs: 6 workgroups per CU): one round of 6 per CU (-4 % against 8 = 1.33 rounds, same-box sweep)
+  long want = (long)(scalar ? 6 : (BI == 64 ? 8 : 3)) * mla_cu_count() / tiles;
   if (want < 1) want = 1;
   long s = (M + want - 1) / want;
   s = ((s + BK - 1) / BK) * BK;                  // whole K steps; spans longer than WG_CHUNK are walked in sub-chunks

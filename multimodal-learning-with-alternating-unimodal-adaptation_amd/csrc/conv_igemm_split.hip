@@ -266,7 +266,7 @@ __global__ __launch_bounds__(64 * WM * WN, WPE) void igemm_split_kernel(const fl
 
 // The output parity classes of a stride-2 input gradient in ONE launch.  Each class is its own gather-GEMM (1, 2, 2 and 4 of the nine
 // taps of a 3x3 kernel) over a quarter of the pixels; launched one after the other, layer3.0 / layer4.0 put 128-148 workgroups on the
-// 256 CUs four times over (the kernel trace of the round-3 step: 27 + 39 + 39 + 65 us for 22 GFLOP).  Here the classes share the
+// MI355X's 256 CUs four times over (the kernel trace of the round-3 step: 27 + 39 + 39 + 65 us for 22 GFLOP).  Here the classes share the
 // grid, longest first (4-tap tiles, then the 2-tap ones, the 1-tap class fills the tail), so the chip stays full until the end.
 struct IGemmClasses {
   IGemmGeom g[4];
@@ -588,9 +588,9 @@ static int pick_scfg(long M, int CO, int weight, int k_total = 1 << 30) {
   for (int c = 0; c < SCFG_COUNT; ++c) {
     if (CO % scfg_bn(c) != 0) continue;
     const double blocks = (double)cdiv(M, scfg_bm(c)) * (CO / scfg_bn(c));
-    const int per_cu = per_cu_tab[c];
-    const double rounds = (double)((long)((blocks + 256 * per_cu - 1) / (256 * per_cu)));
-    const double cost = rounds * per_cu * scfg_bm(c) * scfg_bn(c) / eff[c];
+    const long slots = (long)mla_cu_count() * per_cu_tab[c];
+    const double rounds = (double)(((long)blocks + slots - 1) / slots);
+    const double cost = rounds * per_cu_tab[c] * scfg_bm(c) * scfg_bn(c) / eff[c];
     if (best < 0 || cost < best_cost) { best = c; best_cost = cost; }
   }
   (void)weight;
@@ -636,9 +636,9 @@ static double scfg_cost(int c, long M, int CO) {       // the cost of pick_scfg:
   const double eff[SCFG_COUNT] = {SPLIT_EFF};
   const int per_cu_tab[SCFG_COUNT] = {1, 1, 2, 3, 2, 1};
   const double blocks = (double)cdiv(M, scfg_bm(c)) * (CO / scfg_bn(c));
-  const int per_cu = per_cu_tab[c];
-  const double rounds = (double)((long)((blocks + 256 * per_cu - 1) / (256 * per_cu)));
-  return rounds * per_cu * scfg_bm(c) * scfg_bn(c) / eff[c];
+  const long slots = (long)mla_cu_count() * per_cu_tab[c];
+  const double rounds = (double)(((long)blocks + slots - 1) / slots);
+  return rounds * per_cu_tab[c] * scfg_bm(c) * scfg_bn(c) / eff[c];
 }
 
 // Two-phase schedule for row counts between whole rounds (visual layer3: 37 632 rows x 256 columns = 2.3 rounds of 128x128 tiles, 1.5 of
@@ -661,10 +661,10 @@ static bool plan_two_phase(const IGemmGeom& g, int cfg1, int k_stages, int* cfgA
   for (int k = 0; k < 2; ++k) {
     const int cA = bigs[k];
     const long tiles = (long)cdiv(g.M, scfg_bm(cA)) * gridN;
-    const long full = tiles / 256;                                     // whole rounds of the 256 CUs
+    const long full = tiles / mla_cu_count();                          // whole rounds of the CUs
     // whole ROW tiles that fit those rounds (wide outputs -- the transformer Linears' 6 / 18 / 24 column tiles -- leave up to
     // gridN - 1 workgroup slots of the last round empty)
-    const long row_tiles = full * 256 / gridN;
+    const long row_tiles = full * mla_cu_count() / gridN;
     const long rA = row_tiles * scfg_bm(cA), rem = g.M - rA;
     if (full < 1 || row_tiles < 1 || rem <= 0) continue;
     const double costA = (double)full * scfg_bm(cA) * 128 / eff[cA];
@@ -899,7 +899,7 @@ extern "C" int mla_conv2d_dgrad_split_classes(const float* dy, const void* wspli
 static void wgrad_split_plan(long M, int Cin, int Cout, int T, int* span, int* splits) {
   const int BI = (Cin % 128 == 0 && Cout % 128 == 0) ? 128 : 64;
   const long tiles = (long)(Cin / BI) * T * (Cout / BI);
-  const long slots = BI == 64 ? 512 : 256;
+  const long slots = (BI == 64 ? 2 : 1) * (long)mla_cu_count();
   const double c0 = 250.0;
   long best_s = 1;
   double best_cost = 0;

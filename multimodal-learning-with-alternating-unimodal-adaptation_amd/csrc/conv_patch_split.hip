@@ -538,13 +538,13 @@ bool mla_patch_supported(const IGemmGeom& g, bool force) {
   // round is mostly empty (visual layer3: 294 workgroups, layer4: 128 / 148) -- there the per-tap kernel's 128-row tiles win.
   const int BN = g.CO % 128 == 0 ? 128 : 64;
   const long wgs = (long)cdiv(g.M, PT_BM) * (g.CO / BN);
-  const long rounds = (wgs + 255) / 256;
+  const long cus = mla_cu_count(), rounds = (wgs + cus - 1) / cus;
   static int min_fill = -1;                                                  // percent of the slots of its rounds that must be used
   if (min_fill < 0) {
     const char* e = getenv("MLA_PATCH_MIN_FILL");
     min_fill = e ? atoi(e) : 75;
   }
-  return wgs * 100 >= rounds * 256 * min_fill;
+  return wgs * 100 >= rounds * cus * min_fill;
 }
 
 static int g_patch_persistent = -1;       // -1: $MLA_PATCH_PERSISTENT (default 1)
@@ -572,7 +572,7 @@ int mla_patch_launch(const float* X, const void* Wsp, float* Y, const float* R, 
   // layer1 (64 -> 64): the persistent kernel with the epilogue riding in the next tile's MFMA stages, for the operand
   // combinations the training step uses (everything else: the one-tile-per-workgroup kernel below)
   if (g.C == 64 && g.CO == 64 && patch_persistent_on() && (long)g.M * 64 * 4 < 0xFFFFFFF0L && tiles >= 2) {
-    const int grid = tiles < 256 ? tiles : 256;
+    const int grid = tiles < mla_cu_count() ? tiles : mla_cu_count();
     double* pd = reinterpret_cast<double*>(part);
     bool done = true;
 #define P64(R_, M_, N_, S_) patch64p_kernel<R_, M_, N_, S_><<<grid, 512, 0, st>>>(X, Wsp, Y, R, MASK, pd, g, tiles)

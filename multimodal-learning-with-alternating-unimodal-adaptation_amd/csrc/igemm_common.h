@@ -261,7 +261,7 @@ static inline int check_conv(const char* who, int N, int H, int W, int Cin, int 
   return MLA_OK;
 }
 
-// Tile choice: every CU runs ceil(blocks/256) rounds of MFMA-bound tiles, so minimise
+// Tile choice: every CU runs ceil(blocks/CUs) rounds of MFMA-bound tiles, so minimise
 // rounds * tile area / efficiency (the 64x64 tile pays more barriers per flop).
 enum { CFG_128x128 = 0, CFG_256x64 = 1, CFG_64x64 = 2, CFG_128x64 = 3, CFG_COUNT = 4 };
 static inline int cfg_bm(int cfg) { return (cfg == CFG_128x128 || cfg == CFG_128x64) ? 128 : (cfg == CFG_256x64 ? 256 : 64); }
@@ -291,8 +291,9 @@ static inline int pick_cfg(const long* Ms, const int* weights, int n, int CO, bo
     }
     if (blocks == 0) continue;
     const double avg_w = wblocks / blocks;                        // average taps per block
-    const double rounds = (double)((long)((blocks + 255) / 256));
-    const double cost = rounds * avg_w * cfg_bm(cfg) * cfg_bn(cfg) / (eff[cfg] * (blocks < 512 ? 0.9 : 1.0));
+    const long cus = mla_cu_count();
+    const double rounds = (double)(((long)blocks + cus - 1) / cus);
+    const double cost = rounds * avg_w * cfg_bm(cfg) * cfg_bn(cfg) / (eff[cfg] * (blocks < 2 * cus ? 0.9 : 1.0));
     (void)wsum;
     if (best < 0 || cost < best_cost) { best = cfg; best_cost = cost; }
   }

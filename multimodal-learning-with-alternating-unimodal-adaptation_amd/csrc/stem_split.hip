@@ -594,16 +594,6 @@ __global__ __launch_bounds__(512, 2) void stem_wgrad_split_kernel(const float* _
   }
 }
 
-int stem_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus = n;
-  }
-  return cus;
-}
-
 int stem_check(const char* who, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
   MLA_REQUIRE(KH == 7 && KW == 7 && stride == 2 && pad == 3 && Cout == 64 && (Cin == 1 || Cin == 3),
               "%s: the stem kernels are 7x7 / stride 2 / pad 3, 1 or 3 -> 64 channels (got %dx%d s%d p%d, %d -> %d)", who, KH, KW, stride, pad, Cin, Cout);
@@ -626,7 +616,7 @@ extern "C" int mla_conv2d_stem_supported(int Cin, int Cout, int KH, int KW, int 
   return KH == 7 && KW == 7 && stride == 2 && pad == 3 && Cout == 64 && (Cin == 1 || Cin == 3);
 }
 
-extern "C" size_t mla_conv2d_stem_fwd_partial_elems(void) { return (size_t)stem_cus() * 2 * 2 * 64 * 2; }   // floats: [workgroups][2][64] doubles
+extern "C" size_t mla_conv2d_stem_fwd_partial_elems(void) { return (size_t)mla_cu_count() * 2 * 2 * 64 * 2; }   // floats: [workgroups][2][64] doubles
 
 extern "C" int mla_conv2d_stem_fwd_split(const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout, int KH,
                                          int KW, int stride, int pad, float* bn_partial, int* bn_tiles, void* stream) {
@@ -642,7 +632,7 @@ extern "C" int mla_conv2d_stem_fwd_split(const float* x, const float* w, float* 
   g.y_bytes = (unsigned)((size_t)N * g.OH * g.OW * 64 * 4);
   hipStream_t st = (hipStream_t)stream;
   const int waves = g_stem_waves ? g_stem_waves : (Cin == 1 ? 4 : 8);
-  const int slots = stem_cus() * ((Cin == 1 && waves == 4) ? 2 : 1);      // resident workgroups per CU (registers / LDS)
+  const int slots = mla_cu_count() * ((Cin == 1 && waves == 4) ? 2 : 1);      // resident workgroups per CU (registers / LDS)
   const int grid = g.ntiles < slots ? g.ntiles : slots;
   double* pd = reinterpret_cast<double*>(bn_partial);
   const bool ragged = (g.OH % 16) != 0 || (g.OW % 16) != 0;
@@ -667,7 +657,7 @@ extern "C" int mla_conv2d_stem_fwd_split(const float* x, const float* w, float* 
 
 int mla_wgrad_reduce(const float* part, float* dw, size_t n4, int splits, hipStream_t st);   // conv_igemm.hip
 
-extern "C" size_t mla_conv2d_stem_wgrad_split_ws_bytes(int Cin) { return (size_t)stem_cus() * 49 * Cin * 64 * sizeof(float); }
+extern "C" size_t mla_conv2d_stem_wgrad_split_ws_bytes(int Cin) { return (size_t)mla_cu_count() * 49 * Cin * 64 * sizeof(float); }
 
 extern "C" int mla_conv2d_stem_wgrad_split(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin, int Cout,
                                            int KH, int KW, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
@@ -681,7 +671,7 @@ extern "C" int mla_conv2d_stem_wgrad_split(const float* x, const float* dy, floa
   g.x_bytes = (unsigned)((size_t)N * H * W * Cin * 4);
   const size_t dyb = (size_t)N * g.OH * g.OW * 64 * 4;
   MLA_REQUIRE(dyb < 0xFFFFFFF0UL, "mla_conv2d_stem_wgrad_split: dy must be < 4 GiB (32-bit buffer offsets)");
-  const int grid = g.ntiles < stem_cus() ? g.ntiles : stem_cus();
+  const int grid = g.ntiles < mla_cu_count() ? g.ntiles : mla_cu_count();
   const size_t need = (size_t)grid * 49 * Cin * 64 * sizeof(float);
   if (ws_bytes < need) {
     mla_set_error("mla_conv2d_stem_wgrad_split: workspace %zu < %zu bytes", ws_bytes, need);

@@ -593,16 +593,6 @@ __global__ __launch_bounds__(512, 1) void linear_wgrad_tr_kernel(const float* __
   }
 }
 
-int wt_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus = n;
-  }
-  return cus;
-}
-
 }  // namespace
 
 int mla_wgrad_reduce(const float* part, float* dw, size_t n4, int splits, hipStream_t st);   // conv_igemm.hip
@@ -614,7 +604,7 @@ static bool wf_supported(int W, int Cin, int Cout, int KH, int KW, int stride, i
 static void wf_plan(long M, int Cin, int Cout, int* pairs, int* splits) {
   const long ntiles = (M + 63) / 64;
   *pairs = (Cin / 64) * (Cout / 64);
-  long s = wt_cus() / *pairs;
+  long s = mla_cu_count() / *pairs;
   if (s < 1) s = 1;
   if (s > ntiles) s = ntiles;
   *splits = (int)s;
@@ -624,7 +614,7 @@ bool mla_wgrad_tr_supported(int W, int Cin, int Cout, int KH, int KW, int stride
   return wf_supported(W, Cin, Cout, KH, KW, stride, pad);
 }
 size_t mla_wgrad_tr_ws_bytes(int N, int H, int W, int Cin, int Cout) {
-  if (Cin == 64 && Cout == 64) return (size_t)wt_cus() * WT_RACC * sizeof(float);
+  if (Cin == 64 && Cout == 64) return (size_t)mla_cu_count() * WT_RACC * sizeof(float);
   int pairs, splits;
   wf_plan((long)N * H * W, Cin, Cout, &pairs, &splits);
   return (size_t)splits * 9 * Cin * Cout * sizeof(float);
@@ -646,7 +636,7 @@ int mla_wgrad_tr_launch(const float* x, const float* dy, float* dw, int N, int H
     g.ntiles = N * g.tilesY * g.tilesX;
     g.x_bytes = (unsigned)((size_t)N * H * W * 64 * 4);
     for (int k = 0; k < 4; ++k) g.in_bn[k] = in_bn ? in_bn[k] : nullptr;
-    const int grid = g.ntiles < wt_cus() ? g.ntiles : wt_cus();
+    const int grid = g.ntiles < mla_cu_count() ? g.ntiles : mla_cu_count();
     if (in_bn) wgrad_tr_split_kernel<true><<<grid, 512, 0, st>>>(x, dy, (float*)ws, g);
     else wgrad_tr_split_kernel<false><<<grid, 512, 0, st>>>(x, dy, (float*)ws, g);
     MLA_CHECK_LAUNCH("wgrad_tr_split_kernel");
@@ -669,7 +659,7 @@ int mla_wgrad_tr_launch(const float* x, const float* dy, float* dw, int N, int H
 static void lw_plan(long M, int K, int N, int* pairs, int* splits) {
   *pairs = (K / 192) * (N / 192);
   const long mtiles = (M + LW_MS - 1) / LW_MS;
-  long s = wt_cus() / *pairs;
+  long s = mla_cu_count() / *pairs;
   if (s < 1) s = 1;
   if (s > mtiles) s = mtiles;
   *splits = (int)s;

@@ -130,6 +130,7 @@ class ResNet18Encoder(FlatModule):
             self.rinv[bn] = self._rinv_flat[o:o + c]
             o += c
         self.grad_ready = False
+        self._fwd_training = False          # the most recent forward ran in training mode (backward_from_pooled needs one)
         self._plan_key = None
         self._ws: dict = {}
         # split-bf16 images of the conv weights (conv_math == "split"): per conv a transposed image for the forward
@@ -261,11 +262,12 @@ class ResNet18Encoder(FlatModule):
                 stride = 2 if (li > 1 and bi == 0) else 1
                 oh, ow = ops.conv_out(ch, 3, stride, 1), ops.conv_out(cw, 3, stride, 1)
                 has_ds = bi == 0 and (stride != 1 or inpl != planes)
+                # "fold": whether the most recent forward folded relu(bn1(.)) into conv2 (set by forward()); "a1", that activation, exists
+                # once a forward has not folded this block
                 blk = {"pre": pre, "stride": stride, "cin": inpl, "cout": planes, "in_hw": (ch, cw), "out_hw": (oh, ow),
-                       "ds": has_ds}
-                for nm in ("y1", "a1", "y2", "out"):
+                       "ds": has_ds, "fold": False}
+                for nm in ("y1", "y2", "out"):
                     blk[nm] = torch.empty((N, oh, ow, planes), **f32)
-                blk["fold"] = BN_FOLD and self.conv_math == "split" and ops.conv2d_bnfold_supported(N, oh, ow, planes, planes, 3, 3, 1, 1)
                 if has_ds:
                     blk["yd"] = torch.empty((N, oh, ow, planes), **f32)
                 blocks.append(blk)
@@ -326,10 +328,6 @@ class ResNet18Encoder(FlatModule):
         if not self.training:
             ops.bn_invstd(self.running[self._tot_bn:], self._rinv_flat)       # one launch for all 20 BN layers
         return self
-
-    def _fold(self, blk) -> bool:
-        """True when relu(bn1(y1)) of this block is never materialised (training mode; see BN_FOLD)."""
-        return bool(self.training and blk.get("fold") and FUSE_BN_REDUCE)      # (the fold rides on the fused reduction's read of y1)
 
     def _bn_in(self, ws, bn):
         mean, invstd = ws["stats"][bn]
@@ -394,7 +392,7 @@ class ResNet18Encoder(FlatModule):
         gamma / beta: bn1's affine parameters AT THE TIME OF THAT FORWARD if an optimizer step has changed them since."""
         ws = self._ws
         y = ws["y_stem"]
-        mean, invstd = ws["stats"]["bn1"] if self.training else (self.rm["bn1"], self.rinv["bn1"])
+        mean, invstd = ws["stats"]["bn1"] if self._fwd_training else (self.rm["bn1"], self.rinv["bn1"])
         ga = self.p["bn1.weight"] if gamma is None else gamma.to(y.device, torch.float32).contiguous()
         be = self.p["bn1.bias"] if beta is None else beta.to(y.device, torch.float32).contiguous()
         out = torch.empty_like(y)
@@ -405,7 +403,7 @@ class ResNet18Encoder(FlatModule):
         """relu(bn1(conv1 output)) of a BasicBlock of the live forward (tests / inspection).  Blocks whose consumers re-form it from
         conv1's output (BN_FOLD) never store it: rebuilt here by bn_apply -- the same expression, bit for bit.  gamma / beta: bn1's
         affine parameters AT THE TIME OF THAT FORWARD if an optimizer step has changed them since."""
-        if not self._fold(blk):
+        if not blk["fold"]:
             return blk["a1"]
         bn = blk["pre"] + ".bn1"
         y = blk["y1"]
@@ -447,11 +445,16 @@ class ResNet18Encoder(FlatModule):
             if "x0" not in ws:
                 ws["x0"] = torch.empty((N, H, W, 1), device=self.device, dtype=torch.float32)
             ws["x0"].copy_(x.view(N, H, W, 1))
+        self._fwd_training = False                                  # (until this forward has been enqueued in full)
         self._stem(ws, st)                                                                       # :149-152
         cur = ws["p0"]
         for blk in ws["blocks"]:                                                                 # :154-157
             pre = blk["pre"]
-            fold = self._fold(blk)
+            # decided here and recorded for the backward / block_a1 of this forward (the fold rides on the fused reduction's read of y1)
+            fold = blk["fold"] = bool(BN_FOLD and self.training and FUSE_BN_REDUCE and self.conv_math == "split"
+                                      and ops.conv2d_bnfold_supported(*blk["y1"].shape, blk["cout"], 3, 3, 1, 1))
+            if not fold and "a1" not in blk:
+                blk["a1"] = torch.empty_like(blk["y1"])
             self._conv_bn(ws, st, cur, pre + ".conv1", blk["stride"], 1, blk["y1"], None if fold else blk["a1"], relu=True)
             if blk["ds"]:
                 idn = ws["idn"][:blk["yd"].numel()].view(blk["yd"].shape)
@@ -463,7 +466,7 @@ class ResNet18Encoder(FlatModule):
                           bn_in=self._bn_in(ws, pre + ".bn1") if fold else None)
             blk["xin"] = cur
             cur = blk["out"]
-        self.grad_ready = False
+        self._fwd_training, self.grad_ready = self.training, False
         return cur
 
     # ------------------------------------------------------------------------------------------
@@ -482,7 +485,11 @@ class ResNet18Encoder(FlatModule):
                    ws["bn_ws"], M, C, stream=st)
 
     def backward_from_pooled(self, dfeat: torch.Tensor, P: int) -> None:
-        """dfeat: (NB, 512) gradient of the global-average-pooled feature (NB groups of P pixels)."""
+        """dfeat: (NB, 512) gradient of the global-average-pooled feature (NB groups of P pixels).  Runs against the most recent
+        forward, which must have run in training mode (an eval forward overwrites the activations and saves no statistics)."""
+        if not self._fwd_training:
+            raise MLAHipError(f"{self.modality} encoder: backward_from_pooled needs a training-mode forward, but the most recent forward "
+                              "ran in eval mode (or none has run)")
         ws = self._ws
         st = ops.cur_stream()
         self._bwd_ws(ws)
@@ -550,7 +557,7 @@ class ResNet18Encoder(FlatModule):
             dy2 = DY[pre + ".conv2"]
             self._bn_bwd(ws, st, pre + ".bn2", d, blk["y2"], dy2, have.pop(pre + ".bn2", None))
             da1 = G[2][:n_out].view(oshape)
-            if self._fold(blk):
+            if blk["fold"]:
                 bn_in = self._bn_in(ws, pre + ".bn1")
                 self._wgrad(ws, blk["y1"], dy2, pre + ".conv2", 1, 1, bn_in=bn_in)
                 _, rt = ops.conv2d_dgrad_split_bnmask(dy2, self.wsp[pre + ".conv2"][1], self.p[pre + ".conv2.weight"].shape, oshape, 1, 1, da1,

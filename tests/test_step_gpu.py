@@ -363,7 +363,9 @@ def test_bn_fold_is_bitwise_equivalent():
                 spec, image, label = inputs(seed, step, B, (128, 64), 2, (64, 64))
                 losses = tr.train_step(spec.cuda(), image.cuda(), label.cuda(), step, 10)
             torch.cuda.synchronize()
-            folded = sum(bool(blk["fold"]) for enc in (model.audio_net, model.visual_net) for blk in enc._ws["blocks"])
+            blocks = [blk for enc in (model.audio_net, model.visual_net) for blk in enc._ws["blocks"]]
+            folded = sum(bool(blk["fold"]) for blk in blocks)
+            assert all(("a1" in blk) != blk["fold"] for blk in blocks), "relu(bn1(.)) is allocated exactly where it is materialised"
             runs[fold] = (folded, model.audio_net.flat.cpu(), model.visual_net.flat.cpu(), model.fusion_module.fc_out.flat.cpu(),
                           losses["loss"].cpu(), model.audio_net.running.cpu(), model.visual_net.running.cpu())
     finally:
@@ -372,6 +374,75 @@ def test_bn_fold_is_bitwise_equivalent():
     assert runs[True][0] == 4 and runs[False][0] == 0, "layer1's two blocks of both encoders fold, nothing else does"
     for x, y in zip(runs[True][1:], runs[False][1:]):
         assert torch.equal(x, y)
+
+
+def _audio_encoder_step(enc, x, dfeat, between=None):
+    """forward (training mode) -> `between(enc)` -> backward_from_pooled; returns (features, gradient buffer)."""
+    enc.train()
+    feat = enc.forward(x).clone()
+    if between is not None:
+        between(enc)
+    enc.backward_from_pooled(dfeat, feat.shape[1] * feat.shape[2])
+    torch.cuda.synchronize()
+    return feat, enc.grad.clone()
+
+
+def _fold_case(seed):
+    """A split-arithmetic audio encoder at B = 4 with the patch kernels forced, so that layer1's blocks fold at this size."""
+    from mla_hip.encoder import ResNet18Encoder
+    enc = ResNet18Encoder("audio", "cuda", seed=seed, conv_math="split")
+    spec = O.portable_normal(seed, (4, 1, 128, 64), stream=1, mean=-5.081, std=4.4849)
+    dfeat = O.portable_normal(seed, (4, 512), stream=3)
+    return enc, spec.cuda(), dfeat.cuda()
+
+
+def test_backward_uses_the_fold_plan_of_its_forward():
+    """eval() between a folded training forward and its backward does not change the backward: the gradients are bit-identical to those
+    of forward -> backward (the backward reads the plan that forward recorded, not the current mode)."""
+    from mla_hip import ops
+    saved_patch = ops.conv2d_patch()
+    ops.conv2d_patch(2)
+    try:
+        enc, x, dfeat = _fold_case(61)
+        feat0, g0 = _audio_encoder_step(enc, x, dfeat)
+        assert [blk["fold"] for blk in enc._ws["blocks"]][:2] == [True, True]
+        feat1, g1 = _audio_encoder_step(enc, x, dfeat, between=lambda e: e.eval())
+    finally:
+        ops.conv2d_patch(saved_patch)
+    assert torch.equal(feat0, feat1) and torch.equal(g0, g1)
+
+
+def test_backward_after_an_eval_forward_is_refused():
+    """An eval forward overwrites the activations and saves no batch statistics: a backward after it raises instead of reading them."""
+    from mla_hip import MLAHipError
+    enc, x, dfeat = _fold_case(67)
+    enc.forward(x)
+    enc.eval()
+    feat = enc.forward(x)
+    with pytest.raises(MLAHipError, match="eval mode"):
+        enc.backward_from_pooled(dfeat, feat.shape[1] * feat.shape[2])
+    _audio_encoder_step(enc, x, dfeat)                  # a training forward makes the backward legitimate again
+    assert enc.grad_ready
+
+
+def test_hook_flip_between_steps_is_honoured():
+    """ops.conv2d_patch(0) after a folded step (the workspace exists): the next step folds nothing and equals a fresh encoder's step
+    with the hook already at 0, bit for bit."""
+    from mla_hip import ops
+    saved_patch = ops.conv2d_patch()
+    try:
+        ops.conv2d_patch(2)
+        enc, x, dfeat = _fold_case(71)
+        _audio_encoder_step(enc, x, dfeat)
+        assert any(blk["fold"] for blk in enc._ws["blocks"])
+        ops.conv2d_patch(0)
+        feat, grad = _audio_encoder_step(enc, x, dfeat)
+        assert not any(blk["fold"] for blk in enc._ws["blocks"])
+        fresh, _x, _d = _fold_case(71)
+        feat_ref, grad_ref = _audio_encoder_step(fresh, x, dfeat)
+    finally:
+        ops.conv2d_patch(saved_patch)
+    assert torch.equal(feat, feat_ref) and torch.equal(grad, grad_ref)
 
 
 def test_device_feeder_delivers_batches_in_order():
