@@ -371,6 +371,23 @@ int mla_tokens_assemble_bwd(const float* dx0, const float* colsum_all, const int
  * viewed as (B,1,freq,time), cav_mae.py:339-340). */
 int mla_patchify(const float* img, float* out, int B, int C, int H, int W, int P, int transposed, void* stream);
 
+/* ---- CREMA-D frame augmentation (dataset/dataset.py:128-140, 144-153) ------------------------------------------
+ * N decoded RGB frames (uint8 HWC, as np.asarray(PIL.Image.convert('RGB'))), packed at arbitrary byte offsets of
+ * `frames` and of any sizes, -> out fp32 (B, 3, T, out_h, out_w); frame n is sample n / T, time slot n % T (the
+ * reference's image.unsqueeze(1) + cat(dim=1)).  desc int64 (N, 8) per frame: byte offset, H, W, crop top, crop left,
+ * crop h, crop w, flip.  Per frame the result is bit-identical to
+ *     PIL img.crop((left, top, left + w, top + h)).resize((out_w, out_h), BILINEAR)     RandomResizedCrop / Resize
+ *     .transpose(FLIP_LEFT_RIGHT) if flip                                              RandomHorizontalFlip
+ *     lut[c][u8]                                                                       ToTensor + Normalize
+ * (Pillow's separable 8-bit resample, 22-bit fixed-point coefficients; the filter clamps to the crop, not the frame).
+ * lut fp32 (3, 256) on the device.  `desc` (device, read by the kernel) and `desc_host` (host memory, the same values)
+ * are both needed: the host copy is validated and planned before the launch.
+ * mla_frames_check runs those host checks alone (no GPU): crop inside the frame, sizes > 0, offset + H*W*3 within
+ * frames_bytes, N == B*T, and an LDS plan that fits (extreme downscales of a huge crop do not). */
+int mla_frames_check(const int64_t* desc_host, int N, int B, int T, size_t frames_bytes, int out_h, int out_w);
+int mla_frames_resample(const uint8_t* frames, size_t frames_bytes, const int64_t* desc, const int64_t* desc_host,
+                        const float* lut, float* out, int N, int B, int T, int out_h, int out_w, void* stream);
+
 /* ---- evaluation path (main.py:486-679 `valid`, gs_flag branch) --------------------------------- */
 /* logits = X W^T + b only (main.py:636-639) */
 int mla_head_logits(const float* X, const float* W, const float* b, float* logits, int B, int D, int C, void* stream);

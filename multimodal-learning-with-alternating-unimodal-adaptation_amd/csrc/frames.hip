@@ -1,0 +1,225 @@
+// CREMA-D frame augmentation (dataset/dataset.py:128-153), gfx950: crop -> bilinear resize -> horizontal flip -> ToTensor +
+// Normalize of a batch of decoded uint8 RGB frames, bit-identical to PIL + torchvision on the host.
+//
+//   PIL  img.crop((left, top, left+cw, top+ch)).resize((OW, OH), BILINEAR)      RandomResizedCrop / Resize((224, 224))
+//   PIL  .transpose(FLIP_LEFT_RIGHT) if flip                                     RandomHorizontalFlip
+//   LUT  lut[c][u8] = (u8 / 255 - mean[c]) / std[c], built with torch's CPU ops  ToTensor + Normalize
+//
+// Pillow's 8-bit resample (libImaging/Resample.c) is separable: a horizontal pass over every source row the vertical pass
+// needs, clipped to uint8, then a vertical pass, both in 22-bit fixed point (acc = 2^21 + sum u8 * k; clamp(acc >> 22)).
+// The integer coefficients come from double-precision triangle weights normalised by their sum; they are recomputed here
+// with the exact operation order of Pillow's precompute_coeffs / normalize_coeffs_8bpc and FP contraction off (an FMA in
+// `(xx + 0.5) * scale` or `0.5 + w * 2^22` changes the last bit and with it some pixels).
+//
+// One workgroup per (frame, band of output rows): coefficients of all output columns and of the band's rows into LDS, the
+// horizontal pass of the source rows the band reads into LDS (uint8), then the vertical pass, flip and LUT, written as
+// coalesced fp32 rows straight into the (B, 3, T, OH, OW) batch (frame n = sample n / T, time slot n % T).  No atomics.
+#include <algorithm>
+#include <math.h>
+#include "common.h"
+
+#define FR_THREADS 256
+#define FR_BAND 16                 // output rows per workgroup (halved by the planner until the LDS budget fits)
+#define FR_LDS_MAX 65536
+#define FR_DIM_MAX 65536
+
+// Pillow precompute_coeffs() bounds and (optionally) normalize_coeffs_8bpc() weights of output index xx for a bilinear
+// resize of `in` samples to `out` (box = the whole input: torchvision crops first, so the filter clamps to the crop).
+__host__ __device__ static inline void fr_coeffs(int in, int out, int xx, int* xmin_out, int* xmax_out, int* k) {
+#pragma clang fp contract(off)
+  const double scale = (double)in / out;
+  const double filterscale = scale < 1.0 ? 1.0 : scale;
+  const double support = 1.0 * filterscale;
+  const double center = (xx + 0.5) * scale;
+  const double ss = 1.0 / filterscale;
+  int xmin = (int)(center - support + 0.5);
+  if (xmin < 0) xmin = 0;
+  int xmax = (int)(center + support + 0.5);
+  if (xmax > in) xmax = in;
+  xmax -= xmin;
+  *xmin_out = xmin;
+  *xmax_out = xmax;
+  if (!k) return;
+  // two sweeps instead of Pillow's stored double array: the weights are recomputed bit-identically (same expression)
+  double ww = 0.0;
+  for (int x = 0; x < xmax; ++x) {
+    double t = (x + xmin - center + 0.5) * ss;
+    if (t < 0.0) t = -t;
+    ww += t < 1.0 ? 1.0 - t : 0.0;
+  }
+  for (int x = 0; x < xmax; ++x) {
+    double t = (x + xmin - center + 0.5) * ss;
+    if (t < 0.0) t = -t;
+    double w = t < 1.0 ? 1.0 - t : 0.0;
+    if (ww != 0.0) w /= ww;
+    k[x] = (int)(0.5 + w * (1 << 22));
+  }
+}
+
+static inline int fr_ksize(int in, int out) {   // Pillow: (int)ceil(support) * 2 + 1
+  const double scale = (double)in / out;
+  return (int)ceil(scale < 1.0 ? 1.0 : scale) * 2 + 1;
+}
+
+__device__ __forceinline__ int fr_clip8(int acc) {
+  acc >>= 22;
+  return acc < 0 ? 0 : (acc > 255 ? 255 : acc);
+}
+
+struct FramePlan {
+  int band, rows_cap, kh, kv;
+  size_t lds;
+};
+
+// LDS layout (bytes, each part 16-byte aligned): lut f32[3*256] | hk i32[OW*kh] | hb i32[OW*2] | vk i32[band*kv] |
+// vb i32[band*2] | tmp u8[rows_cap*OW*3]
+__host__ __device__ static inline size_t fr_al(size_t b) { return (b + 15) & ~(size_t)15; }
+static inline size_t fr_lds(int OW, int band, int rows_cap, int kh, int kv) {
+  return fr_al(3 * 256 * 4) + fr_al((size_t)OW * kh * 4) + fr_al((size_t)OW * 8) + fr_al((size_t)band * kv * 4) +
+         fr_al((size_t)band * 8) + fr_al((size_t)rows_cap * OW * 3);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void frames_resample_kernel(const uint8_t* __restrict__ src,
+                                                                      const int64_t* __restrict__ desc,
+                                                                      const float* __restrict__ lut, float* __restrict__ out,
+                                                                      int T, int OH, int OW, int band, int rows_cap, int kh,
+                                                                      int kv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char fr_smem[];
+  float* s_lut = reinterpret_cast<float*>(fr_smem);
+  int* hk = reinterpret_cast<int*>(fr_smem + fr_al(3 * 256 * 4));
+  int* hb = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(hk) + fr_al((size_t)OW * kh * 4));
+  int* vk = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(hb) + fr_al((size_t)OW * 8));
+  int* vb = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(vk) + fr_al((size_t)band * kv * 4));
+  uint8_t* tmp = reinterpret_cast<uint8_t*>(vb) + fr_al((size_t)band * 8);
+
+  const int tid = threadIdx.x;
+  const int n = blockIdx.y;
+  const int y0 = blockIdx.x * band;
+  const int nb = min(band, OH - y0);
+  const int64_t* d = desc + (size_t)n * 8;
+  const size_t off = (size_t)d[0];
+  const int W = (int)d[2], top = (int)d[3], left = (int)d[4], ch = (int)d[5], cw = (int)d[6];
+  const bool flip = d[7] != 0;
+
+  for (int i = tid; i < 3 * 256; i += FR_THREADS) s_lut[i] = lut[i];
+  for (int xx = tid; xx < OW; xx += FR_THREADS) fr_coeffs(cw, OW, xx, &hb[2 * xx], &hb[2 * xx + 1], hk + (size_t)xx * kh);
+  for (int yy = tid; yy < nb; yy += FR_THREADS) fr_coeffs(ch, OH, y0 + yy, &vb[2 * yy], &vb[2 * yy + 1], vk + (size_t)yy * kv);
+  __syncthreads();
+
+  // source rows [r0, r0 + nrows) of the crop feed this band (bounds are monotone in the output index); the host planner
+  // sized rows_cap from the same bounds, the min() only keeps a corrupted descriptor inside LDS
+  const int r0 = vb[0];
+  const int nrows = min(vb[2 * (nb - 1)] + vb[2 * (nb - 1) + 1] - r0, rows_cap);
+
+  // horizontal pass -> tmp[r][xx][c] (uint8, Pillow's intermediate image)
+  for (int i = tid; i < nrows * OW; i += FR_THREADS) {
+    const int r = i / OW, xx = i - r * OW;
+    const uint8_t* row = src + off + ((size_t)(top + r0 + r) * W + left) * 3;
+    const int xmin = hb[2 * xx], xmax = hb[2 * xx + 1];
+    const int* k = hk + (size_t)xx * kh;
+    int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+    const uint8_t* p = row + (size_t)xmin * 3;
+    for (int x = 0; x < xmax; ++x, p += 3) {
+      const int w = k[x];
+      a0 += (int)p[0] * w;
+      a1 += (int)p[1] * w;
+      a2 += (int)p[2] * w;
+    }
+    uint8_t* t = tmp + (size_t)i * 3;
+    t[0] = (uint8_t)fr_clip8(a0);
+    t[1] = (uint8_t)fr_clip8(a1);
+    t[2] = (uint8_t)fr_clip8(a2);
+  }
+  __syncthreads();
+
+  // vertical pass, flip, LUT; consecutive threads write consecutive (or, flipped, mirrored) columns of one row
+  const int b = n / T, tt = n - b * T;
+  const size_t plane = (size_t)OH * OW, cstride = (size_t)T * plane;
+  float* o = out + (size_t)b * 3 * cstride + (size_t)tt * plane;
+  for (int i = tid; i < nb * OW; i += FR_THREADS) {
+    const int yy = i / OW, xx = i - yy * OW;
+    const int ymin = vb[2 * yy] - r0, ymax = vb[2 * yy + 1];
+    const int* k = vk + (size_t)yy * kv;
+    int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+    const uint8_t* p = tmp + ((size_t)ymin * OW + xx) * 3;
+    for (int y = 0; y < ymax; ++y, p += (size_t)OW * 3) {
+      const int w = k[y];
+      a0 += (int)p[0] * w;
+      a1 += (int)p[1] * w;
+      a2 += (int)p[2] * w;
+    }
+    const size_t po = (size_t)(y0 + yy) * OW + (flip ? OW - 1 - xx : xx);
+    o[po] = s_lut[fr_clip8(a0)];
+    o[cstride + po] = s_lut[256 + fr_clip8(a1)];
+    o[2 * cstride + po] = s_lut[512 + fr_clip8(a2)];
+  }
+}
+
+// Host checks of one launch + the LDS plan.  Every descriptor is read from host memory: offset, H, W, crop top, crop left,
+// crop h, crop w, flip.
+static int fr_plan(const int64_t* desc_host, int N, int B, int T, size_t frames_bytes, int OH, int OW, FramePlan* plan) {
+  MLA_REQUIRE(desc_host, "mla_frames: null descriptor table");
+  MLA_REQUIRE(B > 0 && T > 0 && N > 0, "mla_frames: B=%d T=%d N=%d must be > 0", B, T, N);
+  MLA_REQUIRE((long long)B * T == N, "mla_frames: N=%d frames but B*T = %d*%d", N, B, T);
+  MLA_REQUIRE(N < 65536, "mla_frames: N=%d frames per launch (max 65535)", N);
+  MLA_REQUIRE(OH > 0 && OW > 0 && OH <= 4096 && OW <= 4096, "mla_frames: output size %dx%d out of range", OH, OW);
+  int kh = 1, kv = 1;
+  double sy_max = 0.0;
+  for (int n = 0; n < N; ++n) {
+    const int64_t* d = desc_host + (size_t)n * 8;
+    const int64_t off = d[0], H = d[1], W = d[2], top = d[3], left = d[4], ch = d[5], cw = d[6], flip = d[7];
+    MLA_REQUIRE(H > 0 && W > 0 && H <= FR_DIM_MAX && W <= FR_DIM_MAX, "mla_frames: frame %d: size %lldx%lld out of range",
+                n, (long long)H, (long long)W);
+    MLA_REQUIRE(ch > 0 && cw > 0, "mla_frames: frame %d: empty crop %lldx%lld", n, (long long)ch, (long long)cw);
+    MLA_REQUIRE(top >= 0 && left >= 0 && top + ch <= H && left + cw <= W,
+                "mla_frames: frame %d: crop (top %lld, left %lld, h %lld, w %lld) leaves the %lldx%lld frame", n,
+                (long long)top, (long long)left, (long long)ch, (long long)cw, (long long)H, (long long)W);
+    MLA_REQUIRE(flip == 0 || flip == 1, "mla_frames: frame %d: flip flag %lld", n, (long long)flip);
+    MLA_REQUIRE(off >= 0 && (uint64_t)off + (uint64_t)(H * W * 3) <= (uint64_t)frames_bytes,
+                "mla_frames: frame %d: bytes [%lld, %lld) lie outside the %zu-byte buffer", n, (long long)off,
+                (long long)(off + H * W * 3), frames_bytes);
+    kh = std::max(kh, fr_ksize((int)cw, OW));
+    kv = std::max(kv, fr_ksize((int)ch, OH));
+    sy_max = fmax(sy_max, (double)ch / OH);
+  }
+  // exact number of source rows a band of `band` output rows reads, maximised over frames and bands
+  for (int band = FR_BAND; band >= 1; band >>= 1) {
+    int rows_cap = 1;
+    for (int n = 0; n < N; ++n) {
+      const int ch = (int)desc_host[(size_t)n * 8 + 5];
+      for (int y0 = 0; y0 < OH; y0 += band) {
+        const int y1 = std::min(y0 + band, OH) - 1;
+        int a0, a1, b0, b1;
+        fr_coeffs(ch, OH, y0, &a0, &a1, nullptr);
+        fr_coeffs(ch, OH, y1, &b0, &b1, nullptr);
+        rows_cap = std::max(rows_cap, b0 + b1 - a0);
+      }
+    }
+    const size_t lds = fr_lds(OW, band, rows_cap, kh, kv);
+    if (lds <= FR_LDS_MAX) {
+      *plan = FramePlan{band, rows_cap, kh, kv, lds};
+      return MLA_OK;
+    }
+  }
+  MLA_REQUIRE(false, "mla_frames: a %dx%d output of crops up to %.1fx its height needs more than %d bytes of LDS", OH, OW,
+              sy_max, FR_LDS_MAX);
+  return MLA_ERR_INVALID_ARG;
+}
+
+extern "C" int mla_frames_check(const int64_t* desc_host, int N, int B, int T, size_t frames_bytes, int out_h, int out_w) {
+  FramePlan plan;
+  return fr_plan(desc_host, N, B, T, frames_bytes, out_h, out_w, &plan);
+}
+
+extern "C" int mla_frames_resample(const uint8_t* frames, size_t frames_bytes, const int64_t* desc, const int64_t* desc_host,
+                                   const float* lut, float* out, int N, int B, int T, int out_h, int out_w, void* stream) {
+  MLA_REQUIRE(frames && desc && lut && out, "mla_frames_resample: null pointer");
+  FramePlan plan;
+  const int rc = fr_plan(desc_host, N, B, T, frames_bytes, out_h, out_w, &plan);
+  if (rc != MLA_OK) return rc;
+  dim3 grid((unsigned)cdiv(out_h, plan.band), (unsigned)N);
+  hipLaunchKernelGGL(frames_resample_kernel, grid, dim3(FR_THREADS), plan.lds, (hipStream_t)stream, frames, desc, lut, out, T,
+                     out_h, out_w, plan.band, plan.rows_cap, plan.kh, plan.kv);
+  MLA_CHECK_LAUNCH("mla_frames_resample");
+  return MLA_OK;
+}

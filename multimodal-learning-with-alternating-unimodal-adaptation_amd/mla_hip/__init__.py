@@ -8,6 +8,8 @@ from .data import NpyBatcher, load_fbank, load_token  # noqa: F401
 from .dist import Comm  # noqa: F401
 from .encoder import ResNet18Encoder  # noqa: F401
 from .feed import DeviceFeeder  # noqa: F401
+from .frames import (FrameBatcher, decode_frames, frame_descriptors, make_lut, pick_frames, sample_augment,  # noqa: F401
+                     sample_crop, sample_flip, sample_generator)
 from .model import AVClassifier, ConcatFusion, SharedHead  # noqa: F401
 from .m3ae import ConcatFusion3, M3AEClassifier, M3AEEncoder, Modal3Classifier  # noqa: F401
 from .modulation import OGM  # noqa: F401

@@ -117,6 +117,8 @@ PROTOTYPES = {
     "mla_tokens_assemble_bwd_ws_bytes": (_Z, [_I, _I, _I]),
     "mla_tokens_assemble_bwd": (_I, [_P] * 6 + [_I, _I, _I, _I, _P, _Z, _P]),
     "mla_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "mla_frames_check": (_I, [_P, _I, _I, _I, _Z, _I, _I]),
+    "mla_frames_resample": (_I, [_P, _Z, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

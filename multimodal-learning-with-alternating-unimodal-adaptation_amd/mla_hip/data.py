@@ -6,7 +6,8 @@ What the reference writes, one file per sample, with `np.save`:
     <text_feature_path>/<name>_token.npy     BERT token ids, int64 (1, 256)  (data/extract_token.py:38-61)
     <text_feature_path>/<name>_pm.npy        padding mask, float32 (1, 256), 1 = padded   (read at dataset/dataset.py:452-457)
 Frames / images are JPEGs decoded and augmented with PIL + torchvision in the reference (dataset/dataset.py:120-155,
-401-446): that pipeline is out of scope; a caller-supplied function provides the image tensor of a sample.
+401-446).  Here a caller-supplied function provides the image tensor of a sample; the CREMA-D frame pipeline itself
+(dataset.py:120-161, augmentation on the GPU) is `frames.FrameBatcher`.
 
 `NpyBatcher` turns a list of sample names into batches in the reference's tuple order (dataset/dataset.py:161, 480, 803):
 files are opened memory-mapped and copied straight into a small ring of PINNED staging tensors, so `DeviceFeeder`'s copies

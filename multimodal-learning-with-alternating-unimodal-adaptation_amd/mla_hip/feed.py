@@ -19,10 +19,15 @@ The feeder does not pin anything itself: copies are asynchronous when the loader
 A source that RECYCLES pinned host memory (data.NpyBatcher's staging ring) exposes `copied(event)`: the feeder hands it the
 event recorded behind each batch's copies, and the source waits on it before overwriting that memory (a copy that has been
 issued has not necessarily run: the copy stream waits on device events of earlier steps and nothing here host-syncs).
+A source that turns its host batch into something else on the device (frames.FrameBatcher: packed uint8 frames ->
+augmented fp32 images) exposes `device_step(host, dev, scratch)`: the feeder calls it on the copy stream after the batch's
+copies and before the batch's ready event, and yields what it returns instead of the copied tensors.  `scratch` is a dict
+that belongs to the slot (its device outputs live there and are fenced with the slot).  The host tensors of such a source
+may change shape from batch to batch (staging that grows, a short last batch): the slot's device tensors follow them.
 """
 from __future__ import annotations
 
-from typing import Iterable, Iterator, List, Sequence, Tuple
+from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -42,17 +47,27 @@ class DeviceFeeder:
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self._dev: List[List[torch.Tensor]] = []
         self._free: List[torch.cuda.Event] = []          # slot may be overwritten once the step that used it is done
+        self._out: List[Optional[tuple]] = []            # what device_step returned for the slot (sources with that hook)
+        self._scratch: List[dict] = []                   # device_step's per-slot device state
 
     def _issue(self, k: int, batch: Sequence[torch.Tensor]) -> torch.cuda.Event:
+        step = getattr(self.batches, "device_step", None)   # sources that finish their batch on the device (frames.FrameBatcher)
         if k >= len(self._dev):
             self._dev.append([torch.empty(t.shape, dtype=t.dtype, device=self.device) for t in batch])
             self._free.append(None)
+            self._out.append(None)
+            self._scratch.append({})
+        elif step is not None:                           # their host tensors may change shape: the slot follows (the old
+            self._dev[k] = [d if (d.shape == t.shape and d.dtype == t.dtype)        # tensor was last read by this slot's
+                            else torch.empty(t.shape, dtype=t.dtype, device=self.device)  # previous step, on this stream)
+                            for t, d in zip(batch, self._dev[k])]
         ready = torch.cuda.Event()
         with torch.cuda.stream(self.copy_stream):
             if self._free[k] is not None:
                 self.copy_stream.wait_event(self._free[k])       # the step that read this slot has finished (device-side fence)
             for t, d in zip(batch, self._dev[k]):
                 d.copy_(t, non_blocking=True)
+            self._out[k] = tuple(step(batch, self._dev[k], self._scratch[k])) if step is not None else None
             ready.record()
         copied = getattr(self.batches, "copied", None)   # sources that recycle pinned staging memory (data.NpyBatcher) refill a
         if copied is not None:                           # staging tuple only once the copies out of it have completed
@@ -78,7 +93,7 @@ class DeviceFeeder:
         while inflight:
             slot, ready = inflight.pop(0)
             torch.cuda.current_stream().wait_event(ready)        # compute waits for this batch only
-            yield tuple(self._dev[slot])                         # the consumer enqueues its step FIRST ...
+            yield self._out[slot] if self._out[slot] is not None else tuple(self._dev[slot])   # the consumer enqueues its step FIRST ...
             done = torch.cuda.Event()
             done.record()
             self._free[slot] = done

@@ -796,3 +796,33 @@ def ogm_modulate(grad, seg_desc, first_chunk, n_seg: int, total_chunks: int, coe
     check(_lib.load().mla_ogm_modulate(_p(grad), _p(seg_desc, torch.int64), _p(first_chunk, torch.int32), n_seg, total_chunks,
                                        _p(coeff), int(ge), seed, step, _p(ws, torch.uint8) if ws is not None else None,
                                        ws.numel() if ws is not None else 0, stream or cur_stream()), "mla_ogm_modulate")
+
+
+# ---- CREMA-D frame augmentation (dataset/dataset.py:128-153) --------------------------------------------------------------
+def _desc_host(desc_host: torch.Tensor) -> torch.Tensor:
+    if desc_host.is_cuda or desc_host.dtype != torch.int64 or desc_host.dim() != 2 or desc_host.shape[1] != 8 \
+            or not desc_host.is_contiguous():
+        raise MLAHipError(f"frame descriptors: expected a contiguous host int64 (N, 8) tensor, got {desc_host.dtype} "
+                          f"{tuple(desc_host.shape)} on {desc_host.device}")
+    return desc_host
+
+
+def frames_check(desc_host: torch.Tensor, B: int, T: int, frames_bytes: int, out_h: int = 224, out_w: int = 224) -> None:
+    """The host checks of frames_resample alone (no GPU): raises MLAHipError on a descriptor the kernel must not run."""
+    d = _desc_host(desc_host)
+    check(_lib.load().mla_frames_check(d.data_ptr(), d.shape[0], B, T, frames_bytes, out_h, out_w), "mla_frames_check")
+
+
+def frames_resample(frames: torch.Tensor, desc: torch.Tensor, desc_host: torch.Tensor, lut: torch.Tensor, out: torch.Tensor,
+                    T: int, stream: Optional[int] = None) -> torch.Tensor:
+    """frames uint8 (device, packed HWC frames), desc int64 (N, 8) on the device and the same table on the host, lut fp32 (3, 256)
+    -> out fp32 (B, 3, T, out_h, out_w) (see include/mla_hip.h, mla_frames_resample)."""
+    d = _desc_host(desc_host)
+    if tuple(desc.shape) != tuple(d.shape):
+        raise MLAHipError(f"frame descriptors: device table {tuple(desc.shape)} and host table {tuple(d.shape)} differ")
+    if tuple(lut.shape) != (3, 256) or out.dim() != 5 or out.shape[1] != 3 or out.shape[2] != T:
+        raise MLAHipError(f"frames_resample: lut {tuple(lut.shape)} / out {tuple(out.shape)} do not match (3, 256) / (B, 3, {T}, H, W)")
+    B, _, _, OH, OW = out.shape
+    check(_lib.load().mla_frames_resample(_p(frames, torch.uint8), frames.numel(), _p(desc, torch.int64), d.data_ptr(), _p(lut),
+                                          _p(out), d.shape[0], B, T, OH, OW, stream or cur_stream()), "mla_frames_resample")
+    return out

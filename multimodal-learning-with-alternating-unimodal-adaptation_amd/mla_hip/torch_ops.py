@@ -292,3 +292,17 @@ def attention_bwd(do, qkv, o, lse, pad_mask, heads):
     dqkv = torch.empty_like(qkv)
     ops.attention_bwd(do, qkv, o, lse, pad_mask, dqkv, _f32((B, heads, n), qkv), B, heads, n, D // heads)
     return dqkv
+
+
+# ---- CREMA-D frame augmentation (dataset/dataset.py:128-153) --------------------------------------------------------
+@_op("frames_resample(Tensor frames, Tensor desc, Tensor lut, int T, int out_h=224, int out_w=224) -> Tensor")
+def frames_resample(frames, desc, lut, T, out_h=224, out_w=224):
+    """Packed uint8 HWC frames (device) + descriptors int64 (N, 8) (host; validated there, then copied to the device) ->
+    (N / T, 3, T, out_h, out_w) fp32: crop, bilinear resize, flip, LUT (mla_hip.frames)."""
+    desc_host = desc.cpu().contiguous()
+    N = desc_host.shape[0]
+    if T <= 0 or N % T:
+        raise ops.MLAHipError(f"frames_resample: {N} frames are not a whole number of samples of T={T}")
+    out = _f32((N // T, 3, T, out_h, out_w), frames)
+    ops.frames_resample(frames, desc_host.to(frames.device), desc_host, lut, out, T)
+    return out
