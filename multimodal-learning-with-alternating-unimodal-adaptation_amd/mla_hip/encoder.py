@@ -27,13 +27,8 @@ import torch
 
 from . import ops
 from ._lib import MLAHipError
-from .module import BatchNorm2dHolder, Conv2dHolder, FlatModule
+from .module import BatchNorm2dHolder, Conv2dHolder, FlatEncoder
 
-
-# Shipped default arithmetic of the conv / Linear contractions: "split" = every fp32 operand split exactly into three
-# bf16 terms, six bf16 MFMAs per fp32 product, fp32 accumulate -- fp32 in / out, error against fp64 no larger than the fp32
-# MFMA's (tests/test_ops_gpu.py::test_conv_split_is_not_reduced_precision), 1.2-1.3x the throughput.  "f32" = v_mfma_f32_32x32x2_f32.
-DEFAULT_CONV_MATH = "split"
 # measurement switch (same-box A/B): 0 = every BatchNorm backward runs its own reduction pass (the round-1 / early round-2 flow)
 FUSE_BN_REDUCE = os.environ.get("MLA_FUSE_BN_REDUCE", "1") != "0"
 # measurement switch: 0 = the downsample input gradient is its own four-launch pass over dx (round 2)
@@ -70,42 +65,27 @@ def bn_name_for_conv(conv_name: str) -> str:
     return conv_name.replace("conv", "bn")
 
 
-class ResNet18Encoder(FlatModule):
+class ResNet18Encoder(FlatEncoder):
     """ResNet-18 trunk without avgpool/fc (backbone.py:96-99), training-mode BatchNorm.
 
     nn.Module face (module.py): `named_parameters()` / `state_dict()` yield the reference's names in the reference's
     registration order (conv1, bn1, layer1.0.conv1, ... backbone.py:78-95, 27-33) with OIHW conv weights that are
     strided views of the flat HWIO buffer; leaves are nn.Conv2d / nn.BatchNorm2d instances for `weight_init`."""
 
+    side_wgrad = True
+
     def __init__(self, modality: str, device="cuda", seed: Optional[int] = None, conv_math: Optional[str] = None):
-        super().__init__()
+        super().__init__(device, conv_math)
         self.modality = modality
-        self.conv_math = conv_math or os.environ.get("MLA_CONV_MATH", DEFAULT_CONV_MATH)
-        if self.conv_math not in ("f32", "split"):
-            raise MLAHipError(f"conv_math must be 'f32' or 'split', got {self.conv_math!r}")
-        self.device = torch.device(device)
         self.specs = conv_specs(modality)
         # the stem follows conv_math too (round 3): "split" -> stem_split.hip's persistent kernels, "f32" -> the exact fp32 MFMA
         # ($MLA_STEM_SPLIT=0: same-box A/B switch back to the fp32 stem under conv_math="split")
         self.stem_split = (self.conv_math == "split" and os.environ.get("MLA_STEM_SPLIT", "1") != "0"
                            and ops.conv2d_stem_supported(self.specs[0][1], self.specs[0][2], self.specs[0][3], self.specs[0][3], self.specs[0][4], self.specs[0][5]))
-        # ---- flat layout: name -> (offset, shape); conv weights HWIO
-        self.layout: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
-        off = 0
-        for name, cin, cout, k, _s, _p in self.specs:
-            self.layout[name + ".weight"] = (off, (k, k, cin, cout))
-            off += k * k * cin * cout
-        for name, _cin, cout, _k, _s, _p in self.specs:
-            bn = bn_name_for_conv(name)
-            self.layout[bn + ".weight"] = (off, (cout,))
-            off += cout
-            self.layout[bn + ".bias"] = (off, (cout,))
-            off += cout
-        self.numel = off
-        self.flat = torch.zeros(off, device=self.device, dtype=torch.float32)
-        self.grad = torch.zeros(off, device=self.device, dtype=torch.float32)
-        self.p = {k: self.flat[o:o + math.prod(s)].view(s) for k, (o, s) in self.layout.items()}
-        self.g = {k: self.grad[o:o + math.prod(s)].view(s) for k, (o, s) in self.layout.items()}
+        # ---- flat layout: conv weights HWIO, then gamma / beta of every BatchNorm
+        self._alloc_flat([(name + ".weight", (k, k, cin, cout)) for name, cin, cout, k, _s, _p in self.specs] +
+                         [(bn_name_for_conv(name) + leaf, (cout,)) for name, _cin, cout, _k, _s, _p in self.specs
+                          for leaf in (".weight", ".bias")])
         # ---- BN buffers (one flat buffer: running_mean | running_var per BN)
         self.bn_names = [bn_name_for_conv(n) for n, *_ in self.specs]
         self.bn_ch = {bn_name_for_conv(n): cout for n, _ci, cout, *_ in self.specs}
@@ -120,7 +100,6 @@ class ResNet18Encoder(FlatModule):
             o += c
         self.running[tot:].fill_(1.0)
         self.num_batches_tracked = {bn: 0 for bn in self.bn_names}
-        self.training = True
         self._rinv_flat = torch.zeros(tot, device=self.device, dtype=torch.float32)    # 1/sqrt(running_var+eps), eval mode
         self._tot_bn = tot
         self.rinv = {}
@@ -133,32 +112,11 @@ class ResNet18Encoder(FlatModule):
         self._fwd_training = False          # the most recent forward ran in training mode (backward_from_pooled needs one)
         self._plan_key = None
         self._ws: dict = {}
-        # split-bf16 images of the conv weights (conv_math == "split"): per conv a transposed image for the forward
-        # GEMM and a straight one for the input-gradient GEMM, 3 bf16 planes each, in one int16 buffer
-        self.wsp: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
-        self._wsplit_dirty = True
-        if self.conv_math == "split":
-            tot16 = sum(2 * 3 * k * k * cin * cout for _n, cin, cout, k, _s, _p in self.specs if cin % 64 == 0)
-            self._wsplit_flat = torch.empty(tot16, device=self.device, dtype=torch.int16)
-            o16, rows, blocks = 0, [], 0
-            for name, cin, cout, k, _s, _p in self.specs:
-                if cin % 64 != 0:
-                    continue
-                n16 = 3 * k * k * cin * cout
-                self.wsp[name] = (self._wsplit_flat[o16:o16 + n16], self._wsplit_flat[o16 + n16:o16 + 2 * n16])
-                nb = k * k * ((cin + 31) // 32) * ((cout + 31) // 32)
-                for transposed, off in ((1, o16), (0, o16 + n16)):     # descriptor rows of mla_conv2d_wsplit_batch
-                    rows.append([self.layout[name + ".weight"][0], off, k * k, cin, cout, transposed, blocks, 0])
-                    blocks += nb
-                o16 += 2 * n16
-            self._wsplit_desc = torch.tensor(rows, dtype=torch.int32, device=self.device)
-            self._wsplit_blocks = blocks
+        # split-bf16 images of the 64..512-channel conv weights (the stem has kernels of its own), keyed by conv name
+        self._build_wsplit([(name, name + ".weight", k * k, cin, cout) for name, cin, cout, k, _s, _p in self.specs if cin % 64 == 0])
         # Optional second HIP stream for the weight-gradient GEMMs: they are off the dgrad -> BN-backward critical
         # chain, so (with one dy buffer per conv: 288 GB of HBM) they run beside it and fill its kernel tails.
         self.wgrad_stream: Optional[torch.cuda.Stream] = None
-        # Stream that carries this encoder's training chain (set by MLATrainer): anything that touches the encoder from
-        # another stream first waits for it (stream-ordered semantics for forward / state_dict / eval without a device sync).
-        self.tail_stream: Optional[torch.cuda.Stream] = None
         # ---- reference-named parameter / buffer tree (views; nothing is copied)
         for name, _cin, _cout, _k, s_, p_ in self.specs:
             w = self._param_view(self.p[name + ".weight"], self.g[name + ".weight"], lambda t: t.permute(3, 2, 0, 1), name + ".weight")
@@ -169,16 +127,9 @@ class ResNet18Encoder(FlatModule):
             bb = self._param_view(self.p[bn + ".bias"], self.g[bn + ".bias"], lambda t: t, bn + ".bias")
             parent, leaf = self._descend(self, bn)
             parent.add_module(leaf, BatchNorm2dHolder(bw, bb, self.rm[bn], self.rv[bn]))
-        self.register_state_dict_pre_hook(ResNet18Encoder._before_state_dict)
+        self.register_state_dict_pre_hook(ResNet18Encoder._before_state_dict)         # after the base's: the tail has been awaited
         self.register_load_state_dict_post_hook(ResNet18Encoder._after_load_state_dict)
         self.reset_parameters(seed)
-
-    def _await_tail(self) -> None:
-        ts = self.tail_stream
-        if ts is not None:
-            cur = torch.cuda.current_stream()
-            if cur != ts:
-                cur.wait_stream(ts)
 
     # ------------------------------------------------------------------------------------------
     # parameters / state_dict (reference keys and OIHW layout at the boundary)
@@ -207,15 +158,9 @@ class ResNet18Encoder(FlatModule):
 
     @staticmethod
     def _before_state_dict(self, prefix, keep_vars) -> None:
-        """state_dict() hook: stream-order after the encoder's training chain; materialise the BN call counters."""
-        self._await_tail()
+        """state_dict() hook: materialise the BN call counters."""
         for bn in self.bn_names:
             self._bn_module(bn).num_batches_tracked.fill_(self.num_batches_tracked[bn])
-
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        self._await_tail()                                   # the copies below must not race the training chain
-        self._wsplit_dirty = True
-        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     @staticmethod
     def _after_load_state_dict(self, incompatible_keys) -> None:
@@ -315,16 +260,10 @@ class ResNet18Encoder(FlatModule):
     # ------------------------------------------------------------------------------------------
     # forward
     # ------------------------------------------------------------------------------------------
-    def _refresh_wsplit(self, st) -> None:
-        """Re-split the conv weights (they change with every optimizer step; in eval mode only when marked dirty)."""
-        ops.conv2d_wsplit_batch(self.flat, self._wsplit_flat, self._wsplit_desc, self._wsplit_blocks, stream=st)
-        self._wsplit_dirty = False
-
     def train(self, mode: bool = True):
         """nn.Module.train/eval semantics for the BatchNorm layers: eval uses the running statistics."""
         super().train(mode)
         self._await_tail()
-        self._wsplit_dirty = True
         if not self.training:
             ops.bn_invstd(self.running[self._tot_bn:], self._rinv_flat)       # one launch for all 20 BN layers
         return self

@@ -25,7 +25,6 @@ puts every kernel on the calling stream in program order (A/B runs).
 """
 from __future__ import annotations
 
-import contextlib
 from typing import Optional
 
 import torch
@@ -34,8 +33,7 @@ from . import ops
 from ._lib import MLAHipError
 from .dist import Comm
 from .modulation import OGM
-from .optim import FusedSGD
-from .streams import distinct_streams
+from .trainer import StreamTrainer
 
 MODULATIONS = ("Normal", "OGM", "OGM_GE")
 
@@ -47,16 +45,7 @@ def _joint_fusion(model):
     return fusion
 
 
-def _prep_inputs(inputs):
-    if len(inputs) == 2:                                                  # ResNet audio + visual
-        spec, image = inputs
-        if spec.dim() == 3:
-            spec = spec.unsqueeze(1)                                      # main.py:273
-        return (spec.float(), image.float())
-    return tuple(inputs)
-
-
-class JointTrainer:
+class JointTrainer(StreamTrainer):
     def __init__(self, model, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 1e-4, modulation: str = "Normal",
                  alpha: float = 0.3, modulation_starts: int = 0, modulation_ends: int = 50, seed: int = 0,
                  comm: Optional[Comm] = None):
@@ -65,47 +54,13 @@ class JointTrainer:
         if modulation not in MODULATIONS:
             raise NotImplementedError(f"JointTrainer implements --modulation {' | '.join(MODULATIONS)}, not {modulation!r}")
         _joint_fusion(model)
-        self.model = model
-        self.head = model.fusion_module.fc_out
-        self.encoders = model.mla_encoders()                              # [(tag, group, encoder)] in concatenation order
+        super().__init__(model, lr, momentum, weight_decay, False, comm)
         self.M = len(self.encoders)
-        groups = {grp: enc for _t, grp, enc in self.encoders}
-        groups["head"] = self.head
-        self.optimizer = FusedSGD(groups, lr, momentum, weight_decay)
         self.modulation = modulation
         self.modulation_starts, self.modulation_ends = modulation_starts, modulation_ends
-        self.comm = comm if comm is not None else Comm()
         dev = model.device
         self.ogm = OGM(alpha, modulation, seed, dev) if modulation != "Normal" else None
         self._msg = torch.empty(self.head.numel + 1 + self.M, device=dev, dtype=torch.float32)
-        self.losses = {k: torch.zeros(1, device=dev, dtype=torch.float32) for k in ["loss"] + ["loss_" + t for t, _g, _e in self.encoders]}
-        self.last = {}
-        # one stream per encoder chain (forward, backward, all-reduce, modulation, SGD) plus its weight-gradient side stream,
-        # drawn as in MLATrainer (streams.py: encoder chains on hardware queues of their own first)
-        self._can_overlap = dev.type == "cuda" and hasattr(model, "forward_split")
-        pool = distinct_streams(2 * self.M, dev) if self._can_overlap else []
-        self._estreams, self._wstreams = pool[:self.M], pool[self.M:]
-        self.overlap = False
-        self.set_overlap(self._can_overlap)
-
-    def join(self) -> None:
-        """Make the current stream wait for every encoder chain (see MLATrainer.join)."""
-        if self._estreams and torch.cuda.is_available():
-            cur = torch.cuda.current_stream()
-            for es in self._estreams:
-                cur.wait_stream(es)
-
-    def set_overlap(self, on: bool) -> None:
-        """Per-encoder streams on / off (off: every kernel of the step on the current stream, in program order)."""
-        self.join()
-        self.overlap = bool(on) and self._can_overlap
-        for k, (_t, _g, enc) in enumerate(self.encoders):
-            if hasattr(enc, "wgrad_stream"):
-                enc.wgrad_stream = self._wstreams[k] if self.overlap else None
-            enc.tail_stream = self._estreams[k] if self.overlap else None
-
-    def _on(self, stream):
-        return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
 
     def _modulating(self, epoch: int) -> bool:
         return self.ogm is not None and self.modulation_starts <= epoch <= self.modulation_ends
@@ -120,25 +75,14 @@ class JointTrainer:
         m, opt = self.model, self.optimizer
         if not getattr(m, "training", True):
             m.train()
-        inputs = _prep_inputs(inputs)
         B = label.shape[0]
         inv_batch = 1.0 / (B * self.comm.world)
         opt.zero_grad()                                                                   # main.py:164
-        main = torch.cuda.current_stream() if self.overlap else None
-        # 1. forwards (main.py:273), one stream per encoder
-        if self.overlap:
-            fwds, feats, done = m.forward_split(*inputs), [], []
-            for es, f in zip(self._estreams, fwds):
-                es.wait_stream(main)          # inputs ready; the previous step's head has read this encoder's features
-                with torch.cuda.stream(es):
-                    feats.append(f())
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    done.append(ev)
-            for ev in done:
-                main.wait_event(ev)
-        else:
-            feats = m.forward_raw(*inputs)
+        main = torch.cuda.current_stream() if self.overlap_forward else None
+        # 1. forwards (main.py:273), one stream per encoder; the concatenated head needs them all
+        feats, done = self._forwards(inputs)
+        for ev in done or ():
+            main.wait_event(ev)
         for (tag, _g, _e), f in zip(self.encoders, feats):
             self.last[tag] = f
         # 2. the concatenated head (main.py:273-310)
@@ -168,7 +112,7 @@ class JointTrainer:
             self.last["scores"], self.last["ratios"] = self.ogm.info[:self.M], self.ogm.info[3:3 + self.M]
         # 4. encoder chains: backward (loss.backward()) -> all-reduce -> modulation (main.py:392-408) -> SGD (main.py:416)
         for k, (_tag, grp, enc) in enumerate(self.encoders):
-            es = self._estreams[k] if self.overlap else None
+            es = self._estreams[k] if self.overlap_forward else None
             if es is not None:
                 es.wait_stream(main)                          # dX_m (and the coefficients) are ready
             with self._on(es):
@@ -217,7 +161,7 @@ class JointEvaluator:
         """update(spec, image, label) | update(token, padding_mask, image, label) | update(token, pm, image, spec, label).
         Returns (out, out_m) of the local batch."""
         *inputs, label = batch
-        feats = self.model.forward_raw(*_prep_inputs(inputs))
+        feats = self.model.forward_raw(*inputs)
         out, out_m = self.head.concat_logits(list(feats), slot="eval")
         outs = [out] + [out_m[k] for k in range(self.M)]
         if self.comm.active:

@@ -22,9 +22,8 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import MLAHipError
-from .encoder import DEFAULT_CONV_MATH
-from .model import ConcatFusion, N_CLASSES, SharedHead, _Classifier, check_joint_args, concat_fusion_forward
-from .module import FlatModule, Holder
+from .model import ConcatFusion, SharedHead, _Classifier, concat_fusion_forward
+from .module import FlatEncoder
 
 
 def _sincos_1d(embed_dim: int, pos: np.ndarray) -> np.ndarray:                      # m3ae.py:181-194
@@ -52,7 +51,7 @@ def sincos_pos_embed(embed_dim: int, length: int, two_d: bool) -> torch.Tensor:
 # measurement switch (same-box A/B): 0 = bias gradients by separate column-reduction launches
 FUSE_BIAS_GRAD = os.environ.get("MLA_FUSE_BIAS_GRAD", "1") != "0"
 
-class M3AEEncoder(FlatModule):
+class M3AEEncoder(FlatEncoder):
     """nn.Module face (module.py): parameters under the reference's names, order and layouts -- nn.Linear weights
     (out, in) as transposed views of the [in][out] GEMM operands, type embeddings / cls as (1,1,D) -- registered as
     MaskedMultimodalAutoencoder does (direct parameters, text_embedding, image_embedding, encoder: m3ae.py:305-331)
@@ -66,10 +65,7 @@ class M3AEEncoder(FlatModule):
                  text_vocab_size: int = 30522, patch_dim: int = 768, seed: Optional[int] = None, conv_math: Optional[str] = None):
         if kind not in ("text", "image", "audio"):
             raise ValueError("kind must be 'text', 'image' or 'audio'")
-        super().__init__()
-        self.conv_math = conv_math or os.environ.get("MLA_CONV_MATH", DEFAULT_CONV_MATH)     # arithmetic of the Linear GEMMs (encoder.py)
-        if self.conv_math not in ("f32", "split"):
-            raise MLAHipError(f"conv_math must be 'f32' or 'split', got {self.conv_math!r}")
+        super().__init__(device, conv_math)                  # conv_math: here the arithmetic of the Linear GEMMs
         self.split = self.conv_math == "split"
         # "fused": one flash-style kernel per direction, scores never materialised (csrc/attention.hip); "materialized": the
         # round-1 form (QK^T -> masked softmax -> PV as strided batched GEMMs, probabilities kept in HBM), kept as a
@@ -77,7 +73,7 @@ class M3AEEncoder(FlatModule):
         self.attention = os.environ.get("MLA_ATTENTION", "fused")
         if self.attention not in ("fused", "materialized"):
             raise MLAHipError(f"MLA_ATTENTION must be 'fused' or 'materialized', got {self.attention!r}")
-        self.kind, self.device = kind, torch.device(device)
+        self.kind = kind
         if kind == "audio":
             patch_dim = 256                  # conv 16x16 over 1 channel (cav_mae.py:127)
         self.has_cls = kind != "audio"       # CAV-MAE has no [cls] token
@@ -98,17 +94,7 @@ class M3AEEncoder(FlatModule):
         for i in range(depth):
             lay += [(f"encoder.blocks.{i}.{n}", dims[s]) for n, s in self.BLOCK_PARAMS]
         lay += [("encoder.layer_norm.weight", (D,)), ("encoder.layer_norm.bias", (D,))]
-        self.layout: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
-        off = 0
-        for name, shp in lay:
-            self.layout[name] = (off, shp)
-            off += math.prod(shp)
-        self.numel = off
-        f32 = dict(device=self.device, dtype=torch.float32)
-        self.flat = torch.zeros(off, **f32)
-        self.grad = torch.zeros(off, **f32)
-        self.p = {k: self.flat[o:o + math.prod(s)].view(s) for k, (o, s) in self.layout.items()}
-        self.g = {k: self.grad[o:o + math.prod(s)].view(s) for k, (o, s) in self.layout.items()}
+        self._alloc_flat(lay)
         # ---- parameters of the other modality's input path: never used, never receive a gradient (grad stays None, so
         # SGD skips them, like the reference); registered below with their own storage, reference shapes
         if kind == "text":
@@ -123,44 +109,15 @@ class M3AEEncoder(FlatModule):
         self._pos: Dict[int, torch.Tensor] = {}
         self._ws: dict = {}
         self._key = None
-        # split-bf16 images of every Linear weight ([K][N] = a 1-tap conv weight): forward (transposed) and input-gradient
-        self.wsp: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
-        self.tail_stream: Optional[torch.cuda.Stream] = None     # see ResNet18Encoder.tail_stream
-        self.training, self._wsplit_dirty = True, True
-        if self.split:
-            lin = [k for k, (_o, shp) in self.layout.items() if len(shp) == 2 and k.endswith(".weight") and k != "text_embedding.weight"]
-            tot16 = sum(2 * 3 * math.prod(self.layout[k][1]) for k in lin)
-            self._wsplit_flat = torch.empty(tot16, device=self.device, dtype=torch.int16)
-            o16, rows, blocks = 0, [], 0
-            for k in lin:
-                off, (K, N) = self.layout[k]
-                n16 = 3 * K * N
-                self.wsp[k] = (self._wsplit_flat[o16:o16 + n16], self._wsplit_flat[o16 + n16:o16 + 2 * n16])
-                nb = ((K + 31) // 32) * ((N + 31) // 32)
-                for transposed, o in ((1, o16), (0, o16 + n16)):
-                    rows.append([off, o, 1, K, N, transposed, blocks, 0])
-                    blocks += nb
-                o16 += 2 * n16
-            self._wsplit_desc = torch.tensor(rows, dtype=torch.int32, device=self.device)
-            self._wsplit_blocks = blocks
+        # split-bf16 images of every Linear weight ([K][N] = a 1-tap conv weight)
+        self._build_wsplit([(k, k, 1) + shp for k, (_o, shp) in self.layout.items()
+                            if len(shp) == 2 and k.endswith(".weight") and k != "text_embedding.weight"])
         self.reset_parameters(seed)
-
-    def _await_tail(self) -> None:
-        ts = self.tail_stream
-        if ts is not None:
-            cur = torch.cuda.current_stream()
-            if cur != ts:
-                cur.wait_stream(ts)
 
     def _w(self, name: str, which: int):
         """split image of Linear `name` (0: forward, 1: input gradient) or None in f32 mode"""
         e = self.wsp.get(name)
         return None if e is None else e[which]
-
-    def train(self, mode: bool = True):
-        super().train(mode)
-        self._wsplit_dirty = True
-        return self
 
     # ---- reference-named parameter tree -----------------------------------------------------------
     def _to_ref(self, name: str):
@@ -192,12 +149,6 @@ class M3AEEncoder(FlatModule):
                 self.unused[name] = p
             parent, leaf = self._descend(self, self._ref_name(name))
             parent.register_parameter(leaf, p)
-        self.register_state_dict_pre_hook(lambda m, prefix, keep_vars: m._await_tail())
-
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        self._await_tail()
-        self._wsplit_dirty = True
-        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -333,8 +284,7 @@ class M3AEEncoder(FlatModule):
         D, H = self.D, self.H
         hd = D // H
         if self.split and (self.training or self._wsplit_dirty):
-            ops.conv2d_wsplit_batch(self.flat, self._wsplit_flat, self._wsplit_desc, self._wsplit_blocks, stream=st)
-            self._wsplit_dirty = False
+            self._refresh_wsplit(st)
         if self.kind == "text":
             ids = inp.reshape(inp.shape[0], -1).contiguous()                                 # token.squeeze(1)
             B, L = ids.shape
@@ -478,45 +428,24 @@ class M3AEEncoder(FlatModule):
 
 
 class M3AEClassifier(_Classifier):
-    """models/basic_model.py:127-200 under --gs_flag: mae_a (text) + mae_v (image) + ConcatFusion(768 -> C)."""
+    """models/basic_model.py:127-200: mae_a (text) + mae_v (image) + ConcatFusion: Linear(768, C) shared (--gs_flag) or
+    Linear(1536, C) on cat(a, v) (:149-152).  forward returns (a, v) either way: the reference loop calls
+    fusion_module(a, v) itself (main.py:236-237)."""
 
     def __init__(self, args, device="cuda", depth: int = 12, text_vocab_size: int = 30522, seed: Optional[int] = None,
                  conv_math: Optional[str] = None):
-        super().__init__()
-        fusion = getattr(args, "fusion_method", "concat")
-        dataset = getattr(args, "dataset", "Food101")
-        if dataset not in ("MVSA", "Food101", "CREMAD"):                            # basic_model.py:132-144
-            raise NotImplementedError("Incorrect dataset name {}".format(dataset))
-        if fusion != "concat":                                                      # basic_model.py:146-163
-            raise NotImplementedError("Incorrect fusion method: {}!".format(fusion))
-        self.gs_flag = bool(getattr(args, "gs_flag", False))
-        if not self.gs_flag:
-            check_joint_args(args)
-        self.args, self.device = args, torch.device(device)
-        s = (lambda k: None if seed is None else seed + k)
-        # basic_model.py:149-152: Linear(768, C) shared (--gs_flag) or Linear(1536, C) on cat(a, v); either way forward returns
-        # (a, v) and the reference loop calls fusion_module(a, v) itself (main.py:236-237)
-        self.fusion_module = ConcatFusion(768 if self.gs_flag else 1536, N_CLASSES[dataset], device, s(2), joint=not self.gs_flag)
-        self.mae_a = M3AEEncoder("text", device, depth=depth, text_vocab_size=text_vocab_size, seed=s(0), conv_math=conv_math)    # :166
-        self.mae_v = M3AEEncoder("image", device, depth=depth, text_vocab_size=text_vocab_size, seed=s(1), conv_math=conv_math)   # :167
+        super().__init__(args, device, seed, ("Food101", "MVSA", "CREMAD"), ConcatFusion, 768, 2)             # :132-163
+        kw = dict(depth=depth, text_vocab_size=text_vocab_size, conv_math=conv_math)
+        self.mae_a = M3AEEncoder("text", device, seed=self._seed(0), **kw)                                    # :166
+        self.mae_v = M3AEEncoder("image", device, seed=self._seed(1), **kw)                                   # :167
 
     def mla_encoders(self):
         return [("a", "text", self.mae_a), ("v", "image", self.mae_v)]
 
-    def forward_raw(self, token: torch.Tensor, padding_mask: torch.Tensor, visual: torch.Tensor):
-        """Kernel-level joint forward into the reused feature buffers (MLATrainer / Evaluator; no autograd)."""
-        return self.mae_a.forward(token, padding_mask), self.mae_v.forward(visual)
-
-    def forward(self, token: torch.Tensor, padding_mask: torch.Tensor, visual: torch.Tensor):
-        """a, v = model(token, padding_mask, image)  (main.py:426; basic_model.py:182-200), with autograd history."""
-        B, D = visual.shape[0], self.mae_a.D
-        a = self._feature(self.mae_a, lambda out: self.mae_a.forward(token, padding_mask, out), B, D)
-        v = self._feature(self.mae_v, lambda out: self.mae_v.forward(visual, None, out), B, D)
-        return a, v
-
-    def forward_split(self, token: torch.Tensor, padding_mask: torch.Tensor, visual: torch.Tensor):
-        """Per-encoder forward closures in alternation order (for the trainer's per-encoder streams)."""
-        return [lambda: self.mae_a.forward(token, padding_mask), lambda: self.mae_v.forward(visual)]
+    def _calls(self, token: torch.Tensor, padding_mask: torch.Tensor, visual: torch.Tensor):
+        """a, v = model(token, padding_mask, image)  (main.py:426; basic_model.py:182-200)"""
+        return visual.shape[0], [lambda out=None: self.mae_a.forward(token, padding_mask, out),
+                                 lambda out=None: self.mae_v.forward(visual, None, out)]
 
 
 class ConcatFusion3(nn.Module):
@@ -534,43 +463,22 @@ class ConcatFusion3(nn.Module):
 
 
 class Modal3Classifier(_Classifier):
-    """models/basic_model.py:202-275 under --gs_flag: CAV-MAE audio (mae_a) + M3AE image (mae_v) + M3AE text (mae_t),
-    shared head Linear(768 -> 4); MLA alternates a -> v -> t (main.py:432-466)."""
+    """models/basic_model.py:202-275: CAV-MAE audio (mae_a) + M3AE image (mae_v) + M3AE text (mae_t), head Linear(768, 4)
+    shared (--gs_flag) or Linear(2304, 4) on cat(a, v, t) (:218-221); MLA alternates a -> v -> t (main.py:432-466)."""
 
     def __init__(self, args, device="cuda", depth: int = 12, text_vocab_size: int = 30522, seed: Optional[int] = None,
                  conv_math: Optional[str] = None):
-        super().__init__()
-        fusion = getattr(args, "fusion_method", "concat")
-        dataset = getattr(args, "dataset", "IEMOCAP")
-        if dataset != "IEMOCAP":                                                    # basic_model.py:208-211
-            raise NotImplementedError("Incorrect dataset name {}".format(dataset))
-        if fusion != "concat":                                                      # basic_model.py:213-229
-            raise NotImplementedError("Incorrect fusion method: {}!".format(fusion))
-        self.gs_flag = bool(getattr(args, "gs_flag", False))
-        if not self.gs_flag:
-            check_joint_args(args)
-        self.args, self.device = args, torch.device(device)
-        s = (lambda k: None if seed is None else seed + k)
-        # basic_model.py:218-221: Linear(768, C) shared (--gs_flag) or Linear(2304, C) on cat(a, v, t)
-        self.fusion_module = ConcatFusion3(768 if self.gs_flag else 2304, N_CLASSES[dataset], device, s(3), joint=not self.gs_flag)
-        self.mae_a = M3AEEncoder("audio", device, depth=depth, seed=s(0), conv_math=conv_math)                                     # :231 CAVMAEFT
-        self.mae_v = M3AEEncoder("image", device, depth=depth, text_vocab_size=text_vocab_size, seed=s(1), conv_math=conv_math)   # :232
-        self.mae_t = M3AEEncoder("text", device, depth=depth, text_vocab_size=text_vocab_size, seed=s(2), conv_math=conv_math)    # :233
+        super().__init__(args, device, seed, ("IEMOCAP",), ConcatFusion3, 768, 3)                             # :208-229
+        kw = dict(depth=depth, text_vocab_size=text_vocab_size, conv_math=conv_math)
+        self.mae_a = M3AEEncoder("audio", device, depth=depth, seed=self._seed(0), conv_math=conv_math)       # :231 CAVMAEFT
+        self.mae_v = M3AEEncoder("image", device, seed=self._seed(1), **kw)                                   # :232
+        self.mae_t = M3AEEncoder("text", device, seed=self._seed(2), **kw)                                    # :233
 
     def mla_encoders(self):
         return [("a", "audio", self.mae_a), ("v", "image", self.mae_v), ("t", "text", self.mae_t)]
 
-    def forward_raw(self, token, padding_mask, visual, audio):
-        return self.mae_a.forward(audio), self.mae_v.forward(visual), self.mae_t.forward(token, padding_mask)
-
-    def forward(self, token, padding_mask, visual, audio):
-        """a, v, t = model(token, padding_mask, image, spec)  (main.py:424; basic_model.py:252-275), with autograd history."""
-        B, D = visual.shape[0], self.mae_a.D
-        a = self._feature(self.mae_a, lambda out: self.mae_a.forward(audio, None, out), B, D)
-        v = self._feature(self.mae_v, lambda out: self.mae_v.forward(visual, None, out), B, D)
-        t = self._feature(self.mae_t, lambda out: self.mae_t.forward(token, padding_mask, out), B, D)
-        return a, v, t
-
-    def forward_split(self, token, padding_mask, visual, audio):
-        return [lambda: self.mae_a.forward(audio), lambda: self.mae_v.forward(visual),
-                lambda: self.mae_t.forward(token, padding_mask)]
+    def _calls(self, token, padding_mask, visual, audio):
+        """a, v, t = model(token, padding_mask, image, spec)  (main.py:424; basic_model.py:252-275)"""
+        return visual.shape[0], [lambda out=None: self.mae_a.forward(audio, None, out),
+                                 lambda out=None: self.mae_v.forward(visual, None, out),
+                                 lambda out=None: self.mae_t.forward(token, padding_mask, out)]

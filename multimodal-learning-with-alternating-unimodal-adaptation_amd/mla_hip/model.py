@@ -40,14 +40,10 @@ class SharedHead(FlatModule, nn.Linear):
         FlatModule.__init__(self)
         self.in_features, self.out_features = in_features, out_features
         self.device = torch.device(device)
-        n = out_features * in_features
-        self.numel = n + out_features
-        self.flat = torch.zeros(self.numel, device=self.device, dtype=torch.float32)
-        self.grad = torch.zeros(self.numel, device=self.device, dtype=torch.float32)
-        self.weight_grad = self.grad[:n].view(out_features, in_features)
-        self.bias_grad = self.grad[n:]
-        self.weight = self._param_view(self.flat[:n].view(out_features, in_features), self.weight_grad, lambda t: t, "weight")
-        self.bias = self._param_view(self.flat[n:], self.bias_grad, lambda t: t, "bias")
+        self._alloc_flat([("weight", (out_features, in_features)), ("bias", (out_features,))])
+        self.weight_grad, self.bias_grad = self.g["weight"], self.g["bias"]
+        self.weight = self._param_view(self.p["weight"], self.weight_grad, lambda t: t, "weight")
+        self.bias = self._param_view(self.p["bias"], self.bias_grad, lambda t: t, "bias")
         gen = torch.Generator(device="cpu")
         gen.manual_seed(seed) if seed is not None else gen.seed()
         std = math.sqrt(2.0 / (in_features + out_features))           # xavier_normal_, utils/utils.py:107-109
@@ -164,8 +160,30 @@ def check_joint_args(args) -> None:
 
 
 class _Classifier(nn.Module):
-    """Shared protocol behaviour of AVClassifier / M3AEClassifier / Modal3Classifier."""
+    """Shared protocol behaviour of AVClassifier / M3AEClassifier / Modal3Classifier.  A subclass builds its encoders and
+    states ONCE how its inputs reach them: `_calls(*inputs) -> (batch, [run(out=None) -> (B, D) feature])`, one callable per
+    encoder in `mla_encoders()` order; the kernel-level and the autograd forwards below are derived from that list."""
     side_streams = True
+
+    def __init__(self, args, device, seed: Optional[int], datasets, fusion_cls, feat_dim: int, n_enc: int):
+        """datasets: the names the reference's constructor accepts, its default first.  Builds the fusion module (the
+        head draws its seed after the encoders': seed + n_enc); the subclass then builds encoder k with `_seed(k)`."""
+        super().__init__()
+        fusion = getattr(args, "fusion_method", "concat")
+        dataset = getattr(args, "dataset", datasets[0])
+        if dataset not in datasets:
+            raise NotImplementedError("Incorrect dataset name {}".format(dataset))
+        if fusion != "concat":
+            raise NotImplementedError("Incorrect fusion method: {}!".format(fusion))
+        self.gs_flag = bool(getattr(args, "gs_flag", False))
+        if not self.gs_flag:
+            check_joint_args(args)
+        self.args, self.device, self.feat_dim, self._seed0 = args, torch.device(device), feat_dim, seed
+        self.fusion_module = fusion_cls(feat_dim if self.gs_flag else n_enc * feat_dim, N_CLASSES[dataset], device,
+                                        self._seed(n_enc), joint=not self.gs_flag)
+
+    def _seed(self, k: int) -> Optional[int]:
+        return None if self._seed0 is None else self._seed0 + k
 
     @property
     def module(self):
@@ -179,18 +197,33 @@ class _Classifier(nn.Module):
             self._wgrad_side = distinct_streams(1, self.device)[0]
         return self._wgrad_side
 
-    def _feature(self, enc, run, B: int, D: int) -> torch.Tensor:
+    def _feature(self, enc, run, B: int) -> torch.Tensor:
         if torch.is_grad_enabled() and self.training:
             if not hasattr(enc, "_anchor"):
                 enc._anchor = make_anchor(self.device)
                 # protocol path: the weight-gradient GEMMs of a backward run on a side stream beside the dgrad -> BN-backward
                 # chain (joined before the gradients are published), like in MLATrainer's pipeline
-                if self.side_streams and getattr(enc, "wgrad_stream", 0) is None and self.device.type == "cuda":
+                if self.side_streams and enc.side_wgrad and enc.wgrad_stream is None and self.device.type == "cuda":
                     enc.wgrad_stream = self._side_stream()
-            return EncoderFeature.apply(enc._anchor, enc, run, B, D)
-        out = torch.empty((B, D), device=self.device, dtype=torch.float32)
+            return EncoderFeature.apply(enc._anchor, enc, run, B, self.feat_dim)
+        out = torch.empty((B, self.feat_dim), device=self.device, dtype=torch.float32)
         run(out)
         return out
+
+    def forward_split(self, *inputs):
+        """Per-encoder forward closures in alternation order, so the trainer may run each encoder's forward on a stream of
+        its own: no encoder forward depends on the head or on another encoder."""
+        return self._calls(*inputs)[1]
+
+    def forward_raw(self, *inputs):
+        """Kernel-level joint forward into the reused feature buffers (trainers / evaluators; no autograd)."""
+        return tuple(run() for run in self._calls(*inputs)[1])
+
+    def forward(self, *inputs):
+        """The features as fresh (B, D) tensors that carry autograd history to their encoder when grad mode is on and the
+        model is training."""
+        B, runs = self._calls(*inputs)
+        return tuple(self._feature(enc, run, B) for (_t, _g, enc), run in zip(self.mla_encoders(), runs))
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """Accepts DataParallel-style `module.`-prefixed keys as well (main.py:724 strips them by hand)."""
@@ -200,29 +233,15 @@ class _Classifier(nn.Module):
 
 
 class AVClassifier(_Classifier):
-    """Two ResNet-18 encoders + shared head (models/basic_model.py:14-77), --gs_flag configuration."""
+    """Two ResNet-18 encoders + ConcatFusion (models/basic_model.py:14-77): Linear(512, C) shared by both modalities
+    (--gs_flag) or Linear(1024, C) on cat(a, v) (:31-34)."""
 
     def __init__(self, args, device="cuda", seed: Optional[int] = None, conv_math: Optional[str] = None):
-        """conv_math: "f32" (exact fp32 MFMA, default) or "split" (exact bf16 operand split, fp32-equivalent; see
+        """conv_math: "f32" (exact fp32 MFMA) or "split" (exact bf16 operand split, fp32-equivalent; see
         encoder.py); default from $MLA_CONV_MATH."""
-        super().__init__()
-        fusion = getattr(args, "fusion_method", "concat")
-        dataset = getattr(args, "dataset", "CREMAD")
-        if dataset != "CREMAD":                                             # basic_model.py:19-26
-            raise NotImplementedError("Incorrect dataset name {}".format(dataset))
-        n_classes = N_CLASSES[dataset]
-        if fusion != "concat":                                              # basic_model.py:28-40
-            raise NotImplementedError("Incorrect fusion method: {}!".format(fusion))
-        self.gs_flag = bool(getattr(args, "gs_flag", False))
-        if not self.gs_flag:
-            check_joint_args(args)
-        self.args = args
-        self.device = torch.device(device)
-        s = (lambda k: None if seed is None else seed + k)
-        # basic_model.py:31-34: Linear(512, C) shared by both modalities (--gs_flag) or Linear(1024, C) on cat(a, v)
-        self.fusion_module = ConcatFusion(512 if self.gs_flag else 1024, n_classes, device, s(2), joint=not self.gs_flag)
-        self.audio_net = ResNet18Encoder("audio", device, s(0), conv_math)     # basic_model.py:42
-        self.visual_net = ResNet18Encoder("visual", device, s(1), conv_math)   # basic_model.py:43
+        super().__init__(args, device, seed, ("CREMAD",), ConcatFusion, 512, 2)     # basic_model.py:19-40
+        self.audio_net = ResNet18Encoder("audio", device, self._seed(0), conv_math)     # basic_model.py:42
+        self.visual_net = ResNet18Encoder("visual", device, self._seed(1), conv_math)   # basic_model.py:43
         self._feat: Dict[int, dict] = {}
 
     def mla_encoders(self):
@@ -235,48 +254,30 @@ class AVClassifier(_Classifier):
             self._feat[B] = {"a": torch.empty((B, 512), **f32), "v": torch.empty((B, 512), **f32)}
         return self._feat[B]
 
-    def forward_audio(self, audio: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        B = audio.shape[0]
-        fa = self.audio_net.forward(audio)
+    def _pooled(self, tag: str, enc, x: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """Encoder forward + global average pool: adaptive_avg_pool2d + flatten for audio (basic_model.py:61, 64), regroup T +
+        adaptive_avg_pool3d + flatten for visual (:56-65)."""
+        B = x.shape[0]
+        f = enc.forward(x)
         if out is None:
-            out = self._feat_buffers(B)["a"]
-        n, h, w, c = fa.shape
-        self.audio_net._pa = h * w                                           # pooled pixels per sample (for the backward)
-        ops.avgpool_fwd(fa, out, B, h * w, c)                                # adaptive_avg_pool2d + flatten (basic_model.py:61,64)
+            out = self._feat_buffers(B)[tag]
+        n, h, w, c = f.shape
+        enc._pa = (n // B) * h * w                                           # pooled pixels per sample (for the backward)
+        ops.avgpool_fwd(f, out, B, enc._pa, c)
         return out
 
-    def forward_visual(self, visual: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        B = visual.shape[0]
-        fv = self.visual_net.forward(visual)
-        if out is None:
-            out = self._feat_buffers(B)["v"]
-        nt, hv, wv, cv = fv.shape
-        self.visual_net._pa = (nt // B) * hv * wv
-        ops.avgpool_fwd(fv, out, B, self.visual_net._pa, cv)                 # regroup T + adaptive_avg_pool3d + flatten (:56-65)
-        return out
-
-    def forward_raw(self, audio: torch.Tensor, visual: torch.Tensor):
-        """Kernel-level joint forward into the reused feature buffers (MLATrainer / Evaluator; no autograd)."""
+    def _calls(self, spec: torch.Tensor, image: torch.Tensor):
+        """a, v = model(spec.unsqueeze(1).float(), image.float())  (main.py:431; basic_model.py:52-77); the trainers and
+        evaluators hand the spectrogram over as the loader yields it, (B, H, W)."""
+        if spec.dim() == 3:
+            spec = spec.unsqueeze(1)
+        audio, visual = spec.float(), image.float()
         if visual.shape[0] != audio.shape[0]:
             raise MLAHipError("audio/visual batch mismatch")
-        return self.forward_audio(audio), self.forward_visual(visual)
+        return audio.shape[0], [lambda out=None: self._pooled("a", self.audio_net, audio, out),
+                                lambda out=None: self._pooled("v", self.visual_net, visual, out)]
 
     def forward(self, audio: torch.Tensor, visual: torch.Tensor):
-        """a, v = model(spec.unsqueeze(1).float(), image.float())  (main.py:431; basic_model.py:52-77): fresh (B,512)
-        tensors that carry autograd history to their encoder when grad mode is on and the model is training.
-        gs_flag false: a, v, out = model(...) (main.py:273; basic_model.py:72-74)."""
-        if visual.shape[0] != audio.shape[0]:
-            raise MLAHipError("audio/visual batch mismatch")
-        B = audio.shape[0]
-        a = self._feature(self.audio_net, lambda out: self.forward_audio(audio, out), B, 512)
-        v = self._feature(self.visual_net, lambda out: self.forward_visual(visual, out), B, 512)
-        if not self.gs_flag:
-            return self.fusion_module(a, v)                                  # basic_model.py:72-74: a, v, out
-        return a, v
-
-    def forward_split(self, audio: torch.Tensor, visual: torch.Tensor):
-        """Per-encoder forward closures in alternation order, so the trainer may run later encoders' forwards on a
-        side stream: no encoder forward depends on the head or on another encoder."""
-        if visual.shape[0] != audio.shape[0]:
-            raise MLAHipError("audio/visual batch mismatch")
-        return [lambda: self.forward_audio(audio), lambda: self.forward_visual(visual)]
+        """gs_flag false: a, v, out = model(...) (main.py:273; basic_model.py:72-74)."""
+        a, v = super().forward(audio, visual)
+        return (a, v) if self.gs_flag else self.fusion_module(a, v)

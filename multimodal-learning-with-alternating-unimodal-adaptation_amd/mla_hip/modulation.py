@@ -90,8 +90,7 @@ class OGM:
             plan = self._plans[id(enc)] = _Plan(enc, self.device)
         if plan.n_seg == 0:
             return
-        if hasattr(enc, "_await_tail"):
-            enc._await_tail()
+        enc._await_tail()
         works = getattr(enc, "_grad_works", None)
         if works:                       # data-parallel protocol path: the encoder-gradient all-reduce is still in flight
             enc.comm.wait(works)        # (autograd.py leaves it to FusedSGD.step()); modulate the REDUCED gradient

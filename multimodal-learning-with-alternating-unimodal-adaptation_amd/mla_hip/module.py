@@ -21,11 +21,14 @@ re-allocate storage raise (the views would silently detach from the kernels' buf
 """
 from __future__ import annotations
 
+import math
+import os
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
+from . import ops
 from ._lib import MLAHipError
 
 
@@ -89,13 +92,37 @@ class BatchNorm2dHolder(nn.BatchNorm2d):
 class FlatModule(nn.Module):
     """Base of every object that owns flat `flat` / `grad` buffers and exposes them under reference names."""
 
+    # Stream that carries this object's training chain (set on encoders by the trainers): anything that touches it from another
+    # stream first waits for that one (stream-ordered semantics for forward / state_dict / eval without a device sync).
+    tail_stream: Optional[torch.cuda.Stream] = None
+
     def __init__(self):
         nn.Module.__init__(self)        # explicit: subclasses also inherit nn.Linear (SharedHead), whose ctor allocates
         self._entries: List[Tuple[str, nn.Parameter, torch.Tensor]] = []      # (reference name, parameter, grad view)
         self._published: Optional[List[torch.Tensor]] = None                  # grad views currently installed as p.grad
         self.comm = None                                                      # set by mla_hip.DataParallel
 
+    def _await_tail(self) -> None:
+        ts = self.tail_stream
+        if ts is not None:
+            cur = torch.cuda.current_stream()
+            if cur != ts:
+                cur.wait_stream(ts)
+
     # ---- registration -------------------------------------------------------------------------------------
+    def _alloc_flat(self, entries: List[Tuple[str, Tuple[int, ...]]]) -> None:
+        """`layout` name -> (offset, shape) in the order given, the `flat` / `grad` buffers and their per-name views `p` / `g`."""
+        self.layout: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
+        off = 0
+        for name, shp in entries:
+            self.layout[name] = (off, shp)
+            off += math.prod(shp)
+        self.numel = off
+        self.flat = torch.zeros(off, device=self.device, dtype=torch.float32)
+        self.grad = torch.zeros(off, device=self.device, dtype=torch.float32)
+        self.p = {k: self.flat[o:o + math.prod(s)].view(s) for k, (o, s) in self.layout.items()}
+        self.g = {k: self.grad[o:o + math.prod(s)].view(s) for k, (o, s) in self.layout.items()}
+
     def _param_view(self, internal: torch.Tensor, grad_internal: torch.Tensor, to_ref: Callable[[torch.Tensor], torch.Tensor],
                     name: str) -> nn.Parameter:
         """Parameter = `to_ref(internal)` (a VIEW of the flat buffer, reference layout) + the matching gradient view."""
@@ -193,3 +220,67 @@ class FlatModule(nn.Module):
             raise MLAHipError(f"mla_hip modules are pinned to {probe.device} / float32 (their parameters are views of the "
                               f"kernels' flat buffers); requested {out.device} / {out.dtype}")
         return self
+
+
+# Shipped default arithmetic of the conv / Linear contractions: "split" = every fp32 operand split exactly into three
+# bf16 terms, six bf16 MFMAs per fp32 product, fp32 accumulate -- fp32 in / out, error against fp64 no larger than the fp32
+# MFMA's (tests/test_ops_gpu.py::test_conv_split_is_not_reduced_precision), 1.2-1.3x the throughput.  "f32" = v_mfma_f32_32x32x2_f32.
+DEFAULT_CONV_MATH = "split"
+
+
+def _await_tail_hook(module, prefix, keep_vars) -> None:
+    module._await_tail()                                     # state_dict(): stream-order after the encoder's training chain
+
+
+class FlatEncoder(FlatModule):
+    """What every modality encoder shares: the arithmetic switch `conv_math` ("split" / "f32", default $MLA_CONV_MATH), the
+    split-bf16 images of its GEMM weights (re-split at the top of a forward), and the hand-over to the stream that carries
+    its training chain (`tail_stream`).  Subclasses add their layout, reference name tree and launch plans."""
+    # True: the weight-gradient GEMMs may run on a side stream, `wgrad_stream` (None = on the calling stream)
+    side_wgrad = False
+
+    def __init__(self, device, conv_math: Optional[str]):
+        super().__init__()
+        self.conv_math = conv_math or os.environ.get("MLA_CONV_MATH", DEFAULT_CONV_MATH)
+        if self.conv_math not in ("f32", "split"):
+            raise MLAHipError(f"conv_math must be 'f32' or 'split', got {self.conv_math!r}")
+        self.device = torch.device(device)
+        # name -> (forward image, input-gradient image) of the weights _build_wsplit lists; empty under conv_math == "f32"
+        self.wsp: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._wsplit_dirty = True
+        self.register_state_dict_pre_hook(_await_tail_hook)
+
+    def _build_wsplit(self, weights: List[Tuple[str, str, int, int, int]]) -> None:
+        """weights: (wsp key, layout name, taps, K, N) of every [taps][K][N] weight the split arithmetic contracts (a Linear
+        [K][N] is a 1-tap conv weight).  Per weight a transposed image for the forward GEMM and a straight one for the
+        input-gradient GEMM, 3 bf16 planes each, in one int16 buffer, and the descriptor rows of mla_conv2d_wsplit_batch."""
+        if self.conv_math != "split":
+            return
+        tot16 = sum(2 * 3 * taps * K * N for _k, _n, taps, K, N in weights)
+        self._wsplit_flat = torch.empty(tot16, device=self.device, dtype=torch.int16)
+        o16, rows, blocks = 0, [], 0
+        for key, name, taps, K, N in weights:
+            n16 = 3 * taps * K * N
+            self.wsp[key] = (self._wsplit_flat[o16:o16 + n16], self._wsplit_flat[o16 + n16:o16 + 2 * n16])
+            nb = taps * ((K + 31) // 32) * ((N + 31) // 32)
+            for transposed, off in ((1, o16), (0, o16 + n16)):
+                rows.append([self.layout[name][0], off, taps, K, N, transposed, blocks, 0])
+                blocks += nb
+            o16 += 2 * n16
+        self._wsplit_desc = torch.tensor(rows, dtype=torch.int32, device=self.device)
+        self._wsplit_blocks = blocks
+
+    def _refresh_wsplit(self, st) -> None:
+        """Re-split the weights (they change with every optimizer step; in eval mode only when marked dirty)."""
+        ops.conv2d_wsplit_batch(self.flat, self._wsplit_flat, self._wsplit_desc, self._wsplit_blocks, stream=st)
+        self._wsplit_dirty = False
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        self._wsplit_dirty = True
+        return self
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        self._await_tail()                                   # the copies below must not race the training chain
+        self._wsplit_dirty = True
+        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)

@@ -190,8 +190,7 @@ class FusedSGD(torch.optim.Optimizer):
         """torch.optim.SGD's layout (main.py:922): {'state': {index: {'momentum_buffer': tensor}}, 'param_groups': [...]}
         with parameters indexed in `model.parameters()` order; buffers are contiguous copies in the reference layout."""
         for name, g in self.groups.items():
-            if hasattr(g, "_await_tail"):
-                g._await_tail()
+            g._await_tail()
             seg = self.seg_initialized[name]
             for i, (_n, p, _gv) in enumerate(getattr(g, "_entries", [])):
                 if (seg[i] if seg is not None else self.initialized[name]):

@@ -27,33 +27,27 @@ from .optim import FusedSGD
 from .plugin import GSPlugin
 
 
-class MLATrainer:
-    def __init__(self, model, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 1e-4,
-                 gs_mode: str = "as_intended", legacy_zero_grad: bool = False, av_alpha: float = 0.55,
-                 comm: Optional[Comm] = None):
-        """`model`: AVClassifier (ResNet-18 audio+visual) or M3AEClassifier (text+image); anything exposing
-        `mla_encoders()`, `forward(*inputs) -> features` and `fusion_module.fc_out`."""
+class StreamTrainer:
+    """What MLATrainer and JointTrainer share: model / head / encoders / one optimiser group per encoder and one for the head /
+    `comm` / the reported `losses` / `last`, and the per-encoder stream pipeline.
+
+    One HIP stream per encoder carries that encoder's whole chain -- forward, backward, gradient all-reduce, SGD -- and a
+    second one its weight-gradient GEMMs; the stream train_step is called on carries only the head path and hands features /
+    feature gradients over with events.  No encoder forward depends on the head or on another encoder (Q7), and the next
+    STEP's first forward only needs that encoder's own SGD, so the encoder chains run beside each other and across step
+    boundaries and fill each other's kernel tails."""
+
+    def __init__(self, model, lr: float, momentum: float, weight_decay: float, legacy_zero_grad: bool, comm: Optional[Comm]):
         self.model = model
         self.head = model.fusion_module.fc_out
-        self.encoders = model.mla_encoders()                    # [(tag, group, encoder)], alternation order
-        self.gs_plugin = GSPlugin(dim=self.head.in_features, device=model.device, mode=gs_mode)
+        self.encoders = model.mla_encoders()                    # [(tag, group, encoder)], alternation / concatenation order
         groups = {grp: enc for _t, grp, enc in self.encoders}
         groups["head"] = self.head
         self.optimizer = FusedSGD(groups, lr, momentum, weight_decay, legacy_zero_grad)
-        self.av_alpha = av_alpha
         self.comm = comm if comm is not None else Comm()
         dev = model.device
-        self._colsum = torch.empty(self.head.in_features, device=dev, dtype=torch.float32)
-        self._msg = torch.empty(self.head.numel + self.head.in_features + 1, device=dev, dtype=torch.float32)
         self.losses = {k: torch.zeros(1, device=dev, dtype=torch.float32) for k in ["loss"] + ["loss_" + t for t, _g, _e in self.encoders]}
         self.last = {}
-        # One HIP stream per encoder carries that encoder's whole chain -- forward, backward, gradient all-reduce, SGD --
-        # and a second one its weight-gradient GEMMs; the stream train_step is called on carries only the head path
-        # (head forward/backward, packed head exchange, GSPlugin, head SGD) and hands features / feature gradients
-        # over with events.  No encoder forward depends on the head or on another encoder (Q7), the next modality only
-        # needs the updated head, and the next STEP's first forward only needs that encoder's own SGD, so the encoder
-        # chains run beside each other and across step boundaries (the last modality's backward overlaps the next
-        # step's first forward) and fill each other's kernel tails.
         self._can_overlap = dev.type == "cuda" and hasattr(model, "forward_split")
         # encoder chains first (they must not share a hardware queue with each other or with the caller's stream), then the
         # weight-gradient side streams, which may double up when the queues run out (streams.py)
@@ -62,10 +56,6 @@ class MLATrainer:
         self._estreams, self._wstreams = pool[:ne], pool[ne:]
         self.overlap_forward = False
         self.set_overlap(self._can_overlap)
-        # Optional HIP-event brackets around the two data-parallel waits of a step (bench.py --gpus N): the packed head exchange
-        # (critical path, calling stream) and the wait for an encoder's gradient all-reduce in front of its SGD launch (that
-        # encoder's stream).  {"head_exchange": [(start, end)...], "grad_wait": [...]} or None (off: nothing is recorded).
-        self.dist_events: Optional[dict] = None
 
     def join(self) -> None:
         """Make the current stream wait for every encoder chain (parameters, momentum, gradients, BN buffers final).
@@ -81,9 +71,47 @@ class MLATrainer:
         self.join()
         self.overlap_forward = bool(on) and self._can_overlap
         for k, (_t, _g, enc) in enumerate(self.encoders):
-            if hasattr(enc, "wgrad_stream"):
+            if enc.side_wgrad:
                 enc.wgrad_stream = self._wstreams[k] if self.overlap_forward else None
             enc.tail_stream = self._estreams[k] if self.overlap_forward else None
+
+    def _on(self, stream):
+        return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+
+    def _forwards(self, inputs):
+        """The joint forward (main.py:424-431, 273): (features, their completion events).  Under the pipeline each encoder's
+        forward is enqueued on its own stream and the caller decides when to wait for which event; else the events are None."""
+        if not self.overlap_forward:
+            return self.model.forward_raw(*inputs), None
+        main = torch.cuda.current_stream()
+        feats, done = [], []
+        for es, f in zip(self._estreams, self.model.forward_split(*inputs)):
+            es.wait_stream(main)       # inputs are ready; the previous step's head has read this encoder's features
+            with torch.cuda.stream(es):
+                feats.append(f())      # stream order on `es`: after this encoder's SGD of the previous step
+                ev = torch.cuda.Event()
+                ev.record()
+                done.append(ev)
+        return feats, done
+
+
+class MLATrainer(StreamTrainer):
+    def __init__(self, model, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 1e-4,
+                 gs_mode: str = "as_intended", legacy_zero_grad: bool = False, av_alpha: float = 0.55,
+                 comm: Optional[Comm] = None):
+        """`model`: AVClassifier (ResNet-18 audio+visual), M3AEClassifier (text+image) or Modal3Classifier.  The calling
+        stream carries head forward/backward, the packed head exchange, GSPlugin and the head's SGD; the next modality only
+        needs the updated head, so the last modality's backward overlaps the next step's first forward."""
+        super().__init__(model, lr, momentum, weight_decay, legacy_zero_grad, comm)
+        self.gs_plugin = GSPlugin(dim=self.head.in_features, device=model.device, mode=gs_mode)
+        self.av_alpha = av_alpha
+        dev = model.device
+        self._colsum = torch.empty(self.head.in_features, device=dev, dtype=torch.float32)
+        self._msg = torch.empty(self.head.numel + self.head.in_features + 1, device=dev, dtype=torch.float32)
+        # Optional HIP-event brackets around the two data-parallel waits of a step (bench.py --gpus N): the packed head exchange
+        # (critical path, calling stream) and the wait for an encoder's gradient all-reduce in front of its SGD launch (that
+        # encoder's stream).  {"head_exchange": [(start, end)...], "grad_wait": [...]} or None (off: nothing is recorded).
+        self.dist_events: Optional[dict] = None
 
     keep_debug = False
 
@@ -128,9 +156,6 @@ class MLATrainer:
         self.gs_plugin.exp_count += 1                                                         # :442
         return works
 
-    def _on(self, stream):
-        return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
-
     def _ev_begin(self):
         if self.dist_events is None:
             return None
@@ -164,28 +189,10 @@ class MLATrainer:
         m, opt = self.model, self.optimizer
         if not getattr(m, "training", True):
             m.train()                                                                         # main.py:135 model.train()
-        if len(inputs) == 2:                                                                  # ResNet audio+visual
-            spec, image = inputs
-            if spec.dim() == 3:
-                spec = spec.unsqueeze(1)                                                      # main.py:431
-            inputs = (spec.float(), image.float())
         B = label.shape[0]
         inv_batch = 1.0 / (B * self.comm.world)
         opt.zero_grad()                                                                       # main.py:164
-        fwd_done = []
-        if self.overlap_forward:
-            main = torch.cuda.current_stream()
-            fwds = m.forward_split(*inputs)                                                   # main.py:424-431 (joint forward, Q7)
-            feats = []
-            for es, f in zip(self._estreams, fwds):
-                es.wait_stream(main)       # inputs are ready; the previous step's head phases have read this encoder's features
-                with torch.cuda.stream(es):
-                    feats.append(f())      # stream order on `es`: after this encoder's SGD of the previous step
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    fwd_done.append(ev)
-        else:
-            feats = m.forward_raw(*inputs)
+        feats, fwd_done = self._forwards(inputs)                                              # main.py:424-431 (joint forward, Q7)
         for k, ((tag, grp, enc), feat) in enumerate(zip(self.encoders, feats)):
             bs = self._estreams[k] if self.overlap_forward else None
             if bs is not None:
@@ -241,11 +248,6 @@ class Evaluator:
     def update(self, *batch):
         """update(spec, image, label) | update(token, padding_mask, image, label) | update(token, pm, image, spec, label)."""
         *inputs, label = batch
-        if len(inputs) == 2:
-            spec, image = inputs
-            if spec.dim() == 3:
-                spec = spec.unsqueeze(1)
-            inputs = (spec.float(), image.float())
         feats = self.model.forward_raw(*inputs)
         outs = [self.head.logits(f, slot="eval_" + str(k)) for k, f in enumerate(feats)]
         if self.comm.active:                                         # global batch (Q9): (world * B_local, C) in rank order

@@ -66,7 +66,7 @@ def main():
         if a.serial:
             jt.set_overlap(False)
         dt = timed(lambda s: jt.train_step(spec, image, label, s), a.steps, a.warmup)
-        print(json.dumps(dict(base, mode=mode, overlap=jt.overlap, ms_per_step=round(dt * 1e3, 3), samples_per_s=round(B / dt, 1),
+        print(json.dumps(dict(base, mode=mode, overlap=jt.overlap_forward, ms_per_step=round(dt * 1e3, 3), samples_per_s=round(B / dt, 1),
                               vs_mla_ms=None if mla_ms is None else round(dt * 1e3 - mla_ms, 3), loss=round(jt.losses["loss"].item(), 5))), flush=True)
         del jt, model
 
