@@ -1,8 +1,10 @@
 // Shared helpers for the gfx950 kernels of libmla_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "../../include/mla_hip.h"
 
 #define MLA_WAVE 64
@@ -41,6 +43,29 @@ inline int mla_cu_count() {
   }();
   return cus;
 }
+
+// An int setting with an environment default, behind a measurement hook.  The variable is read once, at the first use: its first
+// character when that is a digit in [lo, hi] (numeric: atoi, clamped to [lo, hi]), else dflt.  hook(x) sets x when lo <= x <= hi and
+// answers the current value either way (out-of-range arguments are queries); internal code reads get().
+struct EnvInt {
+  const char* name;
+  int lo, hi, dflt;
+  bool numeric = false;
+  int v = INT_MIN;               // INT_MIN: neither set nor read yet
+  int get() {
+    if (v == INT_MIN) {
+      const char* e = getenv(name);
+      v = dflt;
+      if (e && numeric) { const int x = atoi(e); v = x < lo ? lo : (x > hi ? hi : x); }
+      else if (e && e[0] >= '0' + lo && e[0] <= '0' + hi) v = e[0] - '0';
+    }
+    return v;
+  }
+  int hook(int x) {
+    if (x >= lo && x <= hi) v = x;
+    return get();
+  }
+};
 
 // wave-level reductions (64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {

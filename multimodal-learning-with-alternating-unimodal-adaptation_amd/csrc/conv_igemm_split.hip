@@ -14,13 +14,11 @@
 // the layout the MFMA B operand reads with one ds_read_b128) by mla_conv2d_wsplit; activations are split
 // in the kernel on their way from registers to LDS (v_cvt_pk_bf16_f32, ~5.5 VALU ops per element).
 #include "split_common.h"
-#include <stdlib.h>
 #include <type_traits>
 
 // LDS image of one operand plane: [rows][32 bf16] = 16 dwords per row, no padding; the 16-byte chunk q of row r
 // sits at chunk slot q ^ ((r >> 2) & 3), which makes the MFMA fragment reads (ds_read_b128, 16-lane groups
 // {0-3,12-15,20-27}, ...) and the staging stores conflict-free.
-#define LROW 16
 #ifndef SPLIT_EFF
 #define SPLIT_EFF 1.0, 0.95, 0.8, 0.7, 0.9, 0.93
 #endif
@@ -151,15 +149,7 @@ __device__ __forceinline__ void igemm_split_tile(const float* __restrict__ X, co
     unsigned* Ad = As + buf * ASZ + a_st;
     unsigned* Bd = Bs + buf * BSZ + b_st;
 #pragma unroll
-    for (int p = 0; p < APASS; ++p) {
-      unsigned h0, m0, l0, h1, m1, l1;
-      split_pair<true>(rs.a[p][0], rs.a[p][1], h0, m0, l0);
-      split_pair<true>(rs.a[p][2], rs.a[p][3], h1, m1, l1);
-      unsigned* dst = Ad + p * AROWS * LR;
-      *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
-      *reinterpret_cast<u32x2*>(dst + BM * LR) = u32x2{m0, m1};
-      *reinterpret_cast<u32x2*>(dst + 2 * BM * LR) = u32x2{l0, l1};
-    }
+    for (int p = 0; p < APASS; ++p) split_store4(Ad + p * AROWS * LR, BM * LR, rs.a[p]);
     if (bact) {
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)
@@ -172,30 +162,11 @@ __device__ __forceinline__ void igemm_split_tile(const float* __restrict__ X, co
   const int i = lane & 31, h = lane >> 5;
   const int swz = BKS == 32 ? (i >> 2) & 3 : (i >> 3) & 1;
   const int a_rd = (wm * (BM / WM) + i) * LR, b_rd = (wn * (BN / WN) + i) * LR;
-  struct Frags { bf16x8_t a[3][MI], b[3][NI]; };
-  auto load_frags = [&](int buf, int kk, Frags& f) {   // lane (i, h) holds k = kk*16 + 8h .. +7 of row / column i
-    const unsigned* Ar = As + buf * ASZ + a_rd + (((kk * 2 + h) ^ swz) << 2);
-    const unsigned* Br = Bs + buf * BSZ + b_rd + (((kk * 2 + h) ^ swz) << 2);
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-        f.a[pl][mi] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(Ar + (pl * BM + mi * 32) * LR));
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-        f.b[pl][ni] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(Br + (pl * BN + ni * 32) * LR));
-    }
+  auto load_frags = [&](int buf, int kk, SplitFrags<MI, NI>& f) {
+    load_split_frags<BM, BN, LR>(As + buf * ASZ + a_rd + frag_koff(kk, h, swz), Bs + buf * BSZ + b_rd + frag_koff(kk, h, swz), f);
   };
-  auto mma_frags = [&](const Frags& f) {
-#pragma unroll
-    for (int term = 0; term < TERMS; ++term)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[TERM_A[term]][mi], f.b[TERM_B[term]][ni], acc[mi][ni], 0, 0, 0);
-  };
-  Frags f0, f1;
+  auto mma_frags = [&](const SplitFrags<MI, NI>& f) { split_mma<TERMS>(f.a, f.b, acc); };
+  SplitFrags<MI, NI> f0, f1;
 
   if (nIter > 0) {  // nIter == 0: a dgrad parity class no tap reaches (1x1 stride 2): epilogue only
     load_tiles(rs0);
@@ -313,7 +284,8 @@ __global__ __launch_bounds__(64 * WI * WJ, 1) void wgrad_split_kernel(const floa
   constexpr int XG = NT / (BI / 4), XPX = BK / XG;     // pixel groups per K step, pixels per thread (X operand)
   constexpr int YG = NT / (BJ / 4), YPX = BK / YG;
   static_assert((XPX == 4 || XPX == 2) && (YPX == 4 || YPX == 2), "tile / workgroup mismatch");
-  constexpr int ASZ = 3 * BI * LROW, BSZ = 3 * BJ * LROW;
+  constexpr int LR = BK / 2;                             // dwords per LDS row
+  constexpr int ASZ = 3 * BI * LR, BSZ = 3 * BJ * LR;
   __shared__ __attribute__((aligned(16))) unsigned As[2 * ASZ];
   __shared__ __attribute__((aligned(16))) unsigned Bs[2 * BSZ];
   __shared__ unsigned rowoff[WGS_CHUNK];   // (64x64 tile with half the chunk = three workgroups per CU: 7-17 % slower, measured)
@@ -348,35 +320,16 @@ __global__ __launch_bounds__(64 * WI * WJ, 1) void wgrad_split_kernel(const floa
   const int xg = tid % XG, xc = tid / XG;   // pixel group, 4-channel chunk
   const int yg = tid % YG, yc = tid / YG;
   // LDS store address of channel row 4c+e, pixels g*PX .. +PX-1 (bytes 2*PX*g of the 64-B row, chunk-swizzled by row>>2 & 3 = c & 3)
-  const int x_st = (xc * 4) * LROW + (XPX == 4 ? ((((xg >> 1) ^ (xc & 3)) << 2) + (xg & 1) * 2) : ((((xg >> 2) ^ (xc & 3)) << 2) + (xg & 3)));
-  const int y_st = (yc * 4) * LROW + (YPX == 4 ? ((((yg >> 1) ^ (yc & 3)) << 2) + (yg & 1) * 2) : ((((yg >> 2) ^ (yc & 3)) << 2) + (yg & 3)));
+  const int x_st = (xc * 4) * LR + (XPX == 4 ? ((((xg >> 1) ^ (xc & 3)) << 2) + (xg & 1) * 2) : ((((xg >> 2) ^ (xc & 3)) << 2) + (xg & 3)));
+  const int y_st = (yc * 4) * LR + (YPX == 4 ? ((((yg >> 1) ^ (yc & 3)) << 2) + (yg & 1) * 2) : ((((yg >> 2) ^ (yc & 3)) << 2) + (yg & 3)));
   const int i = lane & 31, h = lane >> 5, swz = (i >> 2) & 3;
-  const int a_rd = (wi * (BI / WI) + i) * LROW, b_rd = (wj * (BJ / WJ) + i) * LROW;
+  const int a_rd = (wi * (BI / WI) + i) * LR, b_rd = (wj * (BJ / WJ) + i) * LR;
 
-  struct Frags { bf16x8_t a[3][MI], b[3][NI]; };
-  auto load_frags = [&](int buf, int kk, Frags& f) {
-    const unsigned* Ar = As + buf * ASZ + a_rd + (((kk * 2 + h) ^ swz) << 2);
-    const unsigned* Br = Bs + buf * BSZ + b_rd + (((kk * 2 + h) ^ swz) << 2);
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-        f.a[pl][mi] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(Ar + (pl * BI + mi * 32) * LROW));
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-        f.b[pl][ni] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(Br + (pl * BJ + ni * 32) * LROW));
-    }
+  auto load_frags = [&](int buf, int kk, SplitFrags<MI, NI>& f) {
+    load_split_frags<BI, BJ, LR>(As + buf * ASZ + a_rd + frag_koff(kk, h, swz), Bs + buf * BSZ + b_rd + frag_koff(kk, h, swz), f);
   };
-  auto mma_frags = [&](const Frags& f) {
-#pragma unroll
-    for (int term = 0; term < 6; ++term)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[TERM_A[term]][mi], f.b[TERM_B[term]][ni], acc[mi][ni], 0, 0, 0);
-  };
-  Frags f0, f1;
+  auto mma_frags = [&](const SplitFrags<MI, NI>& f) { split_mma<6>(f.a, f.b, acc); };
+  SplitFrags<MI, NI> f0, f1;
 
   const bool do_bias = bias_part != nullptr && ti == 0 && t == 0;   // one workgroup per (column tile, pixel range)
   f32x4 bacc = {0.f, 0.f, 0.f, 0.f};
@@ -414,20 +367,15 @@ __global__ __launch_bounds__(64 * WI * WJ, 1) void wgrad_split_kernel(const floa
       constexpr int PX = decltype(px_tag)::value;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {   // channel row 4c+e
-        unsigned* dst = base + e * LROW;
+        unsigned* dst = base + e * LR;
         if constexpr (PX == 4) {
-          unsigned h0, m0, l0, h1, m1, l1;
-          split_pair<true>(reg[0][e], reg[1][e], h0, m0, l0);
-          split_pair<true>(reg[2][e], reg[3][e], h1, m1, l1);
-          *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
-          *reinterpret_cast<u32x2*>(dst + plane_rows * LROW) = u32x2{m0, m1};
-          *reinterpret_cast<u32x2*>(dst + 2 * plane_rows * LROW) = u32x2{l0, l1};
+          split_store4(dst, plane_rows * LR, f32x4{reg[0][e], reg[1][e], reg[2][e], reg[3][e]});
         } else {
           unsigned h0, m0, l0;
           split_pair<true>(reg[0][e], reg[1][e], h0, m0, l0);
           dst[0] = h0;
-          dst[plane_rows * LROW] = m0;
-          dst[2 * plane_rows * LROW] = l0;
+          dst[plane_rows * LR] = m0;
+          dst[2 * plane_rows * LR] = l0;
         }
       }
     };
@@ -568,33 +516,59 @@ extern "C" int mla_conv2d_split_terms(int terms) {   // measurement hook: 3, 6 (
 // way round too: 128x128 at K stage 16 with two workgroups per CU is 6-15 % slower than one at K stage 32, 256x64 at
 // K stage 32 (one per CU) 5-15 % slower than two at K stage 16.
 enum { SCFG_256x128 = 0, SCFG_128x128 = 1, SCFG_128x64 = 2, SCFG_64x64 = 3, SCFG_256x64 = 4, SCFG_192x128 = 5, SCFG_COUNT = 6 };
-static int scfg_bm(int c) { return (c == SCFG_256x128 || c == SCFG_256x64) ? 256 : (c == SCFG_64x64 ? 64 : (c == SCFG_192x128 ? 192 : 128)); }
-static int scfg_bn(int c) { return (c <= SCFG_128x128 || c == SCFG_192x128) ? 128 : 64; }
+struct SplitTile {
+  int bm, bn, wm, wn, bks, wpe;   // the kernels' <BM, BN, WM, WN, ., BKS, WPE>
+  int per_cu;                     // resident workgroups per CU (LDS / VGPRs)
+  double eff;                     // measured per-flop rate relative to the 256x128 tile
+  constexpr int threads() const { return 64 * wm * wn; }
+};
+static constexpr double SCFG_EFF[SCFG_COUNT] = {SPLIT_EFF};
+static constexpr SplitTile SCFG[SCFG_COUNT] = {
+    {256, 128, 4, 2, 32, 1, 1, SCFG_EFF[SCFG_256x128]}, {128, 128, 2, 4, 32, 1, 1, SCFG_EFF[SCFG_128x128]},
+    {128, 64, 2, 2, 32, 1, 2, SCFG_EFF[SCFG_128x64]},   {64, 64, 2, 2, 32, 1, 3, SCFG_EFF[SCFG_64x64]},
+    {256, 64, 4, 2, 16, 4, 2, SCFG_EFF[SCFG_256x64]},   {192, 128, 2, 4, 32, 1, 1, SCFG_EFF[SCFG_192x128]},
+};
+// f(std::integral_constant<int, cfg>): the runtime tile number as a compile-time index into SCFG
+template <typename F>
+static void with_scfg(int cfg, F&& f) {
+  switch (cfg) {
+    case SCFG_256x128: return f(std::integral_constant<int, SCFG_256x128>{});
+    case SCFG_128x128: return f(std::integral_constant<int, SCFG_128x128>{});
+    case SCFG_256x64: return f(std::integral_constant<int, SCFG_256x64>{});
+    case SCFG_192x128: return f(std::integral_constant<int, SCFG_192x128>{});
+    case SCFG_128x64: return f(std::integral_constant<int, SCFG_128x64>{});
+    default: return f(std::integral_constant<int, SCFG_64x64>{});
+  }
+}
 static int g_split_cfg = -1;   // measurement hook: force one tile
 extern "C" int mla_conv2d_split_cfg(int cfg) { g_split_cfg = (cfg >= 0 && cfg < SCFG_COUNT) ? cfg : -1; return g_split_cfg; }
 
 // Minimise rounds * resident workgroups * tile area / efficiency.  Small tiles stage more bytes per MFMA.  The
 // efficiencies are the measured per-flop rates at the ResNet-18 layer shapes relative to the 256x128 tile
 // (scripts/split_probe.py); the ranking they give matches the measured ranking on l1..l4 of both modalities.
-static int pick_scfg(long M, int CO, int weight, int k_total = 1 << 30) {
-  if (g_split_cfg >= 0 && CO % scfg_bn(g_split_cfg) == 0) return g_split_cfg;
-  // one-tap convolutions with a short K (the 1x1 stride-2 downsample convs, K <= 512: 2-16 stages per tile): prologue and epilogue
-  // dominate, the 64x64 tile with three workgroups per CU is fastest at every such shape (forced-tile probe, 10-45 % over the model)
-  if (k_total <= 512 && M <= (1L << 18)) return SCFG_64x64;
-  const double eff[SCFG_COUNT] = {SPLIT_EFF};
-  const int per_cu_tab[SCFG_COUNT] = {1, 1, 2, 3, 2, 1};         // resident workgroups per CU (LDS / VGPRs)
+static double scfg_rounds_cost(int c, double rounds) { return rounds * SCFG[c].per_cu * SCFG[c].bm * SCFG[c].bn / SCFG[c].eff; }
+static double scfg_cost(int c, long M, int CO) {
+  const double blocks = (double)cdiv(M, SCFG[c].bm) * (CO / SCFG[c].bn);
+  const long slots = (long)mla_cu_count() * SCFG[c].per_cu;
+  return scfg_rounds_cost(c, (double)(((long)blocks + slots - 1) / slots));
+}
+static int best_scfg(long M, int CO, double* cost = nullptr) {   // the cheapest tile whose width divides CO (first of equals)
   int best = -1;
   double best_cost = 0;
   for (int c = 0; c < SCFG_COUNT; ++c) {
-    if (CO % scfg_bn(c) != 0) continue;
-    const double blocks = (double)cdiv(M, scfg_bm(c)) * (CO / scfg_bn(c));
-    const long slots = (long)mla_cu_count() * per_cu_tab[c];
-    const double rounds = (double)(((long)blocks + slots - 1) / slots);
-    const double cost = rounds * per_cu_tab[c] * scfg_bm(c) * scfg_bn(c) / eff[c];
-    if (best < 0 || cost < best_cost) { best = c; best_cost = cost; }
+    if (CO % SCFG[c].bn != 0) continue;
+    const double cc = scfg_cost(c, M, CO);
+    if (best < 0 || cc < best_cost) { best = c; best_cost = cc; }
   }
-  (void)weight;
+  if (cost) *cost = best_cost;
   return best;
+}
+static int pick_scfg(long M, int CO, int k_total = 1 << 30) {
+  if (g_split_cfg >= 0 && CO % SCFG[g_split_cfg].bn == 0) return g_split_cfg;
+  // one-tap convolutions with a short K (the 1x1 stride-2 downsample convs, K <= 512: 2-16 stages per tile): prologue and epilogue
+  // dominate, the 64x64 tile with three workgroups per CU is fastest at every such shape (forced-tile probe, 10-45 % over the model)
+  if (k_total <= 512 && M <= (1L << 18)) return SCFG_64x64;
+  return best_scfg(M, CO);
 }
 
 // conv_patch_split.hip: 3x3 / stride 1 / pad 1 forward and input gradient with the A operand served from an LDS-resident patch
@@ -603,78 +577,47 @@ int mla_patch_launch(const float* X, const void* Wsp, float* Y, const float* R, 
                      int* bn_tiles, hipStream_t st);
 bool mla_patch64p_usable(const IGemmGeom& g);
 static int g_wgrad_tr = 1;                            // mla_conv2d_wgrad_tr: the all-taps weight-gradient kernels (wgrad_tr_split.hip)
-static int g_patch = -1;                              // -1: not yet read from $MLA_CONV_PATCH (default 1)
-static int patch_mode() {
-  if (g_patch < 0) {
-    const char* e = getenv("MLA_CONV_PATCH");
-    g_patch = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1;
-  }
-  return g_patch;
-}
 // measurement / test hook: 0 = per-tap gather-GEMM everywhere, 1 = default (patch kernel where its grid fills the chip), 2 = patch
 // kernel wherever the geometry allows; other values: query
-extern "C" int mla_conv2d_patch(int on) {
-  if (on >= 0 && on <= 2) g_patch = on;
-  return patch_mode();
-}
+static EnvInt g_patch{"MLA_CONV_PATCH", 0, 2, 1};
+extern "C" int mla_conv2d_patch(int on) { return g_patch.hook(on); }
 static bool use_patch(const IGemmGeom& g) {
-  return patch_mode() && g_split_terms == 6 && g_split_cfg < 0 && mla_patch_supported(g, patch_mode() == 2);
+  return g_patch.get() && g_split_terms == 6 && g_split_cfg < 0 && mla_patch_supported(g, g_patch.get() == 2);
 }
 
 template <int TERMS>
 static void launch_split_t(int cfg, int total, hipStream_t st, const float* X, const void* Wsp, float* Y, const float* R,
                            const float* MASK, float* part, const float* BIAS, float* Y2, const IGemmGeom& mg) {
-  if (cfg == SCFG_256x128) igemm_split_kernel<256, 128, 4, 2, TERMS, 32, 1><<<total, 512, 0, st>>>(X, Wsp, Y, R, MASK, part, BIAS, Y2, mg);
-  else if (cfg == SCFG_128x128) igemm_split_kernel<128, 128, 2, 4, TERMS, 32, 1><<<total, 512, 0, st>>>(X, Wsp, Y, R, MASK, part, BIAS, Y2, mg);
-  else if (cfg == SCFG_256x64) igemm_split_kernel<256, 64, 4, 2, TERMS, 16, 4><<<total, 512, 0, st>>>(X, Wsp, Y, R, MASK, part, BIAS, Y2, mg);
-  else if (cfg == SCFG_192x128) igemm_split_kernel<192, 128, 2, 4, TERMS, 32, 1><<<total, 512, 0, st>>>(X, Wsp, Y, R, MASK, part, BIAS, Y2, mg);
-  else if (cfg == SCFG_128x64) igemm_split_kernel<128, 64, 2, 2, TERMS, 32, 1><<<total, 256, 0, st>>>(X, Wsp, Y, R, MASK, part, BIAS, Y2, mg);
-  else igemm_split_kernel<64, 64, 2, 2, TERMS, 32, 1><<<total, 256, 0, st>>>(X, Wsp, Y, R, MASK, part, BIAS, Y2, mg);
-}
-
-static double scfg_cost(int c, long M, int CO) {       // the cost of pick_scfg: rounds x resident workgroups x tile area / relative rate
-  const double eff[SCFG_COUNT] = {SPLIT_EFF};
-  const int per_cu_tab[SCFG_COUNT] = {1, 1, 2, 3, 2, 1};
-  const double blocks = (double)cdiv(M, scfg_bm(c)) * (CO / scfg_bn(c));
-  const long slots = (long)mla_cu_count() * per_cu_tab[c];
-  const double rounds = (double)(((long)blocks + slots - 1) / slots);
-  return rounds * per_cu_tab[c] * scfg_bm(c) * scfg_bn(c) / eff[c];
+  with_scfg(cfg, [&](auto c) {
+    constexpr SplitTile t = SCFG[decltype(c)::value];
+    igemm_split_kernel<t.bm, t.bn, t.wm, t.wn, TERMS, t.bks, t.wpe><<<total, t.threads(), 0, st>>>(X, Wsp, Y, R, MASK, part, BIAS, Y2, mg);
+  });
 }
 
 // Two-phase schedule for row counts between whole rounds (visual layer3: 37 632 rows x 256 columns = 2.3 rounds of 128x128 tiles, 1.5 of
 // 192x128 ones -- every single tile shape pays for a mostly empty last round): whole rounds of a big tile over the first rows, then ONE
 // launch of the best tile for the rows that are left (24 576 rows as 256 tiles of 192x128 + 13 056 rows as 204 tiles of 128x128: 1.25 instead
 // of 1.5 tile-round units).  Each output row belongs to exactly one launch; statistics rows of the second launch follow the first's.
-static int g_two_phase = -1;                          // -1: $MLA_CONV_TWO_PHASE (default 1)
-extern "C" int mla_conv2d_two_phase(int on) {         // measurement / test hook: 0 = always one launch, 1 = default; other: query
-  if (on == 0 || on == 1) g_two_phase = on;
-  if (g_two_phase < 0) { const char* e = getenv("MLA_CONV_TWO_PHASE"); g_two_phase = (e && e[0] == '0') ? 0 : 1; }
-  return g_two_phase;
-}
+static EnvInt g_two_phase{"MLA_CONV_TWO_PHASE", 0, 1, 1};   // measurement / test hook: 0 = always one launch, 1 = default; other: query
+extern "C" int mla_conv2d_two_phase(int on) { return g_two_phase.hook(on); }
 static bool plan_two_phase(const IGemmGeom& g, int cfg1, int k_stages, int* cfgA, int* rowsA, int* cfgB) {
-  if (!mla_conv2d_two_phase(-1) || g_split_cfg >= 0 || g.CO % 128 != 0 || g.m0 != 0 || k_stages < 16) return false;
-  const double eff[SCFG_COUNT] = {SPLIT_EFF};
+  if (!g_two_phase.get() || g_split_cfg >= 0 || g.CO % 128 != 0 || g.m0 != 0 || k_stages < 16) return false;
   double best = 0.93 * scfg_cost(cfg1, g.M, g.CO);
   bool found = false;
   const int gridN = g.CO / 128;
   const int bigs[2] = {SCFG_256x128, SCFG_192x128};
   for (int k = 0; k < 2; ++k) {
     const int cA = bigs[k];
-    const long tiles = (long)cdiv(g.M, scfg_bm(cA)) * gridN;
+    const long tiles = (long)cdiv(g.M, SCFG[cA].bm) * gridN;
     const long full = tiles / mla_cu_count();                          // whole rounds of the CUs
     // whole ROW tiles that fit those rounds (wide outputs -- the transformer Linears' 6 / 18 / 24 column tiles -- leave up to
     // gridN - 1 workgroup slots of the last round empty)
     const long row_tiles = full * mla_cu_count() / gridN;
-    const long rA = row_tiles * scfg_bm(cA), rem = g.M - rA;
+    const long rA = row_tiles * SCFG[cA].bm, rem = g.M - rA;
     if (full < 1 || row_tiles < 1 || rem <= 0) continue;
-    const double costA = (double)full * scfg_bm(cA) * 128 / eff[cA];
-    int cB = -1;
+    const double costA = scfg_rounds_cost(cA, (double)full);                // (one 128-column workgroup per CU)
     double costB = 0;
-    for (int c = 0; c < SCFG_COUNT; ++c) {
-      if (g.CO % scfg_bn(c) != 0) continue;
-      const double cc = scfg_cost(c, rem, g.CO);
-      if (cB < 0 || cc < costB) { cB = c; costB = cc; }
-    }
+    const int cB = best_scfg(rem, g.CO, &costB);
     const double total = costA + costB + 0.03 * 256 * 128;
     if (total < best) { best = total; *cfgA = cA; *rowsA = (int)rA; *cfgB = cB; found = true; }
   }
@@ -683,7 +626,7 @@ static bool plan_two_phase(const IGemmGeom& g, int cfg1, int k_stages, int* cfgA
 
 static int launch_split_one(const float* X, const void* Wsp, float* Y, const float* R, const float* MASK, float* part,
                             const IGemmGeom& mg, int cfg, hipStream_t st, const float* BIAS, float* Y2) {
-  const int total = cdiv(mg.M - mg.m0, scfg_bm(cfg)) * (mg.CO / scfg_bn(cfg));
+  const int total = cdiv(mg.M - mg.m0, SCFG[cfg].bm) * (mg.CO / SCFG[cfg].bn);
   if (total <= 0) return MLA_OK;
   if (g_split_terms == 6) launch_split_t<6>(cfg, total, st, X, Wsp, Y, R, MASK, part, BIAS, Y2, mg);
   else if (g_split_terms == 8) launch_split_t<8>(cfg, total, st, X, Wsp, Y, R, MASK, part, BIAS, Y2, mg);
@@ -701,15 +644,15 @@ static int launch_split(const float* X, const void* Wsp, float* Y, const float* 
     IGemmGeom ga = mg;
     ga.M = rowsA;
     if (int rc = launch_split_one(X, Wsp, Y, R, MASK, part, ga, cfgA, st, BIAS, Y2)) return rc;
-    const int tilesA = rowsA / scfg_bm(cfgA);
+    const int tilesA = rowsA / SCFG[cfgA].bm;
     IGemmGeom gb = mg;
     gb.m0 = rowsA;
     gb.bn_tile0 = mg.bn_tile0 + tilesA;
     float* partB = part ? part + (size_t)tilesA * 2 * mg.CO * 2 : nullptr;       // fp64 rows [tile][2][CO]
-    if (row_tiles) *row_tiles = tilesA + cdiv(mg.M - rowsA, scfg_bm(cfgB));
+    if (row_tiles) *row_tiles = tilesA + cdiv(mg.M - rowsA, SCFG[cfgB].bm);
     return launch_split_one(X, Wsp, Y, R, MASK, partB, gb, cfgB, st, BIAS, Y2);
   }
-  if (row_tiles) *row_tiles = cdiv(mg.M, scfg_bm(cfg));
+  if (row_tiles) *row_tiles = cdiv(mg.M, SCFG[cfg].bm);
   return launch_split_one(X, Wsp, Y, R, MASK, part, mg, cfg, st, BIAS, Y2);
 }
 
@@ -735,18 +678,8 @@ extern "C" int mla_conv2d_wsplit_batch(const float* params, void* wsplit, const 
   return MLA_OK;
 }
 
-static int g_dgrad_merge = -1;                        // -1: $MLA_DGRAD_MERGE (default 1)
-static bool dgrad_merge_on() {
-  if (g_dgrad_merge < 0) {
-    const char* e = getenv("MLA_DGRAD_MERGE");
-    g_dgrad_merge = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_dgrad_merge != 0;
-}
-extern "C" int mla_conv2d_dgrad_merge(int on) {       // measurement / test hook: 0 = one launch per parity class, 1 = default; other: query
-  if (on == 0 || on == 1) g_dgrad_merge = on;
-  return dgrad_merge_on() ? 1 : 0;
-}
+static EnvInt g_dgrad_merge{"MLA_DGRAD_MERGE", 0, 1, 1};   // measurement / test hook: 0 = one launch per parity class, 1 = default; other: query
+extern "C" int mla_conv2d_dgrad_merge(int on) { return g_dgrad_merge.hook(on); }
 
 extern "C" int mla_conv2d_fwd_split(const float* x, const void* wsplit_t, float* y, int N, int H, int W, int Cin, int Cout,
                                     int KH, int KW, int stride, int pad, float* bn_partial, int* bn_tiles, void* stream) {
@@ -757,7 +690,7 @@ extern "C" int mla_conv2d_fwd_split(const float* x, const void* wsplit_t, float*
   make_fwd_geom(g, N, H, W, Cin, Cout, KH, KW, stride, pad);
   MLA_REQUIRE(g.OH > 0 && g.OW > 0, "mla_conv2d_fwd_split: empty output");
   if (use_patch(g)) return mla_patch_launch(x, wsplit_t, y, nullptr, nullptr, bn_partial, g, bn_tiles, (hipStream_t)stream);
-  const int cfg = pick_scfg(g.M, Cout, 1, KH * KW * Cin);
+  const int cfg = pick_scfg(g.M, Cout, KH * KW * Cin);
   return launch_split(x, wsplit_t, y, nullptr, nullptr, bn_partial, g, cfg, (hipStream_t)stream, nullptr, nullptr, bn_tiles);
 }
 
@@ -767,7 +700,7 @@ extern "C" int mla_conv2d_fwd_split(const float* x, const void* wsplit_t, float*
 // the materialised path), so the activation tensor is never written (154 MB per block at batch 64) nor read.
 extern "C" int mla_conv2d_bnfold_supported(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
   if (!(Cin == 64 && Cout == 64 && KH == 3 && KW == 3 && stride == 1 && pad == 1) || N <= 0 || H <= 0 || W <= 0) return 0;
-  if (g_split_terms != 6 || g_split_cfg >= 0 || !patch_mode() || !g_wgrad_tr) return 0;
+  if (g_split_terms != 6 || g_split_cfg >= 0 || !g_patch.get() || !g_wgrad_tr) return 0;
   IGemmGeom g;
   make_fwd_geom(g, N, H, W, Cin, Cout, KH, KW, stride, pad);
   // only where the persistent patch kernel is what the unfolded convolution would run on anyway (its grid fills the chip, or it is forced):
@@ -825,7 +758,7 @@ extern "C" int mla_conv2d_dgrad_split_classes(const float* dy, const void* wspli
   MLA_REQUIRE(Cin % 64 == 0, "mla_conv2d_dgrad_split: Cin=%d must be a multiple of 64 (the stem needs no dgrad)", Cin);
   MLA_REQUIRE(dy && wsplit && dx, "mla_conv2d_dgrad_split: null pointer");
   int tiles = 0;
-  if (stride == 2 && dgrad_merge_on() && g_split_terms == 6 && g_split_cfg < 0) {
+  if (stride == 2 && g_dgrad_merge.get() && g_split_terms == 6 && g_split_cfg < 0) {
     // all requested parity classes in one launch, longest K first
     IGemmClasses cs;
     cs.n = 0;
@@ -841,8 +774,8 @@ extern "C" int mla_conv2d_dgrad_split_classes(const float* dy, const void* wspli
     }
     if (nord >= 2) {
       const IGemmGeom& big = gc[order[0]];
-      const int cfg = pick_scfg(big.M, Cin, big.T > 0 ? big.T : 1, KH * KW == 1 ? Cout : 1 << 30);
-      const int bm = scfg_bm(cfg), bn = scfg_bn(cfg);
+      const int cfg = pick_scfg(big.M, Cin, KH * KW == 1 ? Cout : 1 << 30);
+      const int bm = SCFG[cfg].bm, bn = SCFG[cfg].bn;
       cs.first[0] = 0;
       for (int k = 0; k < nord; ++k) {
         const int cls = order[k];
@@ -856,12 +789,10 @@ extern "C" int mla_conv2d_dgrad_split_classes(const float* dy, const void* wspli
       cs.n = nord;
       const int grid = cs.first[nord];
       hipStream_t st = (hipStream_t)stream;
-      if (cfg == SCFG_256x128) igemm_split_classes_kernel<256, 128, 4, 2, 32, 1><<<grid, 512, 0, st>>>(dy, wsplit, dx, relu_src, cs);
-      else if (cfg == SCFG_128x128) igemm_split_classes_kernel<128, 128, 2, 4, 32, 1><<<grid, 512, 0, st>>>(dy, wsplit, dx, relu_src, cs);
-      else if (cfg == SCFG_256x64) igemm_split_classes_kernel<256, 64, 4, 2, 16, 4><<<grid, 512, 0, st>>>(dy, wsplit, dx, relu_src, cs);
-      else if (cfg == SCFG_192x128) igemm_split_classes_kernel<192, 128, 2, 4, 32, 1><<<grid, 512, 0, st>>>(dy, wsplit, dx, relu_src, cs);
-      else if (cfg == SCFG_128x64) igemm_split_classes_kernel<128, 64, 2, 2, 32, 1><<<grid, 256, 0, st>>>(dy, wsplit, dx, relu_src, cs);
-      else igemm_split_classes_kernel<64, 64, 2, 2, 32, 1><<<grid, 256, 0, st>>>(dy, wsplit, dx, relu_src, cs);
+      with_scfg(cfg, [&](auto c) {
+        constexpr SplitTile t = SCFG[decltype(c)::value];
+        igemm_split_classes_kernel<t.bm, t.bn, t.wm, t.wn, t.bks, t.wpe><<<grid, t.threads(), 0, st>>>(dy, wsplit, dx, relu_src, cs);
+      });
       MLA_CHECK_LAUNCH("igemm_split_classes_kernel");
       if (bn_tiles) *bn_tiles = tiles;
       return MLA_OK;
@@ -882,7 +813,7 @@ extern "C" int mla_conv2d_dgrad_split_classes(const float* dy, const void* wspli
         tiles += ptiles;
         continue;
       }
-      const int cfg = pick_scfg(g.M, Cin, g.T > 0 ? g.T : 1, KH * KW == 1 ? Cout : 1 << 30);
+      const int cfg = pick_scfg(g.M, Cin, KH * KW == 1 ? Cout : 1 << 30);
       int rt = 0;
       if (int rc = launch_split(dy, wsplit, dx, res, relu_src, nullptr, g, cfg, (hipStream_t)stream, nullptr, nullptr, &rt)) return rc;
       tiles += rt;
@@ -989,7 +920,7 @@ extern "C" int mla_linear_fwd_split(const float* x, const void* wsplit_t, const 
   MLA_REQUIRE(x && wsplit_t && y, "mla_linear_fwd_split: null pointer");
   IGemmGeom g;
   if (int rc = linear_geom("mla_linear_fwd_split", g, groups, rows, x_group_rows, x_off, y_group_rows, y_off, K, N)) return rc;
-  return launch_split(x, wsplit_t, y, residual, nullptr, nullptr, g, pick_scfg(g.M, N, 1), (hipStream_t)stream, bias, y_gelu);
+  return launch_split(x, wsplit_t, y, residual, nullptr, nullptr, g, pick_scfg(g.M, N), (hipStream_t)stream, bias, y_gelu);
 }
 
 extern "C" int mla_linear_dgrad_split(const float* dy, const void* wsplit, float* dx, const float* residual,
@@ -999,7 +930,7 @@ extern "C" int mla_linear_dgrad_split(const float* dy, const void* wsplit, float
   IGemmGeom g;   // GEMM: [M][N] x [N][K] -> [M][K]
   if (int rc = linear_geom("mla_linear_dgrad_split", g, groups, rows, dy_group_rows, dy_off, dx_group_rows, dx_off, N, K)) return rc;
   g.epi = 1;
-  return launch_split(dy, wsplit, dx, residual, gelu_src, nullptr, g, pick_scfg(g.M, K, 1), (hipStream_t)stream);
+  return launch_split(dy, wsplit, dx, residual, gelu_src, nullptr, g, pick_scfg(g.M, K), (hipStream_t)stream);
 }
 
 // wgrad_tr_split.hip: Linear weight gradient on transposing LDS reads (192 x 192 tiles; dense rows, K and N multiples of 192)

@@ -17,7 +17,6 @@
 // Geometry, tap tables (forward: (kh - 1, kw - 1); input gradient: (1 - kh, 1 - kw) on the transposed weights) and the whole
 // epilogue (BatchNorm statistics, residual, ReLU mask, fused BatchNorm-backward reductions) are those of igemm_split_kernel.
 #include "split_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -145,14 +144,14 @@ __global__ __launch_bounds__(512, 2) void patch_split_kernel(const float* __rest
     for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * 128 * 16) = breg[pl];
   };
 
-  struct Frags { bf16x8_t a[3][MI], b[3][NI]; };
+  typedef SplitFrags<MI, NI> Frags;
   auto load_frags = [&](int slot, int tt, int ppv[MI], int kk, Frags& f) {
-    const unsigned* Br = Bs + slot * BSLOT + tt * BN * 16 + b_rd + (((kk * 2 + h) ^ swz) << 2);
+    const unsigned* Br = Bs + slot * BSLOT + tt * BN * 16 + b_rd + frag_koff(kk, h, swz);
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) {
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
-        const unsigned* Ar = P + pl * PT_PPL + ppv[mi] * 16 + (((kk * 2 + h) ^ ((ppv[mi] >> 2) & 3)) << 2);
+        const unsigned* Ar = P + pl * PT_PPL + ppv[mi] * 16 + frag_koff(kk, h, (ppv[mi] >> 2) & 3);
         f.a[pl][mi] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(Ar));
       }
 #pragma unroll
@@ -160,15 +159,7 @@ __global__ __launch_bounds__(512, 2) void patch_split_kernel(const float* __rest
         f.b[pl][ni] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(Br + (pl * 128 + ni * 32) * 16));
     }
   };
-  auto mma_frags = [&](const Frags& f) {
-#pragma unroll
-    for (int term = 0; term < 6; ++term)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[TERM_A[term]][mi], f.b[TERM_B[term]][ni], acc[mi][ni], 0, 0, 0);
-  };
+  auto mma_frags = [&](const Frags& f) { split_mma<6>(f.a, f.b, acc); };
 
   const int NC = gC / 32;                        // channel chunks
   constexpr int SPC = (9 + TPS - 1) / TPS;       // K stages per chunk
@@ -337,17 +328,17 @@ __global__ __launch_bounds__(512) void patch64p_kernel(const float* __restrict__
   };
   const int swz = (i >> 2) & 3;
   const int b_rd = (wn * 32 + i) * 16;
-  struct Frags { bf16x8_t a[3][MI], b[3]; };
+  typedef SplitFrags<MI, 1> Frags;
   auto load_frags = [&](int slot, int tt, const int (&ppv)[MI], int kk, Frags& f) {
-    const unsigned* Br = Bs + slot * BSLOT + tt * BN * 16 + b_rd + (((kk * 2 + h) ^ swz) << 2);
+    const unsigned* Br = Bs + slot * BSLOT + tt * BN * 16 + b_rd + frag_koff(kk, h, swz);
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) {
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
-        const unsigned* Ar = P + pl * PT_PPL + ppv[mi] * 16 + (((kk * 2 + h) ^ ((ppv[mi] >> 2) & 3)) << 2);
+        const unsigned* Ar = P + pl * PT_PPL + ppv[mi] * 16 + frag_koff(kk, h, (ppv[mi] >> 2) & 3);
         f.a[pl][mi] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(Ar));
       }
-      f.b[pl] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(Br + pl * 128 * 16));
+      f.b[pl][0] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(Br + pl * 128 * 16));
     }
   };
 
@@ -422,11 +413,11 @@ __global__ __launch_bounds__(512) void patch64p_kernel(const float* __restrict__
       pb[mi] = (gr - r0 + 1) * prow + ox + 1;
       pv[mi] = m < g.M ? (4 | (oy >= 1 ? 1 : 0) | (oy + 1 < gH ? 2 : 0)) : 0;
     }
-    f32x16 acc[MI];
+    f32x16 acc[MI][1];
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) acc[mi][e] = 0.f;
+      for (int e = 0; e < 16; ++e) acc[mi][0][e] = 0.f;
 #pragma unroll
     for (int k = 0; k < NSTG; ++k) {
       const int c = k / SPC, st = k - c * SPC, cur = k & 1;
@@ -451,18 +442,10 @@ __global__ __launch_bounds__(512) void patch64p_kernel(const float* __restrict__
 #pragma unroll
           for (int mi = 0; mi < MI; ++mi) ppv[mi] = (pv[mi] & need) == need ? pb[mi] + toff : PT_ZP;
           load_frags(cur, tt, ppv, 0, f0);
-#pragma unroll
-          for (int term = 0; term < 6; ++term)
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-              acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f0.a[TERM_A[term]][mi], f0.b[TERM_B[term]], acc[mi], 0, 0, 0);
+          split_mma<6>(f0.a, f0.b, acc);
           if (tt == 0) b_store(cur ^ 1);                          // that slot's readers passed the previous barrier
           load_frags(cur, tt, ppv, 1, f0);
-#pragma unroll
-          for (int term = 0; term < 6; ++term)
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-              acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f0.a[TERM_A[term]][mi], f0.b[TERM_B[term]], acc[mi], 0, 0, 0);
+          split_mma<6>(f0.a, f0.b, acc);
         }
       }
       if (st == SPC - 1) {                       // chunk boundary: every wave is done with this patch
@@ -472,7 +455,7 @@ __global__ __launch_bounds__(512) void patch64p_kernel(const float* __restrict__
       __syncthreads();
     }
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi) prev[mi] = acc[mi];
+    for (int mi = 0; mi < MI; ++mi) prev[mi] = acc[mi][0];
     prev_off = ((unsigned)(m0 + wm * 64 + 4 * h) * 64u + (unsigned)col) * 4u;
   }
   // ---- the last tile's epilogue, then the launch-long statistics: reduce over the row halves (h) and the four row waves
@@ -539,26 +522,16 @@ bool mla_patch_supported(const IGemmGeom& g, bool force) {
   const int BN = g.CO % 128 == 0 ? 128 : 64;
   const long wgs = (long)cdiv(g.M, PT_BM) * (g.CO / BN);
   const long cus = mla_cu_count(), rounds = (wgs + cus - 1) / cus;
-  static int min_fill = -1;                                                  // percent of the slots of its rounds that must be used
-  if (min_fill < 0) {
-    const char* e = getenv("MLA_PATCH_MIN_FILL");
-    min_fill = e ? atoi(e) : 75;
-  }
-  return wgs * 100 >= rounds * cus * min_fill;
+  // percent of the slots of its rounds that must be used; the clamp changes no answer: <= 0 always passes, > 100 never does
+  static EnvInt min_fill{"MLA_PATCH_MIN_FILL", 0, 101, 75, true};
+  return wgs * 100 >= rounds * cus * min_fill.get();
 }
 
-static int g_patch_persistent = -1;       // -1: $MLA_PATCH_PERSISTENT (default 1)
-static bool patch_persistent_on() {
-  if (g_patch_persistent < 0) {
-    const char* e = getenv("MLA_PATCH_PERSISTENT");
-    g_patch_persistent = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_patch_persistent != 0;
-}
+static EnvInt g_patch_persistent{"MLA_PATCH_PERSISTENT", 0, 1, 1};
 
 // does the persistent 64 -> 64 kernel (and with it the folded-BatchNorm variants) serve this geometry?
 bool mla_patch64p_usable(const IGemmGeom& g) {
-  return g.C == 64 && g.CO == 64 && patch_persistent_on() && (long)g.M * 64 * 4 < 0xFFFFFFF0L && cdiv(g.M, PT_BM) >= 2 &&
+  return g.C == 64 && g.CO == 64 && g_patch_persistent.get() && (long)g.M * 64 * 4 < 0xFFFFFFF0L && cdiv(g.M, PT_BM) >= 2 &&
          mla_patch_supported(g, true);
 }
 
@@ -571,7 +544,7 @@ int mla_patch_launch(const float* X, const void* Wsp, float* Y, const float* R, 
   const int nreq = g.bn_x[0] ? (g.bn_x[1] ? 2 : 1) : 0;
   // layer1 (64 -> 64): the persistent kernel with the epilogue riding in the next tile's MFMA stages, for the operand
   // combinations the training step uses (everything else: the one-tile-per-workgroup kernel below)
-  if (g.C == 64 && g.CO == 64 && patch_persistent_on() && (long)g.M * 64 * 4 < 0xFFFFFFF0L && tiles >= 2) {
+  if (g.C == 64 && g.CO == 64 && g_patch_persistent.get() && (long)g.M * 64 * 4 < 0xFFFFFFF0L && tiles >= 2) {
     const int grid = tiles < mla_cu_count() ? tiles : mla_cu_count();
     double* pd = reinterpret_cast<double*>(part);
     bool done = true;

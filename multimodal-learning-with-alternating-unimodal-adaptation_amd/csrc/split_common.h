@@ -1,4 +1,5 @@
-// Pieces shared by the split-bf16 kernels (conv_igemm_split.hip, stem_split.hip): fp32 -> three bf16 terms, product set.
+// Pieces shared by the split-bf16 kernels (conv_igemm_split.hip, conv_patch_split.hip, wgrad_tr_split.hip, stem_split.hip):
+// fp32 -> three bf16 terms, the product set, and the MFMA / LDS idioms every one of those kernels is built from.
 #pragma once
 #include "igemm_common.h"
 
@@ -53,3 +54,69 @@ __device__ __forceinline__ u32x4 buf_load4u(rsrc_t r, unsigned voff, unsigned so
 __device__ constexpr int TERM_A[8] = {0, 0, 1, 1, 0, 2, 1, 2};
 __device__ constexpr int TERM_B[8] = {0, 1, 0, 1, 2, 0, 2, 1};
 
+__device__ __forceinline__ bf16x8_t as_bf16x8(bf16x8_t v) { return v; }
+__device__ __forceinline__ bf16x8_t as_bf16x8(u32x4 v) { return __builtin_bit_cast(bf16x8_t, v); }
+
+// Helpers for the idioms the split kernels share.  A kernel adopts one only where its generated code stays the same instruction for
+// instruction; the sites that keep a sequence written out (the accumulator clears of the gather-GEMM and patch kernels, the staging
+// stores of the patch and transposing-read kernels, the MFMA groups on wgrad_tr_split.hip's dword-granular frag() and on the stem
+// forward's masked u32x4 fragments) are the ones whose register allocation or schedule moved when routed through here.
+__device__ __forceinline__ void zero_acc(f32x16& acc) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+}
+template <typename T, int N>
+__device__ __forceinline__ void zero_acc(T (&acc)[N]) {   // f32x16[N], f32x16[MI][NI]
+#pragma unroll
+  for (int n = 0; n < N; ++n) zero_acc(acc[n]);
+}
+
+// The product group of one 16-deep k-chunk: acc += sum over the first TERMS products of a[TERM_A] * b[TERM_B], planes as
+// bf16x8_t or as the u32x4 they were read as.  Product order, then mi, then ni: the summation order the bit-exact tests fix.
+template <int TERMS, typename AT, typename BT>
+__device__ __forceinline__ void split_mma(const AT (&a)[3], const BT (&b)[3], f32x16& acc) {
+#pragma unroll
+  for (int term = 0; term < TERMS; ++term)
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a[TERM_A[term]]), as_bf16x8(b[TERM_B[term]]), acc, 0, 0, 0);
+}
+template <int TERMS, int MI, int NI, typename AT, typename BT>
+__device__ __forceinline__ void split_mma(const AT (&a)[3][MI], const BT (&b)[3][NI], f32x16 (&acc)[MI][NI]) {
+#pragma unroll
+  for (int term = 0; term < TERMS; ++term)
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni)
+        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a[TERM_A[term]][mi]), as_bf16x8(b[TERM_B[term]][ni]), acc[mi][ni], 0, 0, 0);
+}
+
+// Four consecutive k of one row -> 8 B in each of the three bf16 planes (`plane` dwords apart)
+__device__ __forceinline__ void split_store4(unsigned* dst, int plane, f32x4 v) {
+  unsigned h0, m0, l0, h1, m1, l1;
+  split_pair<true>(v[0], v[1], h0, m0, l0);
+  split_pair<true>(v[2], v[3], h1, m1, l1);
+  *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
+  *reinterpret_cast<u32x2*>(dst + plane) = u32x2{m0, m1};
+  *reinterpret_cast<u32x2*>(dst + 2 * plane) = u32x2{l0, l1};
+}
+
+// MFMA operand fragments out of an LDS plane image [rows][LR dwords] (one ds_read_b128 each).  Lane (i, h) holds
+// k = kk * 16 + 8 h .. + 7 of row / column i; frag_koff is that chunk's dword offset in a row whose swizzle key is swz.
+template <int MI, int NI>
+struct SplitFrags { bf16x8_t a[3][MI], b[3][NI]; };
+__device__ __forceinline__ bf16x8_t lds_frag(const unsigned* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(p)); }
+__device__ __forceinline__ int frag_koff(int kk, int h, int swz) { return ((kk * 2 + h) ^ swz) << 2; }
+// Ar / Br: this lane's chunk in plane 0, block 0 of images with BM / BN rows per plane
+template <int BM, int BN, int LR, int MI, int NI>
+__device__ __forceinline__ void load_split_frags(const unsigned* Ar, const unsigned* Br, SplitFrags<MI, NI>& f) {
+#pragma unroll
+  for (int pl = 0; pl < 3; ++pl) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) f.a[pl][mi] = lds_frag(Ar + (pl * BM + mi * 32) * LR);
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) f.b[pl][ni] = lds_frag(Br + (pl * BN + ni * 32) * LR);
+  }
+}
+
+// The MFMA C / D layout: accumulator element e of lane (i, h) is column i, row acc_row(e) + 4 h of its 32 x 32 block
+__device__ __forceinline__ constexpr int acc_row(int e) { return (e & 3) + 8 * (e >> 2); }

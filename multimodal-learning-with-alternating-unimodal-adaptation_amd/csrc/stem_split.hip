@@ -155,7 +155,7 @@ __global__ __launch_bounds__(64 * WAVES, (CIN == 3 && WAVES == 4) ? 1 : 2) void 
 #pragma unroll
     for (int e4 = 0; e4 < 4; ++e4) {
       const int e = 4 * eq + e4;
-      const int row = e4 + 8 * eq + 4 * h;                  // = (e & 3) + 8 * (e >> 2) + 4 h
+      const int row = e4 + 8 * eq + 4 * h;                  // = acc_row(e) + 4 h
       const int oy = poy0 + 2 * (MI * wave + mi) + (row >> 4), ox = pox0 + (row & 15);
       int ok;
       if constexpr (RAGGED) ok = (int)(oy < g.OH) & (int)(ox < g.OW);
@@ -211,12 +211,7 @@ __global__ __launch_bounds__(64 * WAVES, (CIN == 3 && WAVES == 4) ? 1 : 2) void 
   // idle for a third of the tile time), so does the LDS store of the prefetched strip; `prev` holds the finished accumulators
   // meanwhile.  The first pass drains an all-zero `prev` whose pixels are all out of range.
   f32x16 prev[MI][2];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) prev[mi][ni][e] = 0.f;
+  zero_acc(prev);
   int pn = 0, poy0 = 1 << 28, pox0 = 0;
   constexpr int NPC = 4 * MI;                                                   // epilogue pieces per tile
   constexpr int NEB = NCH >= NPC + NPART ? NCH - NPART : (NCH < NPC ? NCH : NPC);   // MFMA blocks that carry epilogue pieces
@@ -471,10 +466,7 @@ __global__ __launch_bounds__(512, 2) void stem_wgrad_split_kernel(const float* _
   }
 
   f32x16 acc[KB];
-#pragma unroll
-  for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[kb][e] = 0.f;
+  zero_acc(acc);
 
   // ---- software pipeline.  The work of a tile is a flat sequence of U = 4 * KB units (step s, k block kb), 6 MFMAs each.
   // In the block of unit u the wave issues the LDS reads of unit u + 1's A fragments (other register set), splits -- in the
@@ -555,10 +547,7 @@ __global__ __launch_bounds__(512, 2) void stem_wgrad_split_kernel(const float* _
       // the next tile's strip (loads issued at the top of this tile): one slot per block; unconditional -- without a next tile
       // the registers are stale and the buffer is never read (a branch would end the scheduling region)
       if (u >= ST0) stage_store(cur ^ 1, u - ST0);
-#pragma unroll
-      for (int term = 0; term < 6; ++term)
-        acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, acur.p[TERM_A[term]]),
-                                                          __builtin_bit_cast(bf16x8_t, bcur.p[TERM_B[term]]), acc[kb], 0, 0, 0);
+      split_mma<6>(acur.p, bcur.p, acc[kb]);
       if (kb == 1) load_dy_step(t, tn, s_ + 3, dyv[(s_ + 1) & 1]);
       __builtin_amdgcn_sched_group_barrier(0x100, 16, 0);          // LDS reads of unit u + 1 first
 #pragma unroll
@@ -579,7 +568,7 @@ __global__ __launch_bounds__(512, 2) void stem_wgrad_split_kernel(const float* _
       for (int kb = 0; kb < KB; ++kb) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int row = kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+          const int row = kb * 32 + acc_row(e) + 4 * h;
           const int o = row * 64 + ni * 32 + i;
           const float v = w == 0 ? acc[kb][e] : R[o] + acc[kb][e];
           if (w == 3) {

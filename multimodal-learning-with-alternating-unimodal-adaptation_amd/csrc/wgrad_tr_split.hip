@@ -400,7 +400,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_flat_tr_kernel(const float* __re
 #pragma unroll
     for (int t9 = 0; t9 < 9; ++t9)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) R[rl + (t9 * 64 + (e & 3) + 8 * (e >> 2)) * 64] = acc[t9][e];
+      for (int e = 0; e < 16; ++e) R[rl + (t9 * 64 + acc_row(e)) * 64] = acc[t9][e];
   }
   __syncthreads();
   if (sg == 1) {
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_flat_tr_kernel(const float* __re
     for (int t9 = 0; t9 < 9; ++t9)
 #pragma unroll
       for (int e = 0; e < 16; ++e)
-        out[t9 * tap_stride + (unsigned)((e & 3) + 8 * (e >> 2)) * (unsigned)g.Cout] = R[rl + (t9 * 64 + (e & 3) + 8 * (e >> 2)) * 64] + acc[t9][e];
+        out[t9 * tap_stride + (unsigned)acc_row(e) * (unsigned)g.Cout] = R[rl + (t9 * 64 + acc_row(e)) * 64] + acc[t9][e];
   }
 }
 
@@ -562,7 +562,7 @@ __global__ __launch_bounds__(512, 1) void linear_wgrad_tr_kernel(const float* __
 #pragma unroll
     for (int t9 = 0; t9 < 9; ++t9)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) R[rl + ((t9 / 3) * 32 + (e & 3) + 8 * (e >> 2)) * 192 + (t9 % 3) * 32] = acc[t9][e];
+      for (int e = 0; e < 16; ++e) R[rl + ((t9 / 3) * 32 + acc_row(e)) * 192 + (t9 % 3) * 32] = acc[t9][e];
   }
   __syncthreads();
   if (sg == 1) {
@@ -571,7 +571,7 @@ __global__ __launch_bounds__(512, 1) void linear_wgrad_tr_kernel(const float* __
     for (int t9 = 0; t9 < 9; ++t9)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int r = (t9 / 3) * 32 + (e & 3) + 8 * (e >> 2), c = (t9 % 3) * 32;
+        const int r = (t9 / 3) * 32 + acc_row(e), c = (t9 % 3) * 32;
         out[(unsigned)r * (unsigned)g.N + c] = R[rl + r * 192 + c] + acc[t9][e];
       }
   }
