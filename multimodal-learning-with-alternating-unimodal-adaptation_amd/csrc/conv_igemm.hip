@@ -491,22 +491,15 @@ extern "C" int mla_conv2d_dgrad_classes(const float* dy, const float* w, float* 
   // output parity class, each with its own tile choice (measured: 25 % faster than all classes merged in one
   // launch with interleaved workgroups, 1.56 vs 2.09 ms over the six stride-2 convs).
   int tiles = 0;   // row tiles launched so far = first tile index of the next parity class in the BatchNorm partial buffers
-  for (int py = 0; py < stride; ++py)
-    for (int px = 0; px < stride; ++px) {
-      const int cls = py * stride + px;               // output parity class (py, px): bit of class_mask / residual_mask
-      if (!((class_mask >> cls) & 1)) continue;
-      const float* res = ((residual_mask >> cls) & 1) ? residual : nullptr;
-      IGemmGeom g;
-      make_dgrad_geom(g, py, px, N, H, W, Cin, Cout, KH, KW, stride, pad);
-      const int T = g.T;
-      if (g.M <= 0) continue;
-      const long Mc = g.M;
-      const int wt = T > 0 ? T : 1;
-      const int cfg = pick_cfg(&Mc, &wt, 1, Cin, false);
-      if (int rc = attach_bn_reqs("mla_conv2d_dgrad_bn", g, reqs, nreq, tiles)) return rc;
-      if (int rc = launch_igemm(dy, wt_ws, dx, res, relu_src, nullptr, g, false, cfg, st)) return rc;
-      tiles += cdiv(g.M, cfg_bm(cfg));
-    }
+  if (int rc = for_dgrad_classes("mla_conv2d_dgrad_bn", N, H, W, Cin, Cout, KH, KW, stride, pad, residual, class_mask, residual_mask, reqs,
+                                 nreq, tiles, [&](int, IGemmGeom& g, const float* res) {
+        const long Mc = g.M;
+        const int wt = g.T > 0 ? g.T : 1;
+        const int cfg = pick_cfg(&Mc, &wt, 1, Cin, false);
+        tiles += cdiv(g.M, cfg_bm(cfg));
+        return launch_igemm(dy, wt_ws, dx, res, relu_src, nullptr, g, false, cfg, st);
+      }))
+    return rc;
   if (bn_tiles) *bn_tiles = tiles;
   return MLA_OK;
 }
@@ -554,35 +547,22 @@ extern "C" int mla_conv2d_wgrad(const float* x, const float* dy, float* dw, int 
   if (int rc = check_conv("mla_conv2d_wgrad", N, H, W, Cin, Cout, KH, KW, stride, pad)) return rc;
   MLA_REQUIRE(x && dy && dw && ws, "mla_conv2d_wgrad: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  IGemmGeom g{};
-  g.N = N; g.H = H; g.W = W; g.C = Cin; g.CO = Cout;
-  g.OH = conv_out(H, KH, stride, pad); g.OW = conv_out(W, KW, stride, pad);
-  g.sy = g.sx = stride; g.T = KH * KW; g.M = N * g.OH * g.OW; g.K = g.T * Cin;
-  for (int kh = 0; kh < KH; ++kh)
-    for (int kw = 0; kw < KW; ++kw) g.tap[kh * KW + kw] = pack_tap(kh - pad, kw - pad, kh * KW + kw);
-  g.x_bytes = (unsigned)((size_t)N * H * W * Cin * 4);
+  IGemmGeom g;     // the forward geometry; of what it holds beyond N..K, tap and x_bytes, wgrad_kernel reads y_bytes only
+  make_fwd_geom(g, N, H, W, Cin, Cout, KH, KW, stride, pad);
   g.y_bytes = (unsigned)((size_t)g.M * Cout * 4);
-  int span, splits;
-  wgrad_plan(g.M, Cin, Cout, g.T, &span, &splits);
-  const size_t need = (size_t)splits * g.T * Cin * Cout * sizeof(float);
-  if (ws_bytes < need) {
-    mla_set_error("mla_conv2d_wgrad: workspace %zu < %zu bytes", ws_bytes, need);
-    return MLA_ERR_WORKSPACE;
-  }
-  float* part = (float*)ws;
-  const bool scalar = Cin % 64 != 0;
-  if (scalar) {
-    dim3 grid(cdiv(g.K, 64) * (Cout / 64), splits);
-    wgrad_kernel<64, 64, 2, 2, true><<<grid, 256, 0, st>>>(x, dy, part, g, span);
-  } else if (Cin % 128 == 0 && Cout % 128 == 0) {
-    dim3 grid((Cin / 128) * (Cout / 128) * g.T, splits);
-    wgrad_kernel<128, 128, 2, 2, false><<<grid, 256, 0, st>>>(x, dy, part, g, span);
-  } else {
-    dim3 grid((Cin / 64) * (Cout / 64) * g.T, splits);
-    wgrad_kernel<64, 64, 2, 2, false><<<grid, 256, 0, st>>>(x, dy, part, g, span);
-  }
-  MLA_CHECK_LAUNCH("wgrad_kernel");
-  return mla_wgrad_reduce(part, dw, (size_t)g.T * Cin * Cout / 4, splits, st);
+  return wgrad_slabs("mla_conv2d_wgrad", "wgrad_kernel", wgrad_plan, g.M, Cin, Cout, g.T, ws, ws_bytes, dw, nullptr, st,
+                     [&](float* part, float*, int span, int splits) {
+    if (Cin % 64 != 0) {
+      dim3 grid(cdiv(g.K, 64) * (Cout / 64), splits);
+      wgrad_kernel<64, 64, 2, 2, true><<<grid, 256, 0, st>>>(x, dy, part, g, span);
+    } else if (Cin % 128 == 0 && Cout % 128 == 0) {
+      dim3 grid((Cin / 128) * (Cout / 128) * g.T, splits);
+      wgrad_kernel<128, 128, 2, 2, false><<<grid, 256, 0, st>>>(x, dy, part, g, span);
+    } else {
+      dim3 grid((Cin / 64) * (Cout / 64) * g.T, splits);
+      wgrad_kernel<64, 64, 2, 2, false><<<grid, 256, 0, st>>>(x, dy, part, g, span);
+    }
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -633,20 +613,13 @@ extern "C" int mla_linear_wgrad(const float* x, const float* dy, float* dw_kn, i
   if (int rc = linear_geom("mla_linear_wgrad", g, groups, rows, x_group_rows, x_off, rows, 0, K, N)) return rc;
   g.y_bytes = (unsigned)((size_t)g.M * N * 4);
   hipStream_t st = (hipStream_t)stream;
-  int span, splits;
-  wgrad_plan(g.M, K, N, 1, &span, &splits);
-  const size_t need = (size_t)splits * K * N * sizeof(float);
-  if (ws_bytes < need) {
-    mla_set_error("mla_linear_wgrad: workspace %zu < %zu bytes", ws_bytes, need);
-    return MLA_ERR_WORKSPACE;
-  }
-  float* part = (float*)ws;
-  if (K % 128 == 0 && N % 128 == 0) {
-    wgrad_kernel<128, 128, 2, 2, false><<<dim3((K / 128) * (N / 128), splits), 256, 0, st>>>(x, dy, part, g, span);
-  } else {
-    wgrad_kernel<64, 64, 2, 2, false><<<dim3((K / 64) * (N / 64), splits), 256, 0, st>>>(x, dy, part, g, span);
-  }
-  MLA_CHECK_LAUNCH("wgrad_kernel");
-  return mla_wgrad_reduce(part, dw_kn, (size_t)K * N / 4, splits, st);
+  return wgrad_slabs("mla_linear_wgrad", "wgrad_kernel", wgrad_plan, g.M, K, N, 1, ws, ws_bytes, dw_kn, nullptr, st,
+                     [&](float* part, float*, int span, int splits) {
+    if (K % 128 == 0 && N % 128 == 0) {
+      wgrad_kernel<128, 128, 2, 2, false><<<dim3((K / 128) * (N / 128), splits), 256, 0, st>>>(x, dy, part, g, span);
+    } else {
+      wgrad_kernel<64, 64, 2, 2, false><<<dim3((K / 64) * (N / 64), splits), 256, 0, st>>>(x, dy, part, g, span);
+    }
+  });
 }
 

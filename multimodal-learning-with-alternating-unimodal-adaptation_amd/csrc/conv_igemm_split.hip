@@ -757,31 +757,35 @@ extern "C" int mla_conv2d_dgrad_split_classes(const float* dy, const void* wspli
   if (int rc = check_conv("mla_conv2d_dgrad_split", N, H, W, Cin, Cout, KH, KW, stride, pad)) return rc;
   MLA_REQUIRE(Cin % 64 == 0, "mla_conv2d_dgrad_split: Cin=%d must be a multiple of 64 (the stem needs no dgrad)", Cin);
   MLA_REQUIRE(dy && wsplit && dx, "mla_conv2d_dgrad_split: null pointer");
-  int tiles = 0;
+  int tiles = 0;   // row tiles launched so far = first tile index of the next parity class in the BatchNorm partial buffers
+  auto classes = [&](auto&& f) {
+    return for_dgrad_classes("mla_conv2d_dgrad_split_bn", N, H, W, Cin, Cout, KH, KW, stride, pad, residual, class_mask, residual_mask,
+                             reqs, nreq, tiles, f);
+  };
   if (stride == 2 && g_dgrad_merge.get() && g_split_terms == 6 && g_split_cfg < 0) {
     // all requested parity classes in one launch, longest K first
     IGemmClasses cs;
-    cs.n = 0;
     int order[4], nord = 0;
     IGemmGeom gc[4];
-    for (int cls = 0; cls < 4; ++cls) {
-      if (!((class_mask >> cls) & 1)) continue;
-      make_dgrad_geom(gc[cls], cls / 2, cls % 2, N, H, W, Cin, Cout, KH, KW, stride, pad);
-      if (gc[cls].M <= 0) continue;
-      int pos = nord++;
-      while (pos > 0 && gc[order[pos - 1]].T < gc[cls].T) { order[pos] = order[pos - 1]; --pos; }
-      order[pos] = cls;
-    }
+    const float* resc[4];
+    if (int rc = classes([&](int cls, IGemmGeom& g, const float* res) {
+          gc[cls] = g;
+          resc[cls] = res;
+          int pos = nord++;
+          while (pos > 0 && gc[order[pos - 1]].T < g.T) { order[pos] = order[pos - 1]; --pos; }
+          order[pos] = cls;
+          return MLA_OK;
+        }))
+      return rc;
     if (nord >= 2) {
       const IGemmGeom& big = gc[order[0]];
       const int cfg = pick_scfg(big.M, Cin, KH * KW == 1 ? Cout : 1 << 30);
       const int bm = SCFG[cfg].bm, bn = SCFG[cfg].bn;
       cs.first[0] = 0;
       for (int k = 0; k < nord; ++k) {
-        const int cls = order[k];
-        cs.g[k] = gc[cls];
-        if (int rc = attach_bn_reqs("mla_conv2d_dgrad_split_bn", cs.g[k], reqs, nreq, tiles)) return rc;
-        cs.R[k] = ((residual_mask >> cls) & 1) ? residual : nullptr;
+        cs.g[k] = gc[order[k]];
+        cs.g[k].bn_tile0 = tiles;                       // the partial rows follow the launch order, not the class order
+        cs.R[k] = resc[order[k]];
         const int tm = cdiv(cs.g[k].M, bm);
         cs.first[k + 1] = cs.first[k] + tm * (Cin / bn);
         tiles += tm;
@@ -798,26 +802,18 @@ extern "C" int mla_conv2d_dgrad_split_classes(const float* dy, const void* wspli
       return MLA_OK;
     }
   }
-  for (int py = 0; py < stride; ++py)
-    for (int px = 0; px < stride; ++px) {
-      const int cls = py * stride + px;               // output parity class (py, px): bit of class_mask / residual_mask
-      if (!((class_mask >> cls) & 1)) continue;
-      const float* res = ((residual_mask >> cls) & 1) ? residual : nullptr;
-      IGemmGeom g;
-      make_dgrad_geom(g, py, px, N, H, W, Cin, Cout, KH, KW, stride, pad);
-      if (g.M <= 0) continue;
-      if (int rc = attach_bn_reqs("mla_conv2d_dgrad_split_bn", g, reqs, nreq, tiles)) return rc;
-      if (use_patch(g)) {                               // stride 1: the one parity class is a 3x3 "same" convolution over dy
-        int ptiles = 0;
-        if (int rc = mla_patch_launch(dy, wsplit, dx, res, relu_src, nullptr, g, &ptiles, (hipStream_t)stream)) return rc;
-        tiles += ptiles;
-        continue;
-      }
-      const int cfg = pick_scfg(g.M, Cin, KH * KW == 1 ? Cout : 1 << 30);
-      int rt = 0;
-      if (int rc = launch_split(dy, wsplit, dx, res, relu_src, nullptr, g, cfg, (hipStream_t)stream, nullptr, nullptr, &rt)) return rc;
-      tiles += rt;
-    }
+  if (int rc = classes([&](int, IGemmGeom& g, const float* res) {
+        int rt = 0;
+        if (use_patch(g)) {                               // stride 1: the one parity class is a 3x3 "same" convolution over dy
+          if (int rc = mla_patch_launch(dy, wsplit, dx, res, relu_src, nullptr, g, &rt, (hipStream_t)stream)) return rc;
+        } else {
+          const int cfg = pick_scfg(g.M, Cin, KH * KW == 1 ? Cout : 1 << 30);
+          if (int rc = launch_split(dy, wsplit, dx, res, relu_src, nullptr, g, cfg, (hipStream_t)stream, nullptr, nullptr, &rt)) return rc;
+        }
+        tiles += rt;
+        return (int)MLA_OK;
+      }))
+    return rc;
   if (bn_tiles) *bn_tiles = tiles;
   return MLA_OK;
 }
@@ -868,8 +864,6 @@ extern "C" size_t mla_conv2d_wgrad_split_ws_bytes(int N, int H, int W, int Cin, 
   return b;
 }
 
-int mla_wgrad_reduce(const float* part, float* dw, size_t n4, int splits, hipStream_t st);   // conv_igemm.hip
-
 extern "C" int mla_conv2d_wgrad_split(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin, int Cout,
                                       int KH, int KW, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
   if (int rc = check_conv("mla_conv2d_wgrad_split", N, H, W, Cin, Cout, KH, KW, stride, pad)) return rc;
@@ -881,23 +875,16 @@ extern "C" int mla_conv2d_wgrad_split(const float* x, const float* dy, float* dw
   IGemmGeom g;
   make_fwd_geom(g, N, H, W, Cin, Cout, KH, KW, stride, pad);
   g.y_bytes = (unsigned)((size_t)g.M * Cout * 4);
-  int span, splits;
-  wgrad_split_plan(g.M, Cin, Cout, g.T, &span, &splits);
-  const size_t need = (size_t)splits * g.T * Cin * Cout * sizeof(float);
-  if (ws_bytes < need) {
-    mla_set_error("mla_conv2d_wgrad_split: workspace %zu < %zu bytes", ws_bytes, need);
-    return MLA_ERR_WORKSPACE;
-  }
-  float* part = (float*)ws;
-  if (Cin % 128 == 0 && Cout % 128 == 0) {
-    // 8 waves (64x32 wave tiles): two waves per SIMD with one workgroup per CU; same-box A/B against the 4-wave form (64x64 wave
-    // tiles, a third fewer fragment reads): -9 % time on the 128x128-tile layers (2x4 and 4x2 wave grids measure the same)
-    wgrad_split_kernel<128, 128, 2, 4><<<dim3((Cin / 128) * (Cout / 128) * g.T, splits), 512, 0, st>>>(x, dy, part, g, span);
-  } else {
-    wgrad_split_kernel<64, 64, 2, 2><<<dim3((Cin / 64) * (Cout / 64) * g.T, splits), 256, 0, st>>>(x, dy, part, g, span);
-  }
-  MLA_CHECK_LAUNCH("wgrad_split_kernel");
-  return mla_wgrad_reduce(part, dw, (size_t)g.T * Cin * Cout / 4, splits, st);
+  return wgrad_slabs("mla_conv2d_wgrad_split", "wgrad_split_kernel", wgrad_split_plan, g.M, Cin, Cout, g.T, ws, ws_bytes, dw, nullptr, st,
+                     [&](float* part, float*, int span, int splits) {
+    if (Cin % 128 == 0 && Cout % 128 == 0) {
+      // 8 waves (64x32 wave tiles): two waves per SIMD with one workgroup per CU; same-box A/B against the 4-wave form (64x64 wave
+      // tiles, a third fewer fragment reads): -9 % time on the 128x128-tile layers (2x4 and 4x2 wave grids measure the same)
+      wgrad_split_kernel<128, 128, 2, 4><<<dim3((Cin / 128) * (Cout / 128) * g.T, splits), 512, 0, st>>>(x, dy, part, g, span);
+    } else {
+      wgrad_split_kernel<64, 64, 2, 2><<<dim3((Cin / 64) * (Cout / 64) * g.T, splits), 256, 0, st>>>(x, dy, part, g, span);
+    }
+  });
 }
 
 extern "C" int mla_conv2d_wgrad_split_bnin(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin, int Cout, int KH, int KW,
@@ -963,21 +950,12 @@ extern "C" int mla_linear_wgrad_split_bias(const float* x, const float* dy, floa
   hipStream_t st = (hipStream_t)stream;
   if (g_wgrad_tr && (groups == 1 || (x_group_rows == rows && x_off == 0)) && x_off == 0 && mla_linear_wgrad_tr_supported(g.M, K, N))
     return mla_linear_wgrad_tr_launch(x, dy, dw_kn, dbias, g.M, K, N, ws, ws_bytes, st);     // dense token rows
-  int span, splits;
-  wgrad_split_plan(g.M, K, N, 1, &span, &splits);
-  const size_t need = (size_t)splits * K * N * sizeof(float) + (dbias ? (size_t)splits * N * sizeof(float) : 0);
-  if (ws_bytes < need) {
-    mla_set_error("mla_linear_wgrad_split: workspace %zu < %zu bytes", ws_bytes, need);
-    return MLA_ERR_WORKSPACE;
-  }
-  float* part = (float*)ws;
-  float* bias_part = dbias ? part + (size_t)splits * K * N : nullptr;
-  if (K % 128 == 0 && N % 128 == 0) {
-    wgrad_split_kernel<128, 128, 2, 4><<<dim3((K / 128) * (N / 128), splits), 512, 0, st>>>(x, dy, part, g, span, bias_part);
-  } else {
-    wgrad_split_kernel<64, 64, 2, 2><<<dim3((K / 64) * (N / 64), splits), 256, 0, st>>>(x, dy, part, g, span, bias_part);
-  }
-  MLA_CHECK_LAUNCH("wgrad_split_kernel");
-  if (int rc = mla_wgrad_reduce(part, dw_kn, (size_t)K * N / 4, splits, st)) return rc;
-  return dbias ? mla_wgrad_reduce(bias_part, dbias, (size_t)N / 4, splits, st) : MLA_OK;
+  return wgrad_slabs("mla_linear_wgrad_split", "wgrad_split_kernel", wgrad_split_plan, g.M, K, N, 1, ws, ws_bytes, dw_kn, dbias, st,
+                     [&](float* part, float* bias_part, int span, int splits) {
+    if (K % 128 == 0 && N % 128 == 0) {
+      wgrad_split_kernel<128, 128, 2, 4><<<dim3((K / 128) * (N / 128), splits), 512, 0, st>>>(x, dy, part, g, span, bias_part);
+    } else {
+      wgrad_split_kernel<64, 64, 2, 2><<<dim3((K / 64) * (N / 64), splits), 256, 0, st>>>(x, dy, part, g, span, bias_part);
+    }
+  });
 }

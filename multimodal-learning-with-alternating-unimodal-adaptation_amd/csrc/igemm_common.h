@@ -352,6 +352,48 @@ static inline int attach_bn_reqs(const char* who, IGemmGeom& g, const mla_bn_red
   return MLA_OK;
 }
 
+// The output parity classes (py, px) of an input gradient, in the bit order of class_mask (cls = py * stride + px); classes that are
+// masked out or have no rows are skipped.  f(cls, g, res) gets the class geometry with the BatchNorm requests attached at the running
+// tile offset `tiles` (row tiles launched so far = first tile of this class in the partial buffers; f advances it) and the class's
+// residual pointer, and returns a status.
+template <typename F>
+static inline int for_dgrad_classes(const char* who, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                    const float* residual, int class_mask, int residual_mask, const mla_bn_reduce_req* reqs, int nreq,
+                                    const int& tiles, F&& f) {
+  for (int cls = 0; cls < stride * stride; ++cls) {
+    if (!((class_mask >> cls) & 1)) continue;
+    IGemmGeom g;
+    make_dgrad_geom(g, cls / stride, cls % stride, N, H, W, Cin, Cout, KH, KW, stride, pad);
+    if (g.M <= 0) continue;
+    if (int rc = attach_bn_reqs(who, g, reqs, nreq, tiles)) return rc;
+    if (int rc = f(cls, g, ((residual_mask >> cls) & 1) ? residual : nullptr)) return rc;
+  }
+  return MLA_OK;
+}
+
+// Split-K weight gradient through partial slabs, shared by the conv and Linear entry points of both arithmetics: plan the pixel ranges,
+// check the workspace ([splits][T][Cin][Cout] floats, then [splits][Cout] bias rows when dbias is wanted), launch(part, bias_part, span,
+// splits) the kernel `kernel`, reduce the slabs in a fixed order.
+int mla_wgrad_reduce(const float* part, float* dw, size_t n4, int splits, hipStream_t st);   // conv_igemm.hip
+template <typename Plan, typename Launch>
+static inline int wgrad_slabs(const char* who, const char* kernel, Plan plan, long M, int Cin, int Cout, int T, void* ws, size_t ws_bytes,
+                              float* dw, float* dbias, hipStream_t st, Launch&& launch) {
+  int span, splits;
+  plan(M, Cin, Cout, T, &span, &splits);
+  const size_t slab = (size_t)T * Cin * Cout;
+  const size_t need = (size_t)splits * slab * sizeof(float) + (dbias ? (size_t)splits * Cout * sizeof(float) : 0);
+  if (ws_bytes < need) {
+    mla_set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    return MLA_ERR_WORKSPACE;
+  }
+  float* part = (float*)ws;
+  float* bias_part = dbias ? part + (size_t)splits * slab : nullptr;
+  launch(part, bias_part, span, splits);
+  MLA_CHECK_LAUNCH(kernel);
+  if (int rc = mla_wgrad_reduce(part, dw, slab / 4, splits, st)) return rc;
+  return dbias ? mla_wgrad_reduce(bias_part, dbias, (size_t)Cout / 4, splits, st) : MLA_OK;
+}
+
 // Linear layers as 1-tap gather-GEMMs over token rows (see the Linear entry points in conv_igemm.hip)
 static inline int linear_geom(const char* who, IGemmGeom& g, int groups, int rows, int in_group_rows, int in_off,
                        int out_group_rows, int out_off, int K, int N) {

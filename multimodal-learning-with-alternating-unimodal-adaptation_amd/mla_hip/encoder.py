@@ -272,55 +272,48 @@ class ResNet18Encoder(FlatEncoder):
         mean, invstd = ws["stats"][bn]
         return (mean, invstd, self.p[bn + ".weight"], self.p[bn + ".bias"])
 
+    def _conv_fwd(self, ws, st, x, name, stride, pad, y, partial=None, bn_in=None) -> int:
+        """y = conv `name`(x) on the kernel this layer runs on: the persistent split-arithmetic stem kernel (stem_split.hip), the split
+        kernels (over relu(bn_in(x)) with bn_in, BN_FOLD) or the fp32 MFMA.  partial: receives the BatchNorm column statistics; returns
+        its row tiles."""
+        w = self.p[name + ".weight"]
+        wsp = self.wsp.get(name)
+        if name == "conv1" and self.stem_split:
+            return ops.conv2d_stem_fwd_split(x, w, y=y, bn_partial=partial, stream=st)[1]
+        if bn_in is not None:
+            return ops.conv2d_fwd_split_bnin(x, wsp[0], w.shape, stride, pad, bn_in, y=y, bn_partial=partial, stream=st)[1]
+        if wsp is not None:
+            return ops.conv2d_fwd_split(x, wsp[0], w.shape, stride, pad, y=y, bn_partial=partial, stream=st)[1]
+        return ops.conv2d_fwd(x, w, stride, pad, y=y, bn_partial=partial, stream=st)[1]
+
     def _conv_bn(self, ws, st, x, conv_name, stride, pad, y, out, relu, residual=None, bn_in=None):
         """y = conv(x); BN statistics fused in the conv epilogue; out = [relu](bn(y) [+ residual]).  out = None: the consumers of the
         activation re-form it from y (BN_FOLD); bn_in: x is itself such a BatchNorm input and the convolution runs over relu(bn_in(x))."""
-        w = self.p[conv_name + ".weight"]
         bn = bn_name_for_conv(conv_name)
-        wsp = self.wsp.get(conv_name)
-        if not self.training:                                                  # eval: running statistics, nothing saved
-            if wsp is not None:
-                ops.conv2d_fwd_split(x, wsp[0], w.shape, stride, pad, y=y, stream=st)
-            else:
-                ops.conv2d_fwd(x, w, stride, pad, y=y, stream=st)
-            C = w.shape[3]
-            ops.bn_apply(y, self.rm[bn], self.rinv[bn], self.p[bn + ".weight"], self.p[bn + ".bias"], out, y.numel() // C, C,
-                         relu, residual=residual, stream=st)
-            return
-        if bn_in is not None:
-            _, tiles = ops.conv2d_fwd_split_bnin(x, wsp[0], w.shape, stride, pad, bn_in, y=y, bn_partial=ws["partial"], stream=st)
-        elif wsp is not None:
-            _, tiles = ops.conv2d_fwd_split(x, wsp[0], w.shape, stride, pad, y=y, bn_partial=ws["partial"], stream=st)
-        else:
-            _, tiles = ops.conv2d_fwd(x, w, stride, pad, y=y, bn_partial=ws["partial"], stream=st)
-        C = w.shape[3]
+        C = y.shape[3]
         M = y.numel() // C
+        if not self.training:                                                  # eval: running statistics, nothing saved
+            self._conv_fwd(ws, st, x, conv_name, stride, pad, y)
+            ops.bn_apply(y, self.rm[bn], self.rinv[bn], self.p[bn + ".weight"], self.p[bn + ".bias"], out, M, C, relu, residual=residual, stream=st)
+            return
+        tiles = self._conv_fwd(ws, st, x, conv_name, stride, pad, y, ws["partial"], bn_in)
         mean, invstd = ws["stats"][bn]
         ops.bn_finalize(ws["partial"], tiles, M, C, mean, invstd, self.rm[bn], self.rv[bn], stream=st)
         self.num_batches_tracked[bn] += 1
         if out is None:
             return
-        ops.bn_apply(y, mean, invstd, self.p[bn + ".weight"], self.p[bn + ".bias"], out, M, C, relu, residual=residual,
-                     stream=st)
+        ops.bn_apply(y, mean, invstd, self.p[bn + ".weight"], self.p[bn + ".bias"], out, M, C, relu, residual=residual, stream=st)
 
     def _stem(self, ws, st) -> None:
         """p0 = maxpool(relu(bn1(conv1(x0)))): BN + ReLU are applied inside the max-pool, the (N,112,112,64)-sized ReLU
         output is never written (backbone.py:149-152)."""
-        w = self.p["conv1.weight"]
         x, y = ws["x0"], ws["y_stem"]
         ga, be = self.p["bn1.weight"], self.p["bn1.bias"]
-        stem_split = self.stem_split          # persistent split-arithmetic patch-loader kernel (stem_split.hip); else the fp32 MFMA
         if not self.training:
-            if stem_split:
-                ops.conv2d_stem_fwd_split(x, w, y=y, stream=st)
-            else:
-                ops.conv2d_fwd(x, w, 2, 3, y=y, stream=st)
+            self._conv_fwd(ws, st, x, "conv1", 2, 3, y)
             ops.bn_relu_maxpool_fwd(y, self.rm["bn1"], self.rinv["bn1"], ga, be, ws["p0"], ws["pool_idx"], stream=st)
             return
-        if stem_split:
-            _, tiles = ops.conv2d_stem_fwd_split(x, w, y=y, bn_partial=ws["partial"], stream=st)
-        else:
-            _, tiles = ops.conv2d_fwd(x, w, 2, 3, y=y, bn_partial=ws["partial"], stream=st)
+        tiles = self._conv_fwd(ws, st, x, "conv1", 2, 3, y, ws["partial"])
         mean, invstd = ws["stats"]["bn1"]
         ops.bn_finalize(ws["partial"], tiles, y.numel() // 64, 64, mean, invstd, self.rm["bn1"], self.rv["bn1"], stream=st)
         self.num_batches_tracked["bn1"] += 1
@@ -441,34 +434,38 @@ class ResNet18Encoder(FlatEncoder):
         self._backward_trunk(ws, st)
 
     def _wgrad(self, ws, x, dy, name, stride, pad, bn_in=None) -> None:
-        """Weight gradient of conv `name`; on the side stream when one is attached (after dy has been produced).  bn_in: x is a BatchNorm
-        input and the operand is relu(bn_in(x)) (BN_FOLD)."""
-        side = self.wgrad_stream
-        wgrad = ops.conv2d_wgrad_split if name in self.wsp else ops.conv2d_wgrad
-        if name == "conv1" and self.stem_split:
-            wgrad = ops.conv2d_stem_wgrad_split
+        """Weight gradient of conv `name`, on the same choice of kernels as _conv_fwd; on the side stream when one is attached (after
+        dy has been produced).  bn_in: x is a BatchNorm input and the operand is relu(bn_in(x)) (BN_FOLD)."""
         if bn_in is not None:
-            def wgrad(x_, dy_, dw_, stride_, pad_, ws_):                      # noqa: F811
-                return ops.conv2d_wgrad_split_bnin(x_, dy_, dw_, stride_, pad_, ws_, bn_in)
+            wgrad = ops.conv2d_wgrad_split_bnin
+        elif name == "conv1" and self.stem_split:
+            wgrad = ops.conv2d_stem_wgrad_split
+        else:
+            wgrad = ops.conv2d_wgrad_split if name in self.wsp else ops.conv2d_wgrad
+        args = (x, dy, self.g[name + ".weight"], stride, pad, ws["wgrad_ws"]) + (() if bn_in is None else (bn_in,))
+        side = self.wgrad_stream
         if side is None:
-            wgrad(x, dy, self.g[name + ".weight"], stride, pad, ws["wgrad_ws"])
+            wgrad(*args)
             return
         ev = torch.cuda.Event()
         ev.record()                                   # dy is complete on the main stream at this point
         side.wait_event(ev)
         with torch.cuda.stream(side):
-            wgrad(x, dy, self.g[name + ".weight"], stride, pad, ws["wgrad_ws"])
+            wgrad(*args)
 
     def _dgrad(self, ws, st, dy, name, x_shape, stride, pad, dx, residual=None, relu_src=None, bn_next=(), class_mask=0xF,
-               residual_mask=0xF):
+               residual_mask=0xF, mask_gb=None):
         """Input gradient of conv `name`.  bn_next: [(bn name, its input y, partial buffer)] -- the BatchNorm layers whose
-        backward consumes dx: the epilogue forms their reduction pass; returns {bn name: (partial, tiles)}."""
+        backward consumes dx: the epilogue forms their reduction pass; returns {bn name: (partial, tiles)}.  mask_gb = (gamma, beta):
+        the ReLU mask is relu(bn(.)) > 0 of the one BatchNorm in bn_next, re-formed from its input (BN_FOLD)."""
         wsp = self.wsp.get(name)
         w = self.p[name + ".weight"]
         if not FUSE_BN_REDUCE:
             bn_next = ()
         reqs = [(y,) + tuple(ws["stats"][bn]) + (part,) for bn, y, part in bn_next]
-        if wsp is not None:
+        if mask_gb is not None:
+            r = ops.conv2d_dgrad_split_bnmask(dy, wsp[1], w.shape, x_shape, stride, pad, dx, reqs[0], mask_gb[0], mask_gb[1], stream=st)
+        elif wsp is not None:
             r = ops.conv2d_dgrad_split(dy, wsp[1], w.shape, x_shape, stride, pad, dx=dx, residual=residual, relu_src=relu_src,
                                        stream=st, bn_reqs=reqs, class_mask=class_mask, residual_mask=residual_mask)
         else:
@@ -496,16 +493,12 @@ class ResNet18Encoder(FlatEncoder):
             dy2 = DY[pre + ".conv2"]
             self._bn_bwd(ws, st, pre + ".bn2", d, blk["y2"], dy2, have.pop(pre + ".bn2", None))
             da1 = G[2][:n_out].view(oshape)
-            if blk["fold"]:
-                bn_in = self._bn_in(ws, pre + ".bn1")
-                self._wgrad(ws, blk["y1"], dy2, pre + ".conv2", 1, 1, bn_in=bn_in)
-                _, rt = ops.conv2d_dgrad_split_bnmask(dy2, self.wsp[pre + ".conv2"][1], self.p[pre + ".conv2.weight"].shape, oshape, 1, 1, da1,
-                                                      (blk["y1"],) + tuple(ws["stats"][pre + ".bn1"]) + (bnp[2],), bn_in[2], bn_in[3], stream=st)
-                got = {pre + ".bn1": (bnp[2], rt)}
-            else:
-                self._wgrad(ws, blk["a1"], dy2, pre + ".conv2", 1, 1)
-                got = self._dgrad(ws, st, dy2, pre + ".conv2", oshape, 1, 1, da1, relu_src=blk["a1"],
-                                  bn_next=[(pre + ".bn1", blk["y1"], bnp[2])])
+            # conv2's operand / ReLU mask: relu(bn1(y1)) re-formed from y1 where the forward folded it, else the stored a1
+            bn_in = self._bn_in(ws, pre + ".bn1") if blk["fold"] else None
+            a1 = blk["y1"] if blk["fold"] else blk["a1"]
+            self._wgrad(ws, a1, dy2, pre + ".conv2", 1, 1, bn_in=bn_in)
+            got = self._dgrad(ws, st, dy2, pre + ".conv2", oshape, 1, 1, da1, relu_src=a1 if bn_in is None else None,
+                              bn_next=[(pre + ".bn1", blk["y1"], bnp[2])], mask_gb=None if bn_in is None else bn_in[2:])
             dy1 = DY[pre + ".conv1"]
             self._bn_bwd(ws, st, pre + ".bn1", da1, blk["y1"], dy1, got.get(pre + ".bn1"))
             self._wgrad(ws, xin, dy1, pre + ".conv1", blk["stride"], 1)

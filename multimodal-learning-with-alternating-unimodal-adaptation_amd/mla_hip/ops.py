@@ -77,6 +77,21 @@ def _p(t: Optional[torch.Tensor], dtype=torch.float32) -> Optional[int]:
     return t.data_ptr()
 
 
+def _call(name: str, *args) -> None:
+    """Run the status-returning C entry point `name`; a non-zero status raises MLAHipError with mla_last_error()."""
+    check(getattr(_lib.load(), name)(*args), name)
+
+
+def _begin():
+    """Timer bracket around a launch: t0 = _begin(); _call(...); _end(t0, kind, work[, moved]).  TIMER off: one comparison each."""
+    return None if TIMER is None else TIMER.begin()
+
+
+def _end(t0, kind: str, work: float, moved: float = 0.0) -> None:
+    if t0 is not None:
+        TIMER.end(kind, work, t0, moved)
+
+
 def conv_out(n: int, k: int, s: int, p: int) -> int:
     return (n + 2 * p - k) // s + 1
 
@@ -86,21 +101,21 @@ def video_to_nhwc(src: torch.Tensor, dst: Optional[torch.Tensor] = None, stream:
     B, C, T, H, W = src.shape
     if dst is None:
         dst = torch.empty((B * T, H, W, C), device=src.device, dtype=torch.float32)
-    check(_lib.load().mla_video_to_nhwc(_p(src), _p(dst), B, C, T, H, W, stream or cur_stream()), "mla_video_to_nhwc")
+    _call("mla_video_to_nhwc", _p(src), _p(dst), B, C, T, H, W, stream or cur_stream())
     return dst
 
 
 def nchw_to_nhwc(src: torch.Tensor, stream: Optional[int] = None) -> torch.Tensor:
     N, C, H, W = src.shape
     dst = torch.empty((N, H, W, C), device=src.device, dtype=torch.float32)
-    check(_lib.load().mla_nchw_to_nhwc(_p(src), _p(dst), N, C, H, W, stream or cur_stream()), "mla_nchw_to_nhwc")
+    _call("mla_nchw_to_nhwc", _p(src), _p(dst), N, C, H, W, stream or cur_stream())
     return dst
 
 
 def nhwc_to_nchw(src: torch.Tensor, stream: Optional[int] = None) -> torch.Tensor:
     N, H, W, C = src.shape
     dst = torch.empty((N, C, H, W), device=src.device, dtype=torch.float32)
-    check(_lib.load().mla_nhwc_to_nchw(_p(src), _p(dst), N, C, H, W, stream or cur_stream()), "mla_nhwc_to_nchw")
+    _call("mla_nhwc_to_nchw", _p(src), _p(dst), N, C, H, W, stream or cur_stream())
     return dst
 
 
@@ -114,23 +129,29 @@ def conv2d_fwd_partial_elems(N, H, W, Cin, Cout, KH, KW, stride, pad) -> int:
     return int(_lib.load().mla_conv2d_fwd_partial_elems(N, H, W, Cin, Cout, KH, KW, stride, pad))
 
 
+def _conv_fwd(who: str, entry: str, kind: str, x, w, w_dtype, w_shape, stride: int, pad: int, y, bn_partial, stream, bn_in=(),
+              min_partial: int = 0) -> Tuple[torch.Tensor, int]:
+    """The body of every forward wrapper: `entry`(x, w, y, dims, [bn_in,] bn_partial, &tiles, stream) under a `kind` timer record."""
+    N, H, W, Cin = x.shape
+    KH, KW, Cin2, Cout = w_shape
+    if Cin2 != Cin:
+        raise MLAHipError(f"{who}: x has {Cin} channels, weight expects {Cin2}")
+    if y is None:
+        y = torch.empty((N, conv_out(H, KH, stride, pad), conv_out(W, KW, stride, pad), Cout), device=x.device, dtype=torch.float32)
+    if bn_partial is not None and bn_partial.numel() < min_partial:
+        raise MLAHipError(f"{who}: bn_partial too small")
+    tiles = ctypes.c_int(0)
+    t0 = _begin()
+    _call(entry, _p(x), _p(w, w_dtype), _p(y), N, H, W, Cin, Cout, KH, KW, stride, pad, *[_p(t) for t in bn_in[:4]], _p(bn_partial),
+          ctypes.addressof(tiles), stream or cur_stream())
+    _end(t0, kind, 2.0 * y.numel() * KH * KW * Cin)
+    return y, tiles.value
+
+
 def conv2d_fwd(x: torch.Tensor, w_hwio: torch.Tensor, stride: int, pad: int, y: Optional[torch.Tensor] = None,
                bn_partial: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> Tuple[torch.Tensor, int]:
     """Returns (y, tiles).  If `bn_partial` is given it receives [tiles][2][Cout] column sums / sums of squares."""
-    N, H, W, Cin = x.shape
-    KH, KW, Cin2, Cout = w_hwio.shape
-    if Cin2 != Cin:
-        raise MLAHipError(f"conv2d_fwd: x has {Cin} channels, weight expects {Cin2}")
-    if y is None:
-        y = torch.empty((N, conv_out(H, KH, stride, pad), conv_out(W, KW, stride, pad), Cout), device=x.device,
-                        dtype=torch.float32)
-    tiles = ctypes.c_int(0)
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_conv2d_fwd(_p(x), _p(w_hwio), _p(y), N, H, W, Cin, Cout, KH, KW, stride, pad,
-                                     _p(bn_partial), ctypes.addressof(tiles), stream or cur_stream()), "mla_conv2d_fwd")
-    if t0 is not None:
-        TIMER.end("conv_fwd", 2.0 * y.numel() * KH * KW * Cin, t0)
-    return y, tiles.value
+    return _conv_fwd("conv2d_fwd", "mla_conv2d_fwd", "conv_fwd", x, w_hwio, torch.float32, w_hwio.shape, stride, pad, y, bn_partial, stream)
 
 
 class _BnReduceReq(ctypes.Structure):     # include/mla_hip.h: mla_bn_reduce_req
@@ -157,6 +178,23 @@ def _bn_reqs(bn_reqs, x_shape):
     return arr, len(bn_reqs)
 
 
+def _conv_dgrad(entry: str, dy, w, w_dtype, w_shape, x_shape, stride: int, pad: int, dx, bn_reqs, stream, before=(), after=()):
+    """The body of every input-gradient wrapper: `entry`(dy, w, dx, dims, *before (tensors), requests, nreq, &tiles, *after (tensors or
+    ints), stream).  Returns (dx, tiles) with requests, dx without."""
+    N, H, W, Cin = x_shape
+    KH, KW, _, Cout = w_shape
+    if dx is None:
+        dx = torch.empty((N, H, W, Cin), device=dy.device, dtype=torch.float32)
+    arr, nreq = _bn_reqs(bn_reqs, x_shape)
+    tiles = ctypes.c_int(0)
+    t0 = _begin()
+    _call(entry, _p(dy), _p(w, w_dtype), _p(dx), N, H, W, Cin, Cout, KH, KW, stride, pad, *[_p(t) for t in before],
+          ctypes.addressof(arr) if nreq else None, nreq, ctypes.addressof(tiles), *[a if isinstance(a, int) else _p(a) for a in after],
+          stream or cur_stream())
+    _end(t0, "conv_dgrad", 2.0 * dy.numel() * KH * KW * Cin)
+    return (dx, tiles.value) if nreq else dx
+
+
 def conv2d_dgrad(dy: torch.Tensor, w_hwio: torch.Tensor, x_shape, stride: int, pad: int, wt_ws: torch.Tensor,
                  dx: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
                  relu_src: Optional[torch.Tensor] = None, stream: Optional[int] = None, bn_reqs=None,
@@ -164,22 +202,10 @@ def conv2d_dgrad(dy: torch.Tensor, w_hwio: torch.Tensor, x_shape, stride: int, p
     """Input gradient.  With bn_reqs (see _bn_reqs) the epilogue also forms the reduction pass of those BatchNorm
     backwards and the call returns (dx, tiles) for bn_bwd_from_partial.  class_mask / residual_mask: output parity classes
     (bit py * stride + px) to compute / to add `residual` in (include/mla_hip.h: mla_conv2d_dgrad_classes)."""
-    N, H, W, Cin = x_shape
-    KH, KW, _, Cout = w_hwio.shape
-    if dx is None:
-        dx = torch.empty((N, H, W, Cin), device=dy.device, dtype=torch.float32)
     if wt_ws.numel() < w_hwio.numel():
         raise MLAHipError("conv2d_dgrad: wt_ws too small")
-    arr, nreq = _bn_reqs(bn_reqs, x_shape)
-    tiles = ctypes.c_int(0)
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_conv2d_dgrad_classes(_p(dy), _p(w_hwio), _p(dx), N, H, W, Cin, Cout, KH, KW, stride, pad,
-                                               _p(residual), _p(relu_src), _p(wt_ws), ctypes.addressof(arr) if nreq else None, nreq,
-                                               ctypes.addressof(tiles), class_mask, residual_mask, stream or cur_stream()),
-          "mla_conv2d_dgrad_classes")
-    if t0 is not None:
-        TIMER.end("conv_dgrad", 2.0 * dy.numel() * KH * KW * Cin, t0)
-    return (dx, tiles.value) if nreq else dx
+    return _conv_dgrad("mla_conv2d_dgrad_classes", dy, w_hwio, torch.float32, w_hwio.shape, x_shape, stride, pad, dx, bn_reqs, stream,
+                       before=(residual, relu_src, wt_ws), after=(class_mask, residual_mask))
 
 
 def conv2d_wsplit(w_hwio: torch.Tensor, transposed: bool, out: Optional[torch.Tensor] = None,
@@ -192,37 +218,23 @@ def conv2d_wsplit(w_hwio: torch.Tensor, transposed: bool, out: Optional[torch.Te
         out = torch.empty(n, device=w_hwio.device, dtype=torch.int16)
     if out.numel() < n or out.dtype != torch.int16:
         raise MLAHipError("conv2d_wsplit: out must hold 3*KH*KW*Cin*Cout int16")
-    check(_lib.load().mla_conv2d_wsplit(_p(w_hwio), _p(out, torch.int16), Cin, Cout, KH, KW, int(transposed),
-                                        stream or cur_stream()), "mla_conv2d_wsplit")
+    _call("mla_conv2d_wsplit", _p(w_hwio), _p(out, torch.int16), Cin, Cout, KH, KW, int(transposed), stream or cur_stream())
     return out
 
 
 def conv2d_wsplit_batch(params: torch.Tensor, wsplit: torch.Tensor, desc: torch.Tensor, total_blocks: int,
                         stream: Optional[int] = None) -> None:
     """One launch that re-splits every conv listed in `desc` (int32 device tensor, n x 8; see include/mla_hip.h)."""
-    check(_lib.load().mla_conv2d_wsplit_batch(_p(params), _p(wsplit, torch.int16), _p(desc, torch.int32), desc.shape[0],
-                                              int(total_blocks), stream or cur_stream()), "mla_conv2d_wsplit_batch")
+    _call("mla_conv2d_wsplit_batch", _p(params), _p(wsplit, torch.int16), _p(desc, torch.int32), desc.shape[0], int(total_blocks),
+          stream or cur_stream())
 
 
 def conv2d_fwd_split(x: torch.Tensor, wsplit_t: torch.Tensor, w_shape, stride: int, pad: int,
                      y: Optional[torch.Tensor] = None, bn_partial: Optional[torch.Tensor] = None,
                      stream: Optional[int] = None) -> Tuple[torch.Tensor, int]:
     """conv2d_fwd on the split-bf16 MFMA path; `wsplit_t` = conv2d_wsplit(w, True), w_shape = (KH, KW, Cin, Cout)."""
-    N, H, W, Cin = x.shape
-    KH, KW, Cin2, Cout = w_shape
-    if Cin2 != Cin:
-        raise MLAHipError(f"conv2d_fwd_split: x has {Cin} channels, weight expects {Cin2}")
-    if y is None:
-        y = torch.empty((N, conv_out(H, KH, stride, pad), conv_out(W, KW, stride, pad), Cout), device=x.device,
-                        dtype=torch.float32)
-    tiles = ctypes.c_int(0)
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_conv2d_fwd_split(_p(x), _p(wsplit_t, torch.int16), _p(y), N, H, W, Cin, Cout, KH, KW, stride,
-                                           pad, _p(bn_partial), ctypes.addressof(tiles), stream or cur_stream()),
-          "mla_conv2d_fwd_split")
-    if t0 is not None:
-        TIMER.end("conv_fwd", 2.0 * y.numel() * KH * KW * Cin, t0)
-    return y, tiles.value
+    return _conv_fwd("conv2d_fwd_split", "mla_conv2d_fwd_split", "conv_fwd", x, wsplit_t, torch.int16, w_shape, stride, pad, y, bn_partial,
+                     stream)
 
 
 def conv2d_dgrad_split(dy: torch.Tensor, wsplit: torch.Tensor, w_shape, x_shape, stride: int, pad: int,
@@ -230,20 +242,8 @@ def conv2d_dgrad_split(dy: torch.Tensor, wsplit: torch.Tensor, w_shape, x_shape,
                        relu_src: Optional[torch.Tensor] = None, stream: Optional[int] = None, bn_reqs=None,
                        class_mask: int = 0xF, residual_mask: int = 0xF):
     """conv2d_dgrad on the split-bf16 MFMA path; `wsplit` = conv2d_wsplit(w, False).  bn_reqs as in conv2d_dgrad."""
-    N, H, W, Cin = x_shape
-    KH, KW, _, Cout = w_shape
-    if dx is None:
-        dx = torch.empty((N, H, W, Cin), device=dy.device, dtype=torch.float32)
-    arr, nreq = _bn_reqs(bn_reqs, x_shape)
-    tiles = ctypes.c_int(0)
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_conv2d_dgrad_split_classes(_p(dy), _p(wsplit, torch.int16), _p(dx), N, H, W, Cin, Cout, KH, KW, stride,
-                                                     pad, _p(residual), _p(relu_src), ctypes.addressof(arr) if nreq else None, nreq,
-                                                     ctypes.addressof(tiles), class_mask, residual_mask, stream or cur_stream()),
-          "mla_conv2d_dgrad_split_classes")
-    if t0 is not None:
-        TIMER.end("conv_dgrad", 2.0 * dy.numel() * KH * KW * Cin, t0)
-    return (dx, tiles.value) if nreq else dx
+    return _conv_dgrad("mla_conv2d_dgrad_split_classes", dy, wsplit, torch.int16, w_shape, x_shape, stride, pad, dx, bn_reqs, stream,
+                       before=(residual, relu_src), after=(class_mask, residual_mask))
 
 
 def conv2d_bnfold_supported(N: int, H: int, W: int, Cin: int, Cout: int, KH: int, KW: int, stride: int, pad: int) -> bool:
@@ -254,51 +254,22 @@ def conv2d_bnfold_supported(N: int, H: int, W: int, Cin: int, Cout: int, KH: int
 def conv2d_fwd_split_bnin(x: torch.Tensor, wsplit_t: torch.Tensor, w_shape, stride: int, pad: int, bn_in, y: Optional[torch.Tensor] = None,
                           bn_partial: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> Tuple[torch.Tensor, int]:
     """conv2d_fwd_split over relu(bn(x)); bn_in = (mean, invstd, gamma, beta) per input channel.  x is the BatchNorm's input."""
-    N, H, W, Cin = x.shape
-    KH, KW, Cin2, Cout = w_shape
-    if Cin2 != Cin:
-        raise MLAHipError(f"conv2d_fwd_split_bnin: x has {Cin} channels, weight expects {Cin2}")
-    if y is None:
-        y = torch.empty((N, conv_out(H, KH, stride, pad), conv_out(W, KW, stride, pad), Cout), device=x.device, dtype=torch.float32)
-    tiles = ctypes.c_int(0)
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_conv2d_fwd_split_bnin(_p(x), _p(wsplit_t, torch.int16), _p(y), N, H, W, Cin, Cout, KH, KW, stride, pad,
-                                                _p(bn_in[0]), _p(bn_in[1]), _p(bn_in[2]), _p(bn_in[3]), _p(bn_partial),
-                                                ctypes.addressof(tiles), stream or cur_stream()), "mla_conv2d_fwd_split_bnin")
-    if t0 is not None:
-        TIMER.end("conv_fwd", 2.0 * y.numel() * KH * KW * Cin, t0)
-    return y, tiles.value
+    return _conv_fwd("conv2d_fwd_split_bnin", "mla_conv2d_fwd_split_bnin", "conv_fwd", x, wsplit_t, torch.int16, w_shape, stride, pad, y,
+                     bn_partial, stream, bn_in=bn_in)
 
 
 def conv2d_wgrad_split_bnin(x: torch.Tensor, dy: torch.Tensor, dw_hwio: torch.Tensor, stride: int, pad: int, ws: torch.Tensor, bn_in,
                             stream: Optional[int] = None) -> torch.Tensor:
     """conv2d_wgrad_split with relu(bn(x)) as the input operand; bn_in = (mean, invstd, gamma, beta)."""
-    N, H, W, Cin = x.shape
-    KH, KW, _, Cout = dw_hwio.shape
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_conv2d_wgrad_split_bnin(_p(x), _p(dy), _p(dw_hwio), N, H, W, Cin, Cout, KH, KW, stride, pad, _p(bn_in[0]),
-                                                  _p(bn_in[1]), _p(bn_in[2]), _p(bn_in[3]), _p(ws), ws.numel() * ws.element_size(),
-                                                  stream or cur_stream()), "mla_conv2d_wgrad_split_bnin")
-    if t0 is not None:
-        TIMER.end("conv_wgrad", 2.0 * dy.numel() * KH * KW * Cin, t0)
-    return dw_hwio
+    return _conv_wgrad("mla_conv2d_wgrad_split_bnin", "conv_wgrad", x, dy, dw_hwio, stride, pad, ws, stream, bn_in=bn_in)
 
 
 def conv2d_dgrad_split_bnmask(dy: torch.Tensor, wsplit: torch.Tensor, w_shape, x_shape, stride: int, pad: int, dx: torch.Tensor, bn_req,
                               mask_gamma: torch.Tensor, mask_beta: torch.Tensor, stream: Optional[int] = None):
     """conv2d_dgrad_split whose ReLU mask is relu(bn(bn_req.x)) > 0 -- the BatchNorm whose backward reduction the epilogue forms anyway
     (bn_req = (x, mean, invstd, partial)).  Returns (dx, tiles)."""
-    N, H, W, Cin = x_shape
-    KH, KW, _, Cout = w_shape
-    arr, nreq = _bn_reqs([bn_req], x_shape)
-    tiles = ctypes.c_int(0)
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_conv2d_dgrad_split_bnmask(_p(dy), _p(wsplit, torch.int16), _p(dx), N, H, W, Cin, Cout, KH, KW, stride, pad,
-                                                    ctypes.addressof(arr), nreq, ctypes.addressof(tiles), _p(mask_gamma), _p(mask_beta),
-                                                    stream or cur_stream()), "mla_conv2d_dgrad_split_bnmask")
-    if t0 is not None:
-        TIMER.end("conv_dgrad", 2.0 * dy.numel() * KH * KW * Cin, t0)
-    return dx, tiles.value
+    return _conv_dgrad("mla_conv2d_dgrad_split_bnmask", dy, wsplit, torch.int16, w_shape, x_shape, stride, pad, dx, [bn_req], stream,
+                       after=(mask_gamma, mask_beta))
 
 
 def conv2d_stem_supported(Cin: int, Cout: int, KH: int, KW: int, stride: int, pad: int) -> bool:
@@ -319,39 +290,29 @@ def conv2d_stem_fwd_split(x: torch.Tensor, w_hwio: torch.Tensor, y: Optional[tor
                           bn_partial: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> Tuple[torch.Tensor, int]:
     """The stem convolution (backbone.py:79-83, 149) on the split arithmetic, persistent patch-loader kernel; plain fp32 HWIO
     weights.  Returns (y, partial rows) like conv2d_fwd."""
-    N, H, W, Cin = x.shape
-    KH, KW, Cin2, Cout = w_hwio.shape
-    if Cin2 != Cin:
-        raise MLAHipError(f"conv2d_stem_fwd_split: x has {Cin} channels, weight expects {Cin2}")
-    if y is None:
-        y = torch.empty((N, conv_out(H, KH, 2, 3), conv_out(W, KW, 2, 3), Cout), device=x.device, dtype=torch.float32)
-    if bn_partial is not None and bn_partial.numel() < conv2d_stem_fwd_partial_elems():
-        raise MLAHipError("conv2d_stem_fwd_split: bn_partial too small")
-    tiles = ctypes.c_int(0)
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_conv2d_stem_fwd_split(_p(x), _p(w_hwio), _p(y), N, H, W, Cin, Cout, KH, KW, 2, 3, _p(bn_partial),
-                                                ctypes.addressof(tiles), stream or cur_stream()), "mla_conv2d_stem_fwd_split")
-    if t0 is not None:
-        TIMER.end("stem_fwd", 2.0 * y.numel() * KH * KW * Cin, t0)
-    return y, tiles.value
+    return _conv_fwd("conv2d_stem_fwd_split", "mla_conv2d_stem_fwd_split", "stem_fwd", x, w_hwio, torch.float32, w_hwio.shape, 2, 3, y,
+                     bn_partial, stream, min_partial=conv2d_stem_fwd_partial_elems() if bn_partial is not None else 0)
 
 
 def conv2d_stem_wgrad_split_ws_bytes(Cin: int) -> int:
     return int(_lib.load().mla_conv2d_stem_wgrad_split_ws_bytes(Cin))
 
 
+def _conv_wgrad(entry: str, kind: str, x, dy, dw_hwio, stride: int, pad: int, ws, stream, bn_in=()) -> torch.Tensor:
+    """The body of every weight-gradient wrapper: `entry`(x, dy, dw, dims, [bn_in,] ws, its bytes, stream) under a `kind` timer record."""
+    N, H, W, Cin = x.shape
+    KH, KW, _, Cout = dw_hwio.shape
+    t0 = _begin()
+    _call(entry, _p(x), _p(dy), _p(dw_hwio), N, H, W, Cin, Cout, KH, KW, stride, pad, *[_p(t) for t in bn_in[:4]], _p(ws),
+          ws.numel() * ws.element_size(), stream or cur_stream())
+    _end(t0, kind, 2.0 * dy.numel() * KH * KW * Cin)
+    return dw_hwio
+
+
 def conv2d_stem_wgrad_split(x: torch.Tensor, dy: torch.Tensor, dw_hwio: torch.Tensor, stride: int, pad: int, ws: torch.Tensor,
                             stream: Optional[int] = None) -> torch.Tensor:
     """Stem weight gradient on the split arithmetic (same call shape as conv2d_wgrad)."""
-    N, H, W, Cin = x.shape
-    KH, KW, _, Cout = dw_hwio.shape
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_conv2d_stem_wgrad_split(_p(x), _p(dy), _p(dw_hwio), N, H, W, Cin, Cout, KH, KW, stride, pad,
-                                                  _p(ws), ws.numel() * ws.element_size(), stream or cur_stream()),
-          "mla_conv2d_stem_wgrad_split")
-    if t0 is not None:
-        TIMER.end("stem_wgrad", 2.0 * dy.numel() * KH * KW * Cin, t0)
-    return dw_hwio
+    return _conv_wgrad("mla_conv2d_stem_wgrad_split", "stem_wgrad", x, dy, dw_hwio, stride, pad, ws, stream)
 
 
 def conv2d_wgrad_tr(on: int = -1) -> int:
@@ -390,14 +351,7 @@ def conv2d_wgrad_ws_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad) -> int:
 
 def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, dw_hwio: torch.Tensor, stride: int, pad: int, ws: torch.Tensor,
                  stream: Optional[int] = None) -> torch.Tensor:
-    N, H, W, Cin = x.shape
-    KH, KW, _, Cout = dw_hwio.shape
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_conv2d_wgrad(_p(x), _p(dy), _p(dw_hwio), N, H, W, Cin, Cout, KH, KW, stride, pad,
-                                       _p(ws), ws.numel() * ws.element_size(), stream or cur_stream()), "mla_conv2d_wgrad")
-    if t0 is not None:
-        TIMER.end("conv_wgrad", 2.0 * dy.numel() * KH * KW * Cin, t0)
-    return dw_hwio
+    return _conv_wgrad("mla_conv2d_wgrad", "conv_wgrad", x, dy, dw_hwio, stride, pad, ws, stream)
 
 
 def conv2d_wgrad_split_ws_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad) -> int:
@@ -407,15 +361,7 @@ def conv2d_wgrad_split_ws_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad) -> int:
 def conv2d_wgrad_split(x: torch.Tensor, dy: torch.Tensor, dw_hwio: torch.Tensor, stride: int, pad: int, ws: torch.Tensor,
                        stream: Optional[int] = None) -> torch.Tensor:
     """conv2d_wgrad on the split-bf16 MFMA path (Cin a multiple of 64); ws >= conv2d_wgrad_split_ws_bytes."""
-    N, H, W, Cin = x.shape
-    KH, KW, _, Cout = dw_hwio.shape
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_conv2d_wgrad_split(_p(x), _p(dy), _p(dw_hwio), N, H, W, Cin, Cout, KH, KW, stride, pad,
-                                             _p(ws), ws.numel() * ws.element_size(), stream or cur_stream()),
-          "mla_conv2d_wgrad_split")
-    if t0 is not None:
-        TIMER.end("conv_wgrad", 2.0 * dy.numel() * KH * KW * Cin, t0)
-    return dw_hwio
+    return _conv_wgrad("mla_conv2d_wgrad_split", "conv_wgrad", x, dy, dw_hwio, stride, pad, ws, stream)
 
 
 # ---- batch norm ---------------------------------------------------------------------------------
@@ -425,28 +371,24 @@ def bn_stats_partial_elems(M: int, C: int) -> int:
 
 def bn_stats_partial(x2d: torch.Tensor, M: int, C: int, partial: torch.Tensor, stream: Optional[int] = None) -> int:
     tiles = ctypes.c_int(0)
-    check(_lib.load().mla_bn_stats_partial(_p(x2d), M, C, _p(partial), ctypes.addressof(tiles), stream or cur_stream()),
-          "mla_bn_stats_partial")
+    _call("mla_bn_stats_partial", _p(x2d), M, C, _p(partial), ctypes.addressof(tiles), stream or cur_stream())
     return tiles.value
 
 
 def bn_finalize(partial: torch.Tensor, tiles: int, M: int, C: int, mean: torch.Tensor, invstd: torch.Tensor,
                 running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor],
                 eps: float = BN_EPS, momentum: float = BN_MOMENTUM, stream: Optional[int] = None) -> None:
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_bn_finalize(_p(partial), tiles, M, C, eps, momentum, _p(mean), _p(invstd), _p(running_mean),
-                                      _p(running_var), stream or cur_stream()), "mla_bn_finalize")
-    if t0 is not None:
-        TIMER.end("bn_fwd", 0.0, t0)      # statistics finalize: its time belongs to the BN forward, its bytes are negligible
+    t0 = _begin()
+    _call("mla_bn_finalize", _p(partial), tiles, M, C, eps, momentum, _p(mean), _p(invstd), _p(running_mean), _p(running_var), stream or cur_stream())
+    _end(t0, "bn_fwd", 0.0)      # statistics finalize: its time belongs to the BN forward, its bytes are negligible
 
 
 def bn_apply(x: torch.Tensor, mean, invstd, gamma, beta, out: torch.Tensor, M: int, C: int, relu: bool,
              residual: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_bn_apply(_p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(residual), _p(out), M, C,
-                                   int(relu), stream or cur_stream()), "mla_bn_apply")
-    if t0 is not None:   # BN-fwd-train = 12 B/elem algorithmic; this path moves 8 (+4 with a residual)
-        TIMER.end("bn_fwd", 12.0 * M * C, t0, moved=(12.0 if residual is not None else 8.0) * M * C)
+    t0 = _begin()
+    _call("mla_bn_apply", _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(residual), _p(out), M, C, int(relu), stream or cur_stream())
+    # BN-fwd-train = 12 B/elem algorithmic; this path moves 8 (+4 with a residual)
+    _end(t0, "bn_fwd", 12.0 * M * C, (12.0 if residual is not None else 8.0) * M * C)
     return out
 
 
@@ -456,66 +398,58 @@ def bn_bwd_ws_elems(M: int, C: int) -> int:
 
 def bn_bwd(dout, x, mean, invstd, gamma, dx, dgamma, dbeta, ws, M: int, C: int, relu_out=None, g_out=None,
            stream: Optional[int] = None) -> None:
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_bn_bwd(_p(dout), _p(relu_out), _p(x), _p(mean), _p(invstd), _p(gamma), _p(dx), _p(dgamma),
-                                 _p(dbeta), _p(g_out), _p(ws), M, C, stream or cur_stream()), "mla_bn_bwd")
-    if t0 is not None:   # BN-bwd = 20 B/elem (dy, x for the reductions; dy, x again; write dx)
-        TIMER.end("bn_bwd", 20.0 * M * C, t0, moved=20.0 * M * C)
+    t0 = _begin()
+    _call("mla_bn_bwd", _p(dout), _p(relu_out), _p(x), _p(mean), _p(invstd), _p(gamma), _p(dx), _p(dgamma), _p(dbeta), _p(g_out), _p(ws), M, C,
+          stream or cur_stream())
+    _end(t0, "bn_bwd", 20.0 * M * C, 20.0 * M * C)   # BN-bwd = 20 B/elem (dy, x for the reductions; dy, x again; write dx)
 
 
 def bn_relu_maxpool_fwd(y, mean, invstd, gamma, beta, out, idx, stream: Optional[int] = None) -> None:
     """maxpool3x3s2(relu(bn(y))) without materialising the ReLU output (stem, backbone.py:150-152)."""
     N, H, W, C = y.shape
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_bn_relu_maxpool_fwd(_p(y), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(out),
-                                              _p(idx, torch.uint8), N, H, W, C, stream or cur_stream()),
-          "mla_bn_relu_maxpool_fwd")
-    if t0 is not None:   # read y once, write the pooled quarter + its index bytes
-        by = 4.0 * N * H * W * C + 5.0 * out.numel()
-        TIMER.end("bn_fwd", by, t0, moved=by)
+    t0 = _begin()
+    _call("mla_bn_relu_maxpool_fwd", _p(y), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(out), _p(idx, torch.uint8), N, H, W, C,
+          stream or cur_stream())
+    by = 4.0 * N * H * W * C + 5.0 * out.numel()   # read y once, write the pooled quarter + its index bytes
+    _end(t0, "bn_fwd", by, by)
 
 
 def bn_bwd_pooled(dpool, idx, y, mean, invstd, gamma, beta, dy, dgamma, dbeta, ws, stream: Optional[int] = None) -> None:
     """BatchNorm backward fed by the pooled gradient (max-pool scatter + ReLU mask recomputed on the fly)."""
     N, H, W, C = y.shape
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_bn_bwd_pooled(_p(dpool), _p(idx, torch.uint8), _p(y), _p(mean), _p(invstd), _p(gamma), _p(beta),
-                                        _p(dy), _p(dgamma), _p(dbeta), _p(ws), N, H, W, C, stream or cur_stream()),
-          "mla_bn_bwd_pooled")
-    if t0 is not None:   # y twice, dy once, the pooled gradient + index twice
-        by = 12.0 * N * H * W * C + 10.0 * dpool.numel()
-        TIMER.end("bn_bwd", by, t0, moved=by)
+    t0 = _begin()
+    _call("mla_bn_bwd_pooled", _p(dpool), _p(idx, torch.uint8), _p(y), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(dy), _p(dgamma), _p(dbeta),
+          _p(ws), N, H, W, C, stream or cur_stream())
+    by = 12.0 * N * H * W * C + 10.0 * dpool.numel()   # y twice, dy once, the pooled gradient + index twice
+    _end(t0, "bn_bwd", by, by)
 
 
 def bn_bwd_from_partial(dout, x, mean, invstd, gamma, dx, dgamma, dbeta, partial, tiles: int, M: int, C: int,
                         stream: Optional[int] = None) -> None:
     """BatchNorm backward whose reduction pass was formed by the input-gradient kernel that wrote `dout` (bn_reqs)."""
-    t0 = TIMER.begin() if TIMER is not None else None
-    check(_lib.load().mla_bn_bwd_from_partial(_p(dout), _p(x), _p(mean), _p(invstd), _p(gamma), _p(dx), _p(dgamma), _p(dbeta),
-                                              _p(partial), tiles, M, C, stream or cur_stream()), "mla_bn_bwd_from_partial")
-    if t0 is not None:   # dy, x read once; dx written
-        TIMER.end("bn_bwd", 12.0 * M * C, t0, moved=12.0 * M * C)
+    t0 = _begin()
+    _call("mla_bn_bwd_from_partial", _p(dout), _p(x), _p(mean), _p(invstd), _p(gamma), _p(dx), _p(dgamma), _p(dbeta), _p(partial), tiles, M, C,
+          stream or cur_stream())
+    _end(t0, "bn_bwd", 12.0 * M * C, 12.0 * M * C)   # dy, x read once; dx written
 
 
 # ---- pooling ------------------------------------------------------------------------------------
 def maxpool_fwd(x: torch.Tensor, y: torch.Tensor, idx: torch.Tensor, stream: Optional[int] = None) -> None:
     N, H, W, C = x.shape
-    check(_lib.load().mla_maxpool3x3s2_fwd(_p(x), _p(y), _p(idx, torch.uint8), N, H, W, C, stream or cur_stream()),
-          "mla_maxpool3x3s2_fwd")
+    _call("mla_maxpool3x3s2_fwd", _p(x), _p(y), _p(idx, torch.uint8), N, H, W, C, stream or cur_stream())
 
 
 def maxpool_bwd(dy, idx, dx, x_shape, relu_src=None, stream: Optional[int] = None) -> None:
     N, H, W, C = x_shape
-    check(_lib.load().mla_maxpool3x3s2_bwd(_p(dy), _p(idx, torch.uint8), _p(relu_src), _p(dx), N, H, W, C,
-                                           stream or cur_stream()), "mla_maxpool3x3s2_bwd")
+    _call("mla_maxpool3x3s2_bwd", _p(dy), _p(idx, torch.uint8), _p(relu_src), _p(dx), N, H, W, C, stream or cur_stream())
 
 
 def avgpool_fwd(x, y, NB: int, P: int, C: int, stream: Optional[int] = None) -> None:
-    check(_lib.load().mla_avgpool_fwd(_p(x), _p(y), NB, P, C, stream or cur_stream()), "mla_avgpool_fwd")
+    _call("mla_avgpool_fwd", _p(x), _p(y), NB, P, C, stream or cur_stream())
 
 
 def avgpool_bwd(dy, dx, NB: int, P: int, C: int, relu_src=None, stream: Optional[int] = None) -> None:
-    check(_lib.load().mla_avgpool_bwd(_p(dy), _p(relu_src), _p(dx), NB, P, C, stream or cur_stream()), "mla_avgpool_bwd")
+    _call("mla_avgpool_bwd", _p(dy), _p(relu_src), _p(dx), NB, P, C, stream or cur_stream())
 
 
 # ---- head / projection / optimiser ----------------------------------------------------------------
@@ -526,16 +460,14 @@ def head_ws_elems(B: int, C: int) -> int:
 def head_ce_fwd_bwd(X, W, b, labels, logits, loss, dW, db, dX, ws, inv_batch: float, stream: Optional[int] = None) -> None:
     B, D = X.shape
     C = W.shape[0]
-    check(_lib.load().mla_head_ce_fwd_bwd(_p(X), _p(W), _p(b), _p(labels, torch.int64), _p(logits), _p(loss), _p(dW),
-                                          _p(db), _p(dX), _p(ws), B, D, C, inv_batch, stream or cur_stream()),
-          "mla_head_ce_fwd_bwd")
+    _call("mla_head_ce_fwd_bwd", _p(X), _p(W), _p(b), _p(labels, torch.int64), _p(logits), _p(loss), _p(dW), _p(db), _p(dX), _p(ws), B, D, C,
+          inv_batch, stream or cur_stream())
 
 
 def ce_fwd_bwd(logits, labels, loss, dlogits, ws, inv_batch: float, stream: Optional[int] = None) -> None:
     """nn.CrossEntropyLoss() forward + d logits (main.py:130, 434); ws: B floats."""
     B, C = logits.shape
-    check(_lib.load().mla_ce_fwd_bwd(_p(logits), _p(labels, torch.int64), _p(loss), _p(dlogits), _p(ws), B, C, inv_batch,
-                                     stream or cur_stream()), "mla_ce_fwd_bwd")
+    _call("mla_ce_fwd_bwd", _p(logits), _p(labels, torch.int64), _p(loss), _p(dlogits), _p(ws), B, C, inv_batch, stream or cur_stream())
 
 
 def head_bwd(X, W, dlogits, dW, db, dX, scale: float = 1.0, stream: Optional[int] = None) -> None:
@@ -544,8 +476,7 @@ def head_bwd(X, W, dlogits, dW, db, dX, scale: float = 1.0, stream: Optional[int
     C = W.shape[0]
     if tuple(dlogits.shape) != (B, C):
         raise MLAHipError(f"head_bwd: dlogits {tuple(dlogits.shape)} does not match ({B}, {C})")
-    check(_lib.load().mla_head_bwd(_p(X), _p(W), _p(dlogits), _p(dW), _p(db), _p(dX), B, D, C, scale, stream or cur_stream()),
-          "mla_head_bwd")
+    _call("mla_head_bwd", _p(X), _p(W), _p(dlogits), _p(dW), _p(db), _p(dX), B, D, C, scale, stream or cur_stream())
 
 
 def _concat_ptrs(xs, who: str):
@@ -571,9 +502,8 @@ def concat_head_ce_fwd_bwd(xs, W, b, labels, out, out_m, loss, loss_m, dW, db, d
     if tuple(W.shape) != (C, M * D) or len(dxs) != M:
         raise MLAHipError(f"concat_head_ce_fwd_bwd: W {tuple(W.shape)} does not match {M} x (B, {D})")
     dx = [_p(t) for t in dxs] + [None] * (3 - M)
-    check(_lib.load().mla_concat_head_ce_fwd_bwd(x[0], x[1], x[2], _p(W), _p(b), _p(labels, torch.int64), _p(out), _p(out_m),
-                                                 _p(loss), _p(loss_m), _p(dW), _p(db), dx[0], dx[1], dx[2], _p(ws), M, B, D, C,
-                                                 inv_batch, stream or cur_stream()), "mla_concat_head_ce_fwd_bwd")
+    _call("mla_concat_head_ce_fwd_bwd", x[0], x[1], x[2], _p(W), _p(b), _p(labels, torch.int64), _p(out), _p(out_m), _p(loss), _p(loss_m), _p(dW),
+          _p(db), dx[0], dx[1], dx[2], _p(ws), M, B, D, C, inv_batch, stream or cur_stream())
 
 
 def concat_head_fwd(xs, W, b, out, out_m, stream: Optional[int] = None) -> None:
@@ -582,8 +512,7 @@ def concat_head_fwd(xs, W, b, out, out_m, stream: Optional[int] = None) -> None:
     C = W.shape[0]
     if tuple(W.shape) != (C, M * D):
         raise MLAHipError(f"concat_head_fwd: W {tuple(W.shape)} does not match {M} x (B, {D})")
-    check(_lib.load().mla_concat_head_fwd(x[0], x[1], x[2], _p(W), _p(b), _p(out), _p(out_m), M, B, D, C, stream or cur_stream()),
-          "mla_concat_head_fwd")
+    _call("mla_concat_head_fwd", x[0], x[1], x[2], _p(W), _p(b), _p(out), _p(out_m), M, B, D, C, stream or cur_stream())
 
 
 def concat_head_bwd(xs, W, dlogits, dW, db, dxs, scale: float = 1.0, stream: Optional[int] = None) -> None:
@@ -593,18 +522,16 @@ def concat_head_bwd(xs, W, dlogits, dW, db, dxs, scale: float = 1.0, stream: Opt
     if tuple(W.shape) != (C, M * D) or tuple(dlogits.shape) != (B, C) or len(dxs) != M:
         raise MLAHipError(f"concat_head_bwd: W {tuple(W.shape)} / dlogits {tuple(dlogits.shape)} do not match {M} x ({B}, {D})")
     dx = [_p(t) for t in dxs] + [None] * (3 - M)
-    check(_lib.load().mla_concat_head_bwd(x[0], x[1], x[2], _p(W), _p(dlogits), _p(dW), _p(db), dx[0], dx[1], dx[2], M, B, D, C,
-                                          scale, stream or cur_stream()), "mla_concat_head_bwd")
+    _call("mla_concat_head_bwd", x[0], x[1], x[2], _p(W), _p(dlogits), _p(dW), _p(db), dx[0], dx[1], dx[2], M, B, D, C, scale, stream or cur_stream())
 
 
 def scale_by_device_scalar(x, scalar, stream: Optional[int] = None) -> None:
-    check(_lib.load().mla_scale_by_device_scalar(_p(x), _p(scalar), x.numel(), stream or cur_stream()),
-          "mla_scale_by_device_scalar")
+    _call("mla_scale_by_device_scalar", _p(x), _p(scalar), x.numel(), stream or cur_stream())
 
 
 def colsum(X, r, scale: float, stream: Optional[int] = None) -> None:
     B, D = X.shape
-    check(_lib.load().mla_colsum(_p(X), _p(r), B, D, scale, stream or cur_stream()), "mla_colsum")
+    _call("mla_colsum", _p(X), _p(r), B, D, scale, stream or cur_stream())
 
 
 def gs_ws_elems(D: int, C: int) -> int:
@@ -614,12 +541,11 @@ def gs_ws_elems(D: int, C: int) -> int:
 def gs_project(Pl, r, G, alpha: float, ws, stream: Optional[int] = None) -> None:
     D = Pl.shape[0]
     C = G.shape[0]
-    check(_lib.load().mla_gs_project(_p(Pl), _p(r), _p(G), D, C, alpha, _p(ws), stream or cur_stream()), "mla_gs_project")
+    _call("mla_gs_project", _p(Pl), _p(r), _p(G), D, C, alpha, _p(ws), stream or cur_stream())
 
 
 def sgd_step(p, g, buf, lr: float, momentum: float, wd: float, first: bool, stream: Optional[int] = None) -> None:
-    check(_lib.load().mla_sgd_step(_p(p), _p(g), _p(buf), p.numel(), lr, momentum, wd, int(first),
-                                   stream or cur_stream()), "mla_sgd_step")
+    _call("mla_sgd_step", _p(p), _p(g), _p(buf), p.numel(), lr, momentum, wd, int(first), stream or cur_stream())
 
 
 # ---- transformer encoders (M3AE / CAV-MAE) -----------------------------------------------------------
@@ -632,24 +558,22 @@ def linear_fwd(x, w_kn, bias, y, groups: int, rows: int, K: int, N: int, x_group
     """y[g][y_off+r] = x[g][x_off+r] @ w_kn (+bias) (+residual); y_gelu (optional) also receives gelu(y).
     wsplit: conv2d_wsplit(w_kn.view(1, 1, K, N), True) selects the split-bf16 arithmetic."""
     if wsplit is not None:
-        check(_lib.load().mla_linear_fwd_split(_p(x), _p(wsplit, torch.int16), _p(bias), _p(residual), _p(y), _p(y_gelu), groups,
-                                               rows, x_group_rows or rows, x_off, y_group_rows or rows, y_off, K, N,
-                                               stream or cur_stream()), "mla_linear_fwd_split")
+        _call("mla_linear_fwd_split", _p(x), _p(wsplit, torch.int16), _p(bias), _p(residual), _p(y), _p(y_gelu), groups, rows, x_group_rows or rows,
+              x_off, y_group_rows or rows, y_off, K, N, stream or cur_stream())
         return
-    check(_lib.load().mla_linear_fwd(_p(x), _p(w_kn), _p(bias), _p(residual), _p(y), _p(y_gelu), groups, rows,
-                                     x_group_rows or rows, x_off, y_group_rows or rows, y_off, K, N,
-                                     stream or cur_stream()), "mla_linear_fwd")
+    _call("mla_linear_fwd", _p(x), _p(w_kn), _p(bias), _p(residual), _p(y), _p(y_gelu), groups, rows, x_group_rows or rows, x_off,
+          y_group_rows or rows, y_off, K, N, stream or cur_stream())
 
 
 def linear_dgrad(dy, w_kn, dx, wt_ws, groups: int, rows: int, K: int, N: int, residual=None, gelu_src=None,
                  stream: Optional[int] = None, wsplit=None):
     """dx = dy @ w_kn^T (+residual) (* gelu'(gelu_src)); dense rows.  wsplit: conv2d_wsplit(w_kn.view(1, 1, K, N), False)."""
     if wsplit is not None:
-        check(_lib.load().mla_linear_dgrad_split(_p(dy), _p(wsplit, torch.int16), _p(dx), _p(residual), _p(gelu_src), groups,
-                                                 rows, rows, 0, rows, 0, K, N, stream or cur_stream()), "mla_linear_dgrad_split")
+        _call("mla_linear_dgrad_split", _p(dy), _p(wsplit, torch.int16), _p(dx), _p(residual), _p(gelu_src), groups, rows, rows, 0, rows, 0, K, N,
+              stream or cur_stream())
         return
-    check(_lib.load().mla_linear_dgrad(_p(dy), _p(w_kn), _p(dx), _p(residual), _p(gelu_src), _p(wt_ws), groups, rows,
-                                       rows, 0, rows, 0, K, N, stream or cur_stream()), "mla_linear_dgrad")
+    _call("mla_linear_dgrad", _p(dy), _p(w_kn), _p(dx), _p(residual), _p(gelu_src), _p(wt_ws), groups, rows, rows, 0, rows, 0, K, N,
+          stream or cur_stream())
 
 
 def linear_wgrad_ws_bytes(M: int, K: int, N: int, split: bool = False) -> int:
@@ -662,14 +586,13 @@ def linear_wgrad(x, dy, dw_kn, ws, groups: int, rows: int, K: int, N: int, x_gro
                  stream: Optional[int] = None, split: bool = False, dbias: Optional[torch.Tensor] = None):
     """dw_kn = x^T dy (K, N).  split + dbias: the bias gradient (column sums of dy) comes out of the same pass."""
     if split:
-        check(_lib.load().mla_linear_wgrad_split_bias(_p(x), _p(dy), _p(dw_kn), _p(dbias), groups, rows, x_group_rows or rows, x_off,
-                                                      K, N, _p(ws), ws.numel() * ws.element_size(), stream or cur_stream()),
-              "mla_linear_wgrad_split_bias")
+        _call("mla_linear_wgrad_split_bias", _p(x), _p(dy), _p(dw_kn), _p(dbias), groups, rows, x_group_rows or rows, x_off, K, N, _p(ws),
+              ws.numel() * ws.element_size(), stream or cur_stream())
         return
     if dbias is not None:
         raise MLAHipError("linear_wgrad: the fused bias gradient exists on the split arithmetic only (use colsum_rows)")
-    check(_lib.load().mla_linear_wgrad(_p(x), _p(dy), _p(dw_kn), groups, rows, x_group_rows or rows, x_off, K, N, _p(ws),
-                                       ws.numel() * ws.element_size(), stream or cur_stream()), "mla_linear_wgrad")
+    _call("mla_linear_wgrad", _p(x), _p(dy), _p(dw_kn), groups, rows, x_group_rows or rows, x_off, K, N, _p(ws), ws.numel() * ws.element_size(),
+          stream or cur_stream())
 
 
 def colreduce_ws_elems(M: int, C: int) -> int:
@@ -677,17 +600,15 @@ def colreduce_ws_elems(M: int, C: int) -> int:
 
 
 def colsum_rows(x, out, ws, M: int, C: int, stream: Optional[int] = None):
-    check(_lib.load().mla_colsum_rows(_p(x), _p(out), _p(ws), M, C, stream or cur_stream()), "mla_colsum_rows")
+    _call("mla_colsum_rows", _p(x), _p(out), _p(ws), M, C, stream or cur_stream())
 
 
 def layernorm_fwd(x, w, b, y, mean, rstd, M: int, D: int, eps: float = LN_EPS, stream: Optional[int] = None):
-    check(_lib.load().mla_layernorm_fwd(_p(x), _p(w), _p(b), _p(y), _p(mean), _p(rstd), M, D, eps, stream or cur_stream()),
-          "mla_layernorm_fwd")
+    _call("mla_layernorm_fwd", _p(x), _p(w), _p(b), _p(y), _p(mean), _p(rstd), M, D, eps, stream or cur_stream())
 
 
 def layernorm_bwd(dy, x, w, mean, rstd, dx, dw, db, ws, M: int, D: int, add=None, stream: Optional[int] = None):
-    check(_lib.load().mla_layernorm_bwd(_p(dy), _p(x), _p(w), _p(mean), _p(rstd), _p(add), _p(dx), _p(dw), _p(db), _p(ws),
-                                        M, D, stream or cur_stream()), "mla_layernorm_bwd")
+    _call("mla_layernorm_bwd", _p(dy), _p(x), _p(w), _p(mean), _p(rstd), _p(add), _p(dx), _p(dw), _p(db), _p(ws), M, D, stream or cur_stream())
 
 
 def bgemm(A, B, C, batches: int, heads: int, M: int, N: int, K: int, a_strides, b_strides, c_strides, alpha: float = 1.0,
@@ -698,34 +619,30 @@ def bgemm(A, B, C, batches: int, heads: int, M: int, N: int, K: int, a_strides, 
     pa, pb, pc = _p(A) + 4 * a_off, _p(B) + 4 * b_off, _p(C) + 4 * c_off
     if min(a_off, b_off, c_off) < 0 or a_off >= A.numel() or b_off >= B.numel() or c_off >= C.numel():
         raise MLAHipError("bgemm: element offset outside its buffer")
-    check(_lib.load().mla_bgemm(pa, pb, pc, batches, heads, M, N, K, ctypes.addressof(sa), ctypes.addressof(sb),
-                                ctypes.addressof(sc), A.numel() - a_off, B.numel() - b_off, C.numel() - c_off, alpha,
-                                stream or cur_stream()), "mla_bgemm")
+    _call("mla_bgemm", pa, pb, pc, batches, heads, M, N, K, ctypes.addressof(sa), ctypes.addressof(sb), ctypes.addressof(sc), A.numel() - a_off,
+          B.numel() - b_off, C.numel() - c_off, alpha, stream or cur_stream())
 
 
 def softmax_fwd(S, pad_mask, B: int, H: int, n: int, stream: Optional[int] = None):
-    check(_lib.load().mla_softmax_fwd(_p(S), _p(pad_mask), B, H, n, stream or cur_stream()), "mla_softmax_fwd")
+    _call("mla_softmax_fwd", _p(S), _p(pad_mask), B, H, n, stream or cur_stream())
 
 
 def softmax_bwd(P, dP, B: int, H: int, n: int, stream: Optional[int] = None):
-    check(_lib.load().mla_softmax_bwd(_p(P), _p(dP), B, H, n, stream or cur_stream()), "mla_softmax_bwd")
+    _call("mla_softmax_bwd", _p(P), _p(dP), B, H, n, stream or cur_stream())
 
 
 def attention_fwd(qkv, pad_mask, o, lse, B: int, H: int, n: int, hd: int, stream: Optional[int] = None):
     """o = softmax(mask(q k^T * hd^-0.5)) v, fused (models/m3ae.py:102-125); lse (B, H, n) is kept for the backward."""
-    check(_lib.load().mla_attention_fwd(_p(qkv), _p(pad_mask), _p(o), _p(lse), B, H, n, hd, stream or cur_stream()),
-          "mla_attention_fwd")
+    _call("mla_attention_fwd", _p(qkv), _p(pad_mask), _p(o), _p(lse), B, H, n, hd, stream or cur_stream())
 
 
 def attention_bwd(do, qkv, o, lse, pad_mask, dqkv, dvec, B: int, H: int, n: int, hd: int, stream: Optional[int] = None):
-    check(_lib.load().mla_attention_bwd(_p(do), _p(qkv), _p(o), _p(lse), _p(pad_mask), _p(dqkv), _p(dvec), B, H, n, hd,
-                                        stream or cur_stream()), "mla_attention_bwd")
+    _call("mla_attention_bwd", _p(do), _p(qkv), _p(o), _p(lse), _p(pad_mask), _p(dqkv), _p(dvec), B, H, n, hd, stream or cur_stream())
 
 
 def tokens_assemble(x0, table, ids, pos, type_emb, cls, B: int, L: int, D: int, stream: Optional[int] = None):
     V = table.shape[0] if table is not None else 0
-    check(_lib.load().mla_tokens_assemble(_p(x0), _p(table), _p(ids, torch.int64), _p(pos), _p(type_emb), _p(cls), B, L, D, V,
-                                          stream or cur_stream()), "mla_tokens_assemble")
+    _call("mla_tokens_assemble", _p(x0), _p(table), _p(ids, torch.int64), _p(pos), _p(type_emb), _p(cls), B, L, D, V, stream or cur_stream())
 
 
 def tokens_assemble_bwd_ws_bytes(B: int, L: int, D: int) -> int:
@@ -738,9 +655,8 @@ def tokens_assemble_bwd(dx0, colsum_all, ids, dcls, dtype, dtable, B: int, L: in
     V = dtable.shape[0] if dtable is not None else 0
     if dtable is not None and ws is None:
         ws = torch.empty(tokens_assemble_bwd_ws_bytes(B, L, D), device=dx0.device, dtype=torch.uint8)
-    check(_lib.load().mla_tokens_assemble_bwd(_p(dx0), _p(colsum_all), _p(ids, torch.int64), _p(dcls), _p(dtype), _p(dtable),
-                                              B, L, D, V, _p(ws, torch.uint8) if ws is not None else None,
-                                              ws.numel() if ws is not None else 0, stream or cur_stream()), "mla_tokens_assemble_bwd")
+    _call("mla_tokens_assemble_bwd", _p(dx0), _p(colsum_all), _p(ids, torch.int64), _p(dcls), _p(dtype), _p(dtable), B, L, D, V,
+          _p(ws, torch.uint8) if ws is not None else None, ws.numel() if ws is not None else 0, stream or cur_stream())
 
 
 def patchify(img, out, P: int = 16, transposed_hw: Optional[tuple] = None, stream: Optional[int] = None):
@@ -752,13 +668,13 @@ def patchify(img, out, P: int = 16, transposed_hw: Optional[tuple] = None, strea
         B, C = img.shape[0], 1
         H, W = transposed_hw
         tr = 1
-    check(_lib.load().mla_patchify(_p(img), _p(out), B, C, H, W, P, tr, stream or cur_stream()), "mla_patchify")
+    _call("mla_patchify", _p(img), _p(out), B, C, H, W, P, tr, stream or cur_stream())
 
 
 # ---- evaluation path ------------------------------------------------------------------------------------
 def head_logits(X, W, b, logits, stream: Optional[int] = None):
     B, D = X.shape
-    check(_lib.load().mla_head_logits(_p(X), _p(W), _p(b), _p(logits), B, D, W.shape[0], stream or cur_stream()), "mla_head_logits")
+    _call("mla_head_logits", _p(X), _p(W), _p(b), _p(logits), B, D, W.shape[0], stream or cur_stream())
 
 
 def eval_fuse(outs, labels, counts, weights_out, dynamic: bool, alphas, stream: Optional[int] = None):
@@ -766,12 +682,12 @@ def eval_fuse(outs, labels, counts, weights_out, dynamic: bool, alphas, stream: 
     B, C = outs[0].shape
     o = [_p(t) for t in outs] + [None] * (3 - M)
     al = list(alphas) + [0.0] * (3 - len(alphas))
-    check(_lib.load().mla_eval_fuse(o[0], o[1], o[2], _p(labels, torch.int64), _p(counts, torch.int32), _p(weights_out), M, B, C,
-                                    int(dynamic), al[0], al[1], al[2], stream or cur_stream()), "mla_eval_fuse")
+    _call("mla_eval_fuse", o[0], o[1], o[2], _p(labels, torch.int64), _p(counts, torch.int32), _p(weights_out), M, B, C, int(dynamic), al[0], al[1],
+          al[2], stream or cur_stream())
 
 
 def bn_invstd(var, invstd, eps: float = BN_EPS, stream: Optional[int] = None):
-    check(_lib.load().mla_bn_invstd(_p(var), _p(invstd), var.numel(), eps, stream or cur_stream()), "mla_bn_invstd")
+    _call("mla_bn_invstd", _p(var), _p(invstd), var.numel(), eps, stream or cur_stream())
 
 
 # ---- OGM / OGM-GE gradient modulation (main.py:312-410) ---------------------------------------------------------------------
@@ -779,8 +695,7 @@ def ogm_coeff(outs, labels, alpha: float, coeff, info=None, stream: Optional[int
     M = len(outs)
     B, C = outs[0].shape
     ptrs = [_p(t) for t in outs] + [None] * (3 - M)
-    check(_lib.load().mla_ogm_coeff(ptrs[0], ptrs[1], ptrs[2], _p(labels, torch.int64), M, B, C, alpha, _p(coeff), _p(info),
-                                    stream or cur_stream()), "mla_ogm_coeff")
+    _call("mla_ogm_coeff", ptrs[0], ptrs[1], ptrs[2], _p(labels, torch.int64), M, B, C, alpha, _p(coeff), _p(info), stream or cur_stream())
 
 
 def ogm_chunk_elems() -> int:
@@ -793,9 +708,8 @@ def ogm_ws_bytes(total_chunks: int, n_seg: int) -> int:
 
 def ogm_modulate(grad, seg_desc, first_chunk, n_seg: int, total_chunks: int, coeff, ge: bool, seed: int, step: int, ws,
                  stream: Optional[int] = None):
-    check(_lib.load().mla_ogm_modulate(_p(grad), _p(seg_desc, torch.int64), _p(first_chunk, torch.int32), n_seg, total_chunks,
-                                       _p(coeff), int(ge), seed, step, _p(ws, torch.uint8) if ws is not None else None,
-                                       ws.numel() if ws is not None else 0, stream or cur_stream()), "mla_ogm_modulate")
+    _call("mla_ogm_modulate", _p(grad), _p(seg_desc, torch.int64), _p(first_chunk, torch.int32), n_seg, total_chunks, _p(coeff), int(ge), seed, step,
+          _p(ws, torch.uint8) if ws is not None else None, ws.numel() if ws is not None else 0, stream or cur_stream())
 
 
 # ---- CREMA-D frame augmentation (dataset/dataset.py:128-153) --------------------------------------------------------------
@@ -810,7 +724,7 @@ def _desc_host(desc_host: torch.Tensor) -> torch.Tensor:
 def frames_check(desc_host: torch.Tensor, B: int, T: int, frames_bytes: int, out_h: int = 224, out_w: int = 224) -> None:
     """The host checks of frames_resample alone (no GPU): raises MLAHipError on a descriptor the kernel must not run."""
     d = _desc_host(desc_host)
-    check(_lib.load().mla_frames_check(d.data_ptr(), d.shape[0], B, T, frames_bytes, out_h, out_w), "mla_frames_check")
+    _call("mla_frames_check", d.data_ptr(), d.shape[0], B, T, frames_bytes, out_h, out_w)
 
 
 def frames_resample(frames: torch.Tensor, desc: torch.Tensor, desc_host: torch.Tensor, lut: torch.Tensor, out: torch.Tensor,
@@ -823,6 +737,6 @@ def frames_resample(frames: torch.Tensor, desc: torch.Tensor, desc_host: torch.T
     if tuple(lut.shape) != (3, 256) or out.dim() != 5 or out.shape[1] != 3 or out.shape[2] != T:
         raise MLAHipError(f"frames_resample: lut {tuple(lut.shape)} / out {tuple(out.shape)} do not match (3, 256) / (B, 3, {T}, H, W)")
     B, _, _, OH, OW = out.shape
-    check(_lib.load().mla_frames_resample(_p(frames, torch.uint8), frames.numel(), _p(desc, torch.int64), d.data_ptr(), _p(lut),
-                                          _p(out), d.shape[0], B, T, OH, OW, stream or cur_stream()), "mla_frames_resample")
+    _call("mla_frames_resample", _p(frames, torch.uint8), frames.numel(), _p(desc, torch.int64), d.data_ptr(), _p(lut), _p(out), d.shape[0], B, T, OH,
+          OW, stream or cur_stream())
     return out
