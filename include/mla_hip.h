@@ -177,6 +177,33 @@ int mla_conv2d_stem_wgrad_split(const float* x, const float* dy, float* dw_hwio,
 /* measurement hook: force tile 0..4 (256x128, 128x128, 128x64, 64x64, 256x64) where Cout allows; -1 = automatic */
 int mla_conv2d_split_cfg(int cfg);
 
+/* ---- convolution, single-product bf16 arithmetic (conv_math "bf16") ------------------------------
+ * y = sum bf16_rne(a) * bf16_rne(b), fp32 accumulate on v_mfma_f32_32x32x16_bf16: each operand rounded ONCE to bf16 and multiplied
+ * once -- the hi * hi product of the split set alone.  fp32 in, fp32 out, same epilogues; NOT fp32-equivalent (relative error
+ * ~2^-8 per product).  One-plane forms of the split gather-GEMM and per-tap weight-gradient kernels: a third of the LDS image, a
+ * sixth of the MFMAs.  The arithmetic is selected by calling these entry points: they read none of the process-wide hooks above,
+ * so callers of different arithmetic share a process.  Weights are converted by mla_conv2d_wimage_bf16 into
+ * mla_conv2d_wimage_bytes_bf16 of scratch, one bf16 plane [tap][n][k]: transposed = 1 for the forward, 0 for the input gradient
+ * (mla_conv2d_wimage_batch_bf16: descriptor rows as in mla_conv2d_wsplit_batch).  Cin, Cout multiples of 64.
+ * mla_conv2d_dgrad_bf16: class_mask / residual_mask as in mla_conv2d_dgrad_classes, one launch per parity class.
+ * mla_conv2d_tile_bf16 (diagnostic / test query, not needed to run the mode): the tile (index into 256x128, 128x128, 128x64, 64x64,
+ * 256x64, 192x128) a gather-GEMM of M output rows, Cout columns and k_total = taps * Cin picks ON THE CURRENT DEVICE -- the choice
+ * depends on its CU count (256 is assumed when there is no device); -1 for dims it does not take. */
+size_t mla_conv2d_wimage_bytes_bf16(int Cin, int Cout, int KH, int KW);
+int mla_conv2d_wimage_bf16(const float* w_hwio, void* wimage, int Cin, int Cout, int KH, int KW, int transposed, void* stream);
+int mla_conv2d_wimage_batch_bf16(const float* params, void* wimage, const int* desc, int n, int total_blocks, void* stream);
+int mla_conv2d_tile_bf16(int M, int Cout, int k_total);
+int mla_conv2d_fwd_bf16(const float* x, const void* wimage_t, float* y,
+                        int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                        float* bn_partial, int* bn_tiles, void* stream);
+int mla_conv2d_dgrad_bf16(const float* dy, const void* wimage, float* dx,
+                          int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                          const float* residual, const float* relu_src, int class_mask, int residual_mask, void* stream);
+size_t mla_conv2d_wgrad_ws_bytes_bf16(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+int mla_conv2d_wgrad_bf16(const float* x, const float* dy, float* dw_hwio,
+                          int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                          void* ws, size_t ws_bytes, void* stream);
+
 /* ---- BatchNorm2d, training mode (backbone.py:29, 32, 86, 128) -------------------------------- */
 /* x is [M][C] (M = N*H*W).  Statistics: either mla_bn_stats (reads x) or conv-fused partials. */
 size_t mla_bn_partial_scratch_elems(int C);   /* reduction scratch tail included in every *_partial_elems / *_ws_elems below */
@@ -324,6 +351,19 @@ int mla_linear_wgrad_split(const float* x, const float* dy, float* dw_kn, int gr
  * mla_linear_wgrad_split_ws_bytes (weight slabs + one bias row per split-K range). */
 int mla_linear_wgrad_split_bias(const float* x, const float* dy, float* dw_kn, float* dbias, int groups, int rows,
                                 int x_group_rows, int x_off, int K, int N, void* ws, size_t ws_bytes, void* stream);
+/* The same on the single-product bf16 arithmetic (see mla_conv2d_*_bf16): weights converted with
+ * mla_conv2d_wimage_bf16(w_kn, out, Cin = K, Cout = N, 1, 1, transposed, stream). */
+int mla_linear_fwd_bf16(const float* x, const void* wimage_t, const float* bias, const float* residual, float* y,
+                        float* y_gelu, int groups, int rows, int x_group_rows, int x_off, int y_group_rows, int y_off,
+                        int K, int N, void* stream);
+int mla_linear_dgrad_bf16(const float* dy, const void* wimage, float* dx, const float* residual, const float* gelu_src,
+                          int groups, int rows, int dy_group_rows, int dy_off, int dx_group_rows, int dx_off, int K, int N,
+                          void* stream);
+size_t mla_linear_wgrad_ws_bytes_bf16(int M, int K, int N);
+int mla_linear_wgrad_bf16(const float* x, const float* dy, float* dw_kn, int groups, int rows, int x_group_rows, int x_off,
+                          int K, int N, void* ws, size_t ws_bytes, void* stream);
+int mla_linear_wgrad_bias_bf16(const float* x, const float* dy, float* dw_kn, float* dbias, int groups, int rows,
+                               int x_group_rows, int x_off, int K, int N, void* ws, size_t ws_bytes, void* stream);
 /* out[c] = sum_rows x[r][c]  (bias gradients).  ws: mla_colreduce_ws_elems(M, C) floats; C % 64 == 0. */
 size_t mla_colreduce_ws_elems(int M, int C);
 int mla_colsum_rows(const float* x, float* out, float* ws, int M, int C, void* stream);

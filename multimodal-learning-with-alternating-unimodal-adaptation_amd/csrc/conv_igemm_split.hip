@@ -30,13 +30,15 @@
 // BKS = K per stage: 32 (64-B LDS rows, two MFMA k-chunks per barrier) or 16 (32-B rows, one k-chunk per barrier, half
 // the LDS: two 8-wave workgroups per CU, whose prologues / epilogues / barriers then overlap each other).
 // Chunk swizzle of row r: BKS 32: 16-B chunk q -> q ^ ((r >> 2) & 3);  BKS 16: 16-B half q -> q ^ ((r >> 3) & 1).
-template <int BM, int BN, int WM, int WN, int BKS>
+// NP = bf16 planes per operand in LDS: 3 (split arithmetic) or 1 (conv_math "bf16": a third of the image)
+template <int BM, int BN, int WM, int WN, int BKS, int NP = 3>
 struct SplitTileCfg {
   static_assert(BKS == 32 || BKS == 16, "stage depth");
   static constexpr int NT = 64 * WM * WN;
   static constexpr int MI = BM / WM / 32, NI = BN / WN / 32;
   static constexpr int LR = BKS / 2;                                  // dwords per LDS row
-  static constexpr int ASZ = 3 * BM * LR, BSZ = 3 * BN * LR;          // dwords per buffer
+  static constexpr int ASZ = NP * BM * LR, BSZ = NP * BN * LR;        // dwords per buffer
+  static_assert(2 * ASZ >= 4 * WM * BN, "the epilogue's reduction scratch lives in the A buffers");
 };
 
 template <int BM>
@@ -59,7 +61,7 @@ __device__ __forceinline__ void fill_rowinfo(int4* rowinfo, const IGemmGeom& g, 
 
 // One output tile (tm, tn) of the geometry g: rowinfo, K loop over its T * (C / BKS) stages, epilogue.  A device function so that one launch
 // can serve several geometries (igemm_split_classes_kernel: the parity classes of a stride-2 input gradient).
-template <int BM, int BN, int WM, int WN, int TERMS, int BKS>
+template <int BM, int BN, int WM, int WN, int TERMS, int BKS, int NP = 3>
 __device__ __forceinline__ void igemm_split_tile(const float* __restrict__ X, const void* __restrict__ Wsp, float* Y, const float* R,
                                                  const float* MASK, float* __restrict__ part, const float* __restrict__ BIAS,
                                                  float* __restrict__ Y2, const IGemmGeom& g, unsigned* As, unsigned* Bs, int4* rowinfo,
@@ -74,7 +76,7 @@ __device__ __forceinline__ void igemm_split_tile(const float* __restrict__ X, co
   constexpr bool BPART = BN < BROWS;                           // only the first BN*4 threads stage B
   constexpr int NKK = BKS / 16;                                // MFMA k-chunks per stage
   static_assert(APASS >= 1 && AROWS % 16 == 0 && (BN % BROWS == 0 || BPART), "tile / workgroup mismatch");
-  constexpr int ASZ = 3 * BM * LR, BSZ = 3 * BN * LR;          // dwords per buffer
+  constexpr int ASZ = NP * BM * LR, BSZ = NP * BN * LR;        // dwords per buffer
   typedef typename std::conditional<BKS == 32, u32x4, u32x2>::type bchunk_t;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -95,9 +97,9 @@ __device__ __forceinline__ void igemm_split_tile(const float* __restrict__ X, co
   const int nIter = g.T * (gC / BKS);   // K stages: taps x channel chunks
   const unsigned plane_bytes = g.w_bytes / 2;   // one bf16 plane of the whole weight tensor
 
-  struct Stage { f32x4 a[APASS]; bchunk_t b[3][BPASS]; };   // one K stage of both operands in registers, on its way to LDS
+  struct Stage { f32x4 a[APASS]; bchunk_t b[NP][BPASS]; };   // one K stage of both operands in registers, on its way to LDS
   Stage rs0;
-  const rsrc_t xr = make_rsrc(X, g.x_bytes), wr = make_rsrc(Wsp, 3 * plane_bytes);
+  const rsrc_t xr = make_rsrc(X, g.x_bytes), wr = make_rsrc(Wsp, NP * plane_bytes);
   const int arow = tid / ACH, ac = tid % ACH;       // A: row within a pass, float4 chunk
   const int brow = tid >> 2, bq = tid & 3;          // B: row within a pass, chunk
   const bool bact = !BPART || tid < BN * 4;         // wave-uniform (BN*4 is a multiple of 64)
@@ -132,7 +134,7 @@ __device__ __forceinline__ void igemm_split_tile(const float* __restrict__ X, co
     const unsigned wsoff = (unsigned)(((tap_wt(tp) * gCO + tn * BN) * gC + c0) * 2);        // wave-uniform
     if (bact) {
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
+      for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
         for (int p = 0; p < BPASS; ++p) {
           if constexpr (BKS == 32) rs.b[pl][p] = buf_load4u(wr, boff[p], wsoff + pl * plane_bytes);
@@ -149,10 +151,10 @@ __device__ __forceinline__ void igemm_split_tile(const float* __restrict__ X, co
     unsigned* Ad = As + buf * ASZ + a_st;
     unsigned* Bd = Bs + buf * BSZ + b_st;
 #pragma unroll
-    for (int p = 0; p < APASS; ++p) split_store4(Ad + p * AROWS * LR, BM * LR, rs.a[p]);
+    for (int p = 0; p < APASS; ++p) split_store4<NP>(Ad + p * AROWS * LR, BM * LR, rs.a[p]);
     if (bact) {
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
+      for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
         for (int p = 0; p < BPASS; ++p)
           *reinterpret_cast<bchunk_t*>(Bd + (pl * BN + p * BROWS) * LR) = rs.b[pl][p];
@@ -162,11 +164,11 @@ __device__ __forceinline__ void igemm_split_tile(const float* __restrict__ X, co
   const int i = lane & 31, h = lane >> 5;
   const int swz = BKS == 32 ? (i >> 2) & 3 : (i >> 3) & 1;
   const int a_rd = (wm * (BM / WM) + i) * LR, b_rd = (wn * (BN / WN) + i) * LR;
-  auto load_frags = [&](int buf, int kk, SplitFrags<MI, NI>& f) {
+  auto load_frags = [&](int buf, int kk, SplitFrags<MI, NI, NP>& f) {
     load_split_frags<BM, BN, LR>(As + buf * ASZ + a_rd + frag_koff(kk, h, swz), Bs + buf * BSZ + b_rd + frag_koff(kk, h, swz), f);
   };
-  auto mma_frags = [&](const SplitFrags<MI, NI>& f) { split_mma<TERMS>(f.a, f.b, acc); };
-  SplitFrags<MI, NI> f0, f1;
+  auto mma_frags = [&](const SplitFrags<MI, NI, NP>& f) { split_mma<TERMS>(f.a, f.b, acc); };
+  SplitFrags<MI, NI, NP> f0, f1;
 
   if (nIter > 0) {  // nIter == 0: a dgrad parity class no tap reaches (1x1 stride 2): epilogue only
     load_tiles(rs0);
@@ -188,8 +190,11 @@ __device__ __forceinline__ void igemm_split_tile(const float* __restrict__ X, co
   // prologue / epilogue are exposed with one workgroup per CU (~10 us per tile round on the 1x1 convs).
   int it = 0;
   for (; it + 2 < nIter; ++it) {
-    __builtin_amdgcn_iglp_opt(1);   // the compiler's single-wave small-GEMM interleave of DS / VMEM / MFMA for this block: -1.7 % (same-box A/B;
-                                    // strategy 0, the multi-wave one, +0.8 %)
+    // The compiler's single-wave small-GEMM interleave of DS / VMEM / MFMA for this block: -1.7 % (same-box A/B; strategy 0, the
+    // multi-wave one, +0.8 %).  Three planes only: with NP = 1 (one MFMA per fragment pair) the device compile of this file did not
+    // finish within 40 minutes and was killed (hipcc of ROCm 7.2.0, AMD clang 22.0.0git roc-7.2.0 26014, -O3, gfx950); without the
+    // hint it takes 40 s.  Not reduced further; the one-plane loop gets the default schedule.
+    if constexpr (NP == 3) __builtin_amdgcn_iglp_opt(1);
     const int cur = it & 1;
     load_frags(cur, 0, f0);
     if constexpr (NKK == 2) load_frags(cur, 1, f1);   // both halves' fragments in flight before the first MFMA
@@ -219,12 +224,12 @@ __device__ __forceinline__ void igemm_split_tile(const float* __restrict__ X, co
   igemm_epilogue<BM, BN, WM, WN>(acc, rowinfo, reinterpret_cast<float*>(As), Y, R, MASK, part, BIAS, Y2, g, tm, tn);
 }
 
-template <int BM, int BN, int WM, int WN, int TERMS, int BKS, int WPE>
+template <int BM, int BN, int WM, int WN, int TERMS, int BKS, int WPE, int NP = 3>
 __global__ __launch_bounds__(64 * WM * WN, WPE) void igemm_split_kernel(const float* __restrict__ X, const void* __restrict__ Wsp,
                                                                          float* Y, const float* R, const float* MASK,
                                                                          float* __restrict__ part, const float* __restrict__ BIAS,
                                                                          float* __restrict__ Y2, const IGemmGeom g) {
-  typedef SplitTileCfg<BM, BN, WM, WN, BKS> C;
+  typedef SplitTileCfg<BM, BN, WM, WN, BKS, NP> C;
   __shared__ __attribute__((aligned(16))) unsigned As[2 * C::ASZ];
   __shared__ __attribute__((aligned(16))) unsigned Bs[2 * C::BSZ];
   __shared__ int4 rowinfo[BM];  // {n*H*W or -1, oy*sy, ox*sx, output pixel index}
@@ -232,7 +237,7 @@ __global__ __launch_bounds__(64 * WM * WN, WPE) void igemm_split_kernel(const fl
   const int gridN = g.CO / BN;
   int tm, tn;
   tile_coords(wg, (int)gridDim.x / gridN, gridN, tm, tn);
-  igemm_split_tile<BM, BN, WM, WN, TERMS, BKS>(X, Wsp, Y, R, MASK, part, BIAS, Y2, g, As, Bs, rowinfo, tm, tn);
+  igemm_split_tile<BM, BN, WM, WN, TERMS, BKS, NP>(X, Wsp, Y, R, MASK, part, BIAS, Y2, g, As, Bs, rowinfo, tm, tn);
 }
 
 // The output parity classes of a stride-2 input gradient in ONE launch.  Each class is its own gather-GEMM (1, 2, 2 and 4 of the nine
@@ -274,7 +279,7 @@ __global__ __launch_bounds__(64 * WM * WN, WPE) void igemm_split_classes_kernel(
 // WGS_CHUNK pixels; partial slabs and the ordered reduce are those of the fp32 kernel (conv_igemm.hip).
 // ---------------------------------------------------------------------------------------------
 #define WGS_CHUNK 2048
-template <int BI, int BJ, int WI, int WJ>
+template <int BI, int BJ, int WI, int WJ, int NP = 3>
 __global__ __launch_bounds__(64 * WI * WJ, 1) void wgrad_split_kernel(const float* __restrict__ X, const float* __restrict__ dY,
                                                                         float* __restrict__ part, const IGemmGeom g, int span,
                                                                         float* __restrict__ bias_part = nullptr) {
@@ -285,7 +290,8 @@ __global__ __launch_bounds__(64 * WI * WJ, 1) void wgrad_split_kernel(const floa
   constexpr int YG = NT / (BJ / 4), YPX = BK / YG;
   static_assert((XPX == 4 || XPX == 2) && (YPX == 4 || YPX == 2), "tile / workgroup mismatch");
   constexpr int LR = BK / 2;                             // dwords per LDS row
-  constexpr int ASZ = 3 * BI * LR, BSZ = 3 * BJ * LR;
+  constexpr int ASZ = NP * BI * LR, BSZ = NP * BJ * LR;
+  static_assert(2 * ASZ >= (NT / (BJ / 4)) * BJ, "the bias reduction's scratch lives in the A buffers");
   __shared__ __attribute__((aligned(16))) unsigned As[2 * ASZ];
   __shared__ __attribute__((aligned(16))) unsigned Bs[2 * BSZ];
   __shared__ unsigned rowoff[WGS_CHUNK];   // (64x64 tile with half the chunk = three workgroups per CU: 7-17 % slower, measured)
@@ -325,11 +331,11 @@ __global__ __launch_bounds__(64 * WI * WJ, 1) void wgrad_split_kernel(const floa
   const int i = lane & 31, h = lane >> 5, swz = (i >> 2) & 3;
   const int a_rd = (wi * (BI / WI) + i) * LR, b_rd = (wj * (BJ / WJ) + i) * LR;
 
-  auto load_frags = [&](int buf, int kk, SplitFrags<MI, NI>& f) {
+  auto load_frags = [&](int buf, int kk, SplitFrags<MI, NI, NP>& f) {
     load_split_frags<BI, BJ, LR>(As + buf * ASZ + a_rd + frag_koff(kk, h, swz), Bs + buf * BSZ + b_rd + frag_koff(kk, h, swz), f);
   };
-  auto mma_frags = [&](const SplitFrags<MI, NI>& f) { split_mma<6>(f.a, f.b, acc); };
-  SplitFrags<MI, NI> f0, f1;
+  auto mma_frags = [&](const SplitFrags<MI, NI, NP>& f) { split_mma<NP == 3 ? 6 : 1>(f.a, f.b, acc); };
+  SplitFrags<MI, NI, NP> f0, f1;
 
   const bool do_bias = bias_part != nullptr && ti == 0 && t == 0;   // one workgroup per (column tile, pixel range)
   f32x4 bacc = {0.f, 0.f, 0.f, 0.f};
@@ -369,7 +375,9 @@ __global__ __launch_bounds__(64 * WI * WJ, 1) void wgrad_split_kernel(const floa
       for (int e = 0; e < 4; ++e) {   // channel row 4c+e
         unsigned* dst = base + e * LR;
         if constexpr (PX == 4) {
-          split_store4(dst, plane_rows * LR, f32x4{reg[0][e], reg[1][e], reg[2][e], reg[3][e]});
+          split_store4<NP>(dst, plane_rows * LR, f32x4{reg[0][e], reg[1][e], reg[2][e], reg[3][e]});
+        } else if constexpr (NP == 1) {
+          dst[0] = cvt_pk_bf16(reg[0][e], reg[1][e]);
         } else {
           unsigned h0, m0, l0;
           split_pair<true>(reg[0][e], reg[1][e], h0, m0, l0);
@@ -450,7 +458,8 @@ __global__ __launch_bounds__(64 * WI * WJ, 1) void wgrad_split_kernel(const floa
 }
 
 // out[plane][t][n][k] (bf16): transposed = 1: n = co, k = ci (forward conv); 0: n = ci, k = co (input gradient).
-// in is HWIO fp32 [t][ci][co].  One 32x32 (ci x co) tile of one tap per workgroup.
+// in is HWIO fp32 [t][ci][co].  One 32x32 (ci x co) tile of one tap per workgroup.  NP = 1: the hi plane alone, [t][n][k].
+template <int NP = 3>
 __device__ __forceinline__ void weight_split_tile(const float* __restrict__ in, unsigned short* __restrict__ out, int T, int CI,
                                                   int CO, int transposed, int t, int ci0, int co0, float (*tile)[33]) {
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 256 threads: 32 x 8
@@ -467,22 +476,28 @@ __device__ __forceinline__ void weight_split_tile(const float* __restrict__ in, 
     if (transposed) { co = co0 + r; ci = ci0 + tx; v = tile[tx][r]; o = ((size_t)t * CO + co) * CI + ci; }
     else            { ci = ci0 + r; co = co0 + tx; v = tile[r][tx]; o = ((size_t)t * CI + ci) * CO + co; }
     if (ci < CI && co < CO) {
-      unsigned hi, mid, lo;
-      split_pair(v, 0.f, hi, mid, lo);
-      out[o] = (unsigned short)hi;
-      out[plane + o] = (unsigned short)mid;
-      out[2 * plane + o] = (unsigned short)lo;
+      if constexpr (NP == 1) {
+        out[o] = (unsigned short)cvt_pk_bf16(v, 0.f);
+      } else {
+        unsigned hi, mid, lo;
+        split_pair(v, 0.f, hi, mid, lo);
+        out[o] = (unsigned short)hi;
+        out[plane + o] = (unsigned short)mid;
+        out[2 * plane + o] = (unsigned short)lo;
+      }
     }
   }
 }
 
+template <int NP = 3>
 __global__ __launch_bounds__(256) void weight_split_kernel(const float* __restrict__ in, unsigned short* __restrict__ out,
                                                             int T, int CI, int CO, int transposed) {
   __shared__ float tile[32][33];
-  weight_split_tile(in, out, T, CI, CO, transposed, blockIdx.z, blockIdx.y * 32, blockIdx.x * 32, tile);
+  weight_split_tile<NP>(in, out, T, CI, CO, transposed, blockIdx.z, blockIdx.y * 32, blockIdx.x * 32, tile);
 }
 
 // Every conv of an encoder in one launch: desc[j] = {w_off, out_off, T, CI, CO, transposed, first_block, -} (device memory)
+template <int NP = 3>
 __global__ __launch_bounds__(256) void weight_split_batch_kernel(const float* __restrict__ params, unsigned short* __restrict__ out,
                                                                   const int* __restrict__ desc, int n) {
   __shared__ float tile[32][33];
@@ -499,7 +514,7 @@ __global__ __launch_bounds__(256) void weight_split_batch_kernel(const float* __
   const int bx = lb % tc; lb /= tc;
   const int by = lb % tr; lb /= tr;
   if (lb >= T) return;
-  weight_split_tile(params + d[0], out + d[1], T, CI, CO, d[5], lb, by * 32, bx * 32, tile);
+  weight_split_tile<NP>(params + d[0], out + d[1], T, CI, CO, d[5], lb, by * 32, bx * 32, tile);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -664,7 +679,7 @@ extern "C" int mla_conv2d_wsplit(const float* w, void* wsplit, int Cin, int Cout
                                  void* stream) {
   MLA_REQUIRE(w && wsplit, "mla_conv2d_wsplit: null pointer");
   MLA_REQUIRE(Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && KH * KW <= MAX_TAPS, "mla_conv2d_wsplit: bad dims");
-  weight_split_kernel<<<dim3(cdiv(Cout, 32), cdiv(Cin, 32), KH * KW), 256, 0, (hipStream_t)stream>>>(
+  weight_split_kernel<3><<<dim3(cdiv(Cout, 32), cdiv(Cin, 32), KH * KW), 256, 0, (hipStream_t)stream>>>(
       w, (unsigned short*)wsplit, KH * KW, Cin, Cout, transposed ? 1 : 0);
   MLA_CHECK_LAUNCH("weight_split_kernel");
   return MLA_OK;
@@ -673,7 +688,7 @@ extern "C" int mla_conv2d_wsplit(const float* w, void* wsplit, int Cin, int Cout
 extern "C" int mla_conv2d_wsplit_batch(const float* params, void* wsplit, const int* desc, int n, int total_blocks, void* stream) {
   MLA_REQUIRE(params && wsplit && desc, "mla_conv2d_wsplit_batch: null pointer");
   MLA_REQUIRE(n > 0 && n <= 4096 && total_blocks > 0, "mla_conv2d_wsplit_batch: n=%d (1..4096), total_blocks=%d", n, total_blocks);
-  weight_split_batch_kernel<<<total_blocks, 256, 0, (hipStream_t)stream>>>(params, (unsigned short*)wsplit, desc, n);
+  weight_split_batch_kernel<3><<<total_blocks, 256, 0, (hipStream_t)stream>>>(params, (unsigned short*)wsplit, desc, n);
   MLA_CHECK_LAUNCH("weight_split_batch_kernel");
   return MLA_OK;
 }
@@ -958,4 +973,151 @@ extern "C" int mla_linear_wgrad_split_bias(const float* x, const float* dy, floa
       wgrad_split_kernel<64, 64, 2, 2><<<dim3((K / 64) * (N / 64), splits), 256, 0, st>>>(x, dy, part, g, span, bias_part);
     }
   });
+}
+
+// ---------------------------------------------------------------------------------------------
+// conv_math "bf16": y = sum bf16(a) * bf16(b), the hi * hi product of the split set alone, on the one-plane forms of the kernels
+// above (one v_cvt_pk_bf16_f32 per staged pair, one LDS plane per operand, one MFMA per fragment pair).  Selected per call: these
+// entry points read none of the process-wide measurement hooks, so models of different arithmetic share a process and run on
+// different streams.  Plain gather-GEMM and per-tap weight gradient only (no LDS-patch kernel, no merged stride-2 classes, no
+// two-phase launch, no BatchNorm fold / reduction epilogue, no transposing weight-gradient kernels).
+// ---------------------------------------------------------------------------------------------
+// Tile choice: the split table as it stands.  Its per_cu (residency with three planes in LDS), launch-bounds waves and SPLIT_EFF were
+// all measured on the six-product kernels; with a third of the LDS image more workgroups fit and the MFMA share of a K step is a sixth,
+// so the ranking best_scfg forms from them is NOT measured for this mode.  No entry was added or re-weighted without a measurement.
+static int pick_scfg_bf16(long M, int CO, int k_total) {   // pick_scfg without the forced-tile hook
+  if (k_total <= 512 && M <= (1L << 18)) return SCFG_64x64;
+  return best_scfg(M, CO);
+}
+extern "C" int mla_conv2d_tile_bf16(int M, int Cout, int k_total) {
+  return (M > 0 && Cout > 0 && Cout % 64 == 0) ? pick_scfg_bf16(M, Cout, k_total) : -1;
+}
+
+static int launch_bf16(const float* X, const void* Wimg, float* Y, const float* R, const float* MASK, float* part, const IGemmGeom& mg,
+                       int cfg, hipStream_t st, const float* BIAS = nullptr, float* Y2 = nullptr, int* row_tiles = nullptr) {
+  const int total = cdiv(mg.M - mg.m0, SCFG[cfg].bm) * (mg.CO / SCFG[cfg].bn);
+  if (row_tiles) *row_tiles = cdiv(mg.M, SCFG[cfg].bm);
+  if (total <= 0) return MLA_OK;
+  with_scfg(cfg, [&](auto c) {
+    constexpr SplitTile t = SCFG[decltype(c)::value];
+    igemm_split_kernel<t.bm, t.bn, t.wm, t.wn, 1, t.bks, t.wpe, 1><<<total, t.threads(), 0, st>>>(X, Wimg, Y, R, MASK, part, BIAS, Y2, mg);
+  });
+  MLA_CHECK_LAUNCH("igemm_split_kernel (one plane)");
+  return MLA_OK;
+}
+
+extern "C" size_t mla_conv2d_wimage_bytes_bf16(int Cin, int Cout, int KH, int KW) {
+  return (size_t)KH * KW * Cin * Cout * sizeof(unsigned short);
+}
+
+extern "C" int mla_conv2d_wimage_bf16(const float* w, void* wimage, int Cin, int Cout, int KH, int KW, int transposed, void* stream) {
+  MLA_REQUIRE(w && wimage, "mla_conv2d_wimage_bf16: null pointer");
+  MLA_REQUIRE(Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && KH * KW <= MAX_TAPS, "mla_conv2d_wimage_bf16: bad dims");
+  weight_split_kernel<1><<<dim3(cdiv(Cout, 32), cdiv(Cin, 32), KH * KW), 256, 0, (hipStream_t)stream>>>(
+      w, (unsigned short*)wimage, KH * KW, Cin, Cout, transposed ? 1 : 0);
+  MLA_CHECK_LAUNCH("weight_split_kernel (one plane)");
+  return MLA_OK;
+}
+
+extern "C" int mla_conv2d_wimage_batch_bf16(const float* params, void* wimage, const int* desc, int n, int total_blocks, void* stream) {
+  MLA_REQUIRE(params && wimage && desc, "mla_conv2d_wimage_batch_bf16: null pointer");
+  MLA_REQUIRE(n > 0 && n <= 4096 && total_blocks > 0, "mla_conv2d_wimage_batch_bf16: n=%d (1..4096), total_blocks=%d", n, total_blocks);
+  weight_split_batch_kernel<1><<<total_blocks, 256, 0, (hipStream_t)stream>>>(params, (unsigned short*)wimage, desc, n);
+  MLA_CHECK_LAUNCH("weight_split_batch_kernel (one plane)");
+  return MLA_OK;
+}
+
+extern "C" int mla_conv2d_fwd_bf16(const float* x, const void* wimage_t, float* y, int N, int H, int W, int Cin, int Cout, int KH, int KW,
+                                   int stride, int pad, float* bn_partial, int* bn_tiles, void* stream) {
+  if (int rc = check_conv("mla_conv2d_fwd_bf16", N, H, W, Cin, Cout, KH, KW, stride, pad)) return rc;
+  MLA_REQUIRE(Cin % 64 == 0, "mla_conv2d_fwd_bf16: Cin=%d must be a multiple of 64 (the stem keeps its own kernels)", Cin);
+  MLA_REQUIRE(x && wimage_t && y, "mla_conv2d_fwd_bf16: null pointer");
+  IGemmGeom g;
+  make_fwd_geom(g, N, H, W, Cin, Cout, KH, KW, stride, pad);
+  MLA_REQUIRE(g.OH > 0 && g.OW > 0, "mla_conv2d_fwd_bf16: empty output");
+  return launch_bf16(x, wimage_t, y, nullptr, nullptr, bn_partial, g, pick_scfg_bf16(g.M, Cout, KH * KW * Cin), (hipStream_t)stream, nullptr,
+                     nullptr, bn_tiles);
+}
+
+extern "C" int mla_conv2d_dgrad_bf16(const float* dy, const void* wimage, float* dx, int N, int H, int W, int Cin, int Cout, int KH, int KW,
+                                     int stride, int pad, const float* residual, const float* relu_src, int class_mask, int residual_mask,
+                                     void* stream) {
+  if (int rc = check_conv("mla_conv2d_dgrad_bf16", N, H, W, Cin, Cout, KH, KW, stride, pad)) return rc;
+  MLA_REQUIRE(Cin % 64 == 0, "mla_conv2d_dgrad_bf16: Cin=%d must be a multiple of 64 (the stem needs no dgrad)", Cin);
+  MLA_REQUIRE(dy && wimage && dx, "mla_conv2d_dgrad_bf16: null pointer");
+  const int tiles = 0;
+  return for_dgrad_classes("mla_conv2d_dgrad_bf16", N, H, W, Cin, Cout, KH, KW, stride, pad, residual, class_mask, residual_mask, nullptr, 0,
+                           tiles, [&](int, IGemmGeom& g, const float* res) {
+    return launch_bf16(dy, wimage, dx, res, relu_src, nullptr, g, pick_scfg_bf16(g.M, Cin, KH * KW == 1 ? Cout : 1 << 30), (hipStream_t)stream);
+  });
+}
+
+template <typename... A>
+static void launch_wgrad_bf16(int K, int N, int taps, int splits, hipStream_t st, A... a) {
+  if (K % 128 == 0 && N % 128 == 0) wgrad_split_kernel<128, 128, 2, 4, 1><<<dim3((K / 128) * (N / 128) * taps, splits), 512, 0, st>>>(a...);
+  else wgrad_split_kernel<64, 64, 2, 2, 1><<<dim3((K / 64) * (N / 64) * taps, splits), 256, 0, st>>>(a...);
+}
+
+extern "C" size_t mla_conv2d_wgrad_ws_bytes_bf16(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+  const long M = (long)N * conv_out(H, KH, stride, pad) * conv_out(W, KW, stride, pad);
+  int span, splits;
+  wgrad_split_plan(M, Cin, Cout, KH * KW, &span, &splits);
+  return (size_t)splits * KH * KW * Cin * Cout * sizeof(float);
+}
+
+extern "C" int mla_conv2d_wgrad_bf16(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin, int Cout, int KH, int KW,
+                                     int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_conv("mla_conv2d_wgrad_bf16", N, H, W, Cin, Cout, KH, KW, stride, pad)) return rc;
+  MLA_REQUIRE(Cin % 64 == 0, "mla_conv2d_wgrad_bf16: Cin=%d must be a multiple of 64 (the stem keeps its own kernels)", Cin);
+  MLA_REQUIRE(x && dy && dw && ws, "mla_conv2d_wgrad_bf16: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  IGemmGeom g;
+  make_fwd_geom(g, N, H, W, Cin, Cout, KH, KW, stride, pad);
+  g.y_bytes = (unsigned)((size_t)g.M * Cout * 4);
+  return wgrad_slabs("mla_conv2d_wgrad_bf16", "wgrad_split_kernel (one plane)", wgrad_split_plan, g.M, Cin, Cout, g.T, ws, ws_bytes, dw, nullptr,
+                     st, [&](float* part, float*, int span, int splits) {
+    launch_wgrad_bf16(Cin, Cout, g.T, splits, st, x, dy, part, g, span, (float*)nullptr);
+  });
+}
+
+extern "C" int mla_linear_fwd_bf16(const float* x, const void* wimage_t, const float* bias, const float* residual, float* y, float* y_gelu,
+                                   int groups, int rows, int x_group_rows, int x_off, int y_group_rows, int y_off, int K, int N,
+                                   void* stream) {
+  MLA_REQUIRE(x && wimage_t && y, "mla_linear_fwd_bf16: null pointer");
+  IGemmGeom g;
+  if (int rc = linear_geom("mla_linear_fwd_bf16", g, groups, rows, x_group_rows, x_off, y_group_rows, y_off, K, N)) return rc;
+  return launch_bf16(x, wimage_t, y, residual, nullptr, nullptr, g, pick_scfg_bf16(g.M, N, 1 << 30), (hipStream_t)stream, bias, y_gelu);
+}
+
+extern "C" int mla_linear_dgrad_bf16(const float* dy, const void* wimage, float* dx, const float* residual, const float* gelu_src, int groups,
+                                     int rows, int dy_group_rows, int dy_off, int dx_group_rows, int dx_off, int K, int N, void* stream) {
+  MLA_REQUIRE(dy && wimage && dx, "mla_linear_dgrad_bf16: null pointer");
+  IGemmGeom g;   // GEMM: [M][N] x [N][K] -> [M][K]
+  if (int rc = linear_geom("mla_linear_dgrad_bf16", g, groups, rows, dy_group_rows, dy_off, dx_group_rows, dx_off, N, K)) return rc;
+  g.epi = 1;
+  return launch_bf16(dy, wimage, dx, residual, gelu_src, nullptr, g, pick_scfg_bf16(g.M, K, 1 << 30), (hipStream_t)stream);
+}
+
+extern "C" size_t mla_linear_wgrad_ws_bytes_bf16(int M, int K, int N) {
+  int span, splits;
+  wgrad_split_plan(M, K, N, 1, &span, &splits);
+  return (size_t)splits * K * N * sizeof(float) + (size_t)splits * N * sizeof(float);     // weight slabs + bias rows
+}
+
+extern "C" int mla_linear_wgrad_bias_bf16(const float* x, const float* dy, float* dw_kn, float* dbias, int groups, int rows, int x_group_rows,
+                                          int x_off, int K, int N, void* ws, size_t ws_bytes, void* stream) {
+  MLA_REQUIRE(x && dy && dw_kn && ws, "mla_linear_wgrad_bf16: null pointer");
+  IGemmGeom g;
+  if (int rc = linear_geom("mla_linear_wgrad_bf16", g, groups, rows, x_group_rows, x_off, rows, 0, K, N)) return rc;
+  g.y_bytes = (unsigned)((size_t)g.M * N * 4);
+  hipStream_t st = (hipStream_t)stream;
+  return wgrad_slabs("mla_linear_wgrad_bf16", "wgrad_split_kernel (one plane)", wgrad_split_plan, g.M, K, N, 1, ws, ws_bytes, dw_kn, dbias, st,
+                     [&](float* part, float* bias_part, int span, int splits) {
+    launch_wgrad_bf16(K, N, 1, splits, st, x, dy, part, g, span, bias_part);
+  });
+}
+
+extern "C" int mla_linear_wgrad_bf16(const float* x, const float* dy, float* dw_kn, int groups, int rows, int x_group_rows, int x_off, int K,
+                                     int N, void* ws, size_t ws_bytes, void* stream) {
+  return mla_linear_wgrad_bias_bf16(x, dy, dw_kn, nullptr, groups, rows, x_group_rows, x_off, K, N, ws, ws_bytes, stream);
 }

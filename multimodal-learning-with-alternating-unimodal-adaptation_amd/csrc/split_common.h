@@ -73,14 +73,17 @@ __device__ __forceinline__ void zero_acc(T (&acc)[N]) {   // f32x16[N], f32x16[M
 
 // The product group of one 16-deep k-chunk: acc += sum over the first TERMS products of a[TERM_A] * b[TERM_B], planes as
 // bf16x8_t or as the u32x4 they were read as.  Product order, then mi, then ni: the summation order the bit-exact tests fix.
-template <int TERMS, typename AT, typename BT>
-__device__ __forceinline__ void split_mma(const AT (&a)[3], const BT (&b)[3], f32x16& acc) {
+// NP = planes held per operand: 3, or 1 with TERMS = 1 (conv_math "bf16": hi * hi alone, one MFMA per fragment pair).
+template <int TERMS, typename AT, typename BT, int NP>
+__device__ __forceinline__ void split_mma(const AT (&a)[NP], const BT (&b)[NP], f32x16& acc) {
+  static_assert(NP == 3 || (NP == 1 && TERMS == 1), "one plane holds the hi * hi product only");
 #pragma unroll
   for (int term = 0; term < TERMS; ++term)
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a[TERM_A[term]]), as_bf16x8(b[TERM_B[term]]), acc, 0, 0, 0);
 }
-template <int TERMS, int MI, int NI, typename AT, typename BT>
-__device__ __forceinline__ void split_mma(const AT (&a)[3][MI], const BT (&b)[3][NI], f32x16 (&acc)[MI][NI]) {
+template <int TERMS, int MI, int NI, typename AT, typename BT, int NP>
+__device__ __forceinline__ void split_mma(const AT (&a)[NP][MI], const BT (&b)[NP][NI], f32x16 (&acc)[MI][NI]) {
+  static_assert(NP == 3 || (NP == 1 && TERMS == 1), "one plane holds the hi * hi product only");
 #pragma unroll
   for (int term = 0; term < TERMS; ++term)
 #pragma unroll
@@ -90,8 +93,14 @@ __device__ __forceinline__ void split_mma(const AT (&a)[3][MI], const BT (&b)[3]
         acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a[TERM_A[term]][mi]), as_bf16x8(b[TERM_B[term]][ni]), acc[mi][ni], 0, 0, 0);
 }
 
-// Four consecutive k of one row -> 8 B in each of the three bf16 planes (`plane` dwords apart)
+// Four consecutive k of one row -> 8 B in each of the three bf16 planes (`plane` dwords apart); NP = 1: the hi plane alone,
+// one conversion per pair and no residuals
+template <int NP = 3>
 __device__ __forceinline__ void split_store4(unsigned* dst, int plane, f32x4 v) {
+  if constexpr (NP == 1) {
+    *reinterpret_cast<u32x2*>(dst) = u32x2{cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3])};
+    return;
+  }
   unsigned h0, m0, l0, h1, m1, l1;
   split_pair<true>(v[0], v[1], h0, m0, l0);
   split_pair<true>(v[2], v[3], h1, m1, l1);
@@ -102,15 +111,15 @@ __device__ __forceinline__ void split_store4(unsigned* dst, int plane, f32x4 v) 
 
 // MFMA operand fragments out of an LDS plane image [rows][LR dwords] (one ds_read_b128 each).  Lane (i, h) holds
 // k = kk * 16 + 8 h .. + 7 of row / column i; frag_koff is that chunk's dword offset in a row whose swizzle key is swz.
-template <int MI, int NI>
-struct SplitFrags { bf16x8_t a[3][MI], b[3][NI]; };
+template <int MI, int NI, int NP = 3>
+struct SplitFrags { bf16x8_t a[NP][MI], b[NP][NI]; };
 __device__ __forceinline__ bf16x8_t lds_frag(const unsigned* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(p)); }
 __device__ __forceinline__ int frag_koff(int kk, int h, int swz) { return ((kk * 2 + h) ^ swz) << 2; }
 // Ar / Br: this lane's chunk in plane 0, block 0 of images with BM / BN rows per plane
-template <int BM, int BN, int LR, int MI, int NI>
-__device__ __forceinline__ void load_split_frags(const unsigned* Ar, const unsigned* Br, SplitFrags<MI, NI>& f) {
+template <int BM, int BN, int LR, int MI, int NI, int NP>
+__device__ __forceinline__ void load_split_frags(const unsigned* Ar, const unsigned* Br, SplitFrags<MI, NI, NP>& f) {
 #pragma unroll
-  for (int pl = 0; pl < 3; ++pl) {
+  for (int pl = 0; pl < NP; ++pl) {
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) f.a[pl][mi] = lds_frag(Ar + (pl * BM + mi * 32) * LR);
 #pragma unroll

@@ -61,6 +61,14 @@ PROTOTYPES = {
     "mla_conv2d_stem_wgrad_split_ws_bytes": (_Z, [_I]),
     "mla_conv2d_stem_wgrad_split": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _Z, _P]),
     "mla_conv2d_split_cfg": (_I, [_I]),
+    "mla_conv2d_wimage_bytes_bf16": (_Z, [_I] * 4),
+    "mla_conv2d_wimage_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "mla_conv2d_wimage_batch_bf16": (_I, [_P, _P, _P, _I, _I, _P]),
+    "mla_conv2d_tile_bf16": (_I, [_I, _I, _I]),
+    "mla_conv2d_fwd_bf16": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _P, _P]),
+    "mla_conv2d_dgrad_bf16": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _P, _I, _I, _P]),
+    "mla_conv2d_wgrad_ws_bytes_bf16": (_Z, [_I] * 9),
+    "mla_conv2d_wgrad_bf16": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _Z, _P]),
     "mla_bn_partial_scratch_elems": (_Z, [_I]),
     "mla_bn_stats_partial_elems": (_Z, [_I, _I]),
     "mla_bn_stats_partial": (_I, [_P, _I, _I, _P, _P, _P]),
@@ -104,6 +112,11 @@ PROTOTYPES = {
     "mla_linear_wgrad_split_ws_bytes": (_Z, [_I, _I, _I]),
     "mla_linear_wgrad_split": (_I, [_P, _P, _P] + [_I] * 6 + [_P, _Z, _P]),
     "mla_linear_wgrad_split_bias": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    "mla_linear_fwd_bf16": (_I, [_P] * 6 + [_I] * 8 + [_P]),
+    "mla_linear_dgrad_bf16": (_I, [_P] * 5 + [_I] * 8 + [_P]),
+    "mla_linear_wgrad_ws_bytes_bf16": (_Z, [_I, _I, _I]),
+    "mla_linear_wgrad_bf16": (_I, [_P, _P, _P] + [_I] * 6 + [_P, _Z, _P]),
+    "mla_linear_wgrad_bias_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "mla_colreduce_ws_elems": (_Z, [_I, _I]),
     "mla_colsum_rows": (_I, [_P, _P, _P, _I, _I, _P]),
     "mla_layernorm_fwd": (_I, [_P] * 6 + [_I, _I, _F, _P]),

@@ -15,7 +15,10 @@ MI355X-first host design, not a module-by-module port:
     "f32" = exact fp32 MFMA (v_mfma_f32_32x32x2_f32), "split" = fp32 operands split exactly into three bf16 terms,
     six products on v_mfma_f32_32x32x16_bf16 (fp32 in / out / accumulate, same error against fp64; the conv weights
     are re-split once per forward).  The stem (1 / 3 input channels) follows: persistent split-arithmetic kernels (stem_split.hip)
-    under "split", the fp32 MFMA under "f32".
+    under "split", the fp32 MFMA under "f32".  "bf16" = each operand rounded once to bf16, one product, fp32 accumulate (reduced
+    precision, opt-in): the plain gather-GEMM and per-tap weight-gradient kernels in their one-plane form; no LDS-patch kernels, no
+    merged stride-2 input gradient, no BatchNorm fold / fused BatchNorm reduction (they have no one-plane form yet).  Its stem keeps the
+    "split" stem kernels: more accurate than the mode asks for, at no cost (K <= 147).
 """
 from __future__ import annotations
 
@@ -80,7 +83,7 @@ class ResNet18Encoder(FlatEncoder):
         self.specs = conv_specs(modality)
         # the stem follows conv_math too (round 3): "split" -> stem_split.hip's persistent kernels, "f32" -> the exact fp32 MFMA
         # ($MLA_STEM_SPLIT=0: same-box A/B switch back to the fp32 stem under conv_math="split")
-        self.stem_split = (self.conv_math == "split" and os.environ.get("MLA_STEM_SPLIT", "1") != "0"
+        self.stem_split = (self.conv_math in ("split", "bf16") and os.environ.get("MLA_STEM_SPLIT", "1") != "0"
                            and ops.conv2d_stem_supported(self.specs[0][1], self.specs[0][2], self.specs[0][3], self.specs[0][3], self.specs[0][4], self.specs[0][5]))
         # ---- flat layout: conv weights HWIO, then gamma / beta of every BatchNorm
         self._alloc_flat([(name + ".weight", (k, k, cin, cout)) for name, cin, cout, k, _s, _p in self.specs] +
@@ -112,6 +115,8 @@ class ResNet18Encoder(FlatEncoder):
         self._fwd_training = False          # the most recent forward ran in training mode (backward_from_pooled needs one)
         self._plan_key = None
         self._ws: dict = {}
+        # per instance: the BatchNorm-backward reductions ride in the input-gradient epilogues (not on the one-plane kernels)
+        self.fuse_bn_reduce = FUSE_BN_REDUCE and not self.bf16
         # split-bf16 images of the 64..512-channel conv weights (the stem has kernels of its own), keyed by conv name
         self._build_wsplit([(name, name + ".weight", k * k, cin, cout) for name, cin, cout, k, _s, _p in self.specs if cin % 64 == 0])
         # Optional second HIP stream for the weight-gradient GEMMs: they are off the dgrad -> BN-backward critical
@@ -223,6 +228,8 @@ class ResNet18Encoder(FlatEncoder):
                     max_wgrad = max(max_wgrad, ops.conv2d_wgrad_ws_bytes(N, hh, ww, ci, co, k, k, s, p))
                     if self.conv_math == "split":
                         max_wgrad = max(max_wgrad, ops.conv2d_wgrad_split_ws_bytes(N, hh, ww, ci, co, k, k, s, p))
+                    elif self.bf16:
+                        max_wgrad = max(max_wgrad, ops.conv2d_wgrad_ws_bytes_bf16(N, hh, ww, ci, co, k, k, s, p))
                     max_w = max(max_w, ci * co * k * k)
                 max_bnws = max(max_bnws, ops.bn_bwd_ws_elems(N * oh * ow, planes))
                 ch, cw, inpl = oh, ow, planes
@@ -283,7 +290,8 @@ class ResNet18Encoder(FlatEncoder):
         if bn_in is not None:
             return ops.conv2d_fwd_split_bnin(x, wsp[0], w.shape, stride, pad, bn_in, y=y, bn_partial=partial, stream=st)[1]
         if wsp is not None:
-            return ops.conv2d_fwd_split(x, wsp[0], w.shape, stride, pad, y=y, bn_partial=partial, stream=st)[1]
+            fwd = ops.conv2d_fwd_bf16 if self.bf16 else ops.conv2d_fwd_split
+            return fwd(x, wsp[0], w.shape, stride, pad, y=y, bn_partial=partial, stream=st)[1]
         return ops.conv2d_fwd(x, w, stride, pad, y=y, bn_partial=partial, stream=st)[1]
 
     def _conv_bn(self, ws, st, x, conv_name, stride, pad, y, out, relu, residual=None, bn_in=None):
@@ -383,7 +391,7 @@ class ResNet18Encoder(FlatEncoder):
         for blk in ws["blocks"]:                                                                 # :154-157
             pre = blk["pre"]
             # decided here and recorded for the backward / block_a1 of this forward (the fold rides on the fused reduction's read of y1)
-            fold = blk["fold"] = bool(BN_FOLD and self.training and FUSE_BN_REDUCE and self.conv_math == "split"
+            fold = blk["fold"] = bool(BN_FOLD and self.training and self.fuse_bn_reduce and self.conv_math == "split"
                                       and ops.conv2d_bnfold_supported(*blk["y1"].shape, blk["cout"], 3, 3, 1, 1))
             if not fold and "a1" not in blk:
                 blk["a1"] = torch.empty_like(blk["y1"])
@@ -440,6 +448,8 @@ class ResNet18Encoder(FlatEncoder):
             wgrad = ops.conv2d_wgrad_split_bnin
         elif name == "conv1" and self.stem_split:
             wgrad = ops.conv2d_stem_wgrad_split
+        elif self.bf16 and name in self.wsp:
+            wgrad = ops.conv2d_wgrad_bf16
         else:
             wgrad = ops.conv2d_wgrad_split if name in self.wsp else ops.conv2d_wgrad
         args = (x, dy, self.g[name + ".weight"], stride, pad, ws["wgrad_ws"]) + (() if bn_in is None else (bn_in,))
@@ -460,11 +470,14 @@ class ResNet18Encoder(FlatEncoder):
         the ReLU mask is relu(bn(.)) > 0 of the one BatchNorm in bn_next, re-formed from its input (BN_FOLD)."""
         wsp = self.wsp.get(name)
         w = self.p[name + ".weight"]
-        if not FUSE_BN_REDUCE:
+        if not self.fuse_bn_reduce:
             bn_next = ()
         reqs = [(y,) + tuple(ws["stats"][bn]) + (part,) for bn, y, part in bn_next]
         if mask_gb is not None:
             r = ops.conv2d_dgrad_split_bnmask(dy, wsp[1], w.shape, x_shape, stride, pad, dx, reqs[0], mask_gb[0], mask_gb[1], stream=st)
+        elif wsp is not None and self.bf16:
+            r = ops.conv2d_dgrad_bf16(dy, wsp[1], w.shape, x_shape, stride, pad, dx=dx, residual=residual, relu_src=relu_src, stream=st,
+                                      class_mask=class_mask, residual_mask=residual_mask)
         elif wsp is not None:
             r = ops.conv2d_dgrad_split(dy, wsp[1], w.shape, x_shape, stride, pad, dx=dx, residual=residual, relu_src=relu_src,
                                        stream=st, bn_reqs=reqs, class_mask=class_mask, residual_mask=residual_mask)

@@ -66,7 +66,7 @@ class M3AEEncoder(FlatEncoder):
         if kind not in ("text", "image", "audio"):
             raise ValueError("kind must be 'text', 'image' or 'audio'")
         super().__init__(device, conv_math)                  # conv_math: here the arithmetic of the Linear GEMMs
-        self.split = self.conv_math == "split"
+        self.split = self.conv_math in ("split", "bf16")      # both run on weight images and the fused bias gradient
         # "fused": one flash-style kernel per direction, scores never materialised (csrc/attention.hip); "materialized": the
         # round-1 form (QK^T -> masked softmax -> PV as strided batched GEMMs, probabilities kept in HBM), kept as a
         # cross-check of the fused kernels at full size and for A/B measurements
@@ -268,7 +268,7 @@ class M3AEEncoder(FlatEncoder):
         else:
             ws["dP"] = torch.empty((B, H, n, n), **f32)
         ws["wt_ws"] = torch.empty(4 * D * D, **f32)
-        wb = max(ops.linear_wgrad_ws_bytes(m_, k_, n_, sp) for sp in ((False, True) if self.split else (False,))
+        wb = max(ops.linear_wgrad_ws_bytes(m_, k_, n_, sp, sp and self.bf16) for sp in ((False, True) if self.split else (False,))
                  for (m_, k_, n_) in ((M, D, 3 * D), (M, D, 4 * D), (M, 4 * D, D), (M, D, D), (B * ws["L"], self.PD, D)))
         ws["wgrad_ws"] = torch.empty((wb + 3) // 4, **f32)
         ws["red_ws"] = torch.empty(ops.colreduce_ws_elems(M, 4 * D), **f32)
@@ -307,7 +307,7 @@ class M3AEEncoder(FlatEncoder):
             ws["pm"] = None
             ops.patchify(inp.contiguous().float(), ws["patches"], 16, transposed_hw=(F_, T_), stream=st)
             ops.linear_fwd(ws["patches"], self.p["patch_embed_a.proj.weight"], self.p["patch_embed_a.proj.bias"], ws["x0"], 1, B * L,
-                           self.PD, D, stream=st, wsplit=self._w("patch_embed_a.proj.weight", 0))
+                           self.PD, D, stream=st, bf16=self.bf16, wsplit=self._w("patch_embed_a.proj.weight", 0))
             ops.tokens_assemble(ws["x0"], None, None, self.p["pos_embed_a"], self.p["modality_a"], None, B, L, D, stream=st)
         else:
             B = inp.shape[0]
@@ -316,7 +316,7 @@ class M3AEEncoder(FlatEncoder):
             ws["pm"] = None
             ops.patchify(inp.contiguous(), ws["patches"], 16, stream=st)                     # basic_model.py:184-186
             ops.linear_fwd(ws["patches"], self.p["image_embedding.weight"], self.p["image_embedding.bias"], ws["x0"], B, L,
-                           self.PD, D, y_group_rows=L + 1, y_off=1, stream=st, wsplit=self._w("image_embedding.weight", 0))               # m3ae.py:353
+                           self.PD, D, y_group_rows=L + 1, y_off=1, stream=st, bf16=self.bf16, wsplit=self._w("image_embedding.weight", 0))               # m3ae.py:353
             ops.tokens_assemble(ws["x0"], None, None, ws["pos"], self.p["encoder_image_type_embedding"], self.p["cls_token"],
                                 B, L, D, stream=st)
         n, M = ws["n"], ws["M"]
@@ -326,7 +326,7 @@ class M3AEEncoder(FlatEncoder):
             P_ = lambda nm: self.p[f"encoder.blocks.{i}.{nm}"]
             bk["x"] = x
             ops.layernorm_fwd(x, P_("layer_norm1.weight"), P_("layer_norm1.bias"), bk["h1"], bk["st"][0], bk["st"][1], M, D, stream=st)
-            ops.linear_fwd(bk["h1"], P_("attention.qkv_linear.weight"), P_("attention.qkv_linear.bias"), bk["qkv"], 1, M, D, 3 * D, stream=st, wsplit=self._w(f"encoder.blocks.{i}.attention.qkv_linear.weight", 0))
+            ops.linear_fwd(bk["h1"], P_("attention.qkv_linear.weight"), P_("attention.qkv_linear.bias"), bk["qkv"], 1, M, D, 3 * D, stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.attention.qkv_linear.weight", 0))
             if self.attention == "fused":
                 ops.attention_fwd(bk["qkv"], ws["pm"], bk["o"], bk["lse"], B, H, n, hd, stream=st)                                   # m3ae.py:109-122
             else:
@@ -334,12 +334,12 @@ class M3AEEncoder(FlatEncoder):
                 ops.bgemm(bk["qkv"], bk["qkv"], bk["P"], B, H, n, n, hd, qs, (n * 3 * D, hd, 1, 3 * D), ss, scale, b_off=D, stream=st)   # m3ae.py:109
                 ops.softmax_fwd(bk["P"], ws["pm"], B, H, n, stream=st)                                                                    # :111-118
                 ops.bgemm(bk["P"], bk["qkv"], bk["o"], B, H, n, hd, n, ss, (n * 3 * D, hd, 3 * D, 1), os_, 1.0, b_off=2 * D, stream=st)   # :121-122
-            ops.linear_fwd(bk["o"], P_("attention.fc.weight"), P_("attention.fc.bias"), bk["xmid"], 1, M, D, D, residual=x, stream=st, wsplit=self._w(f"encoder.blocks.{i}.attention.fc.weight", 0))  # :123,149
+            ops.linear_fwd(bk["o"], P_("attention.fc.weight"), P_("attention.fc.bias"), bk["xmid"], 1, M, D, D, residual=x, stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.attention.fc.weight", 0))  # :123,149
             ops.layernorm_fwd(bk["xmid"], P_("layer_norm2.weight"), P_("layer_norm2.bias"), bk["h2"], bk["st"][2], bk["st"][3], M, D, stream=st)
             ops.linear_fwd(bk["h2"], P_("transformer_mlp.fc1.weight"), P_("transformer_mlp.fc1.bias"), bk["u"], 1, M, D, 4 * D,
-                           y_gelu=bk["gl"], stream=st, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc1.weight", 0))                                                                               # :76-77
+                           y_gelu=bk["gl"], stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc1.weight", 0))                                                                               # :76-77
             ops.linear_fwd(bk["gl"], P_("transformer_mlp.fc2.weight"), P_("transformer_mlp.fc2.bias"), bk["xout"], 1, M, 4 * D, D,
-                           residual=bk["xmid"], stream=st, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc2.weight", 0))                                                                            # :79,154
+                           residual=bk["xmid"], stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc2.weight", 0))                                                                            # :79,154
             x = bk["xout"]
         ws["xlast"] = x
         ops.layernorm_fwd(x, self.p["encoder.layer_norm.weight"], self.p["encoder.layer_norm.bias"], ws["y"], ws["stf"][0], ws["stf"][1],
@@ -354,10 +354,10 @@ class M3AEEncoder(FlatEncoder):
         """Weight and bias gradient of one Linear (dw = x^T dy, db = column sums of dy).  On the split arithmetic the bias
         gradient comes out of the weight-gradient kernel's own pass over dy (no separate column-reduction launches)."""
         if self.split and FUSE_BIAS_GRAD:
-            ops.linear_wgrad(x, dy, dw, wgw, 1, M, K, N, stream=st, split=True, dbias=db)
+            ops.linear_wgrad(x, dy, dw, wgw, 1, M, K, N, stream=st, split=True, dbias=db, bf16=self.bf16)
         else:
             ops.colsum_rows(dy, db, red, M, N, stream=st)
-            ops.linear_wgrad(x, dy, dw, wgw, 1, M, K, N, stream=st, split=self.split)
+            ops.linear_wgrad(x, dy, dw, wgw, 1, M, K, N, stream=st, split=self.split, bf16=self.bf16)
 
     def backward_from_pooled(self, dfeat: torch.Tensor, P: Optional[int] = None) -> None:
         ws = self._ws
@@ -378,14 +378,14 @@ class M3AEEncoder(FlatEncoder):
             G_ = lambda nm: self.g[f"encoder.blocks.{i}.{nm}"]
             # ---- MLP: xout = xmid + fc2(gelu(fc1(LN2(xmid))))
             self._wgrad_bias(bk["gl"], dx, G_("transformer_mlp.fc2.weight"), G_("transformer_mlp.fc2.bias"), wgw, red, M, 4 * D, D, st)
-            ops.linear_dgrad(dx, P_("transformer_mlp.fc2.weight"), ws["du"], wtw, 1, M, 4 * D, D, gelu_src=bk["u"], stream=st, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc2.weight", 1))
+            ops.linear_dgrad(dx, P_("transformer_mlp.fc2.weight"), ws["du"], wtw, 1, M, 4 * D, D, gelu_src=bk["u"], stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc2.weight", 1))
             self._wgrad_bias(bk["h2"], ws["du"], G_("transformer_mlp.fc1.weight"), G_("transformer_mlp.fc1.bias"), wgw, red, M, D, 4 * D, st)
-            ops.linear_dgrad(ws["du"], P_("transformer_mlp.fc1.weight"), dB_, wtw, 1, M, D, 4 * D, stream=st, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc1.weight", 1))   # d h2
+            ops.linear_dgrad(ws["du"], P_("transformer_mlp.fc1.weight"), dB_, wtw, 1, M, D, 4 * D, stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc1.weight", 1))   # d h2
             ops.layernorm_bwd(dB_, bk["xmid"], P_("layer_norm2.weight"), bk["st"][2], bk["st"][3], dB_, G_("layer_norm2.weight"),
                               G_("layer_norm2.bias"), red, M, D, add=dx, stream=st)                             # d xmid -> dB_
             # ---- attention: xmid = x + fc(PV)
             self._wgrad_bias(bk["o"], dB_, G_("attention.fc.weight"), G_("attention.fc.bias"), wgw, red, M, D, D, st)
-            ops.linear_dgrad(dB_, P_("attention.fc.weight"), dC, wtw, 1, M, D, D, stream=st, wsplit=self._w(f"encoder.blocks.{i}.attention.fc.weight", 1))                    # d o (B,n,D)
+            ops.linear_dgrad(dB_, P_("attention.fc.weight"), dC, wtw, 1, M, D, D, stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.attention.fc.weight", 1))                    # d o (B,n,D)
             if self.attention == "fused":
                 ops.attention_bwd(dC, bk["qkv"], bk["o"], bk["lse"], ws["pm"], ws["dqkv"], ws["dvec"], B, H, n, hd, stream=st)
             else:
@@ -397,7 +397,7 @@ class M3AEEncoder(FlatEncoder):
                 ops.bgemm(ws["dP"], bk["qkv"], ws["dqkv"], B, H, n, hd, n, (H * n * n, n * n, 1, n), (n * 3 * D, hd, 3 * D, 1), qs, scale,
                           c_off=D, stream=st)                                                                                                # dK = s dS^T Q
             self._wgrad_bias(bk["h1"], ws["dqkv"], G_("attention.qkv_linear.weight"), G_("attention.qkv_linear.bias"), wgw, red, M, D, 3 * D, st)
-            ops.linear_dgrad(ws["dqkv"], P_("attention.qkv_linear.weight"), dC, wtw, 1, M, D, 3 * D, stream=st, wsplit=self._w(f"encoder.blocks.{i}.attention.qkv_linear.weight", 1))  # d h1
+            ops.linear_dgrad(ws["dqkv"], P_("attention.qkv_linear.weight"), dC, wtw, 1, M, D, 3 * D, stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.attention.qkv_linear.weight", 1))  # d h1
             ops.layernorm_bwd(dC, bk["x"], P_("layer_norm1.weight"), bk["st"][0], bk["st"][1], dC, G_("layer_norm1.weight"),
                               G_("layer_norm1.bias"), red, M, D, add=dB_, stream=st)                            # d x -> dC
             dx, dC = dC, dx                                                                                     # rotate buffers
@@ -412,7 +412,7 @@ class M3AEEncoder(FlatEncoder):
             if "red_pos" not in ws:
                 ws["red_pos"] = torch.empty(ops.colreduce_ws_elems(B, L * D), device=self.device, dtype=torch.float32)
             ops.colsum_rows(dx, self.g["pos_embed_a"], ws["red_pos"], B, L * D, stream=st)
-            ops.linear_wgrad(ws["patches"], dx, self.g["patch_embed_a.proj.weight"], wgw, 1, B * L, self.PD, D, stream=st, split=self.split)
+            ops.linear_wgrad(ws["patches"], dx, self.g["patch_embed_a.proj.weight"], wgw, 1, B * L, self.PD, D, stream=st, split=self.split, bf16=self.bf16)
         elif self.kind == "text":
             self.g["text_embedding.weight"].zero_()
             if "emb_ws" not in ws:
@@ -424,7 +424,7 @@ class M3AEEncoder(FlatEncoder):
                                     B, L, D, stream=st)
             dimg = dx.view(B, n, D)[:, 1:, :].contiguous().view(B * L, D)       # memory plumbing: drop the cls rows
             ops.colsum_rows(dimg, self.g["image_embedding.bias"], red, B * L, D, stream=st)
-            ops.linear_wgrad(ws["patches"], dimg, self.g["image_embedding.weight"], wgw, 1, B * L, self.PD, D, stream=st, split=self.split)
+            ops.linear_wgrad(ws["patches"], dimg, self.g["image_embedding.weight"], wgw, 1, B * L, self.PD, D, stream=st, split=self.split, bf16=self.bf16)
 
 
 class M3AEClassifier(_Classifier):

@@ -237,8 +237,8 @@ class AVClassifier(_Classifier):
     (--gs_flag) or Linear(1024, C) on cat(a, v) (:31-34)."""
 
     def __init__(self, args, device="cuda", seed: Optional[int] = None, conv_math: Optional[str] = None):
-        """conv_math: "f32" (exact fp32 MFMA) or "split" (exact bf16 operand split, fp32-equivalent; see
-        encoder.py); default from $MLA_CONV_MATH."""
+        """conv_math: "f32" (exact fp32 MFMA), "split" (exact bf16 operand split, fp32-equivalent) or "bf16" (operands
+        rounded once to bf16, one product: reduced precision, opt-in); see encoder.py; default from $MLA_CONV_MATH."""
         super().__init__(args, device, seed, ("CREMAD",), ConcatFusion, 512, 2)     # basic_model.py:19-40
         self.audio_net = ResNet18Encoder("audio", device, self._seed(0), conv_math)     # basic_model.py:42
         self.visual_net = ResNet18Encoder("visual", device, self._seed(1), conv_math)   # basic_model.py:43

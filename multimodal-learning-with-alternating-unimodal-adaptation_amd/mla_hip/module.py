@@ -225,6 +225,7 @@ class FlatModule(nn.Module):
 # Shipped default arithmetic of the conv / Linear contractions: "split" = every fp32 operand split exactly into three
 # bf16 terms, six bf16 MFMAs per fp32 product, fp32 accumulate -- fp32 in / out, error against fp64 no larger than the fp32
 # MFMA's (tests/test_ops_gpu.py::test_conv_split_is_not_reduced_precision), 1.2-1.3x the throughput.  "f32" = v_mfma_f32_32x32x2_f32.
+# "bf16" = each operand rounded once to bf16, ONE product per fp32 product, fp32 accumulate: reduced precision, opt-in only.
 DEFAULT_CONV_MATH = "split"
 
 
@@ -233,17 +234,19 @@ def _await_tail_hook(module, prefix, keep_vars) -> None:
 
 
 class FlatEncoder(FlatModule):
-    """What every modality encoder shares: the arithmetic switch `conv_math` ("split" / "f32", default $MLA_CONV_MATH), the
-    split-bf16 images of its GEMM weights (re-split at the top of a forward), and the hand-over to the stream that carries
-    its training chain (`tail_stream`).  Subclasses add their layout, reference name tree and launch plans."""
+    """What every modality encoder shares: the arithmetic switch `conv_math` ("split" / "f32" / "bf16", default $MLA_CONV_MATH), the
+    bf16 images of its GEMM weights (three planes under "split", one under "bf16"; rebuilt at the top of a forward), and the
+    hand-over to the stream that carries its training chain (`tail_stream`).  Subclasses add their layout, reference name tree
+    and launch plans.  The arithmetic belongs to the instance: encoders of different conv_math share a process."""
     # True: the weight-gradient GEMMs may run on a side stream, `wgrad_stream` (None = on the calling stream)
     side_wgrad = False
 
     def __init__(self, device, conv_math: Optional[str]):
         super().__init__()
         self.conv_math = conv_math or os.environ.get("MLA_CONV_MATH", DEFAULT_CONV_MATH)
-        if self.conv_math not in ("f32", "split"):
-            raise MLAHipError(f"conv_math must be 'f32' or 'split', got {self.conv_math!r}")
+        if self.conv_math not in ("f32", "split", "bf16"):
+            raise MLAHipError(f"conv_math must be 'f32' or 'split' or 'bf16', got {self.conv_math!r}")
+        self.bf16 = self.conv_math == "bf16"
         self.device = torch.device(device)
         # name -> (forward image, input-gradient image) of the weights _build_wsplit lists; empty under conv_math == "f32"
         self.wsp: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -253,14 +256,16 @@ class FlatEncoder(FlatModule):
     def _build_wsplit(self, weights: List[Tuple[str, str, int, int, int]]) -> None:
         """weights: (wsp key, layout name, taps, K, N) of every [taps][K][N] weight the split arithmetic contracts (a Linear
         [K][N] is a 1-tap conv weight).  Per weight a transposed image for the forward GEMM and a straight one for the
-        input-gradient GEMM, 3 bf16 planes each, in one int16 buffer, and the descriptor rows of mla_conv2d_wsplit_batch."""
-        if self.conv_math != "split":
+        input-gradient GEMM, 3 bf16 planes each (one under conv_math "bf16"), in one int16 buffer, and the descriptor rows of
+        mla_conv2d_wsplit_batch / mla_conv2d_wimage_batch_bf16."""
+        if self.conv_math == "f32":
             return
-        tot16 = sum(2 * 3 * taps * K * N for _k, _n, taps, K, N in weights)
+        planes = 1 if self.bf16 else 3
+        tot16 = sum(2 * planes * taps * K * N for _k, _n, taps, K, N in weights)
         self._wsplit_flat = torch.empty(tot16, device=self.device, dtype=torch.int16)
         o16, rows, blocks = 0, [], 0
         for key, name, taps, K, N in weights:
-            n16 = 3 * taps * K * N
+            n16 = planes * taps * K * N
             self.wsp[key] = (self._wsplit_flat[o16:o16 + n16], self._wsplit_flat[o16 + n16:o16 + 2 * n16])
             nb = taps * ((K + 31) // 32) * ((N + 31) // 32)
             for transposed, off in ((1, o16), (0, o16 + n16)):
@@ -272,7 +277,8 @@ class FlatEncoder(FlatModule):
 
     def _refresh_wsplit(self, st) -> None:
         """Re-split the weights (they change with every optimizer step; in eval mode only when marked dirty)."""
-        ops.conv2d_wsplit_batch(self.flat, self._wsplit_flat, self._wsplit_desc, self._wsplit_blocks, stream=st)
+        batch = ops.conv2d_wimage_batch_bf16 if self.bf16 else ops.conv2d_wsplit_batch
+        batch(self.flat, self._wsplit_flat, self._wsplit_desc, self._wsplit_blocks, stream=st)
         self._wsplit_dirty = False
 
     def train(self, mode: bool = True):

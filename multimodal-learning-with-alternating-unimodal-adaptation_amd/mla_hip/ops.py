@@ -246,6 +246,67 @@ def conv2d_dgrad_split(dy: torch.Tensor, wsplit: torch.Tensor, w_shape, x_shape,
                        before=(residual, relu_src), after=(class_mask, residual_mask))
 
 
+# ---- conv_math "bf16": one bf16 rounding per operand, one product (include/mla_hip.h: mla_conv2d_*_bf16) -----------------------------
+def conv2d_wimage_bf16(w_hwio: torch.Tensor, transposed: bool, out: Optional[torch.Tensor] = None,
+                       stream: Optional[int] = None) -> torch.Tensor:
+    """One bf16 plane of the conv weights (int16 storage, [taps][n][k]) for the bf16 kernels: transposed=True for conv2d_fwd_bf16
+    (n=Cout, k=Cin), False for conv2d_dgrad_bf16 (n=Cin, k=Cout)."""
+    KH, KW, Cin, Cout = w_hwio.shape
+    n = int(_lib.load().mla_conv2d_wimage_bytes_bf16(Cin, Cout, KH, KW)) // 2
+    if out is None:
+        out = torch.empty(n, device=w_hwio.device, dtype=torch.int16)
+    if out.numel() < n or out.dtype != torch.int16:
+        raise MLAHipError("conv2d_wimage_bf16: out must hold KH*KW*Cin*Cout int16")
+    _call("mla_conv2d_wimage_bf16", _p(w_hwio), _p(out, torch.int16), Cin, Cout, KH, KW, int(transposed), stream or cur_stream())
+    return out
+
+
+def conv2d_wimage_batch_bf16(params: torch.Tensor, wimage: torch.Tensor, desc: torch.Tensor, total_blocks: int,
+                             stream: Optional[int] = None) -> None:
+    """conv2d_wsplit_batch for the one-plane images (same descriptor rows, out_off in 16-bit elements of `wimage`)."""
+    _call("mla_conv2d_wimage_batch_bf16", _p(params), _p(wimage, torch.int16), _p(desc, torch.int32), desc.shape[0], int(total_blocks),
+          stream or cur_stream())
+
+
+def conv2d_tile_bf16(M: int, Cout: int, k_total: int) -> int:
+    """Diagnostic / test query: the tile (index into 256x128, 128x128, 128x64, 64x64, 256x64, 192x128) a bf16 gather-GEMM of these
+    dims runs on, on the current device (the choice depends on its CU count)."""
+    return int(_lib.load().mla_conv2d_tile_bf16(int(M), int(Cout), int(k_total)))
+
+
+def conv2d_fwd_bf16(x: torch.Tensor, wimage_t: torch.Tensor, w_shape, stride: int, pad: int, y: Optional[torch.Tensor] = None,
+                    bn_partial: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> Tuple[torch.Tensor, int]:
+    """conv2d_fwd on the single-product bf16 arithmetic; `wimage_t` = conv2d_wimage_bf16(w, True), w_shape = (KH, KW, Cin, Cout)."""
+    return _conv_fwd("conv2d_fwd_bf16", "mla_conv2d_fwd_bf16", "conv_fwd", x, wimage_t, torch.int16, w_shape, stride, pad, y, bn_partial,
+                     stream)
+
+
+def conv2d_dgrad_bf16(dy: torch.Tensor, wimage: torch.Tensor, w_shape, x_shape, stride: int, pad: int,
+                      dx: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                      relu_src: Optional[torch.Tensor] = None, stream: Optional[int] = None, class_mask: int = 0xF,
+                      residual_mask: int = 0xF) -> torch.Tensor:
+    """conv2d_dgrad on the single-product bf16 arithmetic; `wimage` = conv2d_wimage_bf16(w, False).  One launch per parity class."""
+    N, H, W, Cin = x_shape
+    KH, KW, _, Cout = w_shape
+    if dx is None:
+        dx = torch.empty((N, H, W, Cin), device=dy.device, dtype=torch.float32)
+    t0 = _begin()
+    _call("mla_conv2d_dgrad_bf16", _p(dy), _p(wimage, torch.int16), _p(dx), N, H, W, Cin, Cout, KH, KW, stride, pad, _p(residual), _p(relu_src),
+          class_mask, residual_mask, stream or cur_stream())
+    _end(t0, "conv_dgrad", 2.0 * dy.numel() * KH * KW * Cin)
+    return dx
+
+
+def conv2d_wgrad_ws_bytes_bf16(N, H, W, Cin, Cout, KH, KW, stride, pad) -> int:
+    return int(_lib.load().mla_conv2d_wgrad_ws_bytes_bf16(N, H, W, Cin, Cout, KH, KW, stride, pad))
+
+
+def conv2d_wgrad_bf16(x: torch.Tensor, dy: torch.Tensor, dw_hwio: torch.Tensor, stride: int, pad: int, ws: torch.Tensor,
+                      stream: Optional[int] = None) -> torch.Tensor:
+    """conv2d_wgrad on the single-product bf16 arithmetic (per-tap kernel; Cin a multiple of 64); ws >= conv2d_wgrad_ws_bytes_bf16."""
+    return _conv_wgrad("mla_conv2d_wgrad_bf16", "conv_wgrad", x, dy, dw_hwio, stride, pad, ws, stream)
+
+
 def conv2d_bnfold_supported(N: int, H: int, W: int, Cin: int, Cout: int, KH: int, KW: int, stride: int, pad: int) -> bool:
     """True where relu(bn(.)) can be folded into the operands of a convolution (64 -> 64 channels, 3x3 / 1 / 1, split arithmetic)."""
     return bool(_lib.load().mla_conv2d_bnfold_supported(N, H, W, Cin, Cout, KH, KW, stride, pad))
@@ -554,11 +615,14 @@ LN_EPS = 1e-5     # nn.LayerNorm default (models/m3ae.py:138)
 
 def linear_fwd(x, w_kn, bias, y, groups: int, rows: int, K: int, N: int, x_group_rows: Optional[int] = None, x_off: int = 0,
                y_group_rows: Optional[int] = None, y_off: int = 0, residual=None, y_gelu=None, stream: Optional[int] = None,
-               wsplit=None):
+               wsplit=None, bf16: bool = False):
     """y[g][y_off+r] = x[g][x_off+r] @ w_kn (+bias) (+residual); y_gelu (optional) also receives gelu(y).
-    wsplit: conv2d_wsplit(w_kn.view(1, 1, K, N), True) selects the split-bf16 arithmetic."""
+    wsplit: conv2d_wsplit(w_kn.view(1, 1, K, N), True) selects the split-bf16 arithmetic; with bf16=True it is
+    conv2d_wimage_bf16(w_kn.view(1, 1, K, N), True) and selects the single-product bf16 arithmetic."""
+    if bf16 and wsplit is None:
+        raise MLAHipError("linear_fwd: bf16 needs the weight image (conv2d_wimage_bf16)")
     if wsplit is not None:
-        _call("mla_linear_fwd_split", _p(x), _p(wsplit, torch.int16), _p(bias), _p(residual), _p(y), _p(y_gelu), groups, rows, x_group_rows or rows,
+        _call("mla_linear_fwd_bf16" if bf16 else "mla_linear_fwd_split", _p(x), _p(wsplit, torch.int16), _p(bias), _p(residual), _p(y), _p(y_gelu), groups, rows, x_group_rows or rows,
               x_off, y_group_rows or rows, y_off, K, N, stream or cur_stream())
         return
     _call("mla_linear_fwd", _p(x), _p(w_kn), _p(bias), _p(residual), _p(y), _p(y_gelu), groups, rows, x_group_rows or rows, x_off,
@@ -566,27 +630,32 @@ def linear_fwd(x, w_kn, bias, y, groups: int, rows: int, K: int, N: int, x_group
 
 
 def linear_dgrad(dy, w_kn, dx, wt_ws, groups: int, rows: int, K: int, N: int, residual=None, gelu_src=None,
-                 stream: Optional[int] = None, wsplit=None):
-    """dx = dy @ w_kn^T (+residual) (* gelu'(gelu_src)); dense rows.  wsplit: conv2d_wsplit(w_kn.view(1, 1, K, N), False)."""
+                 stream: Optional[int] = None, wsplit=None, bf16: bool = False):
+    """dx = dy @ w_kn^T (+residual) (* gelu'(gelu_src)); dense rows.  wsplit: conv2d_wsplit(w_kn.view(1, 1, K, N), False), or with
+    bf16=True conv2d_wimage_bf16(w_kn.view(1, 1, K, N), False)."""
+    if bf16 and wsplit is None:
+        raise MLAHipError("linear_dgrad: bf16 needs the weight image (conv2d_wimage_bf16)")
     if wsplit is not None:
-        _call("mla_linear_dgrad_split", _p(dy), _p(wsplit, torch.int16), _p(dx), _p(residual), _p(gelu_src), groups, rows, rows, 0, rows, 0, K, N,
+        _call("mla_linear_dgrad_bf16" if bf16 else "mla_linear_dgrad_split", _p(dy), _p(wsplit, torch.int16), _p(dx), _p(residual), _p(gelu_src), groups, rows, rows, 0, rows, 0, K, N,
               stream or cur_stream())
         return
     _call("mla_linear_dgrad", _p(dy), _p(w_kn), _p(dx), _p(residual), _p(gelu_src), _p(wt_ws), groups, rows, rows, 0, rows, 0, K, N,
           stream or cur_stream())
 
 
-def linear_wgrad_ws_bytes(M: int, K: int, N: int, split: bool = False) -> int:
+def linear_wgrad_ws_bytes(M: int, K: int, N: int, split: bool = False, bf16: bool = False) -> int:
+    if bf16:
+        return int(_lib.load().mla_linear_wgrad_ws_bytes_bf16(M, K, N))
     if split:
         return int(_lib.load().mla_linear_wgrad_split_ws_bytes(M, K, N))
     return int(_lib.load().mla_linear_wgrad_ws_bytes(M, K, N))
 
 
 def linear_wgrad(x, dy, dw_kn, ws, groups: int, rows: int, K: int, N: int, x_group_rows: Optional[int] = None, x_off: int = 0,
-                 stream: Optional[int] = None, split: bool = False, dbias: Optional[torch.Tensor] = None):
-    """dw_kn = x^T dy (K, N).  split + dbias: the bias gradient (column sums of dy) comes out of the same pass."""
-    if split:
-        _call("mla_linear_wgrad_split_bias", _p(x), _p(dy), _p(dw_kn), _p(dbias), groups, rows, x_group_rows or rows, x_off, K, N, _p(ws),
+                 stream: Optional[int] = None, split: bool = False, dbias: Optional[torch.Tensor] = None, bf16: bool = False):
+    """dw_kn = x^T dy (K, N).  split (or bf16) + dbias: the bias gradient (column sums of dy, fp32) comes out of the same pass."""
+    if split or bf16:
+        _call("mla_linear_wgrad_bias_bf16" if bf16 else "mla_linear_wgrad_split_bias", _p(x), _p(dy), _p(dw_kn), _p(dbias), groups, rows, x_group_rows or rows, x_off, K, N, _p(ws),
               ws.numel() * ws.element_size(), stream or cur_stream())
         return
     if dbias is not None:

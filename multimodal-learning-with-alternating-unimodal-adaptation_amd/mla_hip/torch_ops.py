@@ -75,6 +75,26 @@ def conv2d_wgrad(x, dy, w_shape, stride, pad):
     return ops.conv2d_wgrad(x, dy, _f32(tuple(w_shape), x), stride, pad, ws)
 
 
+# ---- the same convolutions on the single-product bf16 arithmetic (conv_math "bf16") -------------------------------------------
+@_op("conv2d_fwd_bf16(Tensor x, Tensor w_hwio, int stride, int pad) -> Tensor")
+def conv2d_fwd_bf16(x, w_hwio, stride, pad):
+    return ops.conv2d_fwd_bf16(x, ops.conv2d_wimage_bf16(w_hwio, True), tuple(w_hwio.shape), stride, pad)[0]
+
+
+@_op("conv2d_dgrad_bf16(Tensor dy, Tensor w_hwio, int[] x_shape, int stride, int pad, Tensor? residual=None, Tensor? relu_src=None) -> Tensor")
+def conv2d_dgrad_bf16(dy, w_hwio, x_shape, stride, pad, residual=None, relu_src=None):
+    return ops.conv2d_dgrad_bf16(dy, ops.conv2d_wimage_bf16(w_hwio, False), tuple(w_hwio.shape), tuple(x_shape), stride, pad,
+                                 residual=residual, relu_src=relu_src)
+
+
+@_op("conv2d_wgrad_bf16(Tensor x, Tensor dy, int[] w_shape, int stride, int pad) -> Tensor")
+def conv2d_wgrad_bf16(x, dy, w_shape, stride, pad):
+    N, H, W, Cin = x.shape
+    KH, KW, _, Cout = w_shape
+    ws = _f32(ops.conv2d_wgrad_ws_bytes_bf16(N, H, W, Cin, Cout, KH, KW, stride, pad) // 4 + 4, x)
+    return ops.conv2d_wgrad_bf16(x, dy, _f32(tuple(w_shape), x), stride, pad, ws)
+
+
 # ---- batch norm (+ ReLU + residual add), training mode (backbone.py:29-50) ------------------------------------------
 @_op("bn_act_fwd(Tensor y, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta, bool relu, Tensor? residual=None) -> Tensor")
 def bn_act_fwd(y, mean, invstd, gamma, beta, relu, residual=None):
@@ -272,6 +292,37 @@ def linear_wgrad(x, dy):
     N = dy.shape[1]
     dw = _f32((K, N), x)
     ops.linear_wgrad(x, dy, dw, _f32(ops.linear_wgrad_ws_bytes(M, K, N) // 4 + 4, x), 1, M, K, N)
+    return dw
+
+
+@_op("linear_fwd_bf16(Tensor x, Tensor w_kn, Tensor? bias=None, Tensor? residual=None, bool gelu=False) -> Tensor")
+def linear_fwd_bf16(x, w_kn, bias=None, residual=None, gelu=False):
+    """linear_fwd on the single-product bf16 arithmetic (K, N multiples of 64)."""
+    M, K = x.shape
+    N = w_kn.shape[1]
+    y = _f32((M, N), x)
+    yg = _f32((M, N), x) if gelu else None
+    ops.linear_fwd(x, w_kn, bias, y, 1, M, K, N, residual=residual, y_gelu=yg, wsplit=ops.conv2d_wimage_bf16(w_kn.view(1, 1, K, N), True),
+                   bf16=True)
+    return yg if gelu else y
+
+
+@_op("linear_dgrad_bf16(Tensor dy, Tensor w_kn, Tensor? residual=None, Tensor? gelu_src=None) -> Tensor")
+def linear_dgrad_bf16(dy, w_kn, residual=None, gelu_src=None):
+    M, N = dy.shape
+    K = w_kn.shape[0]
+    dx = _f32((M, K), dy)
+    ops.linear_dgrad(dy, w_kn, dx, None, 1, M, K, N, residual=residual, gelu_src=gelu_src,
+                     wsplit=ops.conv2d_wimage_bf16(w_kn.view(1, 1, K, N), False), bf16=True)
+    return dx
+
+
+@_op("linear_wgrad_bf16(Tensor x, Tensor dy) -> Tensor")
+def linear_wgrad_bf16(x, dy):
+    M, K = x.shape
+    N = dy.shape[1]
+    dw = _f32((K, N), x)
+    ops.linear_wgrad(x, dy, dw, _f32(ops.linear_wgrad_ws_bytes(M, K, N, bf16=True) // 4 + 4, x), 1, M, K, N, bf16=True)
     return dw
 
 
