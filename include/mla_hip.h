@@ -174,6 +174,16 @@ size_t mla_conv2d_stem_wgrad_split_ws_bytes(int Cin);
 int mla_conv2d_stem_wgrad_split(const float* x, const float* dy, float* dw_hwio,
                                 int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                                 void* ws, size_t ws_bytes, void* stream);
+/* mla_conv2d_stem_wgrad_split with the apply pass of the stem's BatchNorm / max-pool backward (backbone.py:149-152) formed
+ * inside: instead of dy it reads conv1's output y (N,OH,OW,64), the pooled gradient dpool and window codes idx (N,PH,PW,64) and
+ * bn1's vectors, and forms dy = gamma * invstd * ([bn(y) > 0] g - dbeta/M - xhat * dgamma/M) where it would have loaded it
+ * (the expression of mla_bn_bwd_pooled, bit for bit: dw equals mla_bn_bwd_pooled + mla_conv2d_stem_wgrad_split).  dgamma /
+ * dbeta: from mla_bn_bwd_pooled with dy = NULL.  Same workspace as mla_conv2d_stem_wgrad_split. */
+int mla_conv2d_stem_wgrad_split_bnpool(const float* x, const float* dpool, const uint8_t* idx, const float* y,
+                                       const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                       const float* dgamma, const float* dbeta, float* dw_hwio,
+                                       int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                       void* ws, size_t ws_bytes, void* stream);
 /* measurement hook: force tile 0..4 (256x128, 128x128, 128x64, 64x64, 256x64) where Cout allows; -1 = automatic */
 int mla_conv2d_split_cfg(int cfg);
 
@@ -232,7 +242,9 @@ int mla_bn_bwd_from_partial(const float* dout, const float* x, const float* mean
 int mla_bn_relu_maxpool_fwd(const float* y, const float* mean, const float* invstd, const float* gamma,
                             const float* beta, float* out, uint8_t* idx, int N, int H, int W, int C, void* stream);
 /* ... and its backward: BatchNorm backward whose upstream gradient is gathered from the POOLED gradient dpool (N,OH,OW,C)
- * through idx and masked by bn(y) > 0; dy (N,H,W,C) = gradient w.r.t. y, dgamma / dbeta written; ws >= mla_bn_bwd_ws_elems. */
+ * through idx and masked by bn(y) > 0; dy (N,H,W,C) = gradient w.r.t. y, dgamma / dbeta written; ws >= mla_bn_bwd_ws_elems.
+ * dy = NULL: the reduction half alone (dgamma, dbeta) -- for a consumer that forms dy itself
+ * (mla_conv2d_stem_wgrad_split_bnpool). */
 int mla_bn_bwd_pooled(const float* dpool, const uint8_t* idx, const float* y, const float* mean, const float* invstd,
                       const float* gamma, const float* beta, float* dy, float* dgamma, float* dbeta, float* ws,
                       int N, int H, int W, int C, void* stream);

@@ -521,7 +521,7 @@ __global__ __launch_bounds__(256) void bn_bwd_pooled_apply_kernel(const float* _
                                                                    int W, int C, int OH, int OW) {
   const int c4n = C >> 2, QH = (H + 1) >> 1, QW = (W + 1) >> 1;
   const size_t total = (size_t)N * QH * QW * c4n;
-  const float invM = 1.0f / ((float)N * (float)H * (float)W);
+  const float invM = bn_inv_count(N, H, W);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int cg = (int)(i % c4n);
     size_t p = i / c4n;
@@ -530,7 +530,10 @@ __global__ __launch_bounds__(256) void bn_bwd_pooled_apply_kernel(const float* _
     const int n = (int)(p / QH);
     const f32x4 mu = reinterpret_cast<const f32x4*>(mean)[cg], is = reinterpret_cast<const f32x4*>(invstd)[cg];
     const f32x4 ga = reinterpret_cast<const f32x4*>(gamma)[cg], be = reinterpret_cast<const f32x4*>(beta)[cg];
-    const f32x4 dg = reinterpret_cast<const f32x4*>(dgamma)[cg] * invM, db = reinterpret_cast<const f32x4*>(dbeta)[cg] * invM;
+    const f32x4 dgs = reinterpret_cast<const f32x4*>(dgamma)[cg], dbs = reinterpret_cast<const f32x4*>(dbeta)[cg];
+    f32x4 dg, db;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { dg[e] = bn_bwd_scale(dgs[e], invM); db[e] = bn_bwd_scale(dbs[e], invM); }
     f32x4 wg[2][2];                    // pooled gradient of window (a + wy, b + wx); zero outside the pooled grid
     int ws[2][2][4];                   // its selected positions; -1 outside
 #pragma unroll
@@ -561,15 +564,14 @@ __global__ __launch_bounds__(256) void bn_bwd_pooled_apply_kernel(const float* _
           for (int wx = 0; wx <= px; ++wx) {
             const int code = (py + 1 - 2 * wy) * 3 + (px + 1 - 2 * wx);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) g[e] += ws[wy][wx][e] == code ? wg[wy][wx][e] : 0.f;
+            for (int e = 0; e < 4; ++e) g[e] = pool_pick(g[e], ws[wy][wx][e], code, wg[wy][wx][e]);
           }
         const size_t o = ((size_t)(n * H + iy) * W + ix) * c4n + cg;
         const f32x4 xv = reinterpret_cast<const f32x4*>(y)[o];
-        const f32x4 av = bn_val(xv, mu, is, ga, be);
+        f32x4 r;                       // (the shared expression: the fused stem weight gradient forms the same bits)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) g[e] = av[e] > 0.f ? g[e] : 0.f;
-        const f32x4 xhat = (xv - mu) * is;
-        reinterpret_cast<f32x4*>(out)[o] = ga * is * (g - db - xhat * dg);
+        for (int e = 0; e < 4; ++e) r[e] = bn_bwd_pooled_dy1(xv[e], g[e], mu[e], is[e], ga[e], be[e], dg[e], db[e]);
+        reinterpret_cast<f32x4*>(out)[o] = r;
       }
   }
 }
@@ -710,7 +712,7 @@ extern "C" int mla_bn_bwd_pooled(const float* dpool, const uint8_t* idx, const f
   MLA_REQUIRE(Ml > 0 && Ml < (1L << 31), "mla_bn_bwd_pooled: bad dims");
   const int M = (int)Ml;
   if (int rc = bn_check("mla_bn_bwd_pooled", M, C)) return rc;
-  MLA_REQUIRE(dpool && idx && y && mean && invstd && gamma && beta && dy && dgamma && dbeta && ws, "mla_bn_bwd_pooled: null pointer");
+  MLA_REQUIRE(dpool && idx && y && mean && invstd && gamma && beta && dgamma && dbeta && ws, "mla_bn_bwd_pooled: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
   const int MP = N * OH * OW;
@@ -731,6 +733,7 @@ extern "C" int mla_bn_bwd_pooled(const float* dpool, const uint8_t* idx, const f
     bn_bwd_finalize_kernel<<<cdiv(C, 64), 256, 0, st>>>(scratch, S, C, dgamma, dbeta);
     MLA_CHECK_LAUNCH("bn_bwd_finalize_kernel");
   }
+  if (!dy) return MLA_OK;            // reduction half only: the consumer of dy forms it itself (mla_conv2d_stem_wgrad_split_bnpool)
   const size_t nq = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);     // one thread per 2x2 pixel quad and 4 channels
   bn_bwd_pooled_apply_kernel<<<ew_grid(nq), 256, 0, st>>>(dpool, idx, y, mean, invstd, gamma, beta, dgamma, dbeta, dy, N, H, W, C, OH, OW);
   MLA_CHECK_LAUNCH("bn_bwd_pooled_apply_kernel");

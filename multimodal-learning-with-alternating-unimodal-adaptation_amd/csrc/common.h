@@ -88,6 +88,23 @@ __device__ __forceinline__ float wave_max(float v) {
 // (bn.hip: bn_val; the convolution kernels that fold relu(bn(.)) into their operand staging)
 __device__ __forceinline__ float bn_val1(float x, float mu, float is, float ga, float be) { return fmaf((x - mu) * is, ga, be); }
 
+// The stem's BatchNorm backward fed by the POOLED gradient (bn.hip: bn_bwd_pooled_apply_kernel; stem_split.hip: the weight-gradient
+// kernel that forms conv1's gradient while it loads it).  Both call these two, with the one contraction written out, so the two
+// paths agree bit for bit.
+//   pool_pick: g += the pooled gradient w of a window whose selected position `sel` is this pixel's position `code` in it; the
+//              windows of a pixel are visited in (wy, wx) order starting from g = 0.
+//   bn_bwd_pooled_dy1: dy = gamma * invstd * ([bn(y) > 0] g - dbeta / M - xhat * dgamma / M); dg = dgamma / M, db = dbeta / M.
+//   bn_inv_count, bn_bwd_scale: the 1 / M both use, and dg / db from the reduced sums -- a product the compiler must not contract
+//              into the subtraction that consumes it (it would, in one kernel and not in the other).
+__device__ __forceinline__ float pool_pick(float g, int sel, int code, float w) { return g + (sel == code ? w : 0.f); }
+__device__ __forceinline__ float bn_bwd_pooled_dy1(float y, float g, float mu, float is, float ga, float be, float dg, float db) {
+  const float gm = bn_val1(y, mu, is, ga, be) > 0.f ? g : 0.f;
+  const float xhat = (y - mu) * is;
+  return (ga * is) * fmaf(-xhat, dg, gm - db);
+}
+__device__ __forceinline__ float bn_inv_count(int N, int H, int W) { return 1.0f / ((float)N * (float)H * (float)W); }
+__device__ __forceinline__ float bn_bwd_scale(float sum, float invM) { return __fmul_rn(sum, invM); }
+
 // Logical tile id -> (tm, tn).  Narrow outputs (gridN <= 8: every ResNet conv) keep the row-major order.  Wide outputs
 // (transformer Linears: N = 768..3072, up to 48 column tiles) are walked in column PANELS of 8 tiles: all row tiles of a
 // panel before the next panel, so the panel's B operand (8 x BN x K x 4 B <= 3 MB) stays in the 4 MB per-XCD L2 while A

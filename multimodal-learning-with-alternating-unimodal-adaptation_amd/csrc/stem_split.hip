@@ -21,6 +21,9 @@
 #ifndef WG_VALU
 #define WG_VALU 6
 #endif
+#ifndef WG_VALU_FUSED
+#define WG_VALU_FUSED 16        // the fused audio kernel: ~180 VALU beside the 12 MFMAs of a step
+#endif
 
 namespace {
 
@@ -47,10 +50,22 @@ struct StemGeom {
   unsigned x_bytes, y_bytes;
 };
 
+// Operands of the BatchNorm / max-pool backward that stem_wgrad_split_kernel<CIN, true, .> forms in place of reading dy:
+// the pooled gradient and window codes (N, PH, PW, 64) and bn1's per-channel vectors (bn.hip: bn_bwd_pooled_apply_kernel).
+struct StemBnPool {
+  const float* dpool;
+  const uint8_t* idx;
+  const float *mean, *invstd, *gamma, *beta, *dgamma, *dbeta;
+  int PH, PW;
+  unsigned dp_bytes;                                   // of dpool; idx is a quarter of it
+};
+
 // Branch-free "offset or out of range": the compiler turns `ok ? off : OOB_OFF` with short-circuit conditions into control flow
 // (exec-masked branches with vmcnt(0) waits inside the MFMA loop: measured, it serialised the dy stream).  ok is 0 / 1.
 __device__ __forceinline__ unsigned off_or_oob(int ok, unsigned off) { return off | ((unsigned)ok - 1u); }
 __device__ __forceinline__ int in_range(int v, int n) { return (int)((unsigned)v < (unsigned)n); }
+
+__device__ __forceinline__ int buf_load_u8(rsrc_t r, unsigned voff) { return (int)__builtin_amdgcn_raw_buffer_load_b8(r, (int)voff, 0, 0); }
 
 __device__ __forceinline__ void buf_store1(rsrc_t r, float v, unsigned voff) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, 0, 0);
@@ -363,6 +378,16 @@ __global__ __launch_bounds__(64 * WAVES, (CIN == 3 && WAVES == 4) ? 1 : 2) void 
 //   * dy is streamed straight from global memory in MFMA B layout (lane = channel: 128-B row pieces per instruction), one
 //     step ahead of its use, and split in registers: it is read exactly once (617 MB / 537 MB per launch: the HBM floor).
 // A "step" = 16 pixels of one output row; a 16 x 16 tile = 16 steps, 4 per wave.
+//
+// FUSED: dy = the gradient of conv1's output is never stored (it has no other reader: the stem has no input gradient).  The
+// kernel streams y_stem through the same addresses instead and forms every dy value where it would have loaded it -- the
+// apply pass of the stem's BatchNorm backward (bn_bwd_pooled_apply_kernel; the shared helpers of common.h, so the bits are
+// the same): g = the sum of the pooled gradient over the <= 4 max-pool windows that selected the pixel, masked by bn(y) > 0,
+// then dy = gamma invstd (g - dbeta / M - xhat dgamma / M).  A lane's 8 pixels of one row lie in 5 pooled columns and, on an
+// odd row, 2 pooled rows: 5 or 10 pooled gradients and as many code bytes ride with the 8 y loads (straight from global
+// memory: neighbouring lanes and steps share the windows, so they are L1 / L2 hits), and the row parity of a step is a
+// compile-time constant of the unrolled pipeline.  RAGGED (FUSED only): OH or OW is no multiple of 16 -- pixels outside the
+// output, which load as y = 0, are forced to dy = 0 as the out-of-range dy loads of the plain kernel are.
 // ---------------------------------------------------------------------------------------------------------------------
 template <int CIN>
 struct StemWCfg {
@@ -385,9 +410,11 @@ struct StemWCfg {
 // 8 waves: wave w = (column half ni = w >> 2, row group wq = w & 3).  Two waves per SIMD hide each other's latencies, the
 // 80-register accumulator (KB x 1 x 16) leaves room for a dy prefetch two steps deep (one step deep with one wave per SIMD
 // the kernel was latency-bound on the dy stream: 16 KB in flight per CU), and both column halves share one x strip.
-template <int CIN>
+template <int CIN, bool FUSED, bool RAGGED>
 __global__ __launch_bounds__(512, 2) void stem_wgrad_split_kernel(const float* __restrict__ X, const float* __restrict__ dY,
-                                                                   float* __restrict__ slabs, const StemGeom g, unsigned dy_bytes) {
+                                                                   float* __restrict__ slabs, const StemGeom g, unsigned dy_bytes,
+                                                                   const StemBnPool bp) {
+  static_assert(FUSED || !RAGGED, "the plain kernel needs no ragged form: its out-of-range dy loads are zeros");
   using C = StemWCfg<CIN>;
   constexpr int KB = C::KB, XPD = C::XPD, ARR = C::ARR, HALF = C::HALF, PLANE = C::PLANE, COPY = C::COPY, SBUF = C::SBUF;
   constexpr int NT = 512, NLD = (C::NSL + NT - 1) / NT;
@@ -475,29 +502,109 @@ __global__ __launch_bounds__(512, 2) void stem_wgrad_split_kernel(const float* _
   // global loads of dy for step s + 3 (two steps in flight).  Steps run on across tile boundaries; B-fragment and dy register
   // sets alternate with the step parity (4 steps per tile keeps the parity fixed).
   constexpr int U = 4 * KB;
-  float dyv[2][8];                                    // dy in flight: slot (s & 1) holds step s; [pixel e] of this lane's channel
-  auto load_dy = [&](int t, int s, float (&dst)[8]) { // step s of tile t: output row oy0 + 4 * wq + s, pixels ox0 + 8h + e
+  // dy (FUSED: y) in flight: slot (s & 1) holds step s; [pixel e] of this lane's channel; RAGGED: with it the count nv of leading
+  // pixels that lie inside the output.  FUSED: the pooled gradients wp and codes wc of the windows [pooled row a + wy][pooled
+  // column b0 + c] (a = row / 2, b0 = first pixel / 2) and the count nw of window columns inside the pooled grid.  The windows
+  // are L1 / L2 hits two times out of three (a pooled row serves three pixel rows), so where registers are short (Cin = 3: 80
+  // accumulators) they have ONE slot, refilled for step s + 2 as soon as step s + 1 has been formed from it; else (WDEEP) they
+  // travel with y, three steps ahead, in slot (s & 1) -- whose wy = 1 half slot 0, the even rows, never uses.
+  constexpr bool WDEEP = CIN == 1;
+  constexpr int NWS = WDEEP ? 2 : 1;
+  float dyv[2][8];
+  float wp[NWS][2][5];
+  int wc[NWS][2][5], nv[2], nw[NWS];
+  float mu = 0.f, is = 0.f, ga = 0.f, be = 0.f, dg = 0.f, db = 0.f;
+  rsrc_t dpr = yr, ixr = yr;
+  if constexpr (FUSED) {
+    const int ch = ni * 32 + i;
+    const float invM = bn_inv_count(g.N, g.OH, g.OW);
+    mu = bp.mean[ch]; is = bp.invstd[ch]; ga = bp.gamma[ch]; be = bp.beta[ch];
+    dg = bn_bwd_scale(bp.dgamma[ch], invM); db = bn_bwd_scale(bp.dbeta[ch], invM);
+    dpr = make_rsrc(bp.dpool, bp.dp_bytes);
+    ixr = make_rsrc(bp.idx, bp.dp_bytes >> 2);
+  }
+  // FUSED: one address per row piece, the 8 pixels / 5 windows at constant offsets from it (28 addresses of their own cost the
+  // registers the prefetch needs).  A row that does not exist starts at OOB_ROW, out of range with every offset added; what
+  // lies past the END of an existing row is read as it comes -- the next row or zeros -- and discarded where it is used:
+  // pixels by nv, window columns by nw (both RAGGED only: with whole tiles a row's 8 pixels are inside together and only the
+  // fifth window column can be outside, which gets an address of its own).
+  constexpr unsigned OOB_ROW = 0xFFFFF000u;
+  auto load_dy = [&](int t, int s, int slot) {        // step s of tile t: output row oy0 + 4 * wq + s, pixels ox0 + 8h + e
     int n, oy0, ox0;
     decode(t, n, oy0, ox0);
     const int oy = oy0 + 4 * wq + s;
+    const int tok = (int)(t < g.ntiles);
+    if constexpr (!FUSED) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int ox = ox0 + 8 * h + e;
-      const int ok = (int)(t < g.ntiles) & (int)(oy < g.OH) & (int)(ox < g.OW);
-      dst[e] = buf_load1(yr, off_or_oob(ok, ((unsigned)((n * g.OH + oy) * g.OW + ox) * 64u + (unsigned)(ni * 32 + i)) * 4u), 0);
+      for (int e = 0; e < 8; ++e) {
+        const int ox = ox0 + 8 * h + e;
+        const int ok = tok & (int)(oy < g.OH) & (int)(ox < g.OW);
+        dyv[slot][e] = buf_load1(yr, off_or_oob(ok, ((unsigned)((n * g.OH + oy) * g.OW + ox) * 64u + (unsigned)(ni * 32 + i)) * 4u), 0);
+      }
+    } else {
+      const int ox = ox0 + 8 * h;
+      const int rok = tok & (int)(oy < g.OH) & (int)(ox < g.OW);
+      const unsigned yo = rok ? ((unsigned)((n * g.OH + oy) * g.OW + ox) * 64u + (unsigned)(ni * 32 + i)) * 4u : OOB_ROW;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dyv[slot][e] = buf_load1(yr, yo + 256u * e, 0);
+      if constexpr (RAGGED) nv[slot] = rok ? g.OW - ox : 0;
     }
   };
-  auto load_dy_step = [&](int t, int tn, int s, float (&dst)[8]) {   // step index s may run on into the next tile(s)
-    if (s < 4) load_dy(t, s, dst);
-    else load_dy(tn, s - 4, dst);                     // (lanes masked off when there is no next tile)
+  auto load_win = [&](int t, int s, int slot) {       // the windows of step s of tile t (oy0, ox0, 4 wq, 8 h are even: row parity = s & 1)
+    int n, oy0, ox0;
+    decode(t, n, oy0, ox0);
+    const int a = (oy0 + 4 * wq + s) >> 1, b0 = (ox0 >> 1) + 4 * h;
+    const int tok = (int)(t < g.ntiles);
+#pragma unroll
+    for (int wy = 0; wy < 2; ++wy) {
+      if (wy > (s & 1)) continue;
+      const int wok = tok & (int)(a + wy < bp.PH) & (int)(b0 < bp.PW);       // pooled rows outside the grid contribute nothing: zeros
+      const unsigned o = (unsigned)((n * bp.PH + a + wy) * bp.PW + b0) * 64u + (unsigned)(ni * 32 + i);
+      const unsigned po = wok ? o * 4u : OOB_ROW, co = wok ? o : OOB_ROW;
+#pragma unroll
+      for (int c = 0; c < 5; ++c) {
+        // whole tiles: the fifth column is the only one that can lie past the pooled grid while its pixel is inside: zeros then
+        const unsigned pc = (!RAGGED && c == 4) ? ((wok & (int)(b0 + 4 < bp.PW)) ? po : OOB_ROW) : po;
+        wp[slot][wy][c] = buf_load1(dpr, pc + 256u * c, 0);
+        wc[slot][wy][c] = buf_load_u8(ixr, co + 64u * c);
+      }
+    }
+    if constexpr (RAGGED) nw[slot] = bp.PW - b0;
+  };
+  auto at_step = [&](auto&& ld, int t, int tn, int s, int slot) {   // step index s may run on into the next tile
+    if (s < 4) ld(t, s, slot);
+    else ld(tn, s - 4, slot);                         // (lanes masked off when there is no next tile)
+  };
+  // FUSED: pixel e (column parity e & 1) of a row of parity py: window (wy, wx) holds it at position (py + 1 - 2 wy, px + 1 - 2 wx)
+  auto dy_val = [&](int py, int e) -> float {         // py = step & 1 = its y slot
+    if constexpr (FUSED) {
+      const int c = e >> 1, px = e & 1, wsl = WDEEP ? py : 0;
+      float gs = 0.f;
+#pragma unroll
+      for (int wy = 0; wy < 2; ++wy)
+#pragma unroll
+        for (int wx = 0; wx < 2; ++wx)
+          if (wy <= py && wx <= px) {
+            float w = wp[wsl][wy][c + wx];
+            // a window column past the pooled grid contributes nothing.  Only the right-hand window of a pixel can be one while the
+            // pixel is inside (whole tiles: load_win has zeroed it).
+            if (RAGGED && wx == 1) w = c + wx < nw[wsl] ? w : 0.f;
+            gs = pool_pick(gs, wc[wsl][wy][c + wx], (py + 1 - 2 * wy) * 3 + (px + 1 - 2 * wx), w);
+          }
+      const float d = bn_bwd_pooled_dy1(dyv[py][e], gs, mu, is, ga, be, dg, db);
+      if constexpr (RAGGED) return e < nv[py] ? d : 0.f;
+      else return d;
+    } else {
+      return dyv[py][e];
+    }
   };
   struct BFr { u32x4 p[3]; };                         // dy planes of one step
-  auto split_dy_half = [&](int j, const float (&src)[8], BFr& b) {   // half j = 0, 1: pixel pairs 2j, 2j + 1
+  auto split_dy_half = [&](int j, int slot, BFr& b) { // half j = 0, 1: pixel pairs 2j, 2j + 1
 #pragma unroll
     for (int qq = 0; qq < 2; ++qq) {
       const int q = 2 * j + qq;
       unsigned hi, mid, lo;
-      split_pair<true>(src[2 * q], src[2 * q + 1], hi, mid, lo);
+      split_pair<true>(dy_val(slot, 2 * q), dy_val(slot, 2 * q + 1), hi, mid, lo);
       b.p[0][q] = hi; b.p[1][q] = mid; b.p[2][q] = lo;
     }
   };
@@ -517,11 +624,14 @@ __global__ __launch_bounds__(512, 2) void stem_wgrad_split_kernel(const float* _
   if (t < g.ntiles) {
 #pragma unroll
     for (int u = 0; u < NLD; ++u) stage_store(0, u);
-    load_dy(t, 0, dyv[0]);
-    split_dy_half(0, dyv[0], bf0);                    // step 0's planes (latency exposed once per kernel)
-    split_dy_half(1, dyv[0], bf0);
-    load_dy(t, 1, dyv[1]);
-    load_dy(t, 2, dyv[0]);
+    load_dy(t, 0, 0);
+    if constexpr (FUSED) load_win(t, 0, 0);
+    split_dy_half(0, 0, bf0);                         // step 0's planes (latency exposed once per kernel)
+    split_dy_half(1, 0, bf0);
+    load_dy(t, 1, 1);
+    if constexpr (FUSED) load_win(t, 1, WDEEP ? 1 : 0);
+    load_dy(t, 2, 0);
+    if constexpr (FUSED && WDEEP) load_win(t, 2, 0);
   }
   __syncthreads();
   constexpr int ST0 = U - NLD < 0 ? 0 : U - NLD;      // the last NLD blocks of a tile each store one strip slot
@@ -530,30 +640,37 @@ __global__ __launch_bounds__(512, 2) void stem_wgrad_split_kernel(const float* _
     const bool has_next = tn < g.ntiles;
     if (has_next) stage_load(tn);
     const unsigned* Sc = S + cur * SBUF;
+    // (APRE = false -- the ragged fused visual kernel, which no CREMA-D shape runs: one A set, read where it is used; with the
+    // second set the kernel spills)
+    constexpr bool APRE = !(FUSED && RAGGED && CIN == 3);
     AFr a0, a1;
-    read_a(Sc, 0, a0);
+    if constexpr (APRE) read_a(Sc, 0, a0);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int s_ = u / KB, kb = u - s_ * KB;
-      AFr& acur = (u & 1) ? a1 : a0;
+      AFr& acur = (APRE && (u & 1)) ? a1 : a0;
       AFr& anext = (u & 1) ? a0 : a1;
       BFr& bcur = (s_ & 1) ? bf1 : bf0;
       BFr& bnext = (s_ & 1) ? bf0 : bf1;
-      if (u + 1 < U) read_a(Sc, u + 1, anext);
+      if constexpr (!APRE) read_a(Sc, u, a0);
+      else if (u + 1 < U) read_a(Sc, u + 1, anext);
       // the next step's dy (slot (s + 1) & 1, landed two steps ago) -> planes, half per block; then that slot is free for
       // step s + 3
-      if (kb < 2) split_dy_half(kb, dyv[(s_ + 1) & 1], bnext);
+      if (kb < 2) split_dy_half(kb, (s_ + 1) & 1, bnext);
       // the next tile's strip (loads issued at the top of this tile): one slot per block; unconditional -- without a next tile
       // the registers are stale and the buffer is never read (a branch would end the scheduling region)
       if (u >= ST0) stage_store(cur ^ 1, u - ST0);
       split_mma<6>(acur.p, bcur.p, acc[kb]);
-      if (kb == 1) load_dy_step(t, tn, s_ + 3, dyv[(s_ + 1) & 1]);
+      if (kb == 1) {
+        at_step(load_dy, t, tn, s_ + 3, (s_ + 1) & 1);
+        if constexpr (FUSED) at_step(load_win, t, tn, WDEEP ? s_ + 3 : s_ + 2, WDEEP ? (s_ + 1) & 1 : 0);
+      }
       __builtin_amdgcn_sched_group_barrier(0x100, 16, 0);          // LDS reads of unit u + 1 first
 #pragma unroll
       for (int m = 0; m < 6; ++m) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);         // one MFMA ...
-        __builtin_amdgcn_sched_group_barrier(0x002, WG_VALU, 0);   // ... then a few VALU of the splits
+        __builtin_amdgcn_sched_group_barrier(0x002, (FUSED && CIN == 1) ? WG_VALU_FUSED : WG_VALU, 0);   // ... then a few VALU of the splits (FUSED: and of dy)
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -648,10 +765,12 @@ int mla_wgrad_reduce(const float* part, float* dw, size_t n4, int splits, hipStr
 
 extern "C" size_t mla_conv2d_stem_wgrad_split_ws_bytes(int Cin) { return (size_t)mla_cu_count() * 49 * Cin * 64 * sizeof(float); }
 
-extern "C" int mla_conv2d_stem_wgrad_split(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin, int Cout,
-                                           int KH, int KW, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = stem_check("mla_conv2d_stem_wgrad_split", N, H, W, Cin, Cout, KH, KW, stride, pad)) return rc;
-  MLA_REQUIRE(x && dy && dw && ws, "mla_conv2d_stem_wgrad_split: null pointer");
+// bp == nullptr: dy is the gradient itself; else dy is conv1's output y and the kernel forms the gradient from *bp
+static int stem_wgrad_launch(const char* who, const float* x, const float* dy, const StemBnPool* bp, float* dw, int N, int H, int W,
+                             int Cin, int Cout, int KH, int KW, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = stem_check(who, N, H, W, Cin, Cout, KH, KW, stride, pad)) return rc;
+  MLA_REQUIRE(x && dy && dw && ws, "%s: null pointer", who);
+  MLA_REQUIRE(!bp || (bp->dpool && bp->idx && bp->mean && bp->invstd && bp->gamma && bp->beta && bp->dgamma && bp->dbeta), "%s: null pointer", who);
   StemGeom g;
   g.N = N; g.H = H; g.W = W;
   g.OH = conv_out(H, 7, 2, 3); g.OW = conv_out(W, 7, 2, 3);
@@ -659,16 +778,46 @@ extern "C" int mla_conv2d_stem_wgrad_split(const float* x, const float* dy, floa
   g.ntiles = N * g.tilesY * g.tilesX;
   g.x_bytes = (unsigned)((size_t)N * H * W * Cin * 4);
   const size_t dyb = (size_t)N * g.OH * g.OW * 64 * 4;
-  MLA_REQUIRE(dyb < 0xFFFFFFF0UL, "mla_conv2d_stem_wgrad_split: dy must be < 4 GiB (32-bit buffer offsets)");
+  MLA_REQUIRE(dyb < 0xFFFFFFF0UL, "%s: dy must be < 4 GiB (32-bit buffer offsets)", who);
   const int grid = g.ntiles < mla_cu_count() ? g.ntiles : mla_cu_count();
   const size_t need = (size_t)grid * 49 * Cin * 64 * sizeof(float);
   if (ws_bytes < need) {
-    mla_set_error("mla_conv2d_stem_wgrad_split: workspace %zu < %zu bytes", ws_bytes, need);
+    mla_set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need);
     return MLA_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (Cin == 1) stem_wgrad_split_kernel<1><<<grid, 512, 0, st>>>(x, dy, (float*)ws, g, (unsigned)dyb);
-  else stem_wgrad_split_kernel<3><<<grid, 512, 0, st>>>(x, dy, (float*)ws, g, (unsigned)dyb);
+  StemBnPool b = {};
+  if (bp) {
+    b = *bp;
+    b.PH = conv_out(g.OH, 3, 2, 1); b.PW = conv_out(g.OW, 3, 2, 1);
+    b.dp_bytes = (unsigned)((size_t)N * b.PH * b.PW * 64 * 4);          // (a quarter of dy or less: < 4 GiB)
+  }
+  const bool ragged = (g.OH % 16) != 0 || (g.OW % 16) != 0;
+#define STEM_WG(CIN_, FU_, RG_) stem_wgrad_split_kernel<CIN_, FU_, RG_><<<grid, 512, 0, st>>>(x, dy, (float*)ws, g, (unsigned)dyb, b)
+  if (!bp) {
+    if (Cin == 1) STEM_WG(1, false, false);
+    else STEM_WG(3, false, false);
+  } else if (Cin == 1) {
+    if (ragged) STEM_WG(1, true, true);
+    else STEM_WG(1, true, false);
+  } else {
+    if (ragged) STEM_WG(3, true, true);
+    else STEM_WG(3, true, false);
+  }
+#undef STEM_WG
   MLA_CHECK_LAUNCH("stem_wgrad_split_kernel");
   return mla_wgrad_reduce((const float*)ws, dw, (size_t)49 * Cin * 64 / 4, grid, st);
+}
+
+extern "C" int mla_conv2d_stem_wgrad_split(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin, int Cout,
+                                           int KH, int KW, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
+  return stem_wgrad_launch("mla_conv2d_stem_wgrad_split", x, dy, nullptr, dw, N, H, W, Cin, Cout, KH, KW, stride, pad, ws, ws_bytes, stream);
+}
+
+extern "C" int mla_conv2d_stem_wgrad_split_bnpool(const float* x, const float* dpool, const uint8_t* idx, const float* y, const float* mean,
+                                                  const float* invstd, const float* gamma, const float* beta, const float* dgamma,
+                                                  const float* dbeta, float* dw, int N, int H, int W, int Cin, int Cout, int KH, int KW,
+                                                  int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
+  StemBnPool bp = {dpool, idx, mean, invstd, gamma, beta, dgamma, dbeta, 0, 0, 0u};
+  return stem_wgrad_launch("mla_conv2d_stem_wgrad_split_bnpool", x, y, &bp, dw, N, H, W, Cin, Cout, KH, KW, stride, pad, ws, ws_bytes, stream);
 }

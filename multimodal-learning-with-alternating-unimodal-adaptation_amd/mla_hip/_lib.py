@@ -60,6 +60,7 @@ PROTOTYPES = {
     "mla_conv2d_stem_fwd_split": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _P, _P]),
     "mla_conv2d_stem_wgrad_split_ws_bytes": (_Z, [_I]),
     "mla_conv2d_stem_wgrad_split": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _Z, _P]),
+    "mla_conv2d_stem_wgrad_split_bnpool": (_I, [_P] * 11 + [_I] * 9 + [_P, _Z, _P]),
     "mla_conv2d_split_cfg": (_I, [_I]),
     "mla_conv2d_wimage_bytes_bf16": (_Z, [_I] * 4),
     "mla_conv2d_wimage_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),

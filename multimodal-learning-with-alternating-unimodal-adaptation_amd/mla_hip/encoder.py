@@ -40,6 +40,9 @@ DS_DGRAD_FOLD = os.environ.get("MLA_DS_DGRAD_FOLD", "1") != "0"
 # activation re-form it from conv1's output (bit-identical: ops.conv2d_*_bnin / _bnmask), where the kernels support it (the 64-channel
 # blocks of layer1 on the split arithmetic).  MLA_BN_FOLD=0 restores the bn_apply pass.
 BN_FOLD = os.environ.get("MLA_BN_FOLD", "1") != "0"
+# measurement switch (same-box A/B): 0 = the stem's BatchNorm backward writes conv1's gradient and the weight gradient reads it back; 1 =
+# the split stem weight-gradient kernel forms it in its load path (ops.conv2d_stem_wgrad_split_bnpool: the same bits, no buffer)
+STEM_BWD_FUSE = os.environ.get("MLA_STEM_BWD_FUSE", "1") != "0"
 
 
 def conv_specs(modality: str) -> List[Tuple[str, int, int, int, int, int]]:
@@ -117,6 +120,8 @@ class ResNet18Encoder(FlatEncoder):
         self._ws: dict = {}
         # per instance: the BatchNorm-backward reductions ride in the input-gradient epilogues (not on the one-plane kernels)
         self.fuse_bn_reduce = FUSE_BN_REDUCE and not self.bf16
+        # per instance: conv1's gradient is formed inside the split stem weight-gradient kernel (conv_math "split" only)
+        self.stem_bwd_fuse = STEM_BWD_FUSE and self.stem_split and self.conv_math == "split"
         # split-bf16 images of the 64..512-channel conv weights (the stem has kernels of its own), keyed by conv name
         self._build_wsplit([(name, name + ".weight", k * k, cin, cout) for name, cin, cout, k, _s, _p in self.specs if cin % 64 == 0])
         # Optional second HIP stream for the weight-gradient GEMMs: they are off the dgrad -> BN-backward critical
@@ -250,7 +255,7 @@ class ResNet18Encoder(FlatEncoder):
         f32 = dict(device=self.device, dtype=torch.float32)
         ws["G"] = [torch.empty(max_act, **f32) for _ in range(4)]
         # one dy buffer per conv output (never reused inside a backward, so the side-stream wgrads need no extra fences)
-        ws["DY"] = {"conv1": torch.empty_like(ws["y_stem"])}
+        ws["DY"] = {}                                  # ("conv1": on first use -- never when the stem weight gradient forms it itself)
         for blk in ws["blocks"]:
             ws["DY"][blk["pre"] + ".conv1"] = torch.empty_like(blk["y1"])
             ws["DY"][blk["pre"] + ".conv2"] = torch.empty_like(blk["y2"])
@@ -452,16 +457,19 @@ class ResNet18Encoder(FlatEncoder):
             wgrad = ops.conv2d_wgrad_bf16
         else:
             wgrad = ops.conv2d_wgrad_split if name in self.wsp else ops.conv2d_wgrad
-        args = (x, dy, self.g[name + ".weight"], stride, pad, ws["wgrad_ws"]) + (() if bn_in is None else (bn_in,))
+        self._side(wgrad, x, dy, self.g[name + ".weight"], stride, pad, ws["wgrad_ws"], *(() if bn_in is None else (bn_in,)))
+
+    def _side(self, fn, *args) -> None:
+        """fn(*args) on the weight-gradient side stream when one is attached, behind everything enqueued on the main stream so far."""
         side = self.wgrad_stream
         if side is None:
-            wgrad(*args)
+            fn(*args)
             return
         ev = torch.cuda.Event()
-        ev.record()                                   # dy is complete on the main stream at this point
+        ev.record()                                   # the operands are complete on the main stream at this point
         side.wait_event(ev)
         with torch.cuda.stream(side):
-            wgrad(*args)
+            fn(*args)
 
     def _dgrad(self, ws, st, dy, name, x_shape, stride, pad, dx, residual=None, relu_src=None, bn_next=(), class_mask=0xF,
                residual_mask=0xF, mask_gb=None):
@@ -545,9 +553,18 @@ class ResNet18Encoder(FlatEncoder):
         # stem: maxpool -> relu -> bn1 -> conv1
         dpool = G[0][:ws["p0"].numel()].view(ws["p0"].shape)
         mean, invstd = ws["stats"]["bn1"]
-        ops.bn_bwd_pooled(dpool, ws["pool_idx"], ws["y_stem"], mean, invstd, self.p["bn1.weight"], self.p["bn1.bias"],
-                          DY["conv1"], self.g["bn1.weight"], self.g["bn1.bias"], ws["bn_ws"], stream=st)
-        self._wgrad(ws, ws["x0"], DY["conv1"], "conv1", 2, 3)
+        ga, be, dga, dbe = self.p["bn1.weight"], self.p["bn1.bias"], self.g["bn1.weight"], self.g["bn1.bias"]
+        if self.stem_bwd_fuse:
+            # the reduction half alone; the weight-gradient kernel forms conv1's gradient from y_stem, dpool and the codes where it
+            # would have loaded it (no DY["conv1"]).  _side's fence follows the reduction: it covers dgamma / dbeta.
+            ops.bn_bwd_pooled(dpool, ws["pool_idx"], ws["y_stem"], mean, invstd, ga, be, None, dga, dbe, ws["bn_ws"], stream=st)
+            self._side(ops.conv2d_stem_wgrad_split_bnpool, ws["x0"], dpool, ws["pool_idx"], ws["y_stem"], mean, invstd, ga, be, dga, dbe,
+                       self.g["conv1.weight"], ws["wgrad_ws"])
+        else:
+            if "conv1" not in DY:
+                DY["conv1"] = torch.empty_like(ws["y_stem"])
+            ops.bn_bwd_pooled(dpool, ws["pool_idx"], ws["y_stem"], mean, invstd, ga, be, DY["conv1"], dga, dbe, ws["bn_ws"], stream=st)
+            self._wgrad(ws, ws["x0"], DY["conv1"], "conv1", 2, 3)
         if self.wgrad_stream is not None:
             torch.cuda.current_stream().wait_stream(self.wgrad_stream)      # all gradients complete before SGD / all-reduce
         self.grad_ready = True

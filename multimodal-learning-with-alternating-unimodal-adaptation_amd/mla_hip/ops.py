@@ -376,6 +376,19 @@ def conv2d_stem_wgrad_split(x: torch.Tensor, dy: torch.Tensor, dw_hwio: torch.Te
     return _conv_wgrad("mla_conv2d_stem_wgrad_split", "stem_wgrad", x, dy, dw_hwio, stride, pad, ws, stream)
 
 
+def conv2d_stem_wgrad_split_bnpool(x: torch.Tensor, dpool: torch.Tensor, idx: torch.Tensor, y: torch.Tensor, mean, invstd, gamma, beta,
+                                   dgamma, dbeta, dw_hwio: torch.Tensor, ws: torch.Tensor, stream: Optional[int] = None) -> torch.Tensor:
+    """Stem weight gradient that forms conv1's gradient itself: the apply pass of bn_bwd_pooled runs where conv2d_stem_wgrad_split
+    loads dy (same bits); dgamma / dbeta from bn_bwd_pooled(dy=None).  ws as conv2d_stem_wgrad_split."""
+    N, H, W, Cin = x.shape
+    KH, KW, _, Cout = dw_hwio.shape
+    t0 = _begin()
+    _call("mla_conv2d_stem_wgrad_split_bnpool", _p(x), _p(dpool), _p(idx, torch.uint8), _p(y), _p(mean), _p(invstd), _p(gamma), _p(beta),
+          _p(dgamma), _p(dbeta), _p(dw_hwio), N, H, W, Cin, Cout, KH, KW, 2, 3, _p(ws), ws.numel() * ws.element_size(), stream or cur_stream())
+    _end(t0, "stem_wgrad", 2.0 * y.numel() * KH * KW * Cin)
+    return dw_hwio
+
+
 def conv2d_wgrad_tr(on: int = -1) -> int:
     """Measurement hook: 0 / 1 = per-tap / persistent all-taps split weight gradient for the 64 -> 64 3x3 convs; -1: query."""
     return int(_lib.load().mla_conv2d_wgrad_tr(int(on)))
@@ -476,12 +489,16 @@ def bn_relu_maxpool_fwd(y, mean, invstd, gamma, beta, out, idx, stream: Optional
 
 
 def bn_bwd_pooled(dpool, idx, y, mean, invstd, gamma, beta, dy, dgamma, dbeta, ws, stream: Optional[int] = None) -> None:
-    """BatchNorm backward fed by the pooled gradient (max-pool scatter + ReLU mask recomputed on the fly)."""
+    """BatchNorm backward fed by the pooled gradient (max-pool scatter + ReLU mask recomputed on the fly).  dy = None: the
+    reduction half alone (dgamma, dbeta), for conv2d_stem_wgrad_split_bnpool."""
     N, H, W, C = y.shape
     t0 = _begin()
     _call("mla_bn_bwd_pooled", _p(dpool), _p(idx, torch.uint8), _p(y), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(dy), _p(dgamma), _p(dbeta),
           _p(ws), N, H, W, C, stream or cur_stream())
-    by = 12.0 * N * H * W * C + 10.0 * dpool.numel()   # y twice, dy once, the pooled gradient + index twice
+    if dy is None:
+        by = 9.0 * dpool.numel()                        # the pooled gradient + index once, one selected y value per pooled output
+    else:
+        by = 12.0 * N * H * W * C + 10.0 * dpool.numel()   # y twice, dy once, the pooled gradient + index twice
     _end(t0, "bn_bwd", by, by)
 
 
