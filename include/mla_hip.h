@@ -307,6 +307,33 @@ int mla_concat_head_fwd(const float* x0, const float* x1, const float* x2, const
 int mla_concat_head_bwd(const float* x0, const float* x1, const float* x2, const float* W, const float* dlogits, float* dW,
                         float* db, float* dx0, float* dx1, float* dx2, int M, int B, int D, int C, float scale, void* stream);
 
+/* ---- QMF joint step head (--modulation QMF; main.py:170-268, 544-586; utils/utils.py:44-95; main.py:108-125) --------------
+ * One Linear head per modality (audio_fc / visual_fc / txtual_fc): x_m [B][D], W_m [C][D], b_m [C] (x2 / W2 / b2 / dW2 / db2 /
+ * dx2 NULL when M = 2), M = 2 or 3, C <= 128.
+ *   z_m = x_m W_m^T + b_m   [M][B][C];   E_m = logsumexp z_m;   conf = E_m / 10   [M][B];   out = sum_m conf_m z_m   [B][C]
+ * mla_qmf_head_fwd_bwd: the training head in four launches.  ell [M][B] = per-sample CE of z_m.  History (fp64, [M][n_data] each):
+ *   correctness[m][idx_i] += ell_m[i], confidence[m][idx_i] = conf_m[i]; of several samples with one index the LAST writes (numpy's
+ *   `a[idx] += v`).  Then lo / hi = min / max of correctness[m][:], n = (correctness - lo) / (hi - lo), and with j = (i + 1) mod B:
+ *   target [M][B] = sign(n_i - n_j), margin [M][B] = |n_i - n_j|, r = conf_j + margin / (target ? target : 1),
+ *   rank_m = inv_batch sum_i max(0, target (conf_i - r)).
+ *   losses [2M + 2] = { L, CE(z_0) .. CE(z_{M-1}), rank_0 .. rank_{M-1}, CE(out) }, L = w_cml CE(out) + sum CE(z_m) + w_crl sum rank_m
+ *   ((w_cml, w_crl) = (1, 0.1): main.py:265-268; (0, 1): main.py:203, 229).  dW_m, db_m, dx_m: the gradients of L (conf detached in
+ *   `out`, both operands of a ranking pair carry gradient).  A label outside [0, C) or an index outside [0, n_data): NaN losses for
+ *   that sample (and the ranking pairs it is part of), no History write, zero gradient rows.
+ *   ws: mla_qmf_head_ws_elems(B, C, M) floats, 8-byte aligned.
+ * mla_qmf_head_fwd: z, out and conf only (valid(), main.py:576-586), one launch.
+ * No atomics, one writer per History entry, every reduction in a fixed order (bitwise reproducible). */
+size_t mla_qmf_head_ws_elems(int B, int C, int M);
+int mla_qmf_head_fwd_bwd(const float* x0, const float* x1, const float* x2, const float* W0, const float* W1, const float* W2,
+                         const float* b0, const float* b1, const float* b2, const int64_t* labels, const int64_t* idx,
+                         double* correctness, double* confidence, int n_data, float* z, float* out, float* conf, float* ell,
+                         float* target, float* margin, float* losses, float* dW0, float* dW1, float* dW2, float* db0, float* db1,
+                         float* db2, float* dx0, float* dx1, float* dx2, float* ws, int M, int B, int D, int C, float w_cml,
+                         float w_crl, float inv_batch, void* stream);
+int mla_qmf_head_fwd(const float* x0, const float* x1, const float* x2, const float* W0, const float* W1, const float* W2,
+                     const float* b0, const float* b1, const float* b2, float* z, float* out, float* conf, int M, int B, int D,
+                     int C, void* stream);
+
 /* ---- GSPlugin.before_update (utils/utils.py:24-41) ------------------------------------------- */
 /* r[j] = scale * sum_i X[i][j]   (column mean with scale = 1/B; rank-local column sum otherwise) */
 int mla_colsum(const float* X, float* r, int B, int D, float scale, void* stream);

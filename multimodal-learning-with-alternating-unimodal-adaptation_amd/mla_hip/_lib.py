@@ -93,6 +93,9 @@ PROTOTYPES = {
     "mla_concat_head_ce_fwd_bwd": (_I, [_P] * 16 + [_I, _I, _I, _I, _F, _P]),
     "mla_concat_head_fwd": (_I, [_P] * 7 + [_I, _I, _I, _I, _P]),
     "mla_concat_head_bwd": (_I, [_P] * 10 + [_I, _I, _I, _I, _F, _P]),
+    "mla_qmf_head_ws_elems": (_Z, [_I, _I, _I]),
+    "mla_qmf_head_fwd_bwd": (_I, [_P] * 13 + [_I] + [_P] * 17 + [_I, _I, _I, _I, _F, _F, _F, _P]),
+    "mla_qmf_head_fwd": (_I, [_P] * 12 + [_I, _I, _I, _I, _P]),
     "mla_ogm_coeff": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
     "mla_ogm_chunk_elems": (_I, []),
     "mla_ogm_ws_bytes": (_Z, [_I, _I]),

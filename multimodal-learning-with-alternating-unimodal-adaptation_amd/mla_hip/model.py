@@ -146,7 +146,10 @@ class ConcatFusion(nn.Module):
 
 
 def check_joint_args(args) -> None:
-    """What the joint (gs_flag false) classifiers support: `--modulation Normal | OGM | OGM_GE` with concat fusion."""
+    """What the joint (gs_flag false) classifiers support through `args`: `--modulation Normal | OGM | OGM_GE` with concat fusion.
+    `--modulation QMF` (main.py:170-268) lives in `mla_hip.qmf`: build the model with gs_flag false and modulation "Normal", then
+    `attach_qmf_heads(model)` / `QMFTrainer(model, n_data)` add the per-modality audio_fc / visual_fc / txtual_fc heads and the
+    History ranking loss.  `args.modulation == "QMF"` itself still raises here."""
     mod = getattr(args, "modulation", "Normal")
     if mod == "QMF":
         raise NotImplementedError("mla_hip does not implement --modulation QMF (main.py:170-268): it needs the per-modality "
@@ -164,6 +167,7 @@ class _Classifier(nn.Module):
     states ONCE how its inputs reach them: `_calls(*inputs) -> (batch, [run(out=None) -> (B, D) feature])`, one callable per
     encoder in `mla_encoders()` order; the kernel-level and the autograd forwards below are derived from that list."""
     side_streams = True
+    qmf_heads = None            # mla_hip.qmf.attach_qmf_heads: the per-modality heads, in mla_encoders() order
 
     def __init__(self, args, device, seed: Optional[int], datasets, fusion_cls, feat_dim: int, n_enc: int):
         """datasets: the names the reference's constructor accepts, its default first.  Builds the fusion module (the
@@ -223,7 +227,10 @@ class _Classifier(nn.Module):
         """The features as fresh (B, D) tensors that carry autograd history to their encoder when grad mode is on and the
         model is training."""
         B, runs = self._calls(*inputs)
-        return tuple(self._feature(enc, run, B) for (_t, _g, enc), run in zip(self.mla_encoders(), runs))
+        feats = tuple(self._feature(enc, run, B) for (_t, _g, enc), run in zip(self.mla_encoders(), runs))
+        if self.qmf_heads is not None:      # QMF: (audio_fc(a), visual_fc(v)[, txtual_fc(t)]), basic_model.py:67-71, 196-200, 269-273
+            return tuple(head(f) for head, f in zip(self.qmf_heads, feats))
+        return feats
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """Accepts DataParallel-style `module.`-prefixed keys as well (main.py:724 strips them by hand)."""
@@ -280,4 +287,4 @@ class AVClassifier(_Classifier):
     def forward(self, audio: torch.Tensor, visual: torch.Tensor):
         """gs_flag false: a, v, out = model(...) (main.py:273; basic_model.py:72-74)."""
         a, v = super().forward(audio, visual)
-        return (a, v) if self.gs_flag else self.fusion_module(a, v)
+        return (a, v) if self.gs_flag or self.qmf_heads is not None else self.fusion_module(a, v)

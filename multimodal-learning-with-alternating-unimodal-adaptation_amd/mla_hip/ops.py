@@ -603,6 +603,44 @@ def concat_head_bwd(xs, W, dlogits, dW, db, dxs, scale: float = 1.0, stream: Opt
     _call("mla_concat_head_bwd", x[0], x[1], x[2], _p(W), _p(dlogits), _p(dW), _p(db), dx[0], dx[1], dx[2], M, B, D, C, scale, stream or cur_stream())
 
 
+def qmf_head_ws_elems(B: int, C: int, M: int) -> int:
+    return int(_lib.load().mla_qmf_head_ws_elems(B, C, M))
+
+
+def _qmf_ptrs(xs, Ws, bs, who: str):
+    x, M, B, D = _concat_ptrs(xs, who)
+    C = Ws[0].shape[0]
+    if len(Ws) != M or len(bs) != M or any(tuple(W.shape) != (C, D) for W in Ws) or any(tuple(b.shape) != (C,) for b in bs):
+        raise MLAHipError(f"{who}: needs {M} heads of shape ({C}, {D}) / ({C},); got {[tuple(W.shape) for W in Ws]}")
+    pad = [None] * (3 - M)
+    return x, [_p(W) for W in Ws] + pad, [_p(b) for b in bs] + pad, M, B, D, C
+
+
+def qmf_head_fwd_bwd(xs, Ws, bs, labels, idx, correctness, confidence, z, out, conf, ell, target, margin, losses, dWs, dbs, dxs, ws,
+                     w_cml: float, w_crl: float, inv_batch: float, stream: Optional[int] = None) -> None:
+    """QMF training head (main.py:239-268 / 170-229): per-modality logits z (M, B, C), fused `out`, confidences, the History update
+    (correctness / confidence: fp64 (M, n_data), updated in place), ranking targets / margins, losses [L, CE_m.., rank_m.., CE(out)]
+    and every gradient."""
+    x, W, b, M, B, D, C = _qmf_ptrs(xs, Ws, bs, "qmf_head_fwd_bwd")
+    n_data = correctness.shape[1]
+    if tuple(correctness.shape) != (M, n_data) or tuple(confidence.shape) != (M, n_data) or idx.numel() != B or labels.numel() != B:
+        raise MLAHipError(f"qmf_head_fwd_bwd: history {tuple(correctness.shape)} / {tuple(confidence.shape)} must be ({M}, n_data), "
+                          f"labels / idx must hold {B} entries")
+    if len(dWs) != M or len(dbs) != M or len(dxs) != M or ws.numel() < qmf_head_ws_elems(B, C, M):
+        raise MLAHipError("qmf_head_fwd_bwd: one dW / db / dX per modality and a workspace of qmf_head_ws_elems floats are needed")
+    pad = [None] * (3 - M)
+    dW, db, dx = [_p(t) for t in dWs] + pad, [_p(t) for t in dbs] + pad, [_p(t) for t in dxs] + pad
+    _call("mla_qmf_head_fwd_bwd", *x, *W, *b, _p(labels, torch.int64), _p(idx, torch.int64), _p(correctness, torch.float64),
+          _p(confidence, torch.float64), n_data, _p(z), _p(out), _p(conf), _p(ell), _p(target), _p(margin), _p(losses), *dW, *db, *dx,
+          _p(ws), M, B, D, C, w_cml, w_crl, inv_batch, stream or cur_stream())
+
+
+def qmf_head_fwd(xs, Ws, bs, z, out, conf, stream: Optional[int] = None) -> None:
+    """z_m = fc_m(x_m), out = sum_m conf_m z_m, conf_m = logsumexp(z_m) / 10, no gradients (valid(), main.py:576-586)."""
+    x, W, b, M, B, D, C = _qmf_ptrs(xs, Ws, bs, "qmf_head_fwd")
+    _call("mla_qmf_head_fwd", *x, *W, *b, _p(z), _p(out), _p(conf), M, B, D, C, stream or cur_stream())
+
+
 def scale_by_device_scalar(x, scalar, stream: Optional[int] = None) -> None:
     _call("mla_scale_by_device_scalar", _p(x), _p(scalar), x.numel(), stream or cur_stream())
 

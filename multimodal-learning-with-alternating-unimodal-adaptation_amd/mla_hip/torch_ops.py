@@ -235,6 +235,31 @@ def concat_head_bwd(xs, W, dlogits, scale=1.0):
     return dW, db, dxs
 
 
+@_op("qmf_head_fwd_bwd(Tensor[] xs, Tensor[] Ws, Tensor[] bs, Tensor labels, Tensor idx, Tensor(a!) correctness, "
+     "Tensor(b!) confidence, float w_cml, float w_crl, float inv_batch) -> "
+     "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor[], Tensor[], Tensor[])")
+def qmf_head_fwd_bwd(xs, Ws, bs, labels, idx, correctness, confidence, w_cml, w_crl, inv_batch):
+    """QMF training head (main.py:239-268): (z (M, B, C), out, conf (M, B), ell (M, B), target (M, B), margin (M, B),
+    losses [L, CE_m.., rank_m.., CE(out)], [dW_m], [db_m], [dX_m]); the fp64 History (M, n_data) is updated in place."""
+    M, (B, D), C = len(xs), xs[0].shape, Ws[0].shape[0]
+    x0 = xs[0]
+    z, out, losses = _f32((M, B, C), x0), _f32((B, C), x0), _f32(2 * M + 2, x0)
+    conf, ell, target, margin = (_f32((M, B), x0) for _ in range(4))
+    dWs, dbs, dxs = [_f32((C, D), x0) for _ in range(M)], [_f32(C, x0) for _ in range(M)], [_f32((B, D), x0) for _ in range(M)]
+    ops.qmf_head_fwd_bwd(list(xs), list(Ws), list(bs), labels, idx.reshape(-1), correctness, confidence, z, out, conf, ell, target,
+                         margin, losses, dWs, dbs, dxs, _f32(ops.qmf_head_ws_elems(B, C, M), x0), w_cml, w_crl, inv_batch)
+    return z, out, conf, ell, target, margin, losses, dWs, dbs, dxs
+
+
+@_op("qmf_head_fwd(Tensor[] xs, Tensor[] Ws, Tensor[] bs) -> (Tensor, Tensor, Tensor)")
+def qmf_head_fwd(xs, Ws, bs):
+    """(z (M, B, C), out, conf (M, B)) of the QMF heads (valid(), main.py:576-586)"""
+    M, (B, _D), C = len(xs), xs[0].shape, Ws[0].shape[0]
+    z, out, conf = _f32((M, B, C), xs[0]), _f32((B, C), xs[0]), _f32((M, B), xs[0])
+    ops.qmf_head_fwd(list(xs), list(Ws), list(bs), z, out, conf)
+    return z, out, conf
+
+
 @_op("gs_project(Tensor(a!) Pl, Tensor X, Tensor(b!) G, float alpha) -> ()")
 def gs_project(Pl, X, G, alpha):
     """GSPlugin.before_update body (utils/utils.py:34-41) on the batch features X (B, D): Pl and G updated in place."""

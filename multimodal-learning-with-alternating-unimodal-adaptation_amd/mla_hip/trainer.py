@@ -37,12 +37,15 @@ class StreamTrainer:
     STEP's first forward only needs that encoder's own SGD, so the encoder chains run beside each other and across step
     boundaries and fill each other's kernel tails."""
 
-    def __init__(self, model, lr: float, momentum: float, weight_decay: float, legacy_zero_grad: bool, comm: Optional[Comm]):
+    def __init__(self, model, lr: float, momentum: float, weight_decay: float, legacy_zero_grad: bool, comm: Optional[Comm],
+                 extra_groups: Optional[dict] = None):
+        """extra_groups: further optimiser groups (name -> flat-buffer object) after the encoders' and the head's."""
         self.model = model
         self.head = model.fusion_module.fc_out
         self.encoders = model.mla_encoders()                    # [(tag, group, encoder)], alternation / concatenation order
         groups = {grp: enc for _t, grp, enc in self.encoders}
         groups["head"] = self.head
+        groups.update(extra_groups or {})
         self.optimizer = FusedSGD(groups, lr, momentum, weight_decay, legacy_zero_grad)
         self.comm = comm if comm is not None else Comm()
         dev = model.device

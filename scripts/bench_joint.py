@@ -1,6 +1,6 @@
 """Joint concat-fusion step (gs_flag false, main.py:164-417) vs the MLA step, same process, same box: CREMA-D config 1
 shapes (per-GPU batch 64, spectrogram 1x1024x128, frames 3x3x224x224, 6 classes), conv arithmetic split (the shipped
-default) unless MATH=f32.  One JSON line per mode (MLA, Normal, OGM, OGM_GE) with samples/s and ms/step.  Not the headline
+default) unless MATH=f32.  One JSON line per mode (MLA, Normal, OGM, OGM_GE; QMF on request) with samples/s and ms/step.  Not the headline
 bench line (bench.py); numbers go to DESIGN.md.
 
     python scripts/bench_joint.py [--steps 20] [--warmup 5] [--batch 64] [--math split] [--serial]
@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-learning-with-alternating-unimodal-adaptation_amd"))
 import torch  # noqa: E402
 
-from mla_hip import AVClassifier, JointTrainer, MLATrainer  # noqa: E402
+from mla_hip import AVClassifier, JointTrainer, MLATrainer, QMFTrainer  # noqa: E402
 
 SPEC_HW, FRAMES, IMG_HW = (1024, 128), 3, (224, 224)
 
@@ -37,7 +37,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--math", choices=["f32", "split"], default=os.environ.get("MLA_CONV_MATH", "split"))
-    ap.add_argument("--modes", default="MLA,Normal,OGM,OGM_GE", help="comma-separated subset (e.g. one mode per profiler run)")
+    ap.add_argument("--modes", default="MLA,Normal,OGM,OGM_GE", help="comma-separated subset (e.g. one mode per profiler run); QMF is also a mode")
     ap.add_argument("--serial", action="store_true", help="joint modes with set_overlap(False) (A/B of the concurrent backwards)")
     a = ap.parse_args()
     B = a.batch
@@ -69,6 +69,19 @@ def main():
         print(json.dumps(dict(base, mode=mode, overlap=jt.overlap_forward, ms_per_step=round(dt * 1e3, 3), samples_per_s=round(B / dt, 1),
                               vs_mla_ms=None if mla_ms is None else round(dt * 1e3 - mla_ms, 3), loss=round(jt.losses["loss"].item(), 5))), flush=True)
         del jt, model
+    if "QMF" in modes:
+        class QArgs:
+            fusion_method, dataset, gs_flag, modulation = "concat", "CREMAD", False, "Normal"
+        n_data = 6698                                             # CREMA-D training split
+        model = AVClassifier(QArgs(), seed=1, conv_math=a.math)
+        qt = QMFTrainer(model, n_data, seed=2)
+        if a.serial:
+            qt.set_overlap(False)
+        idx = torch.randperm(n_data, device="cuda", generator=g)[:B]
+        dt = timed(lambda s: qt.train_step(spec, image, label, (idx + s * B) % n_data, s), a.steps, a.warmup)
+        print(json.dumps(dict(base, mode="QMF", overlap=qt.overlap_forward, ms_per_step=round(dt * 1e3, 3), samples_per_s=round(B / dt, 1),
+                              vs_mla_ms=None if mla_ms is None else round(dt * 1e3 - mla_ms, 3), loss=round(qt.losses["loss"].item(), 5))), flush=True)
+        del qt, model
 
 
 if __name__ == "__main__":
