@@ -439,6 +439,11 @@ def conv2d_wgrad_split(x: torch.Tensor, dy: torch.Tensor, dw_hwio: torch.Tensor,
 
 
 # ---- batch norm ---------------------------------------------------------------------------------
+def bn_partial_scratch_elems(C: int) -> int:
+    """Floats of the two-stage reduction's scratch tail that follows the [tiles][2][C] rows of every partial buffer."""
+    return int(_lib.load().mla_bn_partial_scratch_elems(C))
+
+
 def bn_stats_partial_elems(M: int, C: int) -> int:
     return int(_lib.load().mla_bn_stats_partial_elems(M, C))
 

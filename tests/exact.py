@@ -15,7 +15,9 @@ lo*hi) are non-zero, while the three dropped ones (mid*lo, lo*mid, lo*lo) are ex
 
 A kernel that loses, doubles or mis-pairs one of these products differs from the reference by hundreds of units.
 """
+import functools
 import math
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
@@ -279,3 +281,329 @@ def assert_bitwise(got, want, name, unit=None):
     in_units = f" = {worst / unit:.1f} units of {unit:g}" if unit else ""
     raise AssertionError(f"{name}: {int(bad.sum())} of {bad.numel()} elements differ; max|d| = {worst:.6e}{in_units}; first at index "
                          f"{first}: got {got[tuple(first)].item()!r}, want {want[tuple(first)].item()!r}")
+
+
+# ==================================================================================================================================
+# Exactly-summable inputs for the REDUCTIONS between the contractions: BatchNorm statistics and backward sums with their finalize
+# paths, the reductions fused into the input-gradient epilogue and the pooled stem backward, column sums, LayerNorm affine gradients
+# (test_reduce_exact_cpu.py proves the builders, test_reduce_exact_gpu.py runs the kernels).
+#
+# All data are small integers held in fp32, scaled where needed by a power of two: mean is an integer per channel (per row for
+# LayerNorm), invstd / rstd a power of two, gamma +-2^j, beta an integer.  Then x * x, g * ((x - mean) * invstd) and bn(x) are exact
+# in fp32, contracted to an fma or not, every term of a sum is a multiple of one unit, and with  sum |term| < 2^24 units  per output
+# (assert_sum_budget, checked before anything is launched) every partial sum in any order, tiling or finalize path is exact.  The
+# reference is int64 arithmetic; a lost, doubled or mis-paired row or tile is off by whole units.
+# ==================================================================================================================================
+SUM_BUDGET = 2 ** 24
+G_UNIT = 2.0 ** -3            # upstream gradients are integers / 8: |g| < 1, see bn_rows_case on the dx tolerance
+BN_EPS32 = torch.tensor(1e-5, dtype=torch.float32).double().item()          # the kernels take eps and momentum as fp32
+BN_MOM32 = torch.tensor(0.1, dtype=torch.float32).double().item()
+
+
+def rand_ints(shape, lo, hi, seed, nonzero=False, dtype=torch.int64):
+    """Uniform integers in [lo, hi]; nonzero: in [lo, -1] and [1, hi] (lo < 0 < hi)."""
+    g = torch.Generator().manual_seed(int(seed))
+    if not nonzero:
+        return torch.randint(lo, hi + 1, tuple(shape), generator=g, dtype=dtype)
+    r = torch.randint(lo, hi, tuple(shape), generator=g, dtype=dtype)
+    return r + (r >= 0).to(dtype)
+
+
+def assert_sum_budget(abs_units, name=""):
+    """abs_units: per output element the sum over ALL rows (tiles) of |term| / unit, as integers.  Below 2^24 every partial sum of
+    every summation order is an exactly representable fp32 value (and an fp64 one by a wide margin).  Returns log2 of the budget used."""
+    worst = int(torch.as_tensor(abs_units).max())
+    assert worst < SUM_BUDGET, f"{name}: sum of |terms| = 2^{math.log2(max(worst, 1)):.2f} units: fp32 partial sums are not exact here"
+    return math.log2(max(worst, 1))
+
+
+def exact_f32(units, unit):
+    """int64 units * unit (a power of two, scalar or per element) as fp32; nothing may round on the way."""
+    d = units.double() * unit
+    f = d.float()
+    assert torch.equal(f.double(), d), "an exact total is not representable in fp32"
+    return f
+
+
+def bn_channels(C, seed):
+    """Per-channel BatchNorm parameters on which xhat and bn(x) are exact for integer x: integer mean and beta, invstd = 2^-k with
+    k in 1..3 (so xhat of x = mean +- 8 is of unit scale, like real normalised data), gamma = +-2^j with j in -1..1; |gamma * invstd| <= 1."""
+    mean_i, k = rand_ints((C,), -3, 3, seed), rand_ints((C,), 1, 3, seed + 1)
+    sign, j = rand_ints((C,), 0, 1, seed + 2) * 2 - 1, rand_ints((C,), -1, 1, seed + 3)
+    return SimpleNamespace(C=C, mean_i=mean_i, k=k, mean=mean_i.float(), invstd=(2.0 ** -k.double()).float(),
+                           gamma=(sign.double() * 2.0 ** j.double()).float(), beta=rand_ints((C,), -2, 2, seed + 4).float())
+
+
+# ---- 1. finalize regimes: fabricated per-tile partials ------------------------------------------------------------------------------
+FINALIZE_TILES = (1, 15, 16, 17, 63, 64, 65,            # lanes unused / one trip / tail of the one-launch kernel
+                  1023, 1024, 1025,                     # one-launch | wide boundary
+                  1025 + 191, 1025 + 256,               # wide kernel: unrolled trip present / absent
+                  16383, 16384, 16385, 20001, 40000)    # wide | two-stage boundary; ragged last chunk
+FINALIZE_CASES = [(C, t) for C in (4, 64) for t in FINALIZE_TILES] + [(1024, t) for t in FINALIZE_TILES if t <= 1025]
+
+
+def _separate_slots(p):
+    """Make the totals of slot 0 and slot 1 differ in every channel (a kernel that swaps the slots must be seen everywhere): where
+    they are equal the sign of slot 1's first tile is flipped, which moves that total by 2 |v| != 0 and keeps sum |v|."""
+    same = p[:, 0].sum(0) == p[:, 1].sum(0)
+    p[0, 1] = torch.where(same, -p[0, 1], p[0, 1])
+    return p
+
+
+def bwd_partials(tiles, C, seed):
+    """fp32 [tiles][2][C] per-tile (sum g, sum g * xhat) rows as bn_reduce_kernel<1> writes them: non-zero integers, so a dropped or
+    doubled tile moves a total by at least 1; tiles * max|v| < 2^20: with a power-of-two row count in the apply pass that follows, dgamma / M, dbeta / M and xhat * dgamma / M are then exact too."""
+    amax = min(1000, (2 ** 20 - 1) // tiles)
+    p = _separate_slots(rand_ints((tiles, 2, C), -amax, amax, seed, nonzero=True))
+    assert (p != 0).all() and (tiles == 1 or (p.min(0).values != p.max(0).values).all()), "tile contributions must be non-zero and distinct"
+    assert_sum_budget(p.abs().sum(0), f"backward partials, {tiles} tiles")
+    tot = p.sum(0)
+    assert (tot[0] != tot[1]).all()
+    return SimpleNamespace(tiles=tiles, C=C, ints=p, partial=p.float(), dbeta=exact_f32(tot[0], 1.0), dgamma=exact_f32(tot[1], 1.0))
+
+
+def fwd_partials(tiles, C, seed):
+    """fp64 [tiles][2][C] per-tile (sum x, sum x^2) rows as the conv epilogue / bn_reduce_kernel<0> write them, for M = 2^k rows (about
+    32 to 64 per tile): sum x in [-32, 96] without 0, sum x^2 in [1024, 4095].  Then |mean| <= 3 and E[x^2] > 16, so the variance is
+    above 7 -- far from the cancellation of E[x^2] - E[x]^2 -- and s / M is exact in fp64 AND in fp32 (s < 2^24).
+    The running mean starts at multiples of 1/4: (1 - momentum) * rm + momentum * mean is then exact in fp64 whether the compiler
+    contracts it or not (running_units), so after the one rounding to fp32 the kernel's value must equal the reference bit for bit."""
+    M = 1 << (32 * tiles - 1).bit_length()
+    s = rand_ints((tiles, 1, C), -32, 96, seed, nonzero=True)
+    q = rand_ints((tiles, 1, C), 1024, 4095, seed + 1)
+    p = torch.cat([s, q], 1)
+    assert_sum_budget(s.abs().sum(0), f"forward partials, {tiles} tiles")
+    assert int(q.sum(0).max()) < 2 ** 53
+    rm4 = rand_ints((C,), -8, 8, seed + 2)
+    rv = (rand_ints((C,), 2, 12, seed + 3).double() / 4).float()
+    return SimpleNamespace(tiles=tiles, C=C, M=M, ints=p, partial=p.double(), S=p[:, 0].sum(0), Q=p[:, 1].sum(0), rm4=rm4,
+                           running_mean=(rm4.double() / 4).float(), running_var=rv)
+
+
+def bn_stats_ref(S, Q, M, running_mean=None, running_var=None):
+    """The statistics of mla_bn_finalize in fp64, from the exact integer totals: mean, invstd[, running_mean, running_var]."""
+    m = S.double() / M
+    var = (Q.double() / M - m * m).clamp_min(0.0)
+    out = [m, 1.0 / torch.sqrt(var + BN_EPS32)]
+    if running_mean is not None:
+        unb = var * (float(M) / float(max(M - 1, 1)))
+        out += [(1.0 - BN_MOM32) * running_mean.double() + BN_MOM32 * m, (1.0 - BN_MOM32) * running_var.double() + BN_MOM32 * unb]
+    return out
+
+
+def running_units(S, rm4, M):
+    """(1 - momentum) * rm4 / 4 + momentum * S / M as an integer count of 2^-29 / M (M = 2^k): momentum = a / 2^27 exactly (fp32 0.1),
+    so the value is ((2^27 - a) * rm4 * M + 4 * a * S) units, below 2^53: every fp64 evaluation of it is exact."""
+    a = int(BN_MOM32 * 2 ** 27)
+    assert a / 2 ** 27 == BN_MOM32 and M & (M - 1) == 0
+    u = (2 ** 27 - a) * rm4 * M + 4 * a * S
+    assert int(u.abs().max()) < 2 ** 53
+    return u, 2.0 ** -29 / M
+
+
+# ---- 2. producer kernels over [M][C] rows -------------------------------------------------------------------------------------------
+BN_C = (4, 8, 16, 32, 64, 256, 1024)
+BN_WRAP_N4 = 8192 * 256 + 448          # float4 elements: the elementwise grid is capped at 8192 workgroups of 256 threads
+
+
+def bn_row_counts(C):
+    """M = 1, 3, one either side of the number of row lanes (1024 / C) and of the 32-row tile, two tiles + 1; for C = 4 and 64 also
+    65537, 2^18 + 1 (the tile rule changes, more than 1024 tiles) and the first M whose elementwise pass wraps its grid-stride loop."""
+    nrl = 1024 // C
+    ms = {1, 3, nrl - 1, nrl + 1, 31, 32, 33, 2 * 32 + 1}
+    if C in (4, 64):
+        ms |= {65537, 2 ** 18 + 1, BN_WRAP_N4 * 4 // C}
+    return sorted(m for m in ms if m > 0)
+
+
+BN_ROW_CASES = [(M, C) for C in BN_C for M in bn_row_counts(C)]
+
+
+def bn_rows_case(M, C, seed):
+    """x = mean + d with integer |d| <= D, g = integer / 8 with |integer| <= G, an integer residual; (G, D) shrinks with M so that
+    M * G * D < 2^24.  Terms of sum g are multiples of 1/8, terms of sum g * xhat multiples of invstd / 8.
+
+    Why g is scaled by 1/8: the apply passes are held to the fp64 formula at atol 1e-6, rtol 2e-5.  With r = g - a - b, a = dbeta / M,
+    b = xhat * dgamma / M, every fp32 rounding of the kernel is relative to one of the terms (< 3e-7 in all).  |g|, |a| < 1, so either
+    |b| >= 2, then |r| >= |b| / 8 and the relative error of r is below 3e-6, or |b| < 2 and the absolute error is below 1e-6;
+    |gamma * invstd| <= 1 scales both alike.  Cancellation cannot push a correct kernel over the tolerance."""
+    G, D = next((g, d) for g, d in ((7, 8), (3, 5), (2, 3), (1, 3)) if M * g * d < SUM_BUDGET)
+    ch = bn_channels(C, seed)
+    i32 = torch.int32
+    dev, gi = rand_ints((M, C), -D, D, seed + 10, dtype=i32), rand_ints((M, C), -G, G, seed + 11, dtype=i32)
+    ri = rand_ints((M, C), -3, 3, seed + 12, dtype=i32)
+    assert_sum_budget(gi.abs().sum(0, dtype=torch.int64), f"sum g, M={M} C={C}")
+    assert_sum_budget((gi * dev).abs().sum(0, dtype=torch.int64), f"sum g * xhat, M={M} C={C}")
+    xi = dev + ch.mean_i.to(i32)
+    assert int((xi.long() * xi.long()).sum(0).max()) < 2 ** 53
+    return SimpleNamespace(M=M, C=C, ch=ch, dev=dev, gi=gi, xi=xi, x=xi.float(), g=(gi.double() * G_UNIT).float(), res=ri.float())
+
+
+def bn_stat_sums(case):
+    """(sum x, sum x^2) per channel, int64."""
+    xl = case.xi.long()
+    return xl.sum(0), (xl * xl).sum(0)
+
+
+def bn_bwd_sums(case, mask=None):
+    """Exact (dgamma, dbeta) as fp32; mask (bool [M][C]): the rows the ReLU passes."""
+    gi = case.gi if mask is None else case.gi * mask.to(case.gi.dtype)
+    db, dg = gi.sum(0, dtype=torch.int64), (gi * case.dev).sum(0, dtype=torch.int64)
+    return exact_f32(dg, G_UNIT * case.ch.invstd.double()), exact_f32(db, G_UNIT)
+
+
+def bn_apply_rows(x, ch, relu=False, residual=None):
+    """relu(bn(x) + residual) in fp64 (exact on these inputs)."""
+    y = ((x.double() - ch.mean.double()) * ch.invstd.double()) * ch.gamma.double() + ch.beta.double()
+    if residual is not None:
+        y = y + residual.double()
+    return y.clamp_min(0.0) if relu else y
+
+
+def bn_dx_rows(g, x, ch, dgamma, dbeta, M):
+    """The BatchNorm input gradient in fp64 from given dgamma / dbeta: gamma * invstd * (g - dbeta / M - xhat * dgamma / M)."""
+    xhat = (x.double() - ch.mean.double()) * ch.invstd.double()
+    return ch.gamma.double() * ch.invstd.double() * (g.double() - dbeta.double() / M - xhat * (dgamma.double() / M))
+
+
+# ---- 3a. BatchNorm-backward reductions in the input-gradient epilogue ---------------------------------------------------------------
+DGRAD_BN_GEOMS = [      # (N, H, W, Cin, Cout, k, s, p), conv2d_patch setting (None: leave the planner's)
+    ((2, 9, 7, 64, 128, 3, 2, 1), None),
+    ((2, 33, 17, 128, 128, 3, 1, 1), None),
+    ((2, 20, 12, 64, 128, 3, 2, 1), None),      # a merged stride-2 geometry (the four parity classes in one launch)
+    ((2, 56, 56, 64, 64, 3, 1, 1), 2),          # the LDS-patch kernels' epilogues (persistent 64 -> 64 and one tile per workgroup)
+]
+
+
+def dgrad_bn_case(geom, seed):
+    """Class D operands (integer dy, w and residual, |.| <= a): dx is an exact integer map.  Two BatchNorm requests with integer inputs
+    z_q = mean_q + d_q, |d_q| <= D.  (a, D) shrink until  sum (|dx| + |residual|) * |d_q| < 2^24  per channel, which bounds the terms of
+    every operand combination (with / without residual, ReLU mask)."""
+    N, H, W, Cin, Cout, k, s, p = geom
+    OH, OW = conv_out(H, k, s, p), conv_out(W, k, s, p)
+    con = lambda a, b: conv_dgrad(a, b, (N, H, W, Cin), s, p)
+    chs = [bn_channels(Cin, seed + 20 + 10 * q) for q in range(2)]
+    for a, D in ((7, 8), (5, 8), (3, 8), (3, 4), (2, 4), (2, 2), (1, 2), (1, 1)):
+        dy, w = rand_ints((N, OH, OW, Cout), -a, a, seed).float(), rand_ints((k, k, Cin, Cout), -a, a, seed + 1).float()
+        res = rand_ints((N, H, W, Cin), -a, a, seed + 2)
+        assert_exact_budget(dy, w, 1.0, contract=con, name=f"dgrad {geom}")
+        dx = con(dy, w)
+        devs = [rand_ints((N, H, W, Cin), -D, D, seed + 3 + q) for q in range(2)]
+        bound = dx.long().abs() + res.abs()
+        if max(int((bound * d.abs()).reshape(-1, Cin).sum(0).max()) for d in devs) < SUM_BUDGET:
+            break
+    for d in devs:
+        assert_sum_budget((bound * d.abs()).reshape(-1, Cin).sum(0), f"dgrad epilogue sum v * xhat {geom}")
+    assert_sum_budget(bound.reshape(-1, Cin).sum(0), f"dgrad epilogue sum v {geom}")
+    msk = torch.randn((N, H, W, Cin), generator=torch.Generator().manual_seed(seed + 5))
+    return SimpleNamespace(geom=geom, dy=dy, w=w, res=res.float(), msk=msk, dx=dx, chs=chs, devs=devs, amax=a,
+                           zs=[(d + c.mean_i).float() for d, c in zip(devs, chs)])
+
+
+def dgrad_bn_sums(case, v, q):
+    """Exact (dgamma_q, dbeta) of the stored map v (integers in fp32) for request q."""
+    C = v.shape[-1]
+    vi = v.long().reshape(-1, C)
+    assert torch.equal(vi.float(), v.reshape(-1, C))
+    return exact_f32((vi * case.devs[q].reshape(-1, C)).sum(0), case.chs[q].invstd.double()), exact_f32(vi.sum(0), 1.0)
+
+
+# ---- 3b. the pooled stem backward -----------------------------------------------------------------------------------------------------
+POOLED_CASES = [(1, 2, 2, 64), (3, 9, 7, 64), (2, 16, 12, 64), (8, 112, 40, 64)]      # the last one: more than one tile of pooled rows
+
+
+def pooled_case(N, H, W, C, seed):
+    """y = mean + d (|d| <= 8) and an integer pooled gradient (|.| <= 7, non-zero): bn(y), the ReLU mask and xhat are exact."""
+    ch = bn_channels(C, seed)
+    OH, OW = conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1)
+    dev = rand_ints((N, H, W, C), -8, 8, seed + 10)
+    dpool = rand_ints((N, OH, OW, C), -7, 7, seed + 11, nonzero=True)
+    assert_sum_budget(torch.tensor(N * OH * OW * 7 * 8), f"pooled sums {N}x{H}x{W}")       # whatever the max-pool selects
+    y = (dev + ch.mean_i).float()
+    return SimpleNamespace(N=N, H=H, W=W, C=C, OH=OH, OW=OW, ch=ch, dev=dev, dpool_i=dpool, dpool=dpool.float(), y=y, act=bn_apply_rows(y, ch, relu=True))
+
+
+def pooled_idx_cpu(case):
+    """The max-pool decisions on the CPU (first maximum in row-major window order), as codes kh * 3 + kw like the kernels'."""
+    _, flat = F.max_pool2d(case.act.permute(0, 3, 1, 2), 3, 2, 1, return_indices=True)
+    flat = flat.permute(0, 2, 3, 1)
+    oy, ox = torch.arange(case.OH).view(1, -1, 1, 1), torch.arange(case.OW).view(1, 1, -1, 1)
+    return ((flat // case.W - (oy * 2 - 1)) * 3 + (flat % case.W - (ox * 2 - 1))).to(torch.uint8)
+
+
+def pooled_sums(case, idx):
+    """Exact scatter-form sums over the POOLED outputs o: dbeta = sum dpool[o] [bn(y[sel o]) > 0], dgamma likewise with xhat(y[sel o]).
+    Returns (dgamma, dbeta, selected values of relu(bn(y)))."""
+    code = idx.long()
+    assert int(code.max()) <= 8
+    oy, ox = torch.arange(case.OH).view(1, -1, 1, 1), torch.arange(case.OW).view(1, 1, -1, 1)
+    iy, ix = oy * 2 - 1 + code // 3, ox * 2 - 1 + code % 3
+    assert int(iy.min()) >= 0 and int(iy.max()) < case.H and int(ix.min()) >= 0 and int(ix.max()) < case.W, "a selected pixel lies in the padding"
+    flat = (iy * case.W + ix).reshape(case.N, -1, case.C)
+    d_sel = case.dev.reshape(case.N, -1, case.C).gather(1, flat)
+    a_sel = case.act.reshape(case.N, -1, case.C).gather(1, flat)
+    gm = case.dpool_i.reshape(case.N, -1, case.C) * (a_sel > 0)
+    return exact_f32((gm * d_sel).sum((0, 1)), case.ch.invstd.double()), exact_f32(gm.sum((0, 1)), 1.0), a_sel.reshape(case.N, case.OH, case.OW, case.C)
+
+
+def pooled_gather(case, idx):
+    """The same upstream gradient in gather form, fp64 [N][H][W][C]: the pooled gradient scattered to the selected pixels (a pixel may be
+    selected by up to four windows), times the ReLU mask."""
+    code = idx.long()
+    oy, ox = torch.arange(case.OH).view(1, -1, 1, 1), torch.arange(case.OW).view(1, 1, -1, 1)
+    flat = ((oy * 2 - 1 + code // 3) * case.W + (ox * 2 - 1 + code % 3)).reshape(case.N, -1, case.C)
+    g = torch.zeros((case.N, case.H * case.W, case.C), dtype=torch.float64).scatter_add_(1, flat, case.dpool.double().reshape(case.N, -1, case.C))
+    return (g * (case.act.reshape(case.N, -1, case.C) > 0)).reshape(case.N, case.H, case.W, case.C)
+
+
+# ---- 4. transformer column reductions -----------------------------------------------------------------------------------------------
+COLSUM_CASES = [(M, C) for C in (64, 768, 1024) for M in (1, 15, 16, 17, 63, 64, 65, 4097, 16385 + 3)]
+LN_CASES = [(M, D) for D in (512, 768, 1024) for M in (1, 3, 15, 16, 17, 1025, 4099)]     # 1025 rows: more than 64 row blocks of 16
+
+
+def colsum_case(M, C, seed):
+    xi = rand_ints((M, C), -7, 7, seed)
+    assert_sum_budget(xi.abs().sum(0), f"column sums {M}x{C}")
+    return SimpleNamespace(x=xi.float(), total=exact_f32(xi.sum(0), 1.0), xi=xi)
+
+
+def ln_case(M, D, seed):
+    """LayerNorm backward: x = mean[row] + d (|d| <= 8), rstd[row] = 2^-k, k in 1..3, dy and add = integers / 8, w = +-2^j per column.
+    db sums multiples of 1/8, dw multiples of 2^-6 (dy * d * 2^-k).  dx (atol 1e-5, rtol 1e-5): r = g - mean(g) - b, b = xhat * mean(g * xhat),
+    |g| = |dy * w| < 2, and the fp32 roundings are below 3e-7 relative to a term.  Either |b| >= 8, then |r| >= |b| / 2 and the relative
+    error is below 1e-6, or |b| < 8 and the absolute error is below 4e-6; rstd <= 1/2 scales both alike."""
+    mean_i, k = rand_ints((M, 1), -3, 3, seed), rand_ints((M, 1), 1, 3, seed + 1)
+    dev, dyi = rand_ints((M, D), -8, 8, seed + 2), rand_ints((M, D), -7, 7, seed + 3)
+    sign, j = rand_ints((D,), 0, 1, seed + 4) * 2 - 1, rand_ints((D,), -1, 1, seed + 5)
+    addi = rand_ints((M, D), -7, 7, seed + 6)
+    dw_units = dyi * dev * 2 ** (3 - k)                                          # units of 2^-6
+    assert_sum_budget(dyi.abs().sum(0), f"LayerNorm db {M}x{D}")
+    assert_sum_budget(dw_units.abs().sum(0), f"LayerNorm dw {M}x{D}")
+    return SimpleNamespace(M=M, D=D, x=(dev + mean_i).float(), dy=(dyi.double() * G_UNIT).float(), add=(addi.double() * G_UNIT).float(),
+                           w=(sign.double() * 2.0 ** j.double()).float(), mean=mean_i.float().reshape(M), rstd=(2.0 ** -k.double()).float().reshape(M),
+                           db=exact_f32(dyi.sum(0), G_UNIT), dw=exact_f32(dw_units.sum(0), 2.0 ** -6))
+
+
+def ln_dx_rows(case, add=None):
+    """The LayerNorm input gradient in fp64: rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * w (+ add)."""
+    g = case.dy.double() * case.w.double()
+    rs = case.rstd.double().unsqueeze(1)
+    xh = (case.x.double() - case.mean.double().unsqueeze(1)) * rs
+    dx = rs * (g - g.mean(1, keepdim=True) - xh * (g * xh).mean(1, keepdim=True))
+    return dx if add is None else dx + add.double()
+
+
+def case_seed(*v):
+    return sum((i + 1) * int(x) for i, x in enumerate(v)) % 100003
+
+
+_REDUCE_BUILDERS = {"fwd_partials": fwd_partials, "bwd_partials": bwd_partials, "bn_rows": bn_rows_case, "dgrad_bn": dgrad_bn_case,
+                    "pooled": pooled_case, "colsum": colsum_case, "ln": ln_case}
+
+
+@functools.lru_cache(maxsize=1)
+def reduce_case(kind, *args):
+    """The one instance of a reduction case that the CPU proofs and the GPU tests share: its seed is a function of the arguments.
+    Only the most recent case is kept (the largest hold hundreds of MB)."""
+    flat = [v for a in args for v in (a if isinstance(a, tuple) else (a,))]
+    return _REDUCE_BUILDERS[kind](*args, case_seed(len(kind), *flat))

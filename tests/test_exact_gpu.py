@@ -8,8 +8,9 @@ small cases.  Every case checks its fp32 budget (exact.assert_exact_budget) befo
 
 Epilogues that are exact on grid data are part of the cases: bias, residual add, ReLU mask, in-place accumulation, rows outside
 a window, and the fused fp64 BatchNorm statistics of the forward kernels (sum y and sum y^2 EQUAL the fp64 sums of the stored y).
-Left out because they are not exact by nature: the GELU outputs, the stem's deviation-form statistics, the fused
-BatchNorm-backward reductions.  What these tests cannot see is the rounding error of dense fp32 accumulation; that stays with the
+Left out because they are not exact by nature: the GELU outputs, the stem's deviation-form statistics.  The fused
+BatchNorm-backward reductions and every other reduction between the contractions are exact on integer data with an integer mean and a
+power-of-two invstd: test_reduce_exact_gpu.py.  What these tests cannot see is the rounding error of dense fp32 accumulation; that stays with the
 2e-5 parity tests (test_ops_gpu.py) and with test_conv_split_is_not_reduced_precision (the statistical claim)."""
 import functools
 
