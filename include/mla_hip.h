@@ -487,6 +487,17 @@ int mla_bn_invstd(const float* var, float* invstd, int n, float eps, void* strea
 int mla_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd,
                  int first, void* stream);
 
+/* ---- torch.optim.Adam (main.py:736-747 --cav_opti; main.py:31 --optimizer Adam) ---------------- */
+/* amsgrad=False, maximize=False, single-tensor rule:  g' = g + wd*p;  m = beta1*m + (1-beta1)*g';
+ * v = beta2*v + (1-beta2)*g'*g';  p -= (lr / (1-beta1^step)) * m / (sqrt(v)/sqrt(1-beta2^step) + eps).
+ * g == NULL means zero gradient (torch-1.8.1 zero_grad semantics).  step >= 1; the caller zeroes m and v before
+ * step 1.  One launch over n contiguous elements; p, g, m, v may start at any 4-byte-aligned address.  The bias corrections
+ * and the step size are formed in double on the host.  Hyper-parameters travel as fp32: beta2 = 0.999 acts as
+ * (double)0.999f, which moves 1-beta2 by 1.3e-5 relative in v and in its bias correction alike.
+ * n == 0, a null p / m / v or step < 1: MLA_ERR_INVALID_ARG. */
+int mla_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                  float wd, int step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,9 +11,9 @@ from .feed import DeviceFeeder  # noqa: F401
 from .frames import (FrameBatcher, decode_frames, frame_descriptors, make_lut, pick_frames, sample_augment,  # noqa: F401
                      sample_crop, sample_flip, sample_generator)
 from .model import AVClassifier, ConcatFusion, SharedHead  # noqa: F401
-from .m3ae import ConcatFusion3, M3AEClassifier, M3AEEncoder, Modal3Classifier  # noqa: F401
+from .m3ae import CAVClassifier, ConcatFusion3, M3AEClassifier, M3AEEncoder, Modal3Classifier  # noqa: F401
 from .modulation import OGM  # noqa: F401
-from .optim import FusedSGD  # noqa: F401
+from .optim import FusedAdam, FusedSGD, cav_param_groups  # noqa: F401
 from .plugin import GSPlugin  # noqa: F401
 from .protocol import CrossEntropyLoss, DataParallel, setup_seed, weight_init  # noqa: F401
 from .trainer import Evaluator, MLATrainer  # noqa: F401

@@ -1,6 +1,6 @@
 """Transformer modality encoders on the HIP kernels: M3AE text / image (reference: models/m3ae.py:48-179,
-300-370; models/basic_model.py:127-200 M3AEClassifier) and the CAV-MAE audio branch (models/cav_mae.py:69-113,
-116-186, 337-351; models/basic_model.py:202-275 Modal3Classifier).
+300-370; models/basic_model.py:127-200 M3AEClassifier) and the two CAV-MAE branches (models/cav_mae.py:69-113,
+116-186, 337-364; models/basic_model.py:202-275 Modal3Classifier, :79-124 CAVClassifier).
 
 One `M3AEEncoder` per modality, like the reference's `mae_a` (text) / `mae_v` (image): pre-LN ViT-B
 (emb 768, 12 heads, mlp x4) over [cls] + 256 tokens, token-mean feature.  DropPath == identity (SURVEY Q10:
@@ -55,7 +55,7 @@ class M3AEEncoder(FlatEncoder):
     """nn.Module face (module.py): parameters under the reference's names, order and layouts -- nn.Linear weights
     (out, in) as transposed views of the [in][out] GEMM operands, type embeddings / cls as (1,1,D) -- registered as
     MaskedMultimodalAutoencoder does (direct parameters, text_embedding, image_embedding, encoder: m3ae.py:305-331)
-    resp. the audio branch of CAVMAEFT (cav_mae.py:116-145)."""
+    resp. the audio ("audio") or the visual ("cav_visual") branch of CAVMAEFT (cav_mae.py:116-145)."""
     BLOCK_PARAMS = [("layer_norm1.weight", "D"), ("layer_norm1.bias", "D"), ("attention.qkv_linear.weight", "D,3D"),
                     ("attention.qkv_linear.bias", "3D"), ("attention.fc.weight", "D,D"), ("attention.fc.bias", "D"),
                     ("layer_norm2.weight", "D"), ("layer_norm2.bias", "D"), ("transformer_mlp.fc1.weight", "D,4D"),
@@ -63,8 +63,8 @@ class M3AEEncoder(FlatEncoder):
 
     def __init__(self, kind: str, device="cuda", depth: int = 12, emb_dim: int = 768, num_heads: int = 12,
                  text_vocab_size: int = 30522, patch_dim: int = 768, seed: Optional[int] = None, conv_math: Optional[str] = None):
-        if kind not in ("text", "image", "audio"):
-            raise ValueError("kind must be 'text', 'image' or 'audio'")
+        if kind not in ("text", "image", "audio", "cav_visual"):
+            raise ValueError("kind must be 'text', 'image', 'audio' or 'cav_visual'")
         super().__init__(device, conv_math)                  # conv_math: here the arithmetic of the Linear GEMMs
         self.split = self.conv_math in ("split", "bf16")      # both run on weight images and the fused bias gradient
         # "fused": one flash-style kernel per direction, scores never materialised (csrc/attention.hip); "materialized": the
@@ -74,10 +74,15 @@ class M3AEEncoder(FlatEncoder):
         if self.attention not in ("fused", "materialized"):
             raise MLAHipError(f"MLA_ATTENTION must be 'fused' or 'materialized', got {self.attention!r}")
         self.kind = kind
+        self.cav = kind in ("audio", "cav_visual")
+        self.sfx = {"audio": "a", "cav_visual": "v"}.get(kind)       # CAVMAEFT's per-modality name suffix
         if kind == "audio":
-            patch_dim = 256                  # conv 16x16 over 1 channel (cav_mae.py:127)
-        self.has_cls = kind != "audio"       # CAV-MAE has no [cls] token
-        self.audio_tokens = 512              # audio_length * 128 / 256 (cav_mae.py:131)
+            patch_dim = 256                  # conv 16x16 over 1 channel (cav_mae.py:126)
+        elif kind == "cav_visual":
+            patch_dim = 768                  # conv 16x16 over 3 channels (cav_mae.py:127)
+        self.has_cls = not self.cav          # CAV-MAE has no [cls] token
+        self.audio_tokens = 512              # audio_length * 128 / 256 (cav_mae.py:129)
+        self.cav_tokens = {"audio": self.audio_tokens, "cav_visual": 196}.get(kind)      # 224 / 16 squared (cav_mae.py:75)
         self.depth, self.D, self.H, self.V, self.PD = depth, emb_dim, num_heads, text_vocab_size, patch_dim
         D = emb_dim
         dims = {"D": (D,), "3D": (3 * D,), "4D": (4 * D,), "D,3D": (D, 3 * D), "D,D": (D, D), "D,4D": (D, 4 * D), "4D,D": (4 * D, D)}
@@ -88,9 +93,10 @@ class M3AEEncoder(FlatEncoder):
         elif kind == "image":
             lay += [("image_embedding.weight", (patch_dim, D)), ("image_embedding.bias", (D,)), ("encoder_image_type_embedding", (D,)),
                     ("cls_token", (D,))]
-        else:   # CAV-MAE audio: conv patch embed (as [256][D]), modality embedding, LEARNED position embedding (tr_pos=True)
-            lay += [("patch_embed_a.proj.weight", (patch_dim, D)), ("patch_embed_a.proj.bias", (D,)), ("modality_a", (D,)),
-                    ("pos_embed_a", (self.audio_tokens, D))]
+        else:   # CAV-MAE: conv patch embed (as [256 | 768][D]), modality embedding, LEARNED position embedding (tr_pos=True)
+            x = self.sfx
+            lay += [(f"patch_embed_{x}.proj.weight", (patch_dim, D)), (f"patch_embed_{x}.proj.bias", (D,)), (f"modality_{x}", (D,)),
+                    (f"pos_embed_{x}", (self.cav_tokens, D))]
         for i in range(depth):
             lay += [(f"encoder.blocks.{i}.{n}", dims[s]) for n, s in self.BLOCK_PARAMS]
         lay += [("encoder.layer_norm.weight", (D,)), ("encoder.layer_norm.bias", (D,))]
@@ -103,7 +109,7 @@ class M3AEEncoder(FlatEncoder):
         elif kind == "image":
             unused_shapes = {"text_embedding.weight": (text_vocab_size, D), "encoder_text_type_embedding": (1, 1, D)}
         else:
-            unused_shapes = {}   # CAVMAEFT's visual branch / unused norms are not materialised (never touched by forward_feat(.,'a'))
+            unused_shapes = {}   # CAVMAEFT's other branch / unused norms are not materialised (never touched by forward_feat)
         self.unused: Dict[str, nn.Parameter] = {}
         self._register_reference_tree(unused_shapes)
         self._pos: Dict[int, torch.Tensor] = {}
@@ -123,19 +129,22 @@ class M3AEEncoder(FlatEncoder):
     def _to_ref(self, name: str):
         """internal flat view -> reference-shaped VIEW (no copy)."""
         D = self.D
-        if name == "patch_embed_a.proj.weight":
-            return lambda t: t.t().view(D, 1, 16, 16)                                    # Conv2d(1, D, 16, 16) weight (cav_mae.py:80)
-        if name in ("cls_token", "encoder_text_type_embedding", "encoder_image_type_embedding", "modality_a"):
+        if name in ("patch_embed_a.proj.weight", "patch_embed_v.proj.weight"):
+            # Conv2d(1 | 3, D, 16, 16) weight (cav_mae.py:80): patchify emits a patch as (c, p1, p2), the order of the conv
+            # weight's trailing dimensions, so splitting the transposed view's second dimension is all it takes
+            return lambda t: t.t().view(D, self.PD // 256, 16, 16)
+        if name in ("cls_token", "encoder_text_type_embedding", "encoder_image_type_embedding", "modality_a", "modality_v"):
             return lambda t: t.view(1, 1, -1)
-        if name == "pos_embed_a":
+        if name in ("pos_embed_a", "pos_embed_v"):
             return lambda t: t.view(1, *t.shape)
         if len(self.layout[name][1]) == 2 and name != "text_embedding.weight":
             return lambda t: t.t()                                                       # nn.Linear.weight is (out, in)
         return lambda t: t
 
     def _register_reference_tree(self, unused_shapes: Dict[str, Tuple[int, ...]]) -> None:
-        if self.kind == "audio":
-            order = ["modality_a", "pos_embed_a", "patch_embed_a.proj.weight", "patch_embed_a.proj.bias"]
+        if self.cav:
+            x = self.sfx
+            order = [f"modality_{x}", f"pos_embed_{x}", f"patch_embed_{x}.proj.weight", f"patch_embed_{x}.proj.bias"]
         else:
             order = ["encoder_image_type_embedding", "encoder_text_type_embedding", "cls_token", "text_embedding.weight",
                      "image_embedding.weight", "image_embedding.bias"]
@@ -162,10 +171,10 @@ class M3AEEncoder(FlatEncoder):
                 t.copy_(torch.randn(shp, generator=gen))                                   # normal_(0, 1)
             elif name in ("cls_token", "encoder_text_type_embedding", "encoder_image_type_embedding"):
                 t.copy_(torch.randn(shp, generator=gen) + 0.02)                            # torch.empty().normal_(0.02): mean .02, std 1
-            elif name == "modality_a":
-                t.copy_(torch.randn(shp, generator=gen) * 0.02)                            # cav_mae.py:171
-            elif name == "pos_embed_a":
-                t.copy_(self._cav_pos_embed())                                             # cav_mae.py:160-161 (sin-cos init, then trained)
+            elif name in ("modality_a", "modality_v"):
+                t.copy_(torch.randn(shp, generator=gen) * 0.02)                            # cav_mae.py:172-173
+            elif name in ("pos_embed_a", "pos_embed_v"):
+                t.copy_(self._cav_pos_embed())                                             # cav_mae.py:161-165 (sin-cos init, then trained)
             elif "layer_norm" in name:
                 t.fill_(1.0 if name.endswith("weight") else 0.0)
             elif len(shp) == 2:
@@ -176,24 +185,25 @@ class M3AEEncoder(FlatEncoder):
                 t.copy_((torch.rand(shp, generator=gen) * 2 - 1) / math.sqrt(fan_in))
 
     def _cav_pos_embed(self) -> torch.Tensor:
-        """get_2d_sincos_pos_embed(D, 8, L/8) of cav_mae.py:47-66 (grid 8 x L/8, 'w goes first')."""
-        D, L = self.D, self.audio_tokens
-        gh, gw = 8, L // 8
+        """get_2d_sincos_pos_embed(D, 8, L/8) (audio) / (D, 14, 14) (visual) of cav_mae.py:51-66, 161-165 ('w goes first')."""
+        D, L = self.D, self.cav_tokens
+        gh, gw = (8, L // 8) if self.kind == "audio" else (14, 14)
         grid = np.stack(np.meshgrid(np.arange(gw, dtype=np.float32), np.arange(gh, dtype=np.float32)), axis=0).reshape([2, 1, gw, gh])
         emb = np.concatenate([_sincos_1d(D // 2, grid[0]), _sincos_1d(D // 2, grid[1])], axis=1)
         return torch.from_numpy(emb.astype(np.float32))
 
     def _ref_name(self, name: str) -> str:
         """internal (M3AE-style) parameter name -> reference state_dict key."""
-        if self.kind != "audio" or not name.startswith("encoder."):
+        if not self.cav or not name.startswith("encoder."):
             return name
+        x = self.sfx
         if name.startswith("encoder.layer_norm."):
-            return name.replace("encoder.layer_norm.", "norm_a.")                          # cav_mae.py:145, 349
+            return name.replace("encoder.layer_norm.", f"norm_{x}.")                       # cav_mae.py:142-143, 350, 363
         _e, _b, i, rest = name.split(".", 3)
         i = int(i)
-        shared = i >= self.depth - 1                                                       # 11 blocks_a + 1 blocks_u (cav_mae.py:141-143)
-        pre = f"blocks_u.{i - (self.depth - 1)}." if shared else f"blocks_a.{i}."
-        sub = {"layer_norm1": "norm1_a" if shared else "norm1", "layer_norm2": "norm2_a" if shared else "norm2",
+        shared = i >= self.depth - 1                                                       # 11 blocks_a|v + 1 blocks_u (cav_mae.py:138-140)
+        pre = f"blocks_u.{i - (self.depth - 1)}." if shared else f"blocks_{x}.{i}."
+        sub = {"layer_norm1": f"norm1_{x}" if shared else "norm1", "layer_norm2": f"norm2_{x}" if shared else "norm2",
                "attention.qkv_linear": "attn.qkv", "attention.fc": "attn.proj", "transformer_mlp.fc1": "mlp.fc1",
                "transformer_mlp.fc2": "mlp.fc2"}
         for k, v in sub.items():
@@ -205,13 +215,13 @@ class M3AEEncoder(FlatEncoder):
         out = {}
         for name in self.layout:
             t = self.g[name]
-            if self.kind == "audio":
+            if self.cav:
                 key = self._ref_name(name)
-                if name == "patch_embed_a.proj.weight":
-                    out[key] = t.t().contiguous().view(self.D, 1, 16, 16)
-                elif name == "modality_a":
+                if name.endswith(".proj.weight"):
+                    out[key] = t.t().contiguous().view(self.D, self.PD // 256, 16, 16)
+                elif name.startswith("modality_"):
                     out[key] = t.clone().view(1, 1, -1)
-                elif name == "pos_embed_a":
+                elif name.startswith("pos_embed_"):
                     out[key] = t.clone().view(1, *t.shape)
                 else:
                     out[key] = t.t().contiguous() if t.dim() == 2 else t.clone()
@@ -246,7 +256,7 @@ class M3AEEncoder(FlatEncoder):
         ws["feat"] = torch.empty((B, D), **f32)
         if self.kind != "text":
             ws["patches"] = torch.empty((B * L, self.PD), **f32)
-        if self.kind != "audio":
+        if not self.cav:
             ws["pos"] = sincos_pos_embed(D, L, two_d=(self.kind == "image")).to(self.device)
         if self.attention == "fused":
             for bk in ws["blocks"]:
@@ -277,7 +287,7 @@ class M3AEEncoder(FlatEncoder):
     # ------------------------------------------------------------------------------------------
     def forward(self, inp: torch.Tensor, padding_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """text: inp = token ids (B,1,L) or (B,L) int64, padding_mask (B,1,L)/(B,L) float (1 = padded);
-        image: inp = (B,3,256,256) fp32.  Returns the (B, D) token-mean feature (basic_model.py:182-200), written into
+        image: inp = (B,3,256,256) fp32; audio: inp = (B,1024,128) fp32; cav_visual: inp = (B,3,224,224) fp32.  Returns the (B, D) token-mean feature (basic_model.py:182-200), written into
         `out` if given (else into the reused workspace buffer)."""
         self._await_tail()
         st = ops.cur_stream()
@@ -309,6 +319,17 @@ class M3AEEncoder(FlatEncoder):
             ops.linear_fwd(ws["patches"], self.p["patch_embed_a.proj.weight"], self.p["patch_embed_a.proj.bias"], ws["x0"], 1, B * L,
                            self.PD, D, stream=st, bf16=self.bf16, wsplit=self._w("patch_embed_a.proj.weight", 0))
             ops.tokens_assemble(ws["x0"], None, None, self.p["pos_embed_a"], self.p["modality_a"], None, B, L, D, stream=st)
+        elif self.kind == "cav_visual":
+            # cav_mae.py:352-355: conv16x16/16 over (B, 3, 224, 224) -> (B, 14*14, D) + pos_embed_v + modality_v
+            if inp.dim() != 4 or inp.shape[1] != 3 or (inp.shape[2] // 16) * (inp.shape[3] // 16) != self.cav_tokens:
+                raise MLAHipError(f"cav_visual encoder expects (B, 3, 224, 224), got {tuple(inp.shape)}")
+            B, L = inp.shape[0], self.cav_tokens
+            ws = self._plan(B, L)
+            ws["pm"] = None
+            ops.patchify(inp.contiguous().float(), ws["patches"], 16, stream=st)
+            ops.linear_fwd(ws["patches"], self.p["patch_embed_v.proj.weight"], self.p["patch_embed_v.proj.bias"], ws["x0"], 1, B * L,
+                           self.PD, D, stream=st, bf16=self.bf16, wsplit=self._w("patch_embed_v.proj.weight", 0))
+            ops.tokens_assemble(ws["x0"], None, None, self.p["pos_embed_v"], self.p["modality_v"], None, B, L, D, stream=st)
         else:
             B = inp.shape[0]
             L = (inp.shape[2] // 16) * (inp.shape[3] // 16)
@@ -404,15 +425,16 @@ class M3AEEncoder(FlatEncoder):
             ws["dA"], ws["dC"] = dx, dC
         # ---- token assembly (m3ae.py:342-366)
         ops.colsum_rows(dx, ws["colsum"], red, M, D, stream=st)
-        if self.kind == "audio":
-            # x0 = conv(patches) + pos_embed_a + modality_a: d modality = d conv-bias = sum over all tokens,
+        if self.cav:
+            # x0 = conv(patches) + pos_embed + modality: d modality = d conv-bias = sum over all tokens,
             # d pos[i] = sum over the batch, d conv-weight = patches^T dx
-            self.g["modality_a"].copy_(ws["colsum"])
-            self.g["patch_embed_a.proj.bias"].copy_(ws["colsum"])
+            x = self.sfx
+            self.g[f"modality_{x}"].copy_(ws["colsum"])
+            self.g[f"patch_embed_{x}.proj.bias"].copy_(ws["colsum"])
             if "red_pos" not in ws:
                 ws["red_pos"] = torch.empty(ops.colreduce_ws_elems(B, L * D), device=self.device, dtype=torch.float32)
-            ops.colsum_rows(dx, self.g["pos_embed_a"], ws["red_pos"], B, L * D, stream=st)
-            ops.linear_wgrad(ws["patches"], dx, self.g["patch_embed_a.proj.weight"], wgw, 1, B * L, self.PD, D, stream=st, split=self.split, bf16=self.bf16)
+            ops.colsum_rows(dx, self.g[f"pos_embed_{x}"], ws["red_pos"], B, L * D, stream=st)
+            ops.linear_wgrad(ws["patches"], dx, self.g[f"patch_embed_{x}.proj.weight"], wgw, 1, B * L, self.PD, D, stream=st, split=self.split, bf16=self.bf16)
         elif self.kind == "text":
             self.g["text_embedding.weight"].zero_()
             if "emb_ws" not in ws:
@@ -482,3 +504,35 @@ class Modal3Classifier(_Classifier):
         return visual.shape[0], [lambda out=None: self.mae_a.forward(audio, None, out),
                                  lambda out=None: self.mae_v.forward(visual, None, out),
                                  lambda out=None: self.mae_t.forward(token, padding_mask, out)]
+
+
+class CAVClassifier(_Classifier):
+    """models/basic_model.py:79-124 (`--lorb large`): two CAV-MAE ViT-B encoders -- mae_a runs CAVMAEFT's audio branch, mae_v its
+    visual branch (forward_feat(., 'a') / (., 'v'), cav_mae.py:337-364); the other branch of each CAVMAEFT is never touched and
+    not materialised -- and ConcatFusion: Linear(768, 6) shared (--gs_flag) or Linear(1536, 6) on cat(a, v) (:95-98).  forward
+    returns (a, v), the token means (:119-124), either way: the reference's large model has no fused forward, main.py:541-542
+    applies fusion_module outside it.
+
+    audio_ckpt / visual_ckpt stand for the reference's hard-coded "/path/to/cavmae-*.pth" (:109-117): each a CAVMAEFT state
+    dict, loaded non-strictly -- the keys of the branch that is not materialised are ignored; None keeps the seeded
+    initialisation."""
+    lorb_large = True
+
+    def __init__(self, args, device="cuda", depth: int = 12, seed: Optional[int] = None, conv_math: Optional[str] = None,
+                 audio_ckpt: Optional[str] = None, visual_ckpt: Optional[str] = None):
+        super().__init__(args, device, seed, ("CREMAD",), ConcatFusion, 768, 2)                               # :82-104
+        self.mae_a = M3AEEncoder("audio", device, depth=depth, seed=self._seed(0), conv_math=conv_math)       # :106
+        self.mae_v = M3AEEncoder("cav_visual", device, depth=depth, seed=self._seed(1), conv_math=conv_math)  # :107
+        for enc, path in ((self.mae_a, audio_ckpt), (self.mae_v, visual_ckpt)):                               # :109-117
+            if path is not None:
+                enc.load_state_dict(torch.load(path, map_location="cpu"), strict=False)   # other-branch keys: unexpected, ignored
+
+    def mla_encoders(self):
+        return [("a", "audio", self.mae_a), ("v", "visual", self.mae_v)]
+
+    def _calls(self, audio: torch.Tensor, visual: torch.Tensor):
+        """a, v = model(spec, image)  (main.py:420; basic_model.py:119-124): spec (B, 1024, 128), image (B, 3, 224, 224)"""
+        if visual.shape[0] != audio.shape[0]:
+            raise MLAHipError("audio/visual batch mismatch")
+        return audio.shape[0], [lambda out=None: self.mae_a.forward(audio, None, out),
+                                lambda out=None: self.mae_v.forward(visual, None, out)]

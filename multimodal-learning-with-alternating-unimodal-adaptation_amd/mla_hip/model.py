@@ -145,7 +145,7 @@ class ConcatFusion(nn.Module):
         return concat_fusion_forward(self, (x, y))
 
 
-def check_joint_args(args) -> None:
+def check_joint_args(args, large_ok: bool = False) -> None:
     """What the joint (gs_flag false) classifiers support through `args`: `--modulation Normal | OGM | OGM_GE` with concat fusion.
     `--modulation QMF` (main.py:170-268) lives in `mla_hip.qmf`: build the model with gs_flag false and modulation "Normal", then
     `attach_qmf_heads(model)` / `QMFTrainer(model, n_data)` add the per-modality audio_fc / visual_fc / txtual_fc heads and the
@@ -156,7 +156,7 @@ def check_joint_args(args) -> None:
                                   "audio_fc / visual_fc heads and the History ranking loss")
     if mod not in ("Normal", "OGM", "OGM_GE"):
         raise NotImplementedError(f"Incorrect modulation: {mod}")
-    if getattr(args, "lorb", "base") == "large":
+    if getattr(args, "lorb", "base") == "large" and not large_ok:
         raise NotImplementedError("mla_hip does not implement --lorb large")
     if getattr(args, "clip", False):
         raise NotImplementedError("mla_hip does not implement --clip")
@@ -167,6 +167,7 @@ class _Classifier(nn.Module):
     states ONCE how its inputs reach them: `_calls(*inputs) -> (batch, [run(out=None) -> (B, D) feature])`, one callable per
     encoder in `mla_encoders()` order; the kernel-level and the autograd forwards below are derived from that list."""
     side_streams = True
+    lorb_large = False          # True on the `--lorb large` family (CAVClassifier)
     qmf_heads = None            # mla_hip.qmf.attach_qmf_heads: the per-modality heads, in mla_encoders() order
 
     def __init__(self, args, device, seed: Optional[int], datasets, fusion_cls, feat_dim: int, n_enc: int):
@@ -181,7 +182,7 @@ class _Classifier(nn.Module):
             raise NotImplementedError("Incorrect fusion method: {}!".format(fusion))
         self.gs_flag = bool(getattr(args, "gs_flag", False))
         if not self.gs_flag:
-            check_joint_args(args)
+            check_joint_args(args, self.lorb_large)
         self.args, self.device, self.feat_dim, self._seed0 = args, torch.device(device), feat_dim, seed
         self.fusion_module = fusion_cls(feat_dim if self.gs_flag else n_enc * feat_dim, N_CLASSES[dataset], device,
                                         self._seed(n_enc), joint=not self.gs_flag)

@@ -669,6 +669,14 @@ def sgd_step(p, g, buf, lr: float, momentum: float, wd: float, first: bool, stre
     _call("mla_sgd_step", _p(p), _p(g), _p(buf), p.numel(), lr, momentum, wd, int(first), stream or cur_stream())
 
 
+def adam_step(p, g, m, v, lr: float, beta1: float, beta2: float, eps: float, wd: float, step: int,
+              stream: Optional[int] = None) -> None:
+    """torch.optim.Adam's single-tensor rule on one flat range (any 4-byte-aligned start); g None = zero gradient."""
+    if not (p.numel() == m.numel() == v.numel() and (g is None or g.numel() == p.numel())):
+        raise MLAHipError("adam_step: p, g, m and v must have the same number of elements")
+    _call("mla_adam_step", _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, wd, int(step), stream or cur_stream())
+
+
 # ---- transformer encoders (M3AE / CAV-MAE) -----------------------------------------------------------
 LN_EPS = 1e-5     # nn.LayerNorm default (models/m3ae.py:138)
 

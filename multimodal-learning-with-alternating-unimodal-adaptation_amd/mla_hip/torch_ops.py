@@ -274,6 +274,12 @@ def sgd_step(p, g, buf, lr, momentum, weight_decay, first):
     ops.sgd_step(p, g, buf, lr, momentum, weight_decay, first)
 
 
+@_op("adam_step(Tensor(a!) p, Tensor? g, Tensor(b!) m, Tensor(c!) v, float lr, float beta1, float beta2, float eps, "
+     "float weight_decay, int step) -> ()")
+def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step):
+    ops.adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step)
+
+
 # ---- transformer rows (models/m3ae.py:65-179; cav_mae.py:86-113) ------------------------------------------------------------
 @_op("layernorm_fwd(Tensor x, Tensor w, Tensor b, float eps=1e-5) -> (Tensor, Tensor, Tensor)")
 def layernorm_fwd(x, w, b, eps=1e-5):

@@ -23,7 +23,7 @@ from .streams import distinct_streams
 
 from . import ops
 from .dist import Comm
-from .optim import FusedSGD
+from .optim import FusedAdam, FusedSGD
 from .plugin import GSPlugin
 
 
@@ -37,16 +37,25 @@ class StreamTrainer:
     STEP's first forward only needs that encoder's own SGD, so the encoder chains run beside each other and across step
     boundaries and fill each other's kernel tails."""
 
-    def __init__(self, model, lr: float, momentum: float, weight_decay: float, legacy_zero_grad: bool, comm: Optional[Comm],
-                 extra_groups: Optional[dict] = None):
-        """extra_groups: further optimiser groups (name -> flat-buffer object) after the encoders' and the head's."""
+    def __init__(self, model, lr, momentum: float, weight_decay: float, legacy_zero_grad: bool, comm: Optional[Comm],
+                 extra_groups: Optional[dict] = None, optimizer: str = "sgd", adam: Optional[dict] = None):
+        """extra_groups: further optimiser groups (name -> flat-buffer object) after the encoders' and the head's.
+        optimizer: "sgd" (FusedSGD(lr, momentum, weight_decay)) or "adam" (FusedAdam(lr, weight_decay, **adam); `lr` may then be a
+        mapping group name -> lr, and `adam` holds betas / eps / param_groups, e.g. param_groups=cav_param_groups(model, lr))."""
         self.model = model
         self.head = model.fusion_module.fc_out
         self.encoders = model.mla_encoders()                    # [(tag, group, encoder)], alternation / concatenation order
         groups = {grp: enc for _t, grp, enc in self.encoders}
         groups["head"] = self.head
         groups.update(extra_groups or {})
-        self.optimizer = FusedSGD(groups, lr, momentum, weight_decay, legacy_zero_grad)
+        if optimizer == "sgd":
+            self.optimizer = FusedSGD(groups, lr, momentum, weight_decay, legacy_zero_grad)
+        elif optimizer == "adam":
+            if comm is not None and comm.world > 1:
+                raise NotImplementedError("optimizer='adam' is not implemented for data-parallel training (comm.world > 1)")
+            self.optimizer = FusedAdam(groups, lr=lr, weight_decay=weight_decay, legacy_zero_grad=legacy_zero_grad, **(adam or {}))
+        else:
+            raise ValueError(f"optimizer must be 'sgd' or 'adam', got {optimizer!r}")
         self.comm = comm if comm is not None else Comm()
         dev = model.device
         self.losses = {k: torch.zeros(1, device=dev, dtype=torch.float32) for k in ["loss"] + ["loss_" + t for t, _g, _e in self.encoders]}
@@ -101,11 +110,15 @@ class StreamTrainer:
 class MLATrainer(StreamTrainer):
     def __init__(self, model, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 1e-4,
                  gs_mode: str = "as_intended", legacy_zero_grad: bool = False, av_alpha: float = 0.55,
-                 comm: Optional[Comm] = None):
-        """`model`: AVClassifier (ResNet-18 audio+visual), M3AEClassifier (text+image) or Modal3Classifier.  The calling
+                 comm: Optional[Comm] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
+                 param_groups: Optional[list] = None):
+        """`model`: AVClassifier (ResNet-18 audio+visual), M3AEClassifier (text+image), Modal3Classifier or CAVClassifier.  The calling
         stream carries head forward/backward, the packed head exchange, GSPlugin and the head's SGD; the next modality only
-        needs the updated head, so the last modality's backward overlaps the next step's first forward."""
-        super().__init__(model, lr, momentum, weight_decay, legacy_zero_grad, comm)
+        needs the updated head, so the last modality's backward overlaps the next step's first forward.
+        optimizer="adam" (main.py:736-747): torch.optim.Adam semantics with `betas`, `eps`, `weight_decay`; `lr` a float, a mapping
+        {"audio" | ...: lr, "head": lr}, or per-parameter `param_groups` such as `cav_param_groups(model, lr)`; `momentum` is unused."""
+        adam = dict(betas=betas, eps=eps, param_groups=param_groups) if optimizer == "adam" else None
+        super().__init__(model, lr, momentum, weight_decay, legacy_zero_grad, comm, optimizer=optimizer, adam=adam)
         self.gs_plugin = GSPlugin(dim=self.head.in_features, device=model.device, mode=gs_mode)
         self.av_alpha = av_alpha
         dev = model.device
