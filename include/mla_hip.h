@@ -467,6 +467,36 @@ int mla_frames_check(const int64_t* desc_host, int N, int B, int T, size_t frame
 int mla_frames_resample(const uint8_t* frames, size_t frames_bytes, const int64_t* desc, const int64_t* desc_host,
                         const float* lut, float* out, int N, int B, int T, int out_h, int out_w, void* stream);
 
+/* ---- CAV-MAE / M3AE-eval image transform (dataset/dataset.py:251-256, 413-420) -----------------------------------
+ * mla_frames_resample generalised.  desc int64 (N, 12) per frame: byte offset, H, W, crop top, crop left, crop h, crop w,
+ * flip, full_h, full_w, win_top, win_left.  The crop is resized to full_h x full_w with `filter` (0 = bilinear, 1 = Pillow's
+ * bicubic: a = -0.5, support 2, negative coefficients rounded away from zero) and the window
+ * [win_top, win_top + out_h) x [win_left, win_left + out_w) of that image goes through the flip and the LUT into
+ * out fp32 (B, 3, T, out_h, out_w).  Only the window is computed.  Per frame the result is bit-identical to
+ *     PIL img.crop(box).resize((full_w, full_h), BICUBIC | BILINEAR)
+ *        .crop((win_left, win_top, win_left + out_w, win_top + out_h))      Resize(size) + CenterCrop(size)
+ *        .transpose(FLIP_LEFT_RIGHT) if flip;  lut[c][u8]                   ToTensor + Normalize
+ * mla_image_check runs the host checks alone (no GPU): those of mla_frames_check, plus full sizes > 0, a window inside
+ * the resized image and a known filter. */
+int mla_image_check(const int64_t* desc_host, int N, int B, int T, size_t frames_bytes, int out_h, int out_w, int filter);
+int mla_image_resample(const uint8_t* frames, size_t frames_bytes, const int64_t* desc, const int64_t* desc_host,
+                       const float* lut, float* out, int N, int B, int T, int out_h, int out_w, int filter, void* stream);
+
+/* ---- CAV-MAE spectrogram augmentation (dataset/dataset.py:281-294, 303-321; --cav_augnois) ----------------------
+ * x, out fp32 (B, T, F), distinct buffers.  desc int64 (B, 8) per sample: flags, f0, fw, t0, tw, roll, scale_bits,
+ * stream_id; flags bit 0 = masks + noise + roll on (0: the sample is only normalised); scale_bits = the fp32 bit pattern
+ * of the noise scale s.  Per element, in fp32 with IEEE division and no contraction:
+ *     v = (aug && (f0 <= f < f0+fw || t0 <= t < t0+tw)) ? 0 : x[b,t,f];   v = (v - mean) / std;
+ *     if aug: v += (u(b, t*F + f) * s) / 10;                              out[b, (t + roll) mod T, f] = v
+ * u(b, i) = (r >> 8) * 2^-24 in [0, 1) with r = word i % 4 of Philox4x32-10(counter i / 4, stream_id[b], seed).
+ * This equals torch's CPU result of the reference's expressions bit for bit given the same uniforms.
+ * F is a multiple of 4 and x / out are 16-byte aligned (a thread moves 4 bins: one Philox block, one 16-byte access).
+ * mla_fbank_check runs the descriptor checks alone (no GPU): f0 + fw <= F, t0 + tw <= T, widths >= 0, |roll| <= T,
+ * F % 4 == 0; mla_fbank_augment also refuses std == 0, misaligned and overlapping buffers. */
+int mla_fbank_check(const int64_t* desc_host, int B, int T, int F);
+int mla_fbank_augment(const float* x, float* out, const int64_t* desc, const int64_t* desc_host, int B, int T, int F,
+                      float mean, float std, uint64_t seed, void* stream);
+
 /* ---- evaluation path (main.py:486-679 `valid`, gs_flag branch) --------------------------------- */
 /* logits = X W^T + b only (main.py:636-639) */
 int mla_head_logits(const float* X, const float* W, const float* b, float* logits, int B, int D, int C, void* stream);

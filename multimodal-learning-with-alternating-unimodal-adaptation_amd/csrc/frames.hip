@@ -14,6 +14,14 @@
 // One workgroup per (frame, band of output rows): coefficients of all output columns and of the band's rows into LDS, the
 // horizontal pass of the source rows the band reads into LDS (uint8), then the vertical pass, flip and LUT, written as
 // coalesced fp32 rows straight into the (B, 3, T, OH, OW) batch (frame n = sample n / T, time slot n % T).  No atomics.
+//
+// mla_image_resample is the same kernel with two more degrees of freedom (CAVDataset, dataset/dataset.py:251-256, and the
+// M3AE / Food-101 eval transform, dataset.py:413-420: Resize(size, BICUBIC) + CenterCrop(size)):
+//   filter   0 = bilinear (support 1), 1 = Pillow's bicubic (a = -0.5, support 2; negative coefficients round away from zero)
+//   window   the crop is resized to full_h x full_w and only the out_h x out_w window at (win_top, win_left) of that image is
+//            computed: the coefficients are those of output indices win_left + xx / win_top + yy of a cw -> full_w /
+//            ch -> full_h resize, so a CenterCrop costs nothing and reads only the source rows its window needs.
+// mla_frames_resample is the instantiation <bilinear, 8-column descriptor> with full = out and a zero window offset.
 #include <algorithm>
 #include <math.h>
 #include "common.h"
@@ -23,13 +31,29 @@
 #define FR_LDS_MAX 65536
 #define FR_DIM_MAX 65536
 
-// Pillow precompute_coeffs() bounds and (optionally) normalize_coeffs_8bpc() weights of output index xx for a bilinear
-// resize of `in` samples to `out` (box = the whole input: torchvision crops first, so the filter clamps to the crop).
+#define FR_BILINEAR 0
+#define FR_BICUBIC 1
+
+// Pillow's filters (libImaging/Resample.c bilinear_filter / bicubic_filter), same expressions
+template <int FILTER>
+__host__ __device__ static inline double fr_filter(double x) {
+#pragma clang fp contract(off)
+  if (x < 0.0) x = -x;
+  if (FILTER == FR_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
+  const double a = -0.5;
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+  return 0.0;
+}
+
+// Pillow precompute_coeffs() bounds and (optionally) normalize_coeffs_8bpc() weights of output index xx for a resize of `in`
+// samples to `out` (box = the whole input: torchvision crops first, so the filter clamps to the crop).
+template <int FILTER>
 __host__ __device__ static inline void fr_coeffs(int in, int out, int xx, int* xmin_out, int* xmax_out, int* k) {
 #pragma clang fp contract(off)
   const double scale = (double)in / out;
   const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 1.0 * filterscale;
+  const double support = (FILTER == FR_BICUBIC ? 2.0 : 1.0) * filterscale;
   const double center = (xx + 0.5) * scale;
   const double ss = 1.0 / filterscale;
   int xmin = (int)(center - support + 0.5);
@@ -42,23 +66,21 @@ __host__ __device__ static inline void fr_coeffs(int in, int out, int xx, int* x
   if (!k) return;
   // two sweeps instead of Pillow's stored double array: the weights are recomputed bit-identically (same expression)
   double ww = 0.0;
+  for (int x = 0; x < xmax; ++x) ww += fr_filter<FILTER>((x + xmin - center + 0.5) * ss);
   for (int x = 0; x < xmax; ++x) {
-    double t = (x + xmin - center + 0.5) * ss;
-    if (t < 0.0) t = -t;
-    ww += t < 1.0 ? 1.0 - t : 0.0;
-  }
-  for (int x = 0; x < xmax; ++x) {
-    double t = (x + xmin - center + 0.5) * ss;
-    if (t < 0.0) t = -t;
-    double w = t < 1.0 ? 1.0 - t : 0.0;
+    double w = fr_filter<FILTER>((x + xmin - center + 0.5) * ss);
     if (ww != 0.0) w /= ww;
-    k[x] = (int)(0.5 + w * (1 << 22));
+    k[x] = (int)(w < 0.0 ? -0.5 + w * (1 << 22) : 0.5 + w * (1 << 22));
   }
 }
+static inline void fr_bounds(int filter, int in, int out, int xx, int* xmin, int* xmax) {
+  if (filter == FR_BICUBIC) fr_coeffs<FR_BICUBIC>(in, out, xx, xmin, xmax, nullptr);
+  else fr_coeffs<FR_BILINEAR>(in, out, xx, xmin, xmax, nullptr);
+}
 
-static inline int fr_ksize(int in, int out) {   // Pillow: (int)ceil(support) * 2 + 1
+static inline int fr_ksize(int filter, int in, int out) {   // Pillow: (int)ceil(support) * 2 + 1
   const double scale = (double)in / out;
-  return (int)ceil(scale < 1.0 ? 1.0 : scale) * 2 + 1;
+  return (int)ceil((filter == FR_BICUBIC ? 2.0 : 1.0) * (scale < 1.0 ? 1.0 : scale)) * 2 + 1;
 }
 
 __device__ __forceinline__ int fr_clip8(int acc) {
@@ -79,6 +101,9 @@ static inline size_t fr_lds(int OW, int band, int rows_cap, int kh, int kv) {
          fr_al((size_t)band * 8) + fr_al((size_t)rows_cap * OW * 3);
 }
 
+// DW = descriptor columns: 8 (offset, H, W, top, left, ch, cw, flip; full = out, window at 0) or 12 (+ full_h, full_w, win_top,
+// win_left)
+template <int FILTER, int DW>
 __global__ __launch_bounds__(FR_THREADS) void frames_resample_kernel(const uint8_t* __restrict__ src,
                                                                       const int64_t* __restrict__ desc,
                                                                       const float* __restrict__ lut, float* __restrict__ out,
@@ -96,14 +121,18 @@ __global__ __launch_bounds__(FR_THREADS) void frames_resample_kernel(const uint8
   const int n = blockIdx.y;
   const int y0 = blockIdx.x * band;
   const int nb = min(band, OH - y0);
-  const int64_t* d = desc + (size_t)n * 8;
+  const int64_t* d = desc + (size_t)n * DW;
   const size_t off = (size_t)d[0];
   const int W = (int)d[2], top = (int)d[3], left = (int)d[4], ch = (int)d[5], cw = (int)d[6];
   const bool flip = d[7] != 0;
+  const int full_h = DW == 12 ? (int)d[8] : OH, full_w = DW == 12 ? (int)d[9] : OW;
+  const int win_top = DW == 12 ? (int)d[10] : 0, win_left = DW == 12 ? (int)d[11] : 0;
 
   for (int i = tid; i < 3 * 256; i += FR_THREADS) s_lut[i] = lut[i];
-  for (int xx = tid; xx < OW; xx += FR_THREADS) fr_coeffs(cw, OW, xx, &hb[2 * xx], &hb[2 * xx + 1], hk + (size_t)xx * kh);
-  for (int yy = tid; yy < nb; yy += FR_THREADS) fr_coeffs(ch, OH, y0 + yy, &vb[2 * yy], &vb[2 * yy + 1], vk + (size_t)yy * kv);
+  for (int xx = tid; xx < OW; xx += FR_THREADS)
+    fr_coeffs<FILTER>(cw, full_w, win_left + xx, &hb[2 * xx], &hb[2 * xx + 1], hk + (size_t)xx * kh);
+  for (int yy = tid; yy < nb; yy += FR_THREADS)
+    fr_coeffs<FILTER>(ch, full_h, win_top + y0 + yy, &vb[2 * yy], &vb[2 * yy + 1], vk + (size_t)yy * kv);
   __syncthreads();
 
   // source rows [r0, r0 + nrows) of the crop feed this band (bounds are monotone in the output index); the host planner
@@ -156,42 +185,52 @@ __global__ __launch_bounds__(FR_THREADS) void frames_resample_kernel(const uint8
 }
 
 // Host checks of one launch + the LDS plan.  Every descriptor is read from host memory: offset, H, W, crop top, crop left,
-// crop h, crop w, flip.
-static int fr_plan(const int64_t* desc_host, int N, int B, int T, size_t frames_bytes, int OH, int OW, FramePlan* plan) {
-  MLA_REQUIRE(desc_host, "mla_frames: null descriptor table");
-  MLA_REQUIRE(B > 0 && T > 0 && N > 0, "mla_frames: B=%d T=%d N=%d must be > 0", B, T, N);
-  MLA_REQUIRE((long long)B * T == N, "mla_frames: N=%d frames but B*T = %d*%d", N, B, T);
-  MLA_REQUIRE(N < 65536, "mla_frames: N=%d frames per launch (max 65535)", N);
-  MLA_REQUIRE(OH > 0 && OW > 0 && OH <= 4096 && OW <= 4096, "mla_frames: output size %dx%d out of range", OH, OW);
+// crop h, crop w, flip (DW = 8) + full_h, full_w, win_top, win_left (DW = 12; with 8 columns full = out and the window is at 0).
+static int fr_plan(const char* who, const int64_t* desc_host, int DW, int filter, int N, int B, int T, size_t frames_bytes, int OH,
+                   int OW, FramePlan* plan) {
+  MLA_REQUIRE(desc_host, "%s: null descriptor table", who);
+  MLA_REQUIRE(filter == FR_BILINEAR || filter == FR_BICUBIC, "%s: unknown filter %d (0 = bilinear, 1 = bicubic)", who, filter);
+  MLA_REQUIRE(B > 0 && T > 0 && N > 0, "%s: B=%d T=%d N=%d must be > 0", who, B, T, N);
+  MLA_REQUIRE((long long)B * T == N, "%s: N=%d frames but B*T = %d*%d", who, N, B, T);
+  MLA_REQUIRE(N < 65536, "%s: N=%d frames per launch (max 65535)", who, N);
+  MLA_REQUIRE(OH > 0 && OW > 0 && OH <= 4096 && OW <= 4096, "%s: output size %dx%d out of range", who, OH, OW);
   int kh = 1, kv = 1;
   double sy_max = 0.0;
   for (int n = 0; n < N; ++n) {
-    const int64_t* d = desc_host + (size_t)n * 8;
+    const int64_t* d = desc_host + (size_t)n * DW;
     const int64_t off = d[0], H = d[1], W = d[2], top = d[3], left = d[4], ch = d[5], cw = d[6], flip = d[7];
-    MLA_REQUIRE(H > 0 && W > 0 && H <= FR_DIM_MAX && W <= FR_DIM_MAX, "mla_frames: frame %d: size %lldx%lld out of range",
-                n, (long long)H, (long long)W);
-    MLA_REQUIRE(ch > 0 && cw > 0, "mla_frames: frame %d: empty crop %lldx%lld", n, (long long)ch, (long long)cw);
+    const int64_t full_h = DW == 12 ? d[8] : OH, full_w = DW == 12 ? d[9] : OW, win_top = DW == 12 ? d[10] : 0,
+                  win_left = DW == 12 ? d[11] : 0;
+    MLA_REQUIRE(H > 0 && W > 0 && H <= FR_DIM_MAX && W <= FR_DIM_MAX, "%s: frame %d: size %lldx%lld out of range", who, n,
+                (long long)H, (long long)W);
+    MLA_REQUIRE(ch > 0 && cw > 0, "%s: frame %d: empty crop %lldx%lld", who, n, (long long)ch, (long long)cw);
     MLA_REQUIRE(top >= 0 && left >= 0 && top + ch <= H && left + cw <= W,
-                "mla_frames: frame %d: crop (top %lld, left %lld, h %lld, w %lld) leaves the %lldx%lld frame", n,
-                (long long)top, (long long)left, (long long)ch, (long long)cw, (long long)H, (long long)W);
-    MLA_REQUIRE(flip == 0 || flip == 1, "mla_frames: frame %d: flip flag %lld", n, (long long)flip);
+                "%s: frame %d: crop (top %lld, left %lld, h %lld, w %lld) leaves the %lldx%lld frame", who, n, (long long)top,
+                (long long)left, (long long)ch, (long long)cw, (long long)H, (long long)W);
+    MLA_REQUIRE(flip == 0 || flip == 1, "%s: frame %d: flip flag %lld", who, n, (long long)flip);
     MLA_REQUIRE(off >= 0 && (uint64_t)off + (uint64_t)(H * W * 3) <= (uint64_t)frames_bytes,
-                "mla_frames: frame %d: bytes [%lld, %lld) lie outside the %zu-byte buffer", n, (long long)off,
+                "%s: frame %d: bytes [%lld, %lld) lie outside the %zu-byte buffer", who, n, (long long)off,
                 (long long)(off + H * W * 3), frames_bytes);
-    kh = std::max(kh, fr_ksize((int)cw, OW));
-    kv = std::max(kv, fr_ksize((int)ch, OH));
-    sy_max = fmax(sy_max, (double)ch / OH);
+    MLA_REQUIRE(full_h > 0 && full_w > 0 && full_h <= FR_DIM_MAX && full_w <= FR_DIM_MAX,
+                "%s: frame %d: resized size %lldx%lld out of range", who, n, (long long)full_h, (long long)full_w);
+    MLA_REQUIRE(win_top >= 0 && win_left >= 0 && win_top + OH <= full_h && win_left + OW <= full_w,
+                "%s: frame %d: window (top %lld, left %lld, %dx%d) leaves the %lldx%lld resized image", who, n, (long long)win_top,
+                (long long)win_left, OH, OW, (long long)full_h, (long long)full_w);
+    kh = std::max(kh, fr_ksize(filter, (int)cw, (int)full_w));
+    kv = std::max(kv, fr_ksize(filter, (int)ch, (int)full_h));
+    sy_max = fmax(sy_max, (double)ch / full_h);
   }
   // exact number of source rows a band of `band` output rows reads, maximised over frames and bands
   for (int band = FR_BAND; band >= 1; band >>= 1) {
     int rows_cap = 1;
     for (int n = 0; n < N; ++n) {
-      const int ch = (int)desc_host[(size_t)n * 8 + 5];
+      const int64_t* d = desc_host + (size_t)n * DW;
+      const int ch = (int)d[5], full_h = DW == 12 ? (int)d[8] : OH, win_top = DW == 12 ? (int)d[10] : 0;
       for (int y0 = 0; y0 < OH; y0 += band) {
         const int y1 = std::min(y0 + band, OH) - 1;
         int a0, a1, b0, b1;
-        fr_coeffs(ch, OH, y0, &a0, &a1, nullptr);
-        fr_coeffs(ch, OH, y1, &b0, &b1, nullptr);
+        fr_bounds(filter, ch, full_h, win_top + y0, &a0, &a1);
+        fr_bounds(filter, ch, full_h, win_top + y1, &b0, &b1);
         rows_cap = std::max(rows_cap, b0 + b1 - a0);
       }
     }
@@ -201,25 +240,50 @@ static int fr_plan(const int64_t* desc_host, int N, int B, int T, size_t frames_
       return MLA_OK;
     }
   }
-  MLA_REQUIRE(false, "mla_frames: a %dx%d output of crops up to %.1fx its height needs more than %d bytes of LDS", OH, OW,
-              sy_max, FR_LDS_MAX);
+  MLA_REQUIRE(false, "%s: a %dx%d output of crops up to %.1fx its height needs more than %d bytes of LDS", who, OH, OW, sy_max,
+              FR_LDS_MAX);
   return MLA_ERR_INVALID_ARG;
+}
+
+template <int FILTER, int DW>
+static void fr_launch(const FramePlan& plan, const uint8_t* frames, const int64_t* desc, const float* lut, float* out, int N, int T,
+                      int out_h, int out_w, void* stream) {
+  dim3 grid((unsigned)cdiv(out_h, plan.band), (unsigned)N);
+  hipLaunchKernelGGL((frames_resample_kernel<FILTER, DW>), grid, dim3(FR_THREADS), plan.lds, (hipStream_t)stream, frames, desc, lut,
+                     out, T, out_h, out_w, plan.band, plan.rows_cap, plan.kh, plan.kv);
 }
 
 extern "C" int mla_frames_check(const int64_t* desc_host, int N, int B, int T, size_t frames_bytes, int out_h, int out_w) {
   FramePlan plan;
-  return fr_plan(desc_host, N, B, T, frames_bytes, out_h, out_w, &plan);
+  return fr_plan("mla_frames", desc_host, 8, FR_BILINEAR, N, B, T, frames_bytes, out_h, out_w, &plan);
 }
 
 extern "C" int mla_frames_resample(const uint8_t* frames, size_t frames_bytes, const int64_t* desc, const int64_t* desc_host,
                                    const float* lut, float* out, int N, int B, int T, int out_h, int out_w, void* stream) {
   MLA_REQUIRE(frames && desc && lut && out, "mla_frames_resample: null pointer");
   FramePlan plan;
-  const int rc = fr_plan(desc_host, N, B, T, frames_bytes, out_h, out_w, &plan);
+  const int rc = fr_plan("mla_frames", desc_host, 8, FR_BILINEAR, N, B, T, frames_bytes, out_h, out_w, &plan);
   if (rc != MLA_OK) return rc;
-  dim3 grid((unsigned)cdiv(out_h, plan.band), (unsigned)N);
-  hipLaunchKernelGGL(frames_resample_kernel, grid, dim3(FR_THREADS), plan.lds, (hipStream_t)stream, frames, desc, lut, out, T,
-                     out_h, out_w, plan.band, plan.rows_cap, plan.kh, plan.kv);
+  fr_launch<FR_BILINEAR, 8>(plan, frames, desc, lut, out, N, T, out_h, out_w, stream);
   MLA_CHECK_LAUNCH("mla_frames_resample");
+  return MLA_OK;
+}
+
+extern "C" int mla_image_check(const int64_t* desc_host, int N, int B, int T, size_t frames_bytes, int out_h, int out_w,
+                               int filter) {
+  FramePlan plan;
+  return fr_plan("mla_image", desc_host, 12, filter, N, B, T, frames_bytes, out_h, out_w, &plan);
+}
+
+extern "C" int mla_image_resample(const uint8_t* frames, size_t frames_bytes, const int64_t* desc, const int64_t* desc_host,
+                                  const float* lut, float* out, int N, int B, int T, int out_h, int out_w, int filter,
+                                  void* stream) {
+  MLA_REQUIRE(frames && desc && lut && out, "mla_image_resample: null pointer");
+  FramePlan plan;
+  const int rc = fr_plan("mla_image", desc_host, 12, filter, N, B, T, frames_bytes, out_h, out_w, &plan);
+  if (rc != MLA_OK) return rc;
+  if (filter == FR_BICUBIC) fr_launch<FR_BICUBIC, 12>(plan, frames, desc, lut, out, N, T, out_h, out_w, stream);
+  else fr_launch<FR_BILINEAR, 12>(plan, frames, desc, lut, out, N, T, out_h, out_w, stream);
+  MLA_CHECK_LAUNCH("mla_image_resample");
   return MLA_OK;
 }

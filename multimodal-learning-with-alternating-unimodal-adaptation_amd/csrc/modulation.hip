@@ -13,6 +13,7 @@
 // counter-based generator (Philox4x32-10 + Box-Muller: element i of the buffer always draws from counter i / 4, so the
 // noise does not depend on the launch geometry).
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -117,26 +118,7 @@ __global__ __launch_bounds__(64) void ogm_stats_final_kernel(const double* __res
   }
 }
 
-// ---- Philox4x32-10 ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  c[1] = (uint32_t)p1;
-  c[3] = (uint32_t)p0;
-  c[0] = n0;
-  c[2] = n2;
-}
-__device__ __forceinline__ void philox4x32(uint64_t counter, uint64_t stream_id, uint64_t seed, uint32_t (&out)[4]) {
-  uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32)};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
-}
+// ---- noise: Philox4x32-10 (philox.h) -> (0, 1) -------------------------------------------------------------------------------
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }   // (0, 1)
 
 // grad[off + i] = grad[off + i] * coeff (+ std_s * z_i): one thread per 4 consecutive elements of a segment

@@ -10,6 +10,8 @@ from .encoder import ResNet18Encoder  # noqa: F401
 from .feed import DeviceFeeder  # noqa: F401
 from .frames import (FrameBatcher, decode_frames, frame_descriptors, make_lut, pick_frames, sample_augment,  # noqa: F401
                      sample_crop, sample_flip, sample_generator)
+from .cav_feed import (CAVBatcher, decode_middle_frames, fbank_descriptors, image_descriptors, pick_middle_frame,  # noqa: F401
+                       resize_center_crop, sample_fbank_aug)
 from .model import AVClassifier, ConcatFusion, SharedHead  # noqa: F401
 from .m3ae import CAVClassifier, ConcatFusion3, M3AEClassifier, M3AEEncoder, Modal3Classifier  # noqa: F401
 from .modulation import OGM  # noqa: F401

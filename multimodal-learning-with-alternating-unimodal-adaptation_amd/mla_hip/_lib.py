@@ -137,6 +137,10 @@ PROTOTYPES = {
     "mla_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "mla_frames_check": (_I, [_P, _I, _I, _I, _Z, _I, _I]),
     "mla_frames_resample": (_I, [_P, _Z, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "mla_image_check": (_I, [_P, _I, _I, _I, _Z, _I, _I, _I]),
+    "mla_image_resample": (_I, [_P, _Z, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "mla_fbank_check": (_I, [_P, _I, _I, _I]),
+    "mla_fbank_augment": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, ctypes.c_uint64, _P]),
 }
 
 _lib = None

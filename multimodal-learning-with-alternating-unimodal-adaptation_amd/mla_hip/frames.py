@@ -21,7 +21,9 @@ distribution and the algorithm are what is matched.)
 DeviceFeeder's `copied()` and `device_step()` hooks: fed through a DeviceFeeder, the kernel runs on the feeder's copy stream
 behind the batch's copies and the feeder yields the reference's tuple (spec, image (B, 3, 3, 224, 224) fp32, label, idx).
 
-Out of scope: the Food-101 / M3AE timm transform (dataset.py:401-446: color jitter, bicubic, 256) and QMF's masking.
+CAVDataset's feed (bicubic Resize + CenterCrop of the middle frame, fbank SpecAug) and the M3AE / Food-101 eval transform
+(the same at size 256) are in `cav_feed` (CAVBatcher subclasses FrameBatcher: same staging ring, fences and hooks).
+Out of scope: the Food-101 / M3AE timm TRAIN transform (dataset.py:401-412: color jitter) and QMF's masking.
 """
 from __future__ import annotations
 
@@ -186,12 +188,15 @@ class _CachedFrame:
 
 
 def decode_frames(visual_feature_path: str, out_path: str, names: Sequence[str], pick_num: int = PICK_NUM,
-                  threads: int = MAX_THREADS) -> int:
+                  threads: int = MAX_THREADS, picker=None) -> int:
     """Decode each sample's picked JPEGs once with PIL into <out_path>/<name>/<t>.npy (uint8 HWC, t = time slot 0..2, in the
     order pick_frames returns them).  FrameBatcher(frame_cache=out_path) then gives batches bit-identical to the JPEG source
-    with a memcpy per frame instead of a decode.  Returns the number of files written."""
+    with a memcpy per frame instead of a decode.  Returns the number of files written.
+    `picker(directory) -> file names` replaces pick_frames(directory, pick_num): cav_feed.decode_middle_frames caches the one
+    frame CAVDataset reads as time slot 0."""
     def one(name):
-        frames = pick_frames(os.path.join(visual_feature_path, name), pick_num)
+        d = os.path.join(visual_feature_path, name)
+        frames = pick_frames(d, pick_num) if picker is None else list(picker(d))
         os.makedirs(os.path.join(out_path, name), exist_ok=True)
         for t, f in enumerate(frames):
             np.save(_cache_path(out_path, name, t), decode_jpeg(os.path.join(visual_feature_path, name, f)))
@@ -201,6 +206,8 @@ def decode_frames(visual_feature_path: str, out_path: str, names: Sequence[str],
 
 
 class FrameBatcher:
+    DESC_COLS = 8                 # columns of a frame descriptor row (cav_feed.CAVBatcher: 12)
+
     def __init__(self, names: Sequence[str], labels: Sequence[int], batch_size: int, audio_feature_path: str,
                  visual_feature_path: Optional[str] = None, frame_cache: Optional[str] = None, train: bool = True,
                  seed: int = 0, epoch: int = 0, threads: int = 8, ring: int = 4, pin: Optional[bool] = None,
@@ -270,12 +277,26 @@ class FrameBatcher:
         shapes = [f.shape[:2] for f in frames]
         return load_fbank(self.audio, self.names[i]), frames, self.sample_boxes(i, shapes)
 
+    def _descriptors(self, shapes, boxes) -> Tuple[np.ndarray, int]:
+        return frame_descriptors(shapes, boxes)
+
+    def _extra_staging(self, mk) -> dict:
+        """Further pinned staging tensors of a subclass's host tuple."""
+        return {}
+
+    def _fill_extra(self, st: dict, ids: Sequence[int], loaded: Sequence[tuple]) -> None:
+        """Fill what _extra_staging added, from the batch's dataset indices and _load results."""
+
+    def _host_tuple(self, st: dict, b: int) -> tuple:
+        return st["spec"][:b], st["frames"], st["desc"][:b * self.T], st["label"][:b], st["idx"][:b]
+
     def _staging(self, k: int, nbytes: int) -> dict:
         st = self._stage[k]
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=self.pin)
         if st is None:
-            st = {"spec": mk((self.B,) + FBANK_SHAPE, torch.float32), "desc": mk((self.B * self.T, 8), torch.int64),
+            st = {"spec": mk((self.B,) + FBANK_SHAPE, torch.float32), "desc": mk((self.B * self.T, self.DESC_COLS), torch.int64),
                   "label": mk((self.B,), torch.int64), "idx": mk((self.B, 1), torch.int64), "frames": None}
+            st.update(self._extra_staging(mk))
             self._stage[k] = st
         if st["frames"] is None or st["frames"].numel() < nbytes:      # grows with the largest batch seen, in MiB steps
             cap = max(nbytes, (st["frames"].numel() * 5 // 4) if st["frames"] is not None else 0)
@@ -314,9 +335,9 @@ class FrameBatcher:
         for bi, ids in enumerate(batches):
             b = len(ids)
             loaded = [f.result() for f in pending]
-            shapes = [f.shape[:2] for _, frames, _ in loaded for f in frames]
-            boxes = [box for _, _, bx in loaded for box in bx]
-            desc, nbytes = frame_descriptors(shapes, boxes)
+            shapes = [f.shape[:2] for l in loaded for f in l[1]]
+            boxes = [box for l in loaded for box in l[2]]
+            desc, nbytes = self._descriptors(shapes, boxes)
             if self._fence[k] is not None:
                 self._fence[k].synchronize()
                 self._fence[k] = None
@@ -326,7 +347,7 @@ class FrameBatcher:
             buf = st["frames"].numpy()
 
             def fill(j):
-                spec, frames, _ = loaded[j]
+                spec, frames = loaded[j][:2]
                 np.copyto(st["spec"][j].numpy(), spec)
                 for t, f in enumerate(frames):
                     o = int(desc[j * self.T + t, 0])
@@ -338,7 +359,8 @@ class FrameBatcher:
             st["desc"][:b * self.T].numpy()[...] = desc
             st["label"][:b] = torch.tensor([self.labels[i] for i in ids], dtype=torch.int64)
             st["idx"][:b, 0] = torch.tensor(ids, dtype=torch.int64)
+            self._fill_extra(st, ids, loaded)
             self._unfenced.append(k)
             pending = submit(batches[bi + 1]) if bi + 1 < len(batches) else []     # the next batch loads while this one is consumed
-            yield st["spec"][:b], st["frames"], st["desc"][:b * self.T], st["label"][:b], st["idx"][:b]
+            yield self._host_tuple(st, b)
             k = (k + 1) % self.ring

@@ -877,3 +877,53 @@ def frames_resample(frames: torch.Tensor, desc: torch.Tensor, desc_host: torch.T
     _call("mla_frames_resample", _p(frames, torch.uint8), frames.numel(), _p(desc, torch.int64), d.data_ptr(), _p(lut), _p(out), d.shape[0], B, T, OH,
           OW, stream or cur_stream())
     return out
+
+
+# ---- CAV-MAE batch feed (dataset/dataset.py:251-256, 281-294, 303-321) -----------------------------------------------------
+def _table_host(t: torch.Tensor, cols: int, what: str) -> torch.Tensor:
+    if t.is_cuda or t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
+        raise MLAHipError(f"{what}: expected a contiguous host int64 (N, {cols}) tensor, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def image_check(desc_host: torch.Tensor, B: int, T: int, frames_bytes: int, out_h: int = 224, out_w: int = 224, filter: int = 1) -> None:
+    """The host checks of image_resample alone (no GPU): raises MLAHipError on a descriptor the kernel must not run."""
+    d = _table_host(desc_host, 12, "image descriptors")
+    _call("mla_image_check", d.data_ptr(), d.shape[0], B, T, frames_bytes, out_h, out_w, filter)
+
+
+def image_resample(frames: torch.Tensor, desc: torch.Tensor, desc_host: torch.Tensor, lut: torch.Tensor, out: torch.Tensor,
+                   T: int, filter: int = 1, stream: Optional[int] = None) -> torch.Tensor:
+    """frames uint8 (device, packed HWC frames), desc int64 (N, 12) on the device and the same table on the host, lut fp32 (3, 256)
+    -> out fp32 (B, 3, T, out_h, out_w); filter 0 = bilinear, 1 = bicubic (see include/mla_hip.h, mla_image_resample)."""
+    d = _table_host(desc_host, 12, "image descriptors")
+    if tuple(desc.shape) != tuple(d.shape):
+        raise MLAHipError(f"image descriptors: device table {tuple(desc.shape)} and host table {tuple(d.shape)} differ")
+    if tuple(lut.shape) != (3, 256) or out.dim() != 5 or out.shape[1] != 3 or out.shape[2] != T:
+        raise MLAHipError(f"image_resample: lut {tuple(lut.shape)} / out {tuple(out.shape)} do not match (3, 256) / (B, 3, {T}, H, W)")
+    B, _, _, OH, OW = out.shape
+    _call("mla_image_resample", _p(frames, torch.uint8), frames.numel(), _p(desc, torch.int64), d.data_ptr(), _p(lut), _p(out), d.shape[0], B, T,
+          OH, OW, filter, stream or cur_stream())
+    return out
+
+
+def fbank_check(desc_host: torch.Tensor, T: int = 1024, F: int = 128, std: float = 4.4849) -> None:
+    """The host checks of fbank_augment alone (no GPU): raises MLAHipError on a descriptor the kernel must not run, or std == 0."""
+    d = _table_host(desc_host, 8, "fbank descriptors")
+    if not float(std) != 0.0:                # 0 and NaN
+        raise MLAHipError(f"fbank: std {std} (std == 0 or NaN)")
+    _call("mla_fbank_check", d.data_ptr(), d.shape[0], T, F)
+
+
+def fbank_augment(x: torch.Tensor, out: torch.Tensor, desc: torch.Tensor, desc_host: torch.Tensor, mean: float, std: float, seed: int,
+                  stream: Optional[int] = None) -> torch.Tensor:
+    """x fp32 (B, T, F) -> out (another buffer): SpecAug masks, (x - mean) / std, Philox noise and roll per the descriptor rows
+    int64 (B, 8), on the device and the same table on the host (see include/mla_hip.h, mla_fbank_augment)."""
+    d = _table_host(desc_host, 8, "fbank descriptors")
+    if x.dim() != 3 or tuple(out.shape) != tuple(x.shape) or tuple(desc.shape) != (x.shape[0], 8) or d.shape[0] != x.shape[0]:
+        raise MLAHipError(f"fbank_augment: x {tuple(x.shape)} / out {tuple(out.shape)} / descriptors {tuple(desc.shape)}, {tuple(d.shape)} do not "
+                          "match (B, T, F) / (B, T, F) / (B, 8)")
+    B, T, F = x.shape
+    _call("mla_fbank_augment", _p(x), _p(out), _p(desc, torch.int64), d.data_ptr(), B, T, F, mean, std, int(seed) & 0xFFFFFFFFFFFFFFFF,
+          stream or cur_stream())
+    return out

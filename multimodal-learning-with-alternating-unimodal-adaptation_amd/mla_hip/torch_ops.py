@@ -388,3 +388,27 @@ def frames_resample(frames, desc, lut, T, out_h=224, out_w=224):
     out = _f32((N // T, 3, T, out_h, out_w), frames)
     ops.frames_resample(frames, desc_host.to(frames.device), desc_host, lut, out, T)
     return out
+
+
+# ---- CAV-MAE batch feed (dataset/dataset.py:251-256, 281-294, 303-321) ------------------------------------------------
+@_op("image_resample(Tensor frames, Tensor desc, Tensor lut, int T, int out_h=224, int out_w=224, int filter=1) -> Tensor")
+def image_resample(frames, desc, lut, T, out_h=224, out_w=224, filter=1):
+    """Packed uint8 HWC frames (device) + descriptors int64 (N, 12) (host; validated there, then copied to the device) ->
+    (N / T, 3, T, out_h, out_w) fp32: crop, bilinear / bicubic resize, window, flip, LUT (mla_hip.cav_feed)."""
+    desc_host = desc.cpu().contiguous()
+    N = desc_host.shape[0]
+    if T <= 0 or N % T:
+        raise ops.MLAHipError(f"image_resample: {N} frames are not a whole number of samples of T={T}")
+    out = _f32((N // T, 3, T, out_h, out_w), frames)
+    ops.image_resample(frames, desc_host.to(frames.device), desc_host, lut, out, T, filter)
+    return out
+
+
+@_op("fbank_augment(Tensor x, Tensor desc, float mean, float std, int seed) -> Tensor")
+def fbank_augment(x, desc, mean, std, seed):
+    """fbanks fp32 (B, T, F) (device) + descriptors int64 (B, 8) (host; validated there, then copied to the device) -> a new
+    (B, T, F): SpecAug masks, normalisation, Philox noise, roll (mla_hip.cav_feed)."""
+    desc_host = desc.cpu().contiguous()
+    out = torch.empty_like(x)
+    ops.fbank_augment(x, out, desc_host.to(x.device), desc_host, mean, std, seed)
+    return out
