@@ -342,6 +342,27 @@ int mla_colsum(const float* X, float* r, int B, int D, float scale, void* stream
 size_t mla_gs_ws_elems(int D, int C);
 int mla_gs_project(float* Pl, const float* r, float* G, int D, int C, float alpha, float* ws, void* stream);
 
+/* ---- head-only modality phase on stored features (models/basic_model.py:278-319 CLIPClassifier; main.py:432-442) ----
+ * One call = one phase: out = fc_out(X) (main.py:432), loss = CE(out, labels) (:434), the head gradients of loss.backward() (:435),
+ * GSPlugin.before_update on the weight gradient when `project` (:437; utils/utils.py:34-41 literally, in mla_gs_project's order with
+ * r, k, the denominator, the norm and the projected sums carried in fp64 and each stored value rounded once), and
+ * torch.optim.SGD(momentum, weight decay) on weight and bias (:439), in place.  No dX is formed: nothing lies behind the features.
+ * X (B, D), labels int64 (B); W (C, D), b (C) and buf (C*D + C: the momentum of [W | b], `first` != 0: it becomes g + wd p);
+ * Pl (D, D), read and updated only when `project`; logits (B, C) and loss[1] out; ws: mla_feature_ws_elems(B, D, C) floats.
+ * 4 kernel launches and no copy when projecting, 2 otherwise; no atomics, bit-reproducible.  An out-of-range label poisons the loss
+ * with NaN.  C <= 128, D <= 4096; X, W, buf, Pl, logits and ws 16-byte aligned.  Any D and C*D (nothing here needs a multiple of 4). */
+size_t mla_feature_ws_elems(int B, int D, int C);
+int mla_feature_phase(const float* X, const int64_t* labels, float* W, float* b, float* buf, float* Pl, float* logits,
+                      float* loss, float* ws, int B, int D, int C, float inv_batch, int project, double alpha, float lr,
+                      float momentum, float wd, int first, void* stream);
+/* The batch feed of such a model (dataset/dataset.py:864-872 CLIPDataset.__getitem__) from device-resident tables: row idx[b] of
+ * T0 and T1 (N, D) -> out0 / out1 (B, D), labels[idx[b]] -> out_label (B), idx[b] -> out_idx (B, 1), one launch; 16-byte row
+ * accesses when D % 4 == 0 and the tables are 16-byte aligned, scalar otherwise.  The kernel clamps an index to [0, N) and never
+ * reads out of bounds; refusing a bad index is mla_gather_index_check's part, on the host vector the index is uploaded from. */
+int mla_gather_index_check(const int64_t* idx_host, int n, int N);
+int mla_gather_rows2(const float* T0, const float* T1, const int64_t* labels, const int64_t* idx, float* out0, float* out1,
+                     int64_t* out_label, int64_t* out_idx, int N, int D, int B, void* stream);
+
 /* ---- OGM / OGM-GE gradient modulation (main.py:312-410, --modulation OGM | OGM_GE) ---------------------------------
  * mla_ogm_coeff: score_m = sum_i softmax(out_m)[i][label_i] (row order), ratios and the coefficient of every modality
  *   (main.py:373-384 for M = 2: {audio, visual}; 314-337 for M = 3: {audio, visual, text}) -> coeff[M] on the device;

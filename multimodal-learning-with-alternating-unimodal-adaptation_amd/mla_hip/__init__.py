@@ -14,6 +14,8 @@ from .cav_feed import (CAVBatcher, decode_middle_frames, fbank_descriptors, imag
                        resize_center_crop, sample_fbank_aug)
 from .model import AVClassifier, ConcatFusion, SharedHead  # noqa: F401
 from .m3ae import CAVClassifier, ConcatFusion3, M3AEClassifier, M3AEEncoder, Modal3Classifier  # noqa: F401
+from .clip import CLIPClassifier  # noqa: F401
+from .clip_feed import CLIPFeatureBatcher, epoch_permutation, load_feature_tables  # noqa: F401
 from .modulation import OGM  # noqa: F401
 from .optim import FusedAdam, FusedSGD, cav_param_groups  # noqa: F401
 from .plugin import GSPlugin  # noqa: F401

@@ -112,6 +112,8 @@ class JointTrainer(StreamTrainer):
             self.last["scores"], self.last["ratios"] = self.ogm.info[:self.M], self.ogm.info[3:3 + self.M]
         # 4. encoder chains: backward (loss.backward()) -> all-reduce -> modulation (main.py:392-408) -> SGD (main.py:416)
         for k, (_tag, grp, enc) in enumerate(self.encoders):
+            if enc is None:                                   # stored features (CLIPClassifier): no conv gradient to modulate, dX unused
+                continue
             es = self._estreams[k] if self.overlap_forward else None
             if es is not None:
                 es.wait_stream(main)                          # dX_m (and the coefficients) are ready

@@ -145,7 +145,7 @@ class ConcatFusion(nn.Module):
         return concat_fusion_forward(self, (x, y))
 
 
-def check_joint_args(args, large_ok: bool = False) -> None:
+def check_joint_args(args, large_ok: bool = False, clip_ok: bool = False) -> None:
     """What the joint (gs_flag false) classifiers support through `args`: `--modulation Normal | OGM | OGM_GE` with concat fusion.
     `--modulation QMF` (main.py:170-268) lives in `mla_hip.qmf`: build the model with gs_flag false and modulation "Normal", then
     `attach_qmf_heads(model)` / `QMFTrainer(model, n_data)` add the per-modality audio_fc / visual_fc / txtual_fc heads and the
@@ -158,8 +158,9 @@ def check_joint_args(args, large_ok: bool = False) -> None:
         raise NotImplementedError(f"Incorrect modulation: {mod}")
     if getattr(args, "lorb", "base") == "large" and not large_ok:
         raise NotImplementedError("mla_hip does not implement --lorb large")
-    if getattr(args, "clip", False):
-        raise NotImplementedError("mla_hip does not implement --clip")
+    if getattr(args, "clip", False) and not clip_ok:
+        raise NotImplementedError("--clip (stored CLIP features) is mla_hip.CLIPClassifier; this classifier has encoders and does not "
+                                  "take args.clip")
 
 
 class _Classifier(nn.Module):
@@ -168,6 +169,7 @@ class _Classifier(nn.Module):
     encoder in `mla_encoders()` order; the kernel-level and the autograd forwards below are derived from that list."""
     side_streams = True
     lorb_large = False          # True on the `--lorb large` family (CAVClassifier)
+    feature_only = False        # True on CLIPClassifier: stored features, no encoder behind them (mla_encoders() carries None)
     qmf_heads = None            # mla_hip.qmf.attach_qmf_heads: the per-modality heads, in mla_encoders() order
 
     def __init__(self, args, device, seed: Optional[int], datasets, fusion_cls, feat_dim: int, n_enc: int):
@@ -182,7 +184,7 @@ class _Classifier(nn.Module):
             raise NotImplementedError("Incorrect fusion method: {}!".format(fusion))
         self.gs_flag = bool(getattr(args, "gs_flag", False))
         if not self.gs_flag:
-            check_joint_args(args, self.lorb_large)
+            check_joint_args(args, self.lorb_large, self.feature_only)
         self.args, self.device, self.feat_dim, self._seed0 = args, torch.device(device), feat_dim, seed
         self.fusion_module = fusion_cls(feat_dim if self.gs_flag else n_enc * feat_dim, N_CLASSES[dataset], device,
                                         self._seed(n_enc), joint=not self.gs_flag)

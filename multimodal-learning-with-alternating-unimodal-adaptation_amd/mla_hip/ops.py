@@ -669,6 +669,48 @@ def sgd_step(p, g, buf, lr: float, momentum: float, wd: float, first: bool, stre
     _call("mla_sgd_step", _p(p), _p(g), _p(buf), p.numel(), lr, momentum, wd, int(first), stream or cur_stream())
 
 
+def feature_ws_elems(B: int, D: int, C: int) -> int:
+    return int(_lib.load().mla_feature_ws_elems(B, D, C))
+
+
+def feature_phase(X, labels, W, b, buf, Pl, logits, loss, ws, inv_batch: float, project: bool, alpha: float, lr: float,
+                  momentum: float, wd: float, first: bool, stream: Optional[int] = None) -> None:
+    """One head-only modality phase (main.py:432-442) on stored features, in place: logits / loss out; W (C, D), b (C), the
+    momentum buffer `buf` over [W | b] and, when `project`, Pl (D, D) updated (see include/mla_hip.h, mla_feature_phase)."""
+    if X.dim() != 2 or W.dim() != 2 or W.shape[1] != X.shape[1]:
+        raise MLAHipError(f"feature_phase: X {tuple(X.shape)} {X.dtype} does not match the head weight {tuple(W.shape)}")
+    B, D = X.shape
+    C = W.shape[0]
+    if labels.numel() != B or b.numel() != C or buf.numel() != C * D + C or tuple(logits.shape) != (B, C) or loss.numel() != 1 \
+            or (project and (Pl is None or tuple(Pl.shape) != (D, D))) or (C <= 128 and ws.numel() < feature_ws_elems(B, D, C)):
+        raise MLAHipError(f"feature_phase: labels {tuple(labels.shape)} / bias {tuple(b.shape)} / momentum {tuple(buf.shape)} / logits "
+                          f"{tuple(logits.shape)} / Pl {None if Pl is None else tuple(Pl.shape)} / workspace {ws.numel()} do not match "
+                          f"B={B}, D={D}, C={C}")
+    _call("mla_feature_phase", _p(X), _p(labels, torch.int64), _p(W), _p(b), _p(buf), _p(Pl), _p(logits), _p(loss), _p(ws), B, D, C,
+          inv_batch, int(bool(project)), alpha, lr, momentum, wd, int(bool(first)), stream or cur_stream())
+
+
+def gather_index_check(idx_host: torch.Tensor, N: int) -> None:
+    """Refuse an index vector (host int64) with an entry outside [0, N) before it is uploaded (no GPU)."""
+    if idx_host.is_cuda or idx_host.dtype != torch.int64 or not idx_host.is_contiguous():
+        raise MLAHipError(f"gather index: expected a contiguous host int64 tensor, got {idx_host.dtype} on {idx_host.device}")
+    _call("mla_gather_index_check", idx_host.data_ptr(), idx_host.numel(), N)
+
+
+def gather_rows2(T0, T1, labels, idx, out0, out1, out_label, out_idx, stream: Optional[int] = None) -> None:
+    """Rows idx (B) int64 of the device tables T0, T1 (N, D) fp32 and of labels (N) int64 -> out0, out1 (B, D), out_label (B),
+    out_idx (B, 1), one launch (see include/mla_hip.h, mla_gather_rows2)."""
+    if T0.dim() != 2 or tuple(T1.shape) != tuple(T0.shape) or labels.numel() != T0.shape[0]:
+        raise MLAHipError(f"gather_rows2: tables {tuple(T0.shape)} / {tuple(T1.shape)} / labels {tuple(labels.shape)} do not match (N, D)")
+    N, D = T0.shape
+    B = idx.numel()
+    if tuple(out0.shape) != (B, D) or tuple(out1.shape) != (B, D) or out_label.numel() != B or out_idx.numel() != B:
+        raise MLAHipError(f"gather_rows2: outputs {tuple(out0.shape)} / {tuple(out1.shape)} / {tuple(out_label.shape)} / "
+                          f"{tuple(out_idx.shape)} do not match B={B}, D={D}")
+    _call("mla_gather_rows2", _p(T0), _p(T1), _p(labels, torch.int64), _p(idx, torch.int64), _p(out0), _p(out1), _p(out_label, torch.int64),
+          _p(out_idx, torch.int64), N, D, B, stream or cur_stream())
+
+
 def adam_step(p, g, m, v, lr: float, beta1: float, beta2: float, eps: float, wd: float, step: int,
               stream: Optional[int] = None) -> None:
     """torch.optim.Adam's single-tensor rule on one flat range (any 4-byte-aligned start); g None = zero gradient."""

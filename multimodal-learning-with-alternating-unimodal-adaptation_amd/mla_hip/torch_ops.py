@@ -274,6 +274,30 @@ def sgd_step(p, g, buf, lr, momentum, weight_decay, first):
     ops.sgd_step(p, g, buf, lr, momentum, weight_decay, first)
 
 
+@_op("feature_phase(Tensor X, Tensor labels, Tensor(a!) W, Tensor(b!) b, Tensor(c!) buf, Tensor(d!)? Pl, float inv_batch, "
+     "bool project, float alpha, float lr, float momentum, float weight_decay, bool first) -> (Tensor, Tensor)")
+def feature_phase(X, labels, W, b, buf, Pl, inv_batch, project, alpha, lr, momentum, weight_decay, first):
+    """One head-only modality phase on stored features (main.py:432-442): (logits, loss[1]); W, b, the momentum buffer over
+    [W | b] and (when `project`) Pl updated in place."""
+    B, D = X.shape
+    C = W.shape[0]
+    logits, loss = _f32((B, C), X), _f32(1, X)
+    ops.feature_phase(X, labels, W, b, buf, Pl, logits, loss, _f32(max(ops.feature_ws_elems(B, D, C), 1), X), inv_batch, project, alpha,
+                      lr, momentum, weight_decay, first)
+    return logits, loss
+
+
+@_op("gather_rows2(Tensor T0, Tensor T1, Tensor labels, Tensor idx) -> (Tensor, Tensor, Tensor, Tensor)")
+def gather_rows2(T0, T1, labels, idx):
+    """(out0 (B, D), out1 (B, D), label (B), idx (B, 1)): rows `idx` of two device-resident feature tables and their labels."""
+    B, D = idx.numel(), T0.shape[1]
+    out0, out1 = _f32((B, D), T0), _f32((B, D), T0)
+    lab = torch.empty(B, device=T0.device, dtype=torch.int64)
+    oi = torch.empty((B, 1), device=T0.device, dtype=torch.int64)
+    ops.gather_rows2(T0, T1, labels, idx.reshape(-1), out0, out1, lab, oi)
+    return out0, out1, lab, oi
+
+
 @_op("adam_step(Tensor(a!) p, Tensor? g, Tensor(b!) m, Tensor(c!) v, float lr, float beta1, float beta2, float eps, "
      "float weight_decay, int step) -> ()")
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step):

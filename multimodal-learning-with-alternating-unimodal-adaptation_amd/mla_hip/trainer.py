@@ -15,6 +15,7 @@ audio step), Q8 (av_alpha fixed at 0.55 in the reported loss).
 from __future__ import annotations
 
 import contextlib
+import os
 from typing import Optional
 
 import torch
@@ -45,7 +46,8 @@ class StreamTrainer:
         self.model = model
         self.head = model.fusion_module.fc_out
         self.encoders = model.mla_encoders()                    # [(tag, group, encoder)], alternation / concatenation order
-        groups = {grp: enc for _t, grp, enc in self.encoders}
+        self.feature_only = bool(getattr(model, "feature_only", False))       # stored features: no encoder, no encoder group
+        groups = {grp: enc for _t, grp, enc in self.encoders if enc is not None}
         groups["head"] = self.head
         groups.update(extra_groups or {})
         if optimizer == "sgd":
@@ -60,7 +62,7 @@ class StreamTrainer:
         dev = model.device
         self.losses = {k: torch.zeros(1, device=dev, dtype=torch.float32) for k in ["loss"] + ["loss_" + t for t, _g, _e in self.encoders]}
         self.last = {}
-        self._can_overlap = dev.type == "cuda" and hasattr(model, "forward_split")
+        self._can_overlap = dev.type == "cuda" and hasattr(model, "forward_split") and not self.feature_only
         # encoder chains first (they must not share a hardware queue with each other or with the caller's stream), then the
         # weight-gradient side streams, which may double up when the queues run out (streams.py)
         ne = len(self.encoders)
@@ -83,6 +85,8 @@ class StreamTrainer:
         self.join()
         self.overlap_forward = bool(on) and self._can_overlap
         for k, (_t, _g, enc) in enumerate(self.encoders):
+            if enc is None:
+                continue
             if enc.side_wgrad:
                 enc.wgrad_stream = self._wstreams[k] if self.overlap_forward else None
             enc.tail_stream = self._estreams[k] if self.overlap_forward else None
@@ -112,7 +116,8 @@ class MLATrainer(StreamTrainer):
                  gs_mode: str = "as_intended", legacy_zero_grad: bool = False, av_alpha: float = 0.55,
                  comm: Optional[Comm] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
                  param_groups: Optional[list] = None):
-        """`model`: AVClassifier (ResNet-18 audio+visual), M3AEClassifier (text+image), Modal3Classifier or CAVClassifier.  The calling
+        """`model`: AVClassifier (ResNet-18 audio+visual), M3AEClassifier (text+image), Modal3Classifier, CAVClassifier or
+        CLIPClassifier (stored features: train_step(token_feat, image_feat, label, batch_step, len_dataloader)).  The calling
         stream carries head forward/backward, the packed head exchange, GSPlugin and the head's SGD; the next modality only
         needs the updated head, so the last modality's backward overlaps the next step's first forward.
         optimizer="adam" (main.py:736-747): torch.optim.Adam semantics with `betas`, `eps`, `weight_decay`; `lr` a float, a mapping
@@ -128,8 +133,43 @@ class MLATrainer(StreamTrainer):
         # (critical path, calling stream) and the wait for an encoder's gradient all-reduce in front of its SGD launch (that
         # encoder's stream).  {"head_exchange": [(start, end)...], "grad_wait": [...]} or None (off: nothing is recorded).
         self.dist_events: Optional[dict] = None
+        # Feature-only model (CLIPClassifier): a phase is one mla_feature_phase call.  $MLA_FEATURE_FUSED=0 (read here) or
+        # `fused_feature_phase = False` runs the same step on the general chain instead (A/B measurements).
+        self.fused_feature_phase = self.feature_only and os.environ.get("MLA_FEATURE_FUSED", "1") != "0"
+        self._fbufs: dict = {}
+        if self.feature_only and self.comm.world > 1:
+            raise NotImplementedError("data-parallel training (comm.world > 1) is not implemented for a feature-only model")
 
     keep_debug = False
+
+    def _fused_phase(self, name: str, feat: torch.Tensor, label: torch.Tensor, inv_batch: float, batch_step: int,
+                     len_dataloader: int) -> None:
+        """One modality phase (main.py:432-442) of a feature-only model as ONE mla_feature_phase call: head forward, CE, head
+        gradients, GSPlugin.before_update and the head's SGD on the optimiser's own momentum buffer; no dX, and the projected
+        gradient never reaches memory (so `keep_debug` takes the chain)."""
+        head, opt, gs = self.head, self.optimizer, self.gs_plugin
+        B, D, C = feat.shape[0], head.in_features, head.out_features
+        if (B, name) not in self._fbufs:
+            f32 = dict(device=feat.device, dtype=torch.float32)
+            self._fbufs[(B, name)] = (torch.empty((B, C), **f32), torch.empty(1, **f32), torch.empty(ops.feature_ws_elems(B, D, C), **f32))
+        logits, loss, ws = self._fbufs[(B, name)]
+        fires = gs.mode == "as_intended" and gs.exp_count != 0                                # utils/utils.py:29-32 (Q1, Q5)
+        if fires and gs.Pl.shape[0] != D:
+            gs._resize(D)
+        lr, mom, wd = opt._hyper("head")
+        n = head.weight.numel()
+        ops.feature_phase(feat, label, head.flat[:n].view(C, D), head.flat[n:], opt.buf["head"], gs.Pl if fires else None, logits, loss,
+                          ws, inv_batch, fires, gs.alpha(batch_step, len_dataloader), lr, mom, wd, first=not opt.initialized["head"])
+        opt.initialized["head"] = True
+        gs._fired = gs._fired or fires
+        gs.exp_count += 1                                                                     # :442
+        self.last["out_" + name] = logits
+        self.losses["loss_" + name].copy_(loss)
+
+    def _fused_ok(self) -> bool:
+        opt = self.optimizer
+        return (self.fused_feature_phase and not self.keep_debug and isinstance(opt, FusedSGD)
+                and opt.seg_initialized["head"] is None)
 
     def _phase(self, name: str, enc, feat: torch.Tensor, label: torch.Tensor, inv_batch: float,
                batch_step: int, len_dataloader: int, bstream):
@@ -141,7 +181,9 @@ class MLATrainer(StreamTrainer):
         logits, loss, dX = self.head.forward_backward(feat, label, inv_batch, slot=name)               # :432-435
         self.last["out_" + name] = logits
         self.losses["loss_" + name].copy_(loss)
-        if bstream is None:
+        if enc is None:
+            works = []                                                                        # stored features: nothing behind dX
+        elif bstream is None:
             enc.backward_from_pooled(dX, enc._pa)                                             # loss.backward()
             works = self.comm.allreduce_flat_async(enc.grad)                                 # overlaps what follows
         else:
@@ -209,6 +251,14 @@ class MLATrainer(StreamTrainer):
         inv_batch = 1.0 / (B * self.comm.world)
         opt.zero_grad()                                                                       # main.py:164
         feats, fwd_done = self._forwards(inputs)                                              # main.py:424-431 (joint forward, Q7)
+        if self.feature_only:                                                                 # main.py:428-429, 432-454: head phases only
+            for (tag, _g, _e), feat in zip(self.encoders, feats):
+                self.last[tag] = feat
+                if self._fused_ok():
+                    self._fused_phase(tag, feat, label, inv_batch, batch_step, len_dataloader)
+                else:
+                    self._phase(tag, None, feat, label, inv_batch, batch_step, len_dataloader, None)
+            feats = ()
         for k, ((tag, grp, enc), feat) in enumerate(zip(self.encoders, feats)):
             bs = self._estreams[k] if self.overlap_forward else None
             if bs is not None:
