@@ -6,16 +6,13 @@
 //
 // Latency-bound at the step's shapes (64 x 1024 x 6): few launches, wave-per-class dot products with 64-lane shuffle
 // reductions, no atomics, every sum in a fixed order (bitwise reproducible from run to run).
-#include "common.h"
-
-#define CH_MAXC 128
-#define CH_MAXM 3
+#include "head_common.h"
 
 namespace {
 
 struct ConcatPtrs {
-  const float* x[CH_MAXM];   // (B, D) features of modality m
-  float* dx[CH_MAXM];        // (B, D) feature gradients (backward variants)
+  const float* x[MLA_HEAD_MAXM];   // (B, D) features of modality m
+  float* dx[MLA_HEAD_MAXM];        // (B, D) feature gradients (backward variants)
 };
 
 // One workgroup (4 waves) per sample.  Wave w forms the logits of classes c = w, w + 4, ...: for every modality the partial
@@ -28,8 +25,8 @@ __global__ __launch_bounds__(256) void concat_head_fwd_kernel(const ConcatPtrs p
                                                                float* __restrict__ out, float* __restrict__ out_m,
                                                                float* __restrict__ dlogits, float* __restrict__ rowloss, int M,
                                                                int B, int D, int C, float inv_batch) {
-  __shared__ float lg[CH_MAXC];
-  __shared__ float lgm[CH_MAXM][CH_MAXC];
+  __shared__ float lg[MLA_HEAD_MAXC];
+  __shared__ float lgm[MLA_HEAD_MAXM][MLA_HEAD_MAXC];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x;
   const int MD = M * D;
@@ -39,9 +36,7 @@ __global__ __launch_bounds__(256) void concat_head_fwd_kernel(const ConcatPtrs p
     float tot = 0.f;
     for (int m = 0; m < M; ++m) {
       const float* x = p.x[m] + (size_t)row * D;
-      float s = 0.f;
-      for (int d = lane; d < D; d += 64) s += x[d] * w[(size_t)m * D + d];
-      s = wave_sum(s);
+      const float s = head_row_dot(x, w + (size_t)m * D, D, lane);
       tot += s;
       const float om = s + bias[c] * invM;                               // main.py:298-302: + fc_out.bias / 2 (/ 3)
       if (lane == 0) {
@@ -63,17 +58,12 @@ __global__ __launch_bounds__(256) void concat_head_fwd_kernel(const ConcatPtrs p
   if (wave <= M) {
     // wave 0: the trained logits `out`; wave 1 + m: out_m (loss value only)
     const float* l = wave == 0 ? lg : lgm[wave - 1];
-    const float l0 = lane < C ? l[lane] : -INFINITY;
-    const float l1 = lane + 64 < C ? l[lane + 64] : -INFINITY;
-    const float mx = wave_max(fmaxf(l0, l1));
-    const float e0 = lane < C ? expf(l0 - mx) : 0.f, e1 = lane + 64 < C ? expf(l1 - mx) : 0.f;
-    const float s = wave_sum(e0 + e1);
-    const float lse = mx + logf(s);
-    if (lane == 0) rowloss[(size_t)wave * B + row] = lab_ok ? (lse - l[lab]) * inv_batch : NAN;
+    const Softmax2 q = head_softmax2(l, C, lane);
+    if (lane == 0) rowloss[(size_t)wave * B + row] = lab_ok ? (q.lse - l[lab]) * inv_batch : NAN;
     if (wave == 0) {
       __builtin_amdgcn_wave_barrier();              // every lane has read lg before it is overwritten with dlogits
-      const float d0 = lab_ok ? (e0 / s - (lane == lab ? 1.f : 0.f)) * inv_batch : 0.f;
-      const float d1 = lab_ok ? (e1 / s - (lane + 64 == lab ? 1.f : 0.f)) * inv_batch : 0.f;
+      const float d0 = lab_ok ? head_ce_grad(q.e0, q.s, lane == lab, inv_batch) : 0.f;
+      const float d1 = lab_ok ? head_ce_grad(q.e1, q.s, lane + 64 == lab, inv_batch) : 0.f;
       if (lane < C) {
         lg[lane] = d0;
         dlogits[(size_t)row * C + lane] = d0;
@@ -123,15 +113,11 @@ __global__ __launch_bounds__(256) void concat_head_dw_kernel(const ConcatPtrs p,
     dW[(size_t)c * MD + j] = a * scale;
   }
   if (blockIdx.x == 0 && threadIdx.x < 64) {
-    float a = 0.f;
-    for (int r = threadIdx.x; r < B; r += 64) a += dlogits[(size_t)r * C + c];
-    a = wave_sum(a);
+    const float a = head_col_sum(dlogits, B, C, c, threadIdx.x);
     if (threadIdx.x == 0) db[c] = a * scale;
     if (c == 0 && rowloss) {
       for (int k = 0; k <= M; ++k) {
-        float l = 0.f;
-        for (int r = threadIdx.x; r < B; r += 64) l += rowloss[(size_t)k * B + r];
-        l = wave_sum(l);
+        const float l = head_col_sum(rowloss + (size_t)k * B, B, 1, 0, threadIdx.x);
         if (threadIdx.x == 0) {
           if (k == 0) *loss = l;
           else loss_m[k - 1] = l;
@@ -160,8 +146,8 @@ extern "C" int mla_concat_head_ce_fwd_bwd(const float* x0, const float* x1, cons
   MLA_REQUIRE(x0 && x1 && (M == 2 || x2) && W && b && labels && out && out_m && loss && loss_m && dW && db && dx0 && dx1 &&
                   (M == 2 || dx2) && ws,
               "mla_concat_head_ce_fwd_bwd: null pointer");
-  MLA_REQUIRE(B > 0 && D > 0 && C > 0 && C <= CH_MAXC, "mla_concat_head_ce_fwd_bwd: need B, D > 0 and 0 < C <= %d (got %d)",
-              CH_MAXC, C);
+  MLA_REQUIRE(B > 0 && D > 0 && C > 0 && C <= MLA_HEAD_MAXC, "mla_concat_head_ce_fwd_bwd: need B, D > 0 and 0 < C <= %d (got %d)",
+              MLA_HEAD_MAXC, C);
   hipStream_t st = (hipStream_t)stream;
   const ConcatPtrs p = make_ptrs(x0, x1, M == 3 ? x2 : nullptr, dx0, dx1, M == 3 ? dx2 : nullptr);
   float* dlogits = ws;
@@ -178,7 +164,7 @@ extern "C" int mla_concat_head_fwd(const float* x0, const float* x1, const float
                                    float* out_m, int M, int B, int D, int C, void* stream) {
   MLA_REQUIRE(M == 2 || M == 3, "mla_concat_head_fwd: M must be 2 or 3 (got %d)", M);
   MLA_REQUIRE(x0 && x1 && (M == 2 || x2) && W && b && out && out_m, "mla_concat_head_fwd: null pointer");
-  MLA_REQUIRE(B > 0 && D > 0 && C > 0 && C <= CH_MAXC, "mla_concat_head_fwd: need B, D > 0 and 0 < C <= %d (got %d)", CH_MAXC, C);
+  MLA_REQUIRE(B > 0 && D > 0 && C > 0 && C <= MLA_HEAD_MAXC, "mla_concat_head_fwd: need B, D > 0 and 0 < C <= %d (got %d)", MLA_HEAD_MAXC, C);
   const ConcatPtrs p = make_ptrs(x0, x1, M == 3 ? x2 : nullptr, nullptr, nullptr, nullptr);
   concat_head_fwd_kernel<false><<<B, 256, 0, (hipStream_t)stream>>>(p, W, b, nullptr, out, out_m, nullptr, nullptr, M, B, D, C,
                                                                     0.f);

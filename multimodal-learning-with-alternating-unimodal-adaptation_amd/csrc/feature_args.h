@@ -4,10 +4,10 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/mla_hip.h"
+#include "head_common.h"
 
 void mla_set_error(const char* fmt, ...);
 
-#define FEATURE_MAXC 128        // the two-slot softmax of the head kernels (head_gs_sgd.hip: HEAD_MAXC)
 #define FEATURE_MAXD 4096       // the feature mean (fp64) / one row of Pl in LDS: 32 KB
 #define FEATURE_KROWS 8         // rows of Pl one workgroup of the gradient launch forms k for
 
@@ -37,8 +37,8 @@ static inline int feature_phase_plan(const void* X, const void* labels, const vo
     mla_set_error("mla_feature_phase: need B, D, C > 0 (got %d, %d, %d)", B, D, C);
     return MLA_ERR_INVALID_ARG;
   }
-  if (C > FEATURE_MAXC) {
-    mla_set_error("mla_feature_phase: need 0 < C <= %d (got %d)", FEATURE_MAXC, C);
+  if (C > MLA_HEAD_MAXC) {
+    mla_set_error("mla_feature_phase: need 0 < C <= %d (got %d)", MLA_HEAD_MAXC, C);
     return MLA_ERR_INVALID_ARG;
   }
   if (D > FEATURE_MAXD) {

@@ -11,64 +11,47 @@
 //   4. feat_finish_kernel  that row again, / ||.||_F, stored; g_c = sum_j G[c][j] Pl[i][j]; SGD on W[c][i]   (projecting only)
 //
 // Grid dependencies are kernel boundaries: no cooperative launch, no flag another workgroup waits on, no atomics.  Head and cross
-// entropy keep the order of the chain's kernels (lane-strided wave reductions for logits, row-sequential sums for dW, db and the loss):
-// logits and loss are the chain's bit for bit.  The projection is the literal utils/utils.py:34-41 in the chain's lane / stride order,
-// but r, k, the denominator, the norm and the projected sums are carried in fp64 and every stored value is rounded once: with features
+// entropy are written on the chain's helpers (head_common.h: head_row_dot, head_softmax2, head_ce_grad, head_col_sum; dW sums its rows
+// in order, as head_dw_block does): logits and loss are the chain's bit for bit.  The projection is the literal utils/utils.py:34-41
+// in the chain's lane / stride order, but r, k, the denominator, the norm and the projected sums are carried in fp64 and every stored value is rounded once: with features
 // of both signs some denominators come within a few hundred ulp of zero, where an fp32 r or k decides the answer.
 // Also here: mla_gather_rows2, the batch feed of such a model from device-resident feature tables (dataset/dataset.py:864-872).
-#include "common.h"
+#include "head_common.h"
 #include "feature_args.h"
 
 // Waves per workgroup of the two launches that walk the classes (1 and 4).  Each class is still formed by ONE wave with lanes striding
-// the features (the chain's summation order); 16 waves instead of the chain's 4 shorten the chain of dependent row reads and
+// the features (head_row_dot); 16 waves instead of the chain's 4 shorten the chain of dependent row reads and
 // reductions per wave from ceil(C / 4) to ceil(C / 16).
 #define FEAT_WAVES 16
 
-// torch.optim.SGD on one element (sgd_kernel's expression)
-__device__ __forceinline__ void sgd_elem(float* __restrict__ p, float* __restrict__ buf, float g, float lr, float momentum, float wd,
-                                         int first) {
-  const float pv = *p;
-  const float d = g + wd * pv;
-  const float b = first ? d : momentum * *buf + d;
-  *buf = b;
-  *p = pv - lr * b;
-}
-
-// ---- 1. head forward + softmax + d logits: head_fwd_kernel without its dX half ---------------------------------------------
+// ---- 1. head forward + softmax + d logits on the helpers of head_common.h (head_fwd_kernel without its dX half) -----------
 __global__ __launch_bounds__(64 * FEAT_WAVES) void feat_fwd_kernel(const float* __restrict__ X, const float* __restrict__ W,
                                                         const float* __restrict__ bias, const int64_t* __restrict__ labels,
                                                         float* __restrict__ logits, float* __restrict__ rowloss,
                                                         float* __restrict__ dlogits, int D, int C, float inv_batch) {
-  __shared__ float lg[FEATURE_MAXC];
+  __shared__ float lg[MLA_HEAD_MAXC];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x;
   const float* x = X + (size_t)row * D;
   for (int c = wave; c < C; c += FEAT_WAVES) {
-    float s = 0.f;
-    for (int d = lane; d < D; d += 64) s += x[d] * W[(size_t)c * D + d];
-    s = wave_sum(s);
+    const float s = head_row_dot(x, W + (size_t)c * D, D, lane);
     if (lane == 0) lg[c] = s + bias[c];
   }
   __syncthreads();
   if (wave != 0) return;
-  float l0 = lane < C ? lg[lane] : -INFINITY;
-  float l1 = lane + 64 < C ? lg[lane + 64] : -INFINITY;
-  const float m = wave_max(fmaxf(l0, l1));
-  const float e0 = lane < C ? expf(l0 - m) : 0.f, e1 = lane + 64 < C ? expf(l1 - m) : 0.f;
-  const float s = wave_sum(e0 + e1);
+  const Softmax2 p = head_softmax2(lg, C, lane);
   const long lab_raw = (long)labels[row];
   const bool lab_ok = lab_raw >= 0 && lab_raw < C;   // out of range: NaN loss, no out-of-bounds LDS read
   const int lab = lab_ok ? (int)lab_raw : 0;
-  const float lse = m + logf(s);
-  if (lane == 0) rowloss[row] = lab_ok ? (lse - lg[lab]) * inv_batch : NAN;
-  const float d0 = (e0 / s - (lane == lab ? 1.f : 0.f)) * inv_batch;
-  const float d1 = (e1 / s - (lane + 64 == lab ? 1.f : 0.f)) * inv_batch;
+  if (lane == 0) rowloss[row] = lab_ok ? (p.lse - lg[lab]) * inv_batch : NAN;
+  const float d0 = head_ce_grad(p.e0, p.s, lane == lab, inv_batch);
+  const float d1 = head_ce_grad(p.e1, p.s, lane + 64 == lab, inv_batch);
   if (lane < C) {
-    logits[(size_t)row * C + lane] = l0;
+    logits[(size_t)row * C + lane] = p.l0;
     dlogits[(size_t)row * C + lane] = d0;
   }
   if (lane + 64 < C) {
-    logits[(size_t)row * C + lane + 64] = l1;
+    logits[(size_t)row * C + lane + 64] = p.l1;
     dlogits[(size_t)row * C + lane + 64] = d1;
   }
 }
@@ -85,10 +68,10 @@ struct FeatGradArgs {
   float inv_batch, lr, momentum, wd;
 };
 
-// ---- 2. blocks [0, grad_blocks): dW[c][d] = sum_rows dl[row][c] X[row][d] (head_grad_kernel's order); the d-chunk-0 block of class
-// c also db[c] and the bias SGD, the one of class 0 the loss.  Blocks past them (projecting): r = mean(X, 0) into LDS in fp64 (every
-// block its own copy, rows in order; block 0 of them publishes it), then k_i = Pl[i] . r for FEATURE_KROWS rows of Pl (one wave per
-// row, lanes striding the columns, fp64 accumulators).
+// ---- 2. blocks [0, grad_blocks): dW[c][d] = sum_rows dl[row][c] X[row][d] (rows in order, as head_dw_block); the d-chunk-0 block
+// of class c also db[c] and the bias SGD, the one of class 0 the loss.  Blocks past them (projecting): r = mean(X, 0) into LDS in
+// fp64 (every block its own copy, rows in order; block 0 of them publishes it), then k_i = Pl[i] . r for FEATURE_KROWS rows of Pl
+// (one wave per row, lanes striding the columns, fp64 accumulators).
 __global__ __launch_bounds__(256) void feat_grad_kernel(const FeatGradArgs a) {
   extern __shared__ __attribute__((aligned(16))) double r_s[];
   const int B = a.B, D = a.D, C = a.C;
@@ -123,14 +106,10 @@ __global__ __launch_bounds__(256) void feat_grad_kernel(const FeatGradArgs a) {
     else sgd_elem(a.W + e, a.bufW + e, g, a.lr, a.momentum, a.wd, a.first);
   }
   if (chunk == 0 && threadIdx.x < 64) {
-    float g = 0.f;
-    for (int r = threadIdx.x; r < B; r += 64) g += a.dlogits[(size_t)r * C + c];
-    g = wave_sum(g);
+    const float g = head_col_sum(a.dlogits, B, C, c, threadIdx.x);
     if (threadIdx.x == 0) sgd_elem(a.b + c, a.bufb + c, g, a.lr, a.momentum, a.wd, a.first);
     if (c == 0) {
-      float l = 0.f;
-      for (int r = threadIdx.x; r < B; r += 64) l += a.rowloss[r];
-      l = wave_sum(l);
+      const float l = head_col_sum(a.rowloss, B, 1, 0, threadIdx.x);
       if (threadIdx.x == 0) *a.loss = l;
     }
   }

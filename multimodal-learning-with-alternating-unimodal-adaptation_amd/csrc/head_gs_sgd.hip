@@ -4,9 +4,7 @@
 //   head-gradient projection      GSPlugin.before_update (utils/utils.py:24-41), literal
 //   SGD momentum + weight decay   torch.optim.SGD.step (main.py:749, 439, 451), one flat launch per group
 // Wave-per-row kernels with 64-lane shuffle reductions; no atomics (bitwise reproducible).
-#include "common.h"
-
-#define HEAD_MAXC 128
+#include "head_common.h"
 
 // ---- head: one workgroup per sample ------------------------------------------------------------
 __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ X, const float* __restrict__ W,
@@ -18,33 +16,26 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
   // striding the features: the summation order of the one-wave-per-sample form, bit-identical results), wave 0 does the
   // softmax / loss, then wave w forms dX for the feature slots d = 64 (w + 4 m) + lane.  The one-wave form was a chain of
   // C dependent reductions and C dependent row reads of W: 206 us at C = 101, D = 768 on the step's critical path.
-  __shared__ float lg[HEAD_MAXC];
+  __shared__ float lg[MLA_HEAD_MAXC];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x;
   const float* x = X + (size_t)row * D;
   for (int c = wave; c < C; c += 4) {
-    float s = 0.f;
-    for (int d = lane; d < D; d += 64) s += x[d] * W[(size_t)c * D + d];
-    s = wave_sum(s);
+    const float s = head_row_dot(x, W + (size_t)c * D, D, lane);
     if (lane == 0) lg[c] = s + bias[c];
   }
   __syncthreads();
   if (wave == 0) {
-    float l0 = lane < C ? lg[lane] : -INFINITY;
-    float l1 = lane + 64 < C ? lg[lane + 64] : -INFINITY;
-    const float m = wave_max(fmaxf(l0, l1));
-    const float e0 = lane < C ? expf(l0 - m) : 0.f, e1 = lane + 64 < C ? expf(l1 - m) : 0.f;
-    const float s = wave_sum(e0 + e1);
+    const Softmax2 p = head_softmax2(lg, C, lane);
     const long lab_raw = (long)labels[row];
     const bool lab_ok = lab_raw >= 0 && lab_raw < C;   // out of range: NaN loss (the reference's CE kernel asserts), no OOB LDS read
     const int lab = lab_ok ? (int)lab_raw : 0;
-    const float lse = m + logf(s);
-    if (lane < C) logits[(size_t)row * C + lane] = l0;
-    if (lane + 64 < C) logits[(size_t)row * C + lane + 64] = l1;
-    if (lane == 0) rowloss[row] = lab_ok ? (lse - lg[lab]) * inv_batch : NAN;
+    if (lane < C) logits[(size_t)row * C + lane] = p.l0;
+    if (lane + 64 < C) logits[(size_t)row * C + lane + 64] = p.l1;
+    if (lane == 0) rowloss[row] = lab_ok ? (p.lse - lg[lab]) * inv_batch : NAN;
     __builtin_amdgcn_wave_barrier();
-    const float d0 = (e0 / s - (lane == lab ? 1.f : 0.f)) * inv_batch;
-    const float d1 = (e1 / s - (lane + 64 == lab ? 1.f : 0.f)) * inv_batch;
+    const float d0 = head_ce_grad(p.e0, p.s, lane == lab, inv_batch);
+    const float d1 = head_ce_grad(p.e1, p.s, lane + 64 == lab, inv_batch);
     if (lane < C) {
       lg[lane] = d0;
       dlogits[(size_t)row * C + lane] = d0;
@@ -62,28 +53,31 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
   }
 }
 
-// grid (ceil(D/256), C): dW[c][d] = sum_rows dl[row][c] X[row][d]; block (0,c) also db[c]; block (0,0) the loss.
-__global__ __launch_bounds__(256) void head_grad_kernel(const float* __restrict__ X, const float* __restrict__ dlogits,
-                                                         const float* __restrict__ rowloss, float* __restrict__ dW,
-                                                         float* __restrict__ db, float* __restrict__ loss, int B, int D, int C) {
+// Block (x, c) of a (ceil(D/256), C) grid: dW[c][d] = scale * sum_rows dl[row][c] X[row][d] (rows in order); block (0, c) also
+// db[c]; `with_loss`: block (0, 0) also the loss.  The body of head_grad_kernel (the literals 1.f and true, and the loss row) and of
+// head_dw_kernel (scale, false).
+__device__ __forceinline__ void head_dw_block(const float* __restrict__ X, const float* __restrict__ dlogits,
+                                              const float* __restrict__ rowloss, float* __restrict__ dW, float* __restrict__ db,
+                                              float* __restrict__ loss, int B, int D, int C, float scale, bool with_loss) {
   const int c = blockIdx.y, d = blockIdx.x * 256 + threadIdx.x;
   if (d < D) {
     float a = 0.f;
     for (int r = 0; r < B; ++r) a += dlogits[(size_t)r * C + c] * X[(size_t)r * D + d];
-    dW[(size_t)c * D + d] = a;
+    dW[(size_t)c * D + d] = a * scale;
   }
   if (blockIdx.x == 0 && threadIdx.x < 64) {
-    float a = 0.f;
-    for (int r = threadIdx.x; r < B; r += 64) a += dlogits[(size_t)r * C + c];
-    a = wave_sum(a);
-    if (threadIdx.x == 0) db[c] = a;
-    if (c == 0) {
-      float l = 0.f;
-      for (int r = threadIdx.x; r < B; r += 64) l += rowloss[r];
-      l = wave_sum(l);
+    const float a = head_col_sum(dlogits, B, C, c, threadIdx.x);
+    if (threadIdx.x == 0) db[c] = a * scale;
+    if (with_loss && c == 0) {
+      const float l = head_col_sum(rowloss, B, 1, 0, threadIdx.x);
       if (threadIdx.x == 0) *loss = l;
     }
   }
+}
+__global__ __launch_bounds__(256) void head_grad_kernel(const float* __restrict__ X, const float* __restrict__ dlogits,
+                                                         const float* __restrict__ rowloss, float* __restrict__ dW,
+                                                         float* __restrict__ db, float* __restrict__ loss, int B, int D, int C) {
+  head_dw_block(X, dlogits, rowloss, dW, db, loss, B, D, C, 1.f, true);
 }
 
 extern "C" size_t mla_head_ws_elems(int B, int C) { return (size_t)B * C + B; }
@@ -92,7 +86,7 @@ extern "C" int mla_head_ce_fwd_bwd(const float* X, const float* W, const float* 
                                    float* loss, float* dW, float* db, float* dX, float* ws, int B, int D, int C,
                                    float inv_batch, void* stream) {
   MLA_REQUIRE(X && W && b && labels && logits && loss && dW && db && dX && ws, "mla_head_ce_fwd_bwd: null pointer");
-  MLA_REQUIRE(B > 0 && D > 0 && C > 0 && C <= HEAD_MAXC, "mla_head_ce_fwd_bwd: need 0 < C <= %d (got %d)", HEAD_MAXC, C);
+  MLA_REQUIRE(B > 0 && D > 0 && C > 0 && C <= MLA_HEAD_MAXC, "mla_head_ce_fwd_bwd: need 0 < C <= %d (got %d)", MLA_HEAD_MAXC, C);
   hipStream_t st = (hipStream_t)stream;
   float* dlogits = ws;
   float* rowloss = ws + (size_t)B * C;
@@ -126,9 +120,7 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(const float* __restrict
     dlogits[(size_t)row * C + c] = ok ? (expf(l[c] - m) / s - (c == lab ? 1.f : 0.f)) * inv_batch : 0.f;
 }
 __global__ __launch_bounds__(64) void sum_to_scalar_kernel(const float* __restrict__ v, float* __restrict__ out, int n) {
-  float a = 0.f;
-  for (int i = threadIdx.x; i < n; i += 64) a += v[i];
-  a = wave_sum(a);
+  const float a = head_col_sum(v, n, 1, 0, threadIdx.x);
   if (threadIdx.x == 0) *out = a;
 }
 extern "C" int mla_ce_fwd_bwd(const float* logits, const int64_t* labels, float* loss, float* dlogits, float* ws, int B, int C,
@@ -155,18 +147,7 @@ __global__ __launch_bounds__(256) void head_dx_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(256) void head_dw_kernel(const float* __restrict__ X, const float* __restrict__ dlogits,
                                                        float* __restrict__ dW, float* __restrict__ db, int B, int D, int C,
                                                        float scale) {
-  const int c = blockIdx.y, d = blockIdx.x * 256 + threadIdx.x;
-  if (d < D) {
-    float a = 0.f;
-    for (int r = 0; r < B; ++r) a += dlogits[(size_t)r * C + c] * X[(size_t)r * D + d];
-    dW[(size_t)c * D + d] = a * scale;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < 64) {
-    float a = 0.f;
-    for (int r = threadIdx.x; r < B; r += 64) a += dlogits[(size_t)r * C + c];
-    a = wave_sum(a);
-    if (threadIdx.x == 0) db[c] = a * scale;
-  }
+  head_dw_block(X, dlogits, nullptr, dW, db, nullptr, B, D, C, scale, false);
 }
 extern "C" int mla_head_bwd(const float* X, const float* W, const float* dlogits, float* dW, float* db, float* dX, int B, int D,
                             int C, float scale, void* stream) {
@@ -289,7 +270,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     reinterpret_cast<f32x4*>(buf)[i] = b;
     reinterpret_cast<f32x4*>(p)[i] = pv - b * lr;
   }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {     // sgd_elem's expression (head_common.h), with g == nullptr as a zero gradient
     const size_t i = (n4 << 2) + threadIdx.x;
     const float pv = p[i];
     const float d = (g ? g[i] : 0.f) + wd * pv;
@@ -327,9 +308,7 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const float* __restric
   if (row >= B) return;
   const float* x = X + (size_t)row * D;
   for (int c = 0; c < C; ++c) {
-    float s = 0.f;
-    for (int d = lane; d < D; d += 64) s += x[d] * W[(size_t)c * D + d];
-    s = wave_sum(s);
+    const float s = head_row_dot(x, W + (size_t)c * D, D, lane);
     if (lane == 0) logits[(size_t)row * C + c] = s + bias[c];
   }
 }
@@ -341,10 +320,9 @@ extern "C" int mla_head_logits(const float* X, const float* W, const float* b, f
   return MLA_OK;
 }
 
-#define EVAL_MAXM 3
 struct EvalFuseArgs {
-  const float* out[EVAL_MAXM];   // logits per modality (B, C)
-  float alpha[EVAL_MAXM];        // fixed fusion weights (used when dynamic == 0)
+  const float* out[MLA_HEAD_MAXM];   // logits per modality (B, C)
+  float alpha[MLA_HEAD_MAXM];        // fixed fusion weights (used when dynamic == 0)
   int M, B, C, dynamic;
 };
 
@@ -352,8 +330,8 @@ struct EvalFuseArgs {
 // [C*(1+k) .. C*(2+k)) correct per class.  weights_out[M]: the fusion weights used for this batch.
 __global__ __launch_bounds__(256) void eval_fuse_kernel(const EvalFuseArgs a, const int64_t* __restrict__ labels,
                                                          int* __restrict__ counts, float* __restrict__ weights_out) {
-  __shared__ float ent[EVAL_MAXM];
-  __shared__ float wgt[EVAL_MAXM];
+  __shared__ float ent[MLA_HEAD_MAXM];
+  __shared__ float wgt[MLA_HEAD_MAXM];
   __shared__ float colpart[256];
   const int tid = threadIdx.x;
   if (a.dynamic) {

@@ -12,14 +12,13 @@
 // flat gradient buffer: a deterministic two-level fp64 reduction for the per-tensor statistics, then scale (+ noise) with a
 // counter-based generator (Philox4x32-10 + Box-Muller: element i of the buffer always draws from counter i / 4, so the
 // noise does not depend on the launch geometry).
-#include "common.h"
+#include "head_common.h"
 #include "philox.h"
 
 namespace {
 
-#define OGM_MAXM 3
 struct OgmArgs {
-  const float* out[OGM_MAXM];
+  const float* out[MLA_HEAD_MAXM];
   int M, B, C;
   float alpha;
 };
@@ -27,7 +26,7 @@ struct OgmArgs {
 // one workgroup; thread m < M accumulates score_m over the rows IN ROW ORDER (the reference's python sum())
 __global__ __launch_bounds__(64) void ogm_coeff_kernel(const OgmArgs a, const int64_t* __restrict__ labels, float* __restrict__ coeff,
                                                         float* __restrict__ info) {
-  __shared__ float score[OGM_MAXM];
+  __shared__ float score[MLA_HEAD_MAXM];
   const int m = threadIdx.x;
   if (m < a.M) {
     float s = 0.f;
@@ -44,7 +43,7 @@ __global__ __launch_bounds__(64) void ogm_coeff_kernel(const OgmArgs a, const in
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    float ratio[OGM_MAXM], cf[OGM_MAXM] = {1.f, 1.f, 1.f};
+    float ratio[MLA_HEAD_MAXM], cf[MLA_HEAD_MAXM] = {1.f, 1.f, 1.f};
     if (a.M == 2) {                                          // index 0 = audio, 1 = visual (main.py:376-384)
       ratio[1] = score[1] / score[0];
       ratio[0] = 1.f / ratio[1];
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(64) void ogm_coeff_kernel(const OgmArgs a, const in
       coeff[m2] = cf[m2];
       if (info) {
         info[m2] = score[m2];
-        info[OGM_MAXM + m2] = ratio[m2];
+        info[MLA_HEAD_MAXM + m2] = ratio[m2];
       }
     }
   }

@@ -5,33 +5,20 @@
 //
 // Latency-bound (64 x 512 x 6): four launches for the training call, one for the forward.  Wave-per-class dot products with 64-lane
 // shuffle reductions, no atomics, one writer per History entry, every sum in a fixed order (bitwise reproducible from run to run).
-#include "common.h"
+#include "head_common.h"
 
-#define QH_MAXC 128
-#define QH_MAXM 3
 #define QH_CHUNKS 256         // lo / hi partials per modality (one per thread of the kernel that finishes the reduction)
 
 namespace {
 
 struct QmfPtrs {
-  const float* x[QH_MAXM];    // (B, D) features of modality m
-  const float* W[QH_MAXM];    // (C, D) head weight
-  const float* b[QH_MAXM];    // (C) head bias
-  float* dW[QH_MAXM];
-  float* db[QH_MAXM];
-  float* dx[QH_MAXM];         // (B, D) feature gradients
+  const float* x[MLA_HEAD_MAXM];   // (B, D) features of modality m
+  const float* W[MLA_HEAD_MAXM];   // (C, D) head weight
+  const float* b[MLA_HEAD_MAXM];   // (C) head bias
+  float* dW[MLA_HEAD_MAXM];
+  float* db[MLA_HEAD_MAXM];
+  float* dx[MLA_HEAD_MAXM];        // (B, D) feature gradients
 };
-
-__device__ __forceinline__ double wave_min_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // (a) One workgroup (4 waves) per sample.  Wave w forms z_m[c] for c = w, w + 4, ... of every modality; wave m then forms E_m, c_m
 // and (TRAIN) softmax p_m and the per-sample CE l_m, and makes the History write when this sample is the LAST of the batch that
@@ -46,18 +33,16 @@ __global__ __launch_bounds__(256) void qmf_head_fwd_kernel(const QmfPtrs p, cons
                                                             float* __restrict__ ell, float* __restrict__ prob,
                                                             float* __restrict__ dfused, float* __restrict__ rowcml, int M, int B,
                                                             int D, int C, float inv_batch) {
-  __shared__ float zl[QH_MAXM][QH_MAXC];
-  __shared__ float ol[QH_MAXC];
-  __shared__ float cl[QH_MAXM];
+  __shared__ float zl[MLA_HEAD_MAXM][MLA_HEAD_MAXC];
+  __shared__ float ol[MLA_HEAD_MAXC];
+  __shared__ float cl[MLA_HEAD_MAXM];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x;
   for (int m = 0; m < M; ++m) {
     const float* x = p.x[m] + (size_t)row * D;
     for (int c = wave; c < C; c += 4) {
       const float* w = p.W[m] + (size_t)c * D;
-      float s = 0.f;
-      for (int d = lane; d < D; d += 64) s += x[d] * w[d];
-      s = wave_sum(s) + p.b[m][c];
+      const float s = head_row_dot(x, w, D, lane) + p.b[m][c];
       if (lane == 0) {
         z[((size_t)m * B + row) * C + c] = s;
         zl[m][c] = s;
@@ -76,6 +61,8 @@ __global__ __launch_bounds__(256) void qmf_head_fwd_kernel(const QmfPtrs p, cons
   }
   if (wave < M) {
     const int m = wave;
+    // head_softmax2's expressions, written out: through the helper the LDS address of zl[m][.] is formed another way and the
+    // kernel's instruction stream changes
     const float l0 = lane < C ? zl[m][lane] : -INFINITY;
     const float l1 = lane + 64 < C ? zl[m][lane + 64] : -INFINITY;
     const float mx = wave_max(fmaxf(l0, l1));
@@ -114,14 +101,10 @@ __global__ __launch_bounds__(256) void qmf_head_fwd_kernel(const QmfPtrs p, cons
   if (!TRAIN) return;
   __syncthreads();
   if (wave == 0) {
-    const float l0 = lane < C ? ol[lane] : -INFINITY;
-    const float l1 = lane + 64 < C ? ol[lane + 64] : -INFINITY;
-    const float mx = wave_max(fmaxf(l0, l1));
-    const float e0 = lane < C ? expf(l0 - mx) : 0.f, e1 = lane + 64 < C ? expf(l1 - mx) : 0.f;
-    const float s = wave_sum(e0 + e1);
-    if (lane == 0) rowcml[row] = ok ? (mx + logf(s) - ol[lab]) * inv_batch : NAN;
-    if (lane < C) dfused[(size_t)row * C + lane] = ok ? (e0 / s - (lane == lab ? 1.f : 0.f)) * inv_batch : 0.f;
-    if (lane + 64 < C) dfused[(size_t)row * C + lane + 64] = ok ? (e1 / s - (lane + 64 == lab ? 1.f : 0.f)) * inv_batch : 0.f;
+    const Softmax2 q = head_softmax2(ol, C, lane);
+    if (lane == 0) rowcml[row] = ok ? (q.lse - ol[lab]) * inv_batch : NAN;
+    if (lane < C) dfused[(size_t)row * C + lane] = ok ? head_ce_grad(q.e0, q.s, lane == lab, inv_batch) : 0.f;
+    if (lane + 64 < C) dfused[(size_t)row * C + lane + 64] = ok ? head_ce_grad(q.e1, q.s, lane + 64 == lab, inv_batch) : 0.f;
   }
 }
 
@@ -165,9 +148,9 @@ __global__ __launch_bounds__(256) void qmf_head_rank_kernel(const QmfPtrs p, con
                                                              float* __restrict__ target, float* __restrict__ margin,
                                                              float* __restrict__ rowrank, int M, int B, int D, int C, float w_cml,
                                                              float w_crl, float inv_batch) {
-  __shared__ double slo[QH_MAXM][4], shi[QH_MAXM][4];
-  __shared__ float ta[QH_MAXM][2];                      // t * a of the pairs (i, i + 1) and (i - 1, i)
-  __shared__ float dzl[QH_MAXM][QH_MAXC];
+  __shared__ double slo[MLA_HEAD_MAXM][4], shi[MLA_HEAD_MAXM][4];
+  __shared__ float ta[MLA_HEAD_MAXM][2];                // t * a of the pairs (i, i + 1) and (i - 1, i)
+  __shared__ float dzl[MLA_HEAD_MAXM][MLA_HEAD_MAXC];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x;
   for (int m = 0; m < M; ++m) {
@@ -253,9 +236,7 @@ __global__ __launch_bounds__(256) void qmf_head_dw_kernel(const QmfPtrs p, const
     p.dW[m][(size_t)c * D + d] = a;
   }
   if (blockIdx.x == m * per && threadIdx.x < 64) {
-    float a = 0.f;
-    for (int r = threadIdx.x; r < B; r += 64) a += g[(size_t)r * C];
-    a = wave_sum(a);
+    const float a = head_col_sum(g, B, C, 0, threadIdx.x);
     if (threadIdx.x == 0) p.db[m][c] = a;
     if (blockIdx.x == 0 && c == 0) {
       float clf = 0.f, crl = 0.f;
@@ -274,9 +255,7 @@ __global__ __launch_bounds__(256) void qmf_head_dw_kernel(const QmfPtrs p, const
           losses[1 + M + k] = rk;
         }
       }
-      float cml = 0.f;
-      for (int r = threadIdx.x; r < B; r += 64) cml += rowcml[r];
-      cml = wave_sum(cml);
+      const float cml = head_col_sum(rowcml, B, 1, 0, threadIdx.x);
       if (threadIdx.x == 0) {
         losses[1 + 2 * M] = cml;
         losses[0] = w_cml * cml + clf + w_crl * crl;
@@ -288,7 +267,7 @@ __global__ __launch_bounds__(256) void qmf_head_dw_kernel(const QmfPtrs p, const
 QmfPtrs make_ptrs(const float* const* x, const float* const* W, const float* const* b, float* const* dW, float* const* db,
                   float* const* dx, int M) {
   QmfPtrs p;
-  for (int m = 0; m < QH_MAXM; ++m) {
+  for (int m = 0; m < MLA_HEAD_MAXM; ++m) {
     const bool on = m < M;
     p.x[m] = on ? x[m] : nullptr;
     p.W[m] = on ? W[m] : nullptr;
@@ -313,7 +292,7 @@ int lohi_chunks(int n_data) { return n_data < QH_CHUNKS * 256 ? cdiv(n_data, 256
 // floats: the fp64 lo / hi partials first (the workspace is 8-byte aligned), then prob, dz (M B C each), dfused (B C), rowcml (B),
 // rowrank (M B)
 extern "C" size_t mla_qmf_head_ws_elems(int B, int C, int M) {
-  return (size_t)4 * QH_MAXM * QH_CHUNKS + (size_t)2 * M * B * C + (size_t)B * C + (size_t)B + (size_t)M * B;
+  return (size_t)4 * MLA_HEAD_MAXM * QH_CHUNKS + (size_t)2 * M * B * C + (size_t)B * C + (size_t)B + (size_t)M * B;
 }
 
 extern "C" int mla_qmf_head_fwd_bwd(const float* x0, const float* x1, const float* x2, const float* W0, const float* W1,
@@ -329,13 +308,13 @@ extern "C" int mla_qmf_head_fwd_bwd(const float* x0, const float* x1, const floa
                   all_set((const void* const*)dW, M) && all_set((const void* const*)db, M) && all_set((const void* const*)dx, M) &&
                   labels && idx && correctness && confidence && z && out && conf && ell && target && margin && losses && ws,
               "mla_qmf_head_fwd_bwd: null pointer");
-  MLA_REQUIRE(B > 0 && D > 0 && C > 0 && C <= QH_MAXC && n_data > 0,
-              "mla_qmf_head_fwd_bwd: need B, D, n_data > 0 and 0 < C <= %d (got B %d D %d C %d n_data %d)", QH_MAXC, B, D, C, n_data);
+  MLA_REQUIRE(B > 0 && D > 0 && C > 0 && C <= MLA_HEAD_MAXC && n_data > 0,
+              "mla_qmf_head_fwd_bwd: need B, D, n_data > 0 and 0 < C <= %d (got B %d D %d C %d n_data %d)", MLA_HEAD_MAXC, B, D, C, n_data);
   MLA_REQUIRE(((uintptr_t)ws & 7) == 0, "mla_qmf_head_fwd_bwd: the workspace must be 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const QmfPtrs p = make_ptrs(x, W, b, dW, db, dx, M);
   double* part = (double*)ws;
-  float* prob = ws + (size_t)4 * QH_MAXM * QH_CHUNKS;
+  float* prob = ws + (size_t)4 * MLA_HEAD_MAXM * QH_CHUNKS;
   float* dz = prob + (size_t)M * B * C;
   float* dfused = dz + (size_t)M * B * C;
   float* rowcml = dfused + (size_t)B * C;
@@ -363,7 +342,7 @@ extern "C" int mla_qmf_head_fwd(const float* x0, const float* x1, const float* x
   MLA_REQUIRE(all_set((const void* const*)x, M) && all_set((const void* const*)W, M) && all_set((const void* const*)b, M) && z && out &&
                   conf,
               "mla_qmf_head_fwd: null pointer");
-  MLA_REQUIRE(B > 0 && D > 0 && C > 0 && C <= QH_MAXC, "mla_qmf_head_fwd: need B, D > 0 and 0 < C <= %d (got %d)", QH_MAXC, C);
+  MLA_REQUIRE(B > 0 && D > 0 && C > 0 && C <= MLA_HEAD_MAXC, "mla_qmf_head_fwd: need B, D > 0 and 0 < C <= %d (got %d)", MLA_HEAD_MAXC, C);
   const QmfPtrs p = make_ptrs(x, W, b, nullptr, nullptr, nullptr, M);
   qmf_head_fwd_kernel<false><<<B, 256, 0, (hipStream_t)stream>>>(p, nullptr, nullptr, nullptr, nullptr, 0, z, out, conf, nullptr,
                                                                  nullptr, nullptr, nullptr, M, B, D, C, 0.f);
