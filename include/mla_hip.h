@@ -503,6 +503,30 @@ int mla_image_check(const int64_t* desc_host, int N, int B, int T, size_t frames
 int mla_image_resample(const uint8_t* frames, size_t frames_bytes, const int64_t* desc, const int64_t* desc_host,
                        const float* lut, float* out, int N, int B, int T, int out_h, int out_w, int filter, void* stream);
 
+/* ---- M3AE / Food-101 train image transform (dataset/dataset.py:401-412: timm create_transform, color_jitter=True) ----
+ * RandomResizedCropAndInterpolation(BICUBIC) -> RandomHorizontalFlip -> torchvision ColorJitter(1, 1, 1) -> ToTensor +
+ * Normalize of N images -> out fp32 (N, 3, 1, out_h, out_w).  frames / desc / lut as for mla_image_resample (filter = bicubic,
+ * T = 1).  jit int64 (N, 7) per image: n_ops, op0, op1, op2, brightness bits, contrast bits, saturation bits.  The first
+ * n_ops (0..3) operation ids (0 = brightness, 1 = contrast, 2 = saturation, each at most once; further slots are ignored) are
+ * applied in that order to the flipped uint8 image, each as Pillow's ImageEnhance = Image.blend(degenerate, image, a):
+ *     per byte, fp32, product and sum rounded separately:  t = (float)d + a * (float)(x - d);
+ *     result = (uint8)t for 0 <= a <= 1, else 0 if t <= 0, 255 if t >= 255, (uint8)t otherwise
+ *     d = 0 (brightness);  d = L = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16 of the pixel (saturation);
+ *     d = m = int(S / n + 0.5), S = the sum of L over the image AS IT IS WHEN CONTRAST IS APPLIED, n = out_h * out_w (contrast)
+ * with a the fp32 whose bit pattern the table holds (finite, >= 0).  Per image the result is bit-identical to PIL crop ->
+ * resize(BICUBIC) -> transpose -> ImageEnhance.Brightness / Contrast / Color in the given order -> lut.
+ * Two launches.  staging (uint8, >= N*out_h*out_w*3 bytes) receives the image before contrast; partials (int64, 8-byte aligned,
+ * >= N * ceil(out_h / band) slots, band = 16 unless the LDS plan halves it as mla_image_check describes; N * out_h always
+ * suffices) the per-band luma sums.  Integer sums only: the result does not depend on the order workgroups run in.
+ * `jit` (device) and `jit_host` (host, the same values) as for desc.  mla_image_augment_check runs the host checks alone (no
+ * GPU): those of mla_image_check, operation ids in range and not repeated, factors finite and >= 0, staging and partials
+ * large enough; mla_image_augment also refuses out, staging and partials that overlap. */
+int mla_image_augment_check(const int64_t* desc_host, const int64_t* jit_host, int N, size_t frames_bytes, int out_h, int out_w,
+                            size_t staging_bytes, size_t partials_count);
+int mla_image_augment(const uint8_t* frames, size_t frames_bytes, const int64_t* desc, const int64_t* desc_host,
+                      const int64_t* jit, const int64_t* jit_host, const float* lut, float* out, uint8_t* staging,
+                      size_t staging_bytes, int64_t* partials, size_t partials_count, int N, int out_h, int out_w, void* stream);
+
 /* ---- CAV-MAE spectrogram augmentation (dataset/dataset.py:281-294, 303-321; --cav_augnois) ----------------------
  * x, out fp32 (B, T, F), distinct buffers.  desc int64 (B, 8) per sample: flags, f0, fw, t0, tw, roll, scale_bits,
  * stream_id; flags bit 0 = masks + noise + roll on (0: the sample is only normalised); scale_bits = the fp32 bit pattern

@@ -22,8 +22,22 @@
 //            computed: the coefficients are those of output indices win_left + xx / win_top + yy of a cw -> full_w /
 //            ch -> full_h resize, so a CenterCrop costs nothing and reads only the source rows its window needs.
 // mla_frames_resample is the instantiation <bilinear, 8-column descriptor> with full = out and a zero window offset.
+//
+// mla_image_augment is the M3AE / Food-101 TRAIN transform (dataset/dataset.py:401-412: timm create_transform with
+// color_jitter=True, i.e. torchvision ColorJitter(1, 1, 1) between the flip and ToTensor).  Brightness, saturation and contrast
+// are Pillow's ImageEnhance: Image.blend(degenerate, image, factor) per byte in fp32 without contraction, truncated (clipped
+// when the factor leaves [0, 1]) to uint8 after EACH operation, applied in a drawn order.  The degenerate image is 0
+// (brightness), the pixel's own luma L = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16 (saturation) or the rounded mean luma m
+// of the whole image as it is when contrast is applied.  Two launches, integer reductions only:
+//   frames_augment_kernel   the bicubic instantiation of the resample body; its epilogue applies the flip and the operations that
+//                           precede contrast, writes the uint8 image to a staging buffer (N, OH, OW, 3) and the int64 luma sum of
+//                           its band into partials[n * bands + band] (one slot per workgroup: no atomics, no grid-order dependence)
+//   frames_jitter_kernel    one pixel per thread: m = (2 S + n) / (2 n) from the image's partials (= int(S / n + 0.5)), contrast and
+//                           the operations after it, LUT, coalesced fp32 stores
 #include <algorithm>
 #include <math.h>
+#include <string.h>
+#include <cmath>
 #include "common.h"
 
 #define FR_THREADS 256
@@ -88,6 +102,57 @@ __device__ __forceinline__ int fr_clip8(int acc) {
   return acc < 0 ? 0 : (acc > 255 ? 255 : acc);
 }
 
+// ---- ColorJitter (mla_image_augment): Pillow's ImageEnhance on one pixel ----------------------------------------------------
+#define FR_JIT_COLS 7              // jitter descriptor: n_ops, op0, op1, op2, brightness / contrast / saturation factor bits
+#define FR_BRIGHTNESS 0            // operation ids: torchvision ColorJitter's fn_id
+#define FR_CONTRAST 1
+#define FR_SATURATION 2
+
+struct FrJitter {
+  int n, op[3];
+  float f[3];                      // f[q] = the factor of op[q]
+};
+
+__device__ __forceinline__ FrJitter fr_jitter_load(const int64_t* __restrict__ j) {
+  FrJitter jt;
+  jt.n = min(max((int)j[0], 0), 3);               // the host checked the table; the clamps only bound a corrupted one
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    jt.op[q] = min(max((int)j[1 + q], 0), 2);
+    jt.f[q] = __uint_as_float((unsigned)j[4 + jt.op[q]]);
+  }
+  return jt;
+}
+
+// index of contrast in the operation list, n when it is absent: operations [0, at) run before the reduction, [at, n) after
+__device__ __forceinline__ int fr_contrast_at(const FrJitter& jt) {
+  int at = jt.n;
+#pragma unroll
+  for (int q = 2; q >= 0; --q)
+    if (q < jt.n && jt.op[q] == FR_CONTRAST) at = q;
+  return at;
+}
+
+__device__ __forceinline__ int fr_luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
+
+// Pillow ImagingBlend on one byte: (uint8)(d + a * (x - d)) in fp32, product and sum rounded separately: contraction is switched
+// off here (hipcc's __fmul_rn / __fadd_rn are plain operators and fuse into v_fma_f32, which changes bytes); clipped when a leaves
+// [0, 1].  For a in [0, 1] t lies between d and x, so the clip is the plain truncation.
+__device__ __forceinline__ int fr_blend(int d, int x, float a) {
+#pragma clang fp contract(off)
+  const float p = a * (float)(x - d);
+  const float t = (float)d + p;
+  return t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)t);
+}
+
+// m: the mean luma (contrast only)
+__device__ __forceinline__ void fr_enhance(int op, float a, int m, int& r, int& g, int& b) {
+  const int d = op == FR_BRIGHTNESS ? 0 : (op == FR_CONTRAST ? m : fr_luma(r, g, b));
+  r = fr_blend(d, r, a);
+  g = fr_blend(d, g, a);
+  b = fr_blend(d, b, a);
+}
+
 struct FramePlan {
   int band, rows_cap, kh, kv;
   size_t lds;
@@ -103,12 +168,12 @@ static inline size_t fr_lds(int OW, int band, int rows_cap, int kh, int kv) {
 
 // DW = descriptor columns: 8 (offset, H, W, top, left, ch, cw, flip; full = out, window at 0) or 12 (+ full_h, full_w, win_top,
 // win_left)
-template <int FILTER, int DW>
-__global__ __launch_bounds__(FR_THREADS) void frames_resample_kernel(const uint8_t* __restrict__ src,
-                                                                      const int64_t* __restrict__ desc,
-                                                                      const float* __restrict__ lut, float* __restrict__ out,
-                                                                      int T, int OH, int OW, int band, int rows_cap, int kh,
-                                                                      int kv) {
+// AUG: the epilogue of mla_image_augment's first launch (jit / staging / partials; lut and out unused) instead of the LUT
+template <int FILTER, int DW, bool AUG>
+__device__ __forceinline__ void fr_body(const uint8_t* __restrict__ src, const int64_t* __restrict__ desc,
+                                        const float* __restrict__ lut, float* __restrict__ out, const int64_t* __restrict__ jit,
+                                        uint8_t* __restrict__ staging, int64_t* __restrict__ partials, int T, int OH, int OW,
+                                        int band, int rows_cap, int kh, int kv) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fr_smem[];
   float* s_lut = reinterpret_cast<float*>(fr_smem);
   int* hk = reinterpret_cast<int*>(fr_smem + fr_al(3 * 256 * 4));
@@ -128,7 +193,8 @@ __global__ __launch_bounds__(FR_THREADS) void frames_resample_kernel(const uint8
   const int full_h = DW == 12 ? (int)d[8] : OH, full_w = DW == 12 ? (int)d[9] : OW;
   const int win_top = DW == 12 ? (int)d[10] : 0, win_left = DW == 12 ? (int)d[11] : 0;
 
-  for (int i = tid; i < 3 * 256; i += FR_THREADS) s_lut[i] = lut[i];
+  if (!AUG)
+    for (int i = tid; i < 3 * 256; i += FR_THREADS) s_lut[i] = lut[i];
   for (int xx = tid; xx < OW; xx += FR_THREADS)
     fr_coeffs<FILTER>(cw, full_w, win_left + xx, &hb[2 * xx], &hb[2 * xx + 1], hk + (size_t)xx * kh);
   for (int yy = tid; yy < nb; yy += FR_THREADS)
@@ -164,7 +230,13 @@ __global__ __launch_bounds__(FR_THREADS) void frames_resample_kernel(const uint8
   // vertical pass, flip, LUT; consecutive threads write consecutive (or, flipped, mirrored) columns of one row
   const int b = n / T, tt = n - b * T;
   const size_t plane = (size_t)OH * OW, cstride = (size_t)T * plane;
-  float* o = out + (size_t)b * 3 * cstride + (size_t)tt * plane;
+  float* o = AUG ? nullptr : out + (size_t)b * 3 * cstride + (size_t)tt * plane;
+  FrJitter jt;
+  int npre = 0, lsum = 0;
+  if (AUG) {
+    jt = fr_jitter_load(jit + (size_t)n * FR_JIT_COLS);
+    npre = fr_contrast_at(jt);
+  }
   for (int i = tid; i < nb * OW; i += FR_THREADS) {
     const int yy = i / OW, xx = i - yy * OW;
     const int ymin = vb[2 * yy] - r0, ymax = vb[2 * yy + 1];
@@ -178,10 +250,82 @@ __global__ __launch_bounds__(FR_THREADS) void frames_resample_kernel(const uint8
       a2 += (int)p[2] * w;
     }
     const size_t po = (size_t)(y0 + yy) * OW + (flip ? OW - 1 - xx : xx);
-    o[po] = s_lut[fr_clip8(a0)];
-    o[cstride + po] = s_lut[256 + fr_clip8(a1)];
-    o[2 * cstride + po] = s_lut[512 + fr_clip8(a2)];
+    if (AUG) {
+      int r = fr_clip8(a0), g = fr_clip8(a1), bl = fr_clip8(a2);
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+        if (q < npre) fr_enhance(jt.op[q], jt.f[q], 0, r, g, bl);
+      lsum += fr_luma(r, g, bl);
+      uint8_t* s = staging + ((size_t)n * plane + po) * 3;
+      s[0] = (uint8_t)r;
+      s[1] = (uint8_t)g;
+      s[2] = (uint8_t)bl;
+    } else {
+      o[po] = s_lut[fr_clip8(a0)];
+      o[cstride + po] = s_lut[256 + fr_clip8(a1)];
+      o[2 * cstride + po] = s_lut[512 + fr_clip8(a2)];
+    }
   }
+  if (AUG) {
+    // luma sum of the band: a thread holds at most band * OW / 256 <= 256 pixels of <= 255, a workgroup < 2^24; hk is free since
+    // the horizontal pass (the barrier above) and holds at least 5 ints
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) lsum += __shfl_xor(lsum, o2, 64);
+    if ((tid & 63) == 0) hk[tid >> 6] = lsum;
+    __syncthreads();
+    if (tid == 0) {
+      int64_t sum = 0;
+      for (int w = 0; w < FR_THREADS / 64; ++w) sum += hk[w];
+      partials[(size_t)n * gridDim.x + blockIdx.x] = sum;
+    }
+  }
+}
+
+template <int FILTER, int DW>
+__global__ __launch_bounds__(FR_THREADS) void frames_resample_kernel(const uint8_t* __restrict__ src,
+                                                                      const int64_t* __restrict__ desc,
+                                                                      const float* __restrict__ lut, float* __restrict__ out,
+                                                                      int T, int OH, int OW, int band, int rows_cap, int kh,
+                                                                      int kv) {
+  fr_body<FILTER, DW, false>(src, desc, lut, out, nullptr, nullptr, nullptr, T, OH, OW, band, rows_cap, kh, kv);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void frames_augment_kernel(const uint8_t* __restrict__ src,
+                                                                     const int64_t* __restrict__ desc,
+                                                                     const int64_t* __restrict__ jit, uint8_t* __restrict__ staging,
+                                                                     int64_t* __restrict__ partials, int OH, int OW, int band,
+                                                                     int rows_cap, int kh, int kv) {
+  fr_body<FR_BICUBIC, 12, true>(src, desc, nullptr, nullptr, jit, staging, partials, 1, OH, OW, band, rows_cap, kh, kv);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void frames_jitter_kernel(const uint8_t* __restrict__ staging,
+                                                                    const int64_t* __restrict__ partials,
+                                                                    const int64_t* __restrict__ jit, const float* __restrict__ lut,
+                                                                    float* __restrict__ out, int OH, int OW, int bands) {
+  __shared__ float s_lut[3 * 256];
+  const int tid = threadIdx.x, n = blockIdx.y;
+  for (int i = tid; i < 3 * 256; i += FR_THREADS) s_lut[i] = lut[i];
+  __syncthreads();
+  const FrJitter jt = fr_jitter_load(jit + (size_t)n * FR_JIT_COLS);
+  const int at = fr_contrast_at(jt);
+  const int64_t npix = (int64_t)OH * OW;
+  int m = 0;
+  if (at < jt.n) {               // uniform per workgroup: scalar loads
+    int64_t S = 0;
+    for (int i = 0; i < bands; ++i) S += partials[(size_t)n * bands + i];
+    m = (int)((2 * S + npix) / (2 * npix));
+  }
+  const int64_t p = (int64_t)blockIdx.x * FR_THREADS + tid;
+  if (p >= npix) return;
+  const uint8_t* s = staging + ((size_t)n * npix + p) * 3;
+  int r = s[0], g = s[1], b = s[2];
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+    if (q >= at && q < jt.n) fr_enhance(jt.op[q], jt.f[q], m, r, g, b);
+  float* o = out + (size_t)n * 3 * npix + p;
+  o[0] = s_lut[r];
+  o[npix] = s_lut[256 + g];
+  o[2 * npix] = s_lut[512 + b];
 }
 
 // Host checks of one launch + the LDS plan.  Every descriptor is read from host memory: offset, H, W, crop top, crop left,
@@ -285,5 +429,79 @@ extern "C" int mla_image_resample(const uint8_t* frames, size_t frames_bytes, co
   if (filter == FR_BICUBIC) fr_launch<FR_BICUBIC, 12>(plan, frames, desc, lut, out, N, T, out_h, out_w, stream);
   else fr_launch<FR_BILINEAR, 12>(plan, frames, desc, lut, out, N, T, out_h, out_w, stream);
   MLA_CHECK_LAUNCH("mla_image_resample");
+  return MLA_OK;
+}
+
+// Host checks of the jitter table: int64 (N, 7) rows (n_ops, op0, op1, op2, brightness bits, contrast bits, saturation bits)
+static int fr_jitter_check(const int64_t* jit_host, int N) {
+  MLA_REQUIRE(jit_host, "mla_image_augment: null jitter table");
+  for (int n = 0; n < N; ++n) {
+    const int64_t* j = jit_host + (size_t)n * FR_JIT_COLS;
+    MLA_REQUIRE(j[0] >= 0 && j[0] <= 3, "mla_image_augment: image %d: %lld operations (0..3)", n, (long long)j[0]);
+    unsigned seen = 0;
+    for (int q = 0; q < (int)j[0]; ++q) {
+      const int64_t op = j[1 + q];
+      MLA_REQUIRE(op >= 0 && op <= 2, "mla_image_augment: image %d: unknown operation id %lld (0 = brightness, 1 = contrast, 2 = saturation)",
+                  n, (long long)op);
+      MLA_REQUIRE(!(seen & (1u << op)), "mla_image_augment: image %d: operation %lld is repeated", n, (long long)op);
+      seen |= 1u << op;
+    }
+    for (int q = 0; q < 3; ++q) {
+      const int64_t bits = j[4 + q];
+      MLA_REQUIRE(bits >= 0 && bits <= 0xFFFFFFFFll, "mla_image_augment: image %d: factor %d is not an fp32 bit pattern", n, q);
+      const uint32_t u = (uint32_t)bits;
+      float a;
+      memcpy(&a, &u, sizeof a);
+      MLA_REQUIRE(std::isfinite(a) && a >= 0.f, "mla_image_augment: image %d: factor %d is %g (must be finite and >= 0)", n, q, (double)a);
+    }
+  }
+  return MLA_OK;
+}
+
+static int fr_augment_plan(const int64_t* desc_host, const int64_t* jit_host, int N, size_t frames_bytes, int OH, int OW,
+                           size_t staging_bytes, size_t partials_count, FramePlan* plan) {
+  int rc = fr_plan("mla_image_augment", desc_host, 12, FR_BICUBIC, N, N, 1, frames_bytes, OH, OW, plan);
+  if (rc != MLA_OK) return rc;
+  rc = fr_jitter_check(jit_host, N);
+  if (rc != MLA_OK) return rc;
+  const size_t need_s = (size_t)N * OH * OW * 3, need_p = (size_t)N * cdiv(OH, plan->band);
+  MLA_REQUIRE(staging_bytes >= need_s, "mla_image_augment: staging buffer of %zu bytes, %zu needed (N * out_h * out_w * 3)", staging_bytes,
+              need_s);
+  MLA_REQUIRE(partials_count >= need_p, "mla_image_augment: partials buffer of %zu int64 slots, %zu needed (N * bands of %d rows)",
+              partials_count, need_p, plan->band);
+  return MLA_OK;
+}
+
+extern "C" int mla_image_augment_check(const int64_t* desc_host, const int64_t* jit_host, int N, size_t frames_bytes, int out_h,
+                                       int out_w, size_t staging_bytes, size_t partials_count) {
+  FramePlan plan;
+  return fr_augment_plan(desc_host, jit_host, N, frames_bytes, out_h, out_w, staging_bytes, partials_count, &plan);
+}
+
+static inline bool fr_disjoint(const void* a, size_t an, const void* b, size_t bn) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x + an <= y || y + bn <= x;
+}
+
+extern "C" int mla_image_augment(const uint8_t* frames, size_t frames_bytes, const int64_t* desc, const int64_t* desc_host,
+                                 const int64_t* jit, const int64_t* jit_host, const float* lut, float* out, uint8_t* staging,
+                                 size_t staging_bytes, int64_t* partials, size_t partials_count, int N, int out_h, int out_w,
+                                 void* stream) {
+  MLA_REQUIRE(frames && desc && jit && lut && out && staging && partials, "mla_image_augment: null pointer");
+  FramePlan plan;
+  const int rc = fr_augment_plan(desc_host, jit_host, N, frames_bytes, out_h, out_w, staging_bytes, partials_count, &plan);
+  if (rc != MLA_OK) return rc;
+  const size_t out_bytes = (size_t)N * 3 * out_h * out_w * sizeof(float), part_bytes = partials_count * sizeof(int64_t);
+  MLA_REQUIRE(fr_disjoint(out, out_bytes, staging, staging_bytes) && fr_disjoint(out, out_bytes, partials, part_bytes) &&
+                  fr_disjoint(staging, staging_bytes, partials, part_bytes),
+              "mla_image_augment: out, staging and partials overlap");
+  MLA_REQUIRE((uintptr_t)partials % 8 == 0, "mla_image_augment: partials must be 8-byte aligned");
+  const int bands = cdiv(out_h, plan.band);
+  hipLaunchKernelGGL(frames_augment_kernel, dim3((unsigned)bands, (unsigned)N), dim3(FR_THREADS), plan.lds, (hipStream_t)stream, frames,
+                     desc, jit, staging, partials, out_h, out_w, plan.band, plan.rows_cap, plan.kh, plan.kv);
+  MLA_CHECK_LAUNCH("mla_image_augment (resample)");
+  hipLaunchKernelGGL(frames_jitter_kernel, dim3((unsigned)cdiv((long)out_h * out_w, FR_THREADS), (unsigned)N), dim3(FR_THREADS), 0,
+                     (hipStream_t)stream, staging, partials, jit, lut, out, out_h, out_w, bands);
+  MLA_CHECK_LAUNCH("mla_image_augment (jitter)");
   return MLA_OK;
 }

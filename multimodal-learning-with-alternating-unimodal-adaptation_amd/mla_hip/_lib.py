@@ -143,6 +143,8 @@ PROTOTYPES = {
     "mla_frames_resample": (_I, [_P, _Z, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "mla_image_check": (_I, [_P, _I, _I, _I, _Z, _I, _I, _I]),
     "mla_image_resample": (_I, [_P, _Z, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "mla_image_augment_check": (_I, [_P, _P, _I, _Z, _I, _I, _Z, _Z]),
+    "mla_image_augment": (_I, [_P, _Z, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _Z, _I, _I, _I, _P]),
     "mla_fbank_check": (_I, [_P, _I, _I, _I]),
     "mla_fbank_augment": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, ctypes.c_uint64, _P]),
 }

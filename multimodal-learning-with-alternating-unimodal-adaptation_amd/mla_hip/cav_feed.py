@@ -21,7 +21,7 @@ reference draws from per-worker global numpy / torch streams, so its own sequenc
 the order of the draws are what is matched.)
 
 The same image transform at size 256 is the M3AE / Food-101 EVAL transform (dataset.py:413-420); the M3AE train transform
-(timm create_transform with color jitter) is not built.  CAVDataset returns a 3-tuple without idx; CAVBatcher
+(timm create_transform with color jitter) is `m3ae_feed.M3AEBatcher`.  CAVDataset returns a 3-tuple without idx; CAVBatcher
 yields idx like the other batchers.  The mixup branch of get_image (`filename2`) is never called and not reproduced.
 """
 from __future__ import annotations

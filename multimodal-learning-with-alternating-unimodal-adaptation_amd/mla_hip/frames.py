@@ -22,8 +22,9 @@ DeviceFeeder's `copied()` and `device_step()` hooks: fed through a DeviceFeeder,
 behind the batch's copies and the feeder yields the reference's tuple (spec, image (B, 3, 3, 224, 224) fp32, label, idx).
 
 CAVDataset's feed (bicubic Resize + CenterCrop of the middle frame, fbank SpecAug) and the M3AE / Food-101 eval transform
-(the same at size 256) are in `cav_feed` (CAVBatcher subclasses FrameBatcher: same staging ring, fences and hooks).
-Out of scope: the Food-101 / M3AE timm TRAIN transform (dataset.py:401-412: color jitter) and QMF's masking.
+(the same at size 256) are in `cav_feed` (CAVBatcher subclasses FrameBatcher: same staging ring, fences and hooks); the M3AE /
+Food-101 timm TRAIN transform (dataset.py:401-412: bicubic random crop, flip, color jitter) is in `m3ae_feed` (M3AEBatcher).
+Out of scope: QMF's masking.
 """
 from __future__ import annotations
 
@@ -275,7 +276,17 @@ class FrameBatcher:
         else:
             frames = self.sample_frames(i)
         shapes = [f.shape[:2] for f in frames]
-        return load_fbank(self.audio, self.names[i]), frames, self.sample_boxes(i, shapes)
+        return self._load_side(i), frames, self.sample_boxes(i, shapes)
+
+    # what is loaded beside the frames: the fbank here, the token pair in m3ae_feed.M3AEBatcher
+    def _load_side(self, i: int):
+        return load_fbank(self.audio, self.names[i])
+
+    def _side_staging(self, mk) -> dict:
+        return {"spec": mk((self.B,) + FBANK_SHAPE, torch.float32)}
+
+    def _fill_side(self, st: dict, j: int, side) -> None:
+        np.copyto(st["spec"][j].numpy(), side)
 
     def _descriptors(self, shapes, boxes) -> Tuple[np.ndarray, int]:
         return frame_descriptors(shapes, boxes)
@@ -294,8 +305,9 @@ class FrameBatcher:
         st = self._stage[k]
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=self.pin)
         if st is None:
-            st = {"spec": mk((self.B,) + FBANK_SHAPE, torch.float32), "desc": mk((self.B * self.T, self.DESC_COLS), torch.int64),
+            st = {"desc": mk((self.B * self.T, self.DESC_COLS), torch.int64),
                   "label": mk((self.B,), torch.int64), "idx": mk((self.B, 1), torch.int64), "frames": None}
+            st.update(self._side_staging(mk))
             st.update(self._extra_staging(mk))
             self._stage[k] = st
         if st["frames"] is None or st["frames"].numel() < nbytes:      # grows with the largest batch seen, in MiB steps
@@ -347,8 +359,8 @@ class FrameBatcher:
             buf = st["frames"].numpy()
 
             def fill(j):
-                spec, frames = loaded[j][:2]
-                np.copyto(st["spec"][j].numpy(), spec)
+                side, frames = loaded[j][:2]
+                self._fill_side(st, j, side)
                 for t, f in enumerate(frames):
                     o = int(desc[j * self.T + t, 0])
                     if isinstance(f, _CachedFrame):

@@ -949,6 +949,38 @@ def image_resample(frames: torch.Tensor, desc: torch.Tensor, desc_host: torch.Te
     return out
 
 
+# ---- M3AE / Food-101 train image transform (dataset/dataset.py:401-412) ------------------------------------------------------
+def image_augment_check(desc_host: torch.Tensor, jitter_host: torch.Tensor, frames_bytes: int, out_h: int = 256, out_w: int = 256,
+                        staging_bytes: Optional[int] = None, partials_count: Optional[int] = None) -> None:
+    """The host checks of image_augment alone (no GPU): raises MLAHipError on tables or buffer sizes the kernels must not run with.
+    staging_bytes / partials_count default to the sizes that always suffice (N * out_h * out_w * 3, N * out_h)."""
+    d, j = _table_host(desc_host, 12, "image descriptors"), _table_host(jitter_host, 7, "jitter descriptors")
+    if j.shape[0] != d.shape[0]:
+        raise MLAHipError(f"image_augment: {d.shape[0]} image descriptors but {j.shape[0]} jitter descriptors")
+    N = d.shape[0]
+    _call("mla_image_augment_check", d.data_ptr(), j.data_ptr(), N, frames_bytes, out_h, out_w,
+          N * out_h * out_w * 3 if staging_bytes is None else staging_bytes, N * out_h if partials_count is None else partials_count)
+
+
+def image_augment(frames: torch.Tensor, desc: torch.Tensor, desc_host: torch.Tensor, jitter: torch.Tensor, jitter_host: torch.Tensor,
+                  lut: torch.Tensor, out: torch.Tensor, staging: torch.Tensor, partials: torch.Tensor,
+                  stream: Optional[int] = None) -> torch.Tensor:
+    """frames uint8 (device, packed HWC frames), desc int64 (N, 12) and jitter int64 (N, 7), each on the device and the same table
+    on the host, lut fp32 (3, 256) -> out fp32 (N, 3, 1, out_h, out_w): crop, bicubic resize, flip, ColorJitter, LUT.  staging uint8
+    and partials int64 are device work buffers (see include/mla_hip.h, mla_image_augment)."""
+    d, j = _table_host(desc_host, 12, "image descriptors"), _table_host(jitter_host, 7, "jitter descriptors")
+    if tuple(desc.shape) != tuple(d.shape) or tuple(jitter.shape) != tuple(j.shape) or j.shape[0] != d.shape[0]:
+        raise MLAHipError(f"image_augment: device tables {tuple(desc.shape)}, {tuple(jitter.shape)} and host tables {tuple(d.shape)}, "
+                          f"{tuple(j.shape)} differ")
+    if tuple(lut.shape) != (3, 256) or out.dim() != 5 or tuple(out.shape[:3]) != (d.shape[0], 3, 1):
+        raise MLAHipError(f"image_augment: lut {tuple(lut.shape)} / out {tuple(out.shape)} do not match (3, 256) / ({d.shape[0]}, 3, 1, H, W)")
+    N, _, _, OH, OW = out.shape
+    _call("mla_image_augment", _p(frames, torch.uint8), frames.numel(), _p(desc, torch.int64), d.data_ptr(), _p(jitter, torch.int64),
+          j.data_ptr(), _p(lut), _p(out), _p(staging, torch.uint8), staging.numel(), _p(partials, torch.int64), partials.numel(), N, OH, OW,
+          stream or cur_stream())
+    return out
+
+
 def fbank_check(desc_host: torch.Tensor, T: int = 1024, F: int = 128, std: float = 4.4849) -> None:
     """The host checks of fbank_augment alone (no GPU): raises MLAHipError on a descriptor the kernel must not run, or std == 0."""
     d = _table_host(desc_host, 8, "fbank descriptors")

@@ -436,3 +436,17 @@ def fbank_augment(x, desc, mean, std, seed):
     out = torch.empty_like(x)
     ops.fbank_augment(x, out, desc_host.to(x.device), desc_host, mean, std, seed)
     return out
+
+
+# ---- M3AE / Food-101 train image transform (dataset/dataset.py:401-412) -------------------------------------------------
+@_op("image_augment(Tensor frames, Tensor desc, Tensor jitter, Tensor lut, int out_h=256, int out_w=256) -> Tensor")
+def image_augment(frames, desc, jitter, lut, out_h=256, out_w=256):
+    """Packed uint8 HWC frames (device) + descriptors int64 (N, 12) and jitter descriptors int64 (N, 7) (host; validated there,
+    then copied to the device) -> (N, 3, 1, out_h, out_w) fp32: crop, bicubic resize, flip, ColorJitter, LUT (mla_hip.m3ae_feed)."""
+    desc_host, jit_host = desc.cpu().contiguous(), jitter.cpu().contiguous()
+    N = desc_host.shape[0]
+    out = _f32((N, 3, 1, out_h, out_w), frames)
+    staging = torch.empty(N * out_h * out_w * 3, dtype=torch.uint8, device=frames.device)
+    partials = torch.empty(N * out_h, dtype=torch.int64, device=frames.device)
+    ops.image_augment(frames, desc_host.to(frames.device), desc_host, jit_host.to(frames.device), jit_host, lut, out, staging, partials)
+    return out
