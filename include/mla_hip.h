@@ -542,6 +542,24 @@ int mla_fbank_check(const int64_t* desc_host, int B, int T, int F);
 int mla_fbank_augment(const float* x, float* out, const int64_t* desc, const int64_t* desc_host, int B, int T, int F,
                       float mean, float std, uint64_t seed, void* stream);
 
+/* ---- Modal3Dataset missing-modality masks (dataset/dataset.py:794-801; IEMOCAP, --modal3) -----------------------
+ * The reference multiplies a sample's spectrogram, image, token ids and padding mask by its 0/1 mask entries.  Here the P
+ * images a batch does have are transformed into image_compact fp32 (P, 3, S, S) (P >= 0; may be NULL when P = 0) and one
+ * launch finishes the batch.  mdesc int64 (B, 4) per sample: audio present, image present, text present, image slot (in
+ * [0, P) when the image is present, -1 when not).
+ *     image_out[b] (fp32 (B, 3, S, S)) = image_compact[slot] when the image is present, else zeros;
+ *     spec[b] (fp32 (B, T*F)), token[b] (int64 (B, L)), pm[b] (fp32 (B, L)): overwritten with zeros IN PLACE when their
+ *     modality is absent, otherwise not touched.
+ * Selection, not multiplication: an absent row may hold NaN, Inf or garbage (the batcher does not load it) and comes out as
+ * zeros with every bit clear -- +0.0 where the reference's x * 0 gives -0.0 for negative x; the values are equal.
+ * 3*S*S, T*F and L are multiples of 4 and all five buffers 16-byte aligned (rows move as 16-byte units); image_out overlaps
+ * no input.  `mdesc` (device) and `mdesc_host` (host, the same values) as for the other feed kernels: flags must be 0 or 1,
+ * the slots of the rows with an image a permutation of 0..P-1, and P the number of such rows.
+ * mla_modal3_assemble_check runs the size and table checks alone (no GPU). */
+int mla_modal3_assemble_check(const int64_t* mdesc_host, int B, int P, int S, int TF, int L);
+int mla_modal3_assemble(const float* image_compact, float* spec, int64_t* token, float* pm, const int64_t* mdesc,
+                        const int64_t* mdesc_host, float* image_out, int B, int P, int S, int TF, int L, void* stream);
+
 /* ---- evaluation path (main.py:486-679 `valid`, gs_flag branch) --------------------------------- */
 /* logits = X W^T + b only (main.py:636-639) */
 int mla_head_logits(const float* X, const float* W, const float* b, float* logits, int B, int D, int C, void* stream);

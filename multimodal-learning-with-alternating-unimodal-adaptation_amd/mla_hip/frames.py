@@ -23,7 +23,8 @@ behind the batch's copies and the feeder yields the reference's tuple (spec, ima
 
 CAVDataset's feed (bicubic Resize + CenterCrop of the middle frame, fbank SpecAug) and the M3AE / Food-101 eval transform
 (the same at size 256) are in `cav_feed` (CAVBatcher subclasses FrameBatcher: same staging ring, fences and hooks); the M3AE /
-Food-101 timm TRAIN transform (dataset.py:401-412: bicubic random crop, flip, color jitter) is in `m3ae_feed` (M3AEBatcher).
+Food-101 timm TRAIN transform (dataset.py:401-412: bicubic random crop, flip, color jitter) is in `m3ae_feed` (M3AEBatcher);
+Modal3Dataset's three-modality feed with its missing-modality masks (dataset.py:596-803) is in `modal3_feed` (Modal3Batcher).
 Out of scope: QMF's masking.
 """
 from __future__ import annotations
@@ -311,7 +312,7 @@ class FrameBatcher:
             st.update(self._extra_staging(mk))
             self._stage[k] = st
         if st["frames"] is None or st["frames"].numel() < nbytes:      # grows with the largest batch seen, in MiB steps
-            cap = max(nbytes, (st["frames"].numel() * 5 // 4) if st["frames"] is not None else 0)
+            cap = max(nbytes, 1, (st["frames"].numel() * 5 // 4) if st["frames"] is not None else 0)
             st["frames"] = mk(((cap + (1 << 20) - 1) >> 20) << 20, torch.uint8)
         return st
 
@@ -347,7 +348,8 @@ class FrameBatcher:
         for bi, ids in enumerate(batches):
             b = len(ids)
             loaded = [f.result() for f in pending]
-            shapes = [f.shape[:2] for l in loaded for f in l[1]]
+            first = np.cumsum([0] + [len(l[1]) for l in loaded])        # a sample's first descriptor row: j * T, unless a subclass's
+            shapes = [f.shape[:2] for l in loaded for f in l[1]]          # _load leaves frames out (modal3_feed: a masked-out image)
             boxes = [box for l in loaded for box in l[2]]
             desc, nbytes = self._descriptors(shapes, boxes)
             if self._fence[k] is not None:
@@ -362,13 +364,13 @@ class FrameBatcher:
                 side, frames = loaded[j][:2]
                 self._fill_side(st, j, side)
                 for t, f in enumerate(frames):
-                    o = int(desc[j * self.T + t, 0])
+                    o = int(desc[first[j] + t, 0])
                     if isinstance(f, _CachedFrame):
                         f.copy_to(buf[o:o + f.size])
                     else:
                         np.copyto(buf[o:o + f.size].reshape(f.shape), f)
             list(self._pool.map(fill, range(b)))
-            st["desc"][:b * self.T].numpy()[...] = desc
+            st["desc"][:len(desc)].numpy()[...] = desc
             st["label"][:b] = torch.tensor([self.labels[i] for i in ids], dtype=torch.int64)
             st["idx"][:b, 0] = torch.tensor(ids, dtype=torch.int64)
             self._fill_extra(st, ids, loaded)

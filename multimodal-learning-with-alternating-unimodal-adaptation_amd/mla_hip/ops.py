@@ -1001,3 +1001,33 @@ def fbank_augment(x: torch.Tensor, out: torch.Tensor, desc: torch.Tensor, desc_h
     _call("mla_fbank_augment", _p(x), _p(out), _p(desc, torch.int64), d.data_ptr(), B, T, F, mean, std, int(seed) & 0xFFFFFFFFFFFFFFFF,
           stream or cur_stream())
     return out
+
+
+# ---- Modal3Dataset missing-modality masks (dataset/dataset.py:794-801) --------------------------------------------------------
+def modal3_assemble_check(mask_desc_host: torch.Tensor, P: int, S: int = 256, TF: int = 1024 * 128, L: int = 256) -> None:
+    """The size and table checks of modal3_assemble alone (no GPU): raises MLAHipError on a mask table the kernel must not run."""
+    d = _table_host(mask_desc_host, 4, "mask descriptors")
+    _call("mla_modal3_assemble_check", d.data_ptr(), d.shape[0], P, S, TF, L)
+
+
+def modal3_assemble(image_compact: Optional[torch.Tensor], spec: torch.Tensor, token: torch.Tensor, pm: torch.Tensor,
+                    mask_desc: torch.Tensor, mask_desc_host: torch.Tensor, image_out: torch.Tensor,
+                    stream: Optional[int] = None) -> torch.Tensor:
+    """image_compact fp32 (P, 3, S, S) (None when no sample has an image) -> image_out fp32 (B, 3, S, S): row b is the compact
+    image of its slot, or zeros; spec fp32 (B, ...), token int64 (B, ...) and pm fp32 (B, ...) get the rows of absent modalities
+    zeroed in place.  mask_desc int64 (B, 4) (audio, image, text present, image slot) on the device and the same table on the host
+    (see include/mla_hip.h, mla_modal3_assemble)."""
+    d = _table_host(mask_desc_host, 4, "mask descriptors")
+    B = d.shape[0]
+    P = 0 if image_compact is None else image_compact.shape[0]
+    if tuple(mask_desc.shape) != tuple(d.shape):
+        raise MLAHipError(f"mask descriptors: device table {tuple(mask_desc.shape)} and host table {tuple(d.shape)} differ")
+    if B == 0 or image_out.dim() != 4 or tuple(image_out.shape[:2]) != (B, 3) or image_out.shape[2] != image_out.shape[3] \
+            or (P and image_compact.numel() != P * image_out[0].numel()) or spec.shape[0] != B or token.shape[0] != B \
+            or tuple(pm.shape) != tuple(token.shape):
+        raise MLAHipError(f"modal3_assemble: image_compact {None if image_compact is None else tuple(image_compact.shape)} / spec "
+                          f"{tuple(spec.shape)} / token {tuple(token.shape)} / pm {tuple(pm.shape)} / image_out {tuple(image_out.shape)} do "
+                          f"not match (P, 3, S, S) / (B, ...) / (B, ...) / token's shape / (B, 3, S, S) with B = {B}")
+    _call("mla_modal3_assemble", _p(image_compact) if P else None, _p(spec), _p(token, torch.int64), _p(pm), _p(mask_desc, torch.int64),
+          d.data_ptr(), _p(image_out), B, P, image_out.shape[2], spec[0].numel(), token[0].numel(), stream or cur_stream())
+    return image_out

@@ -450,3 +450,15 @@ def image_augment(frames, desc, jitter, lut, out_h=256, out_w=256):
     partials = torch.empty(N * out_h, dtype=torch.int64, device=frames.device)
     ops.image_augment(frames, desc_host.to(frames.device), desc_host, jit_host.to(frames.device), jit_host, lut, out, staging, partials)
     return out
+
+
+# ---- Modal3Dataset missing-modality masks (dataset/dataset.py:794-801) ---------------------------------------------------
+@_op("modal3_assemble(Tensor image_compact, Tensor(a!) spec, Tensor(b!) token, Tensor(c!) pm, Tensor mask_desc, int size=256) -> Tensor")
+def modal3_assemble(image_compact, spec, token, pm, mask_desc, size=256):
+    """The P transformed images fp32 (P, 3, size, size) (device; P may be 0) + mask descriptors int64 (B, 4) (host; validated
+    there, then copied to the device) -> a new (B, 3, size, size): each sample's image or zeros; spec, token and pm rows of
+    absent modalities are zeroed in place (mla_hip.modal3_feed)."""
+    desc_host = mask_desc.cpu().contiguous()
+    out = _f32((desc_host.shape[0], 3, size, size), spec)
+    ops.modal3_assemble(image_compact if image_compact.shape[0] else None, spec, token, pm, desc_host.to(spec.device), desc_host, out)
+    return out
