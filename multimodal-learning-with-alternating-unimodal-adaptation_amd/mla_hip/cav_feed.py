@@ -27,7 +27,7 @@ yields idx like the other batchers.  The mixup branch of get_image (`filename2`)
 from __future__ import annotations
 
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -35,7 +35,8 @@ import torch
 from . import ops
 from ._lib import MLAHipError
 from .data import FBANK_SHAPE
-from .frames import MEAN, STD, FrameBatcher, decode_frames, decode_jpeg, load_cached_frame, sample_generator
+from .frames import (MEAN, STD, Batcher, ImagePart, Part, Placement, SampleKey, decode_frames, fbank_part, list_frames,
+                     sample_generator, slot_buffer)
 
 NORM_MEAN, NORM_STD = -5.081, 4.4849           # dataset.py:259-260
 FREQM, TIMEM = 48, 192                         # dataset.py:281
@@ -66,12 +67,7 @@ def image_descriptors(shapes: Sequence[Tuple[int, int]], boxes: Sequence[Tuple[i
 
 def pick_middle_frame(visual_path: str) -> str:
     """File name of the frame CAVDataset reads (dataset.py:308-310): os.listdir order, NOT sorted, entry int(n / 2)."""
-    try:
-        allimages = os.listdir(visual_path)
-    except OSError as e:
-        raise MLAHipError(f"{visual_path}: cannot list frames ({e})") from e
-    if not allimages:
-        raise MLAHipError(f"{visual_path}: no frames")
+    allimages = list_frames(visual_path)
     return allimages[int(len(allimages) / 2)]
 
 
@@ -115,72 +111,71 @@ def fbank_descriptors(draws: Sequence[Optional[Tuple[int, int, int, int, float, 
     return desc
 
 
-class CAVBatcher(FrameBatcher):
-    DESC_COLS = 12
+def middle_frame_path(visual: str, name: str, T: int = 1) -> List[str]:
+    """Frame source of CAVDataset and Modal3Dataset for frames.ImagePart: the middle frame of the directory <visual>/<name>."""
+    d = os.path.join(visual, name)
+    return [os.path.join(d, pick_middle_frame(d))]
 
+
+class ResizeCenterCrop:
+    """Transform for frames.ImagePart: the whole frame through Resize(size, BICUBIC) + CenterCrop(size); no flip, no draws."""
+    cols, kernel, filter = 12, "image_resample", BICUBIC
+
+    def __init__(self, size: int):
+        self.size = int(size)
+
+    def place(self, shapes: Sequence[Tuple[int, int]], key: SampleKey) -> List[Placement]:
+        return [Placement((0, 0, H, W, 0), resize_center_crop(H, W, self.size)) for (H, W) in shapes]
+
+    @staticmethod
+    def table(shapes, placed: Sequence[Placement]) -> Tuple[np.ndarray, int]:
+        return image_descriptors(shapes, [p.crop for p in placed], [p.window for p in placed])
+
+
+class FbankDraws(NamedTuple):
+    masks_noise_roll: Optional[Tuple[int, int, int, int, float, int]]      # sample_fbank_aug's result; None: only normalised
+    stream_id: int
+
+
+class SpecAugPart(Part):
+    """CAVDataset's spectrogram transform, listed after frames.fbank_part: a sample's SpecAug draws when `on` (train and
+    --cav_augnois) and its noise stream as "fdesc" (B, 8); the device step replaces the raw "spec" the fbank part left in `out`
+    by mla_fbank_augment's result (which is always normalised) in the slot's own buffer."""
+    tensors = {"fdesc": (1, (8,), torch.int64)}
+
+    def __init__(self, on: bool, norm_mean: float, norm_std: float, seed: int):
+        self.on, self.norm_mean, self.norm_std, self.seed = bool(on), float(norm_mean), float(norm_std), int(seed)
+
+    def load(self, name: str, key: SampleKey) -> FbankDraws:
+        return FbankDraws(sample_fbank_aug(sample_generator(*key), *FBANK_SHAPE) if self.on else None, fbank_stream_id(*key))
+
+    def pack(self, st: dict, recs: Sequence[FbankDraws], b: int, empty) -> dict:
+        st["fdesc"][:b].numpy()[...] = fbank_descriptors([r.masks_noise_roll for r in recs], [r.stream_id for r in recs])
+        return {"fdesc": st["fdesc"][:b]}
+
+    def device(self, host: dict, dev: dict, scratch: dict, out: dict, B: int) -> None:
+        raw = out["spec"]
+        buf = slot_buffer(scratch, "spec", raw.shape[0], B, FBANK_SHAPE, torch.float32, raw.device)
+        out["spec"] = ops.fbank_augment(raw, buf, dev["fdesc"], host["fdesc"], self.norm_mean, self.norm_std, self.seed)
+
+
+class CAVBatcher(Batcher):
     def __init__(self, names: Sequence[str], labels: Sequence[int], batch_size: int, audio_feature_path: str,
                  visual_feature_path: Optional[str] = None, frame_cache: Optional[str] = None, train: bool = True,
                  augnois: bool = False, seed: int = 0, epoch: int = 0, threads: int = 8, ring: int = 4, pin: Optional[bool] = None,
                  drop_last: bool = False, out_size: int = 224, mean: Sequence[float] = MEAN, std: Sequence[float] = STD,
                  norm_mean: float = NORM_MEAN, norm_std: float = NORM_STD):
         """CAVDataset batches from the fbank .npy files and either the JPEG frame directories (`visual_feature_path`) or a
-        decode_middle_frames cache (`frame_cache`), on FrameBatcher's staging ring, `copied()` fence and `device_step()` hook.
+        decode_middle_frames cache (`frame_cache`), on frames.Batcher's loop, staging ring, `copied()` fence and `device_step()` hook.
         Yields host tuples (spec_raw, frames uint8 (capacity,), image_desc int64 (B, 12), fbank_desc int64 (B, 8), label, idx);
         through a DeviceFeeder the device tuple is (spec (B, 1024, 128), image (B, 3, out, out), label, idx), the shapes
         CAVClassifier.forward takes.  The spectrogram is augmented only when `train and augnois` and always normalised; the
         image transform is the same in train and eval.  out_size=256 gives the M3AE / Food-101 eval transform."""
-        super().__init__(names, labels, batch_size, audio_feature_path, visual_feature_path=visual_feature_path,
-                         frame_cache=frame_cache, train=train, seed=seed, epoch=epoch, threads=threads, ring=ring, pin=pin,
-                         drop_last=drop_last, out_size=out_size, pick_num=1, mean=mean, std=std)
+        images = ImagePart(visual_feature_path, frame_cache, middle_frame_path, 1, ResizeCenterCrop(out_size), out_size, mean, std)
         if float(norm_std) == 0.0:
             raise ValueError("norm_std must not be 0")
-        self.augnois, self.norm_mean, self.norm_std = bool(augnois), float(norm_mean), float(norm_std)
-
-    def sample_frames(self, i: int) -> List[np.ndarray]:
-        """[the decoded uint8 (H, W, 3) middle frame of dataset index i], from the JPEGs or the cache."""
-        name = self.names[i]
-        if self.cache is not None:
-            return [load_cached_frame(self.cache, name, 0)]
-        d = os.path.join(self.visual, name)
-        return [decode_jpeg(os.path.join(d, pick_middle_frame(d)))]
-
-    def sample_boxes(self, i: int, shapes: Sequence[Tuple[int, int]]) -> List[tuple]:
-        """(top, left, h, w, flip, full_h, full_w, win_top, win_left) per frame: the whole frame, no flip, no draws."""
-        return [(0, 0, H, W, 0) + resize_center_crop(H, W, self.size) for (H, W) in shapes]
-
-    def sample_fbank(self, i: int) -> Optional[Tuple[int, int, int, int, float, int]]:
-        """The spectrogram draws of dataset index i for the current epoch; None when the sample is only normalised."""
-        if not (self.train and self.augnois):
-            return None
-        return sample_fbank_aug(sample_generator(self.seed, self.epoch, i), *FBANK_SHAPE)
-
-    def _load(self, i: int):
-        return super()._load(i) + (self.sample_fbank(i),)
-
-    def _descriptors(self, shapes, boxes):
-        return image_descriptors(shapes, [b[:5] for b in boxes], [b[5:] for b in boxes])
-
-    def _extra_staging(self, mk) -> dict:
-        return {"fdesc": mk((self.B, 8), torch.int64)}
-
-    def _fill_extra(self, st, ids, loaded) -> None:
-        sids = [fbank_stream_id(self.seed, self.epoch, i) for i in ids]
-        st["fdesc"][:len(ids)].numpy()[...] = fbank_descriptors([l[3] for l in loaded], sids)
-
-    def _host_tuple(self, st, b):
-        return st["spec"][:b], st["frames"], st["desc"][:b], st["fdesc"][:b], st["label"][:b], st["idx"][:b]
-
-    def device_step(self, host: Sequence[torch.Tensor], dev: Sequence[torch.Tensor], scratch: dict) -> tuple:
-        """DeviceFeeder hook, run on its copy stream behind the copies of `dev` (= `host` on the device): both kernels into the
-        slot's buffers; returns (spec, image, label, idx)."""
-        raw, frames, desc, fdesc, label, idx = dev
-        b = label.shape[0]
-        if "image" not in scratch or scratch["image"].shape[0] < b:
-            n = max(b, self.B)
-            scratch["image"] = torch.empty((n, 3, 1, self.size, self.size), dtype=torch.float32, device=raw.device)
-            scratch["spec"] = torch.empty((n,) + FBANK_SHAPE, dtype=torch.float32, device=raw.device)
-        if "lut" not in scratch:
-            scratch["lut"] = self.lut.to(raw.device)
-        img = ops.image_resample(frames, desc, host[2], scratch["lut"], scratch["image"][:b], 1, BICUBIC)
-        spec = ops.fbank_augment(raw, scratch["spec"][:b], fdesc, host[3], self.norm_mean, self.norm_std, self.seed)
-        return spec, img.view(b, 3, self.size, self.size), label, idx
+        self.audio = audio_feature_path
+        parts = [images, fbank_part(audio_feature_path), SpecAugPart(train and augnois, norm_mean, norm_std, seed)]
+        super().__init__(names, labels, batch_size, parts, ("spec", "frames", "desc", "fdesc", "label", "idx"),
+                         ("spec", "image", "label", "idx"), seed=seed, epoch=epoch, threads=threads, ring=ring, pin=pin,
+                         drop_last=drop_last)

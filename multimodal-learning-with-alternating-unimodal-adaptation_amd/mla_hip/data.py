@@ -48,6 +48,56 @@ def load_token(text_feature_path: str, name: str) -> Tuple[np.ndarray, np.ndarra
             _load(os.path.join(text_feature_path, name + "_pm.npy"), TOKEN_SHAPE, np.float32))
 
 
+def batch_ids(n: int, batch_size: int, drop_last: bool) -> List[range]:
+    """The dataset indices of each batch, in order; a short last batch is kept unless `drop_last`."""
+    batches = [range(b0, min(b0 + batch_size, n)) for b0 in range(0, n, batch_size)]
+    return batches[:-1] if drop_last and batches and len(batches[-1]) < batch_size else batches
+
+
+class StagingRing:
+    """A ring of host staging slots that a batcher refills in turn.  A slot is reused only after the H2D copies that read it
+    have COMPLETED: the consumer (DeviceFeeder) hands the event it recorded behind those copies to `copied()`, and the slot's
+    refill synchronizes on it.  ("Issued" is not enough: DeviceFeeder's copy stream waits on device events of earlier steps and
+    MLATrainer never host-syncs, so the host can run many batches ahead of the DMA engine.)  Without a consumer that calls
+    `copied()` -- list(batcher), a plain loop -- nothing is fenced, and nothing needs to be: such a consumer reads a batch before
+    it asks for the next.  What a slot holds (`slots[k]`, None at first) is its batcher's business."""
+
+    def __init__(self, ring: int = 4, pin: Optional[bool] = None):
+        self.pin = torch.cuda.is_available() if pin is None else bool(pin)
+        self.slots: List[Optional[object]] = [None] * max(2, ring)
+        self._fence: List[Optional[object]] = [None] * len(self.slots)
+        self._unfenced: List[int] = []    # slots yielded and not yet fenced, oldest first
+        self._next = 0
+
+    def empty(self, shape, dtype) -> torch.Tensor:
+        return torch.empty(shape, dtype=dtype, pin_memory=self.pin)
+
+    def restart(self) -> None:
+        """A new pass over the data begins at slot 0; fences of the last pass stay."""
+        self._next, self._unfenced = 0, []
+
+    def copied(self, event) -> None:
+        """Consumer hook: `event` (anything with .synchronize(), e.g. torch.cuda.Event) completes when the asynchronous copies
+        out of the OLDEST batch not yet reported have finished.  DeviceFeeder calls it once per batch, in order."""
+        if self._unfenced:
+            self._fence[self._unfenced.pop(0)] = event
+
+    def acquire(self) -> int:
+        """The slot to refill next, once the DMA out of it has run."""
+        k = self._next
+        if self._fence[k] is not None:
+            self._fence[k].synchronize()
+            self._fence[k] = None
+        if k in self._unfenced:                    # consumer without copied(): it has consumed the batch by now
+            self._unfenced.remove(k)
+        return k
+
+    def yielded(self, k: int) -> None:
+        """Slot k goes out to the consumer; the next acquire() takes the slot after it."""
+        self._unfenced.append(k)
+        self._next = (k + 1) % len(self.slots)
+
+
 class NpyBatcher:
     def __init__(self, names: Sequence[str], labels: Sequence[int], batch_size: int, audio_feature_path: Optional[str] = None,
                  text_feature_path: Optional[str] = None, image_fn: Optional[Callable[[str], torch.Tensor]] = None,
@@ -67,55 +117,31 @@ class NpyBatcher:
         self.names, self.labels, self.B = list(names), [int(x) for x in labels], int(batch_size)
         self.audio, self.text, self.image_fn, self.order = audio_feature_path, text_feature_path, image_fn, order
         self.drop_last = drop_last
-        self.pin = torch.cuda.is_available() if pin is None else bool(pin)
-        # A staging tuple is reused only after the H2D copies that read it have COMPLETED: the consumer (DeviceFeeder) hands
-        # the event it recorded behind those copies to `copied()`, and the slot's refill synchronizes on it.  ("Issued" is not
-        # enough: DeviceFeeder's copy stream waits on device events of earlier steps and MLATrainer never host-syncs, so the
-        # host can run many batches ahead of the DMA engine.)  Without a consumer that calls `copied()` -- list(batcher),
-        # a plain loop -- nothing is fenced, and nothing needs to be: such a consumer reads a batch before it asks for the next.
-        self.ring = max(2, ring)
-        self._stage: List[Optional[tuple]] = [None] * self.ring
-        self._fence: List[Optional[object]] = [None] * self.ring
-        self._unfenced: List[int] = []    # staging slots yielded and not yet fenced, oldest first
+        self._ring = StagingRing(ring, pin)
 
     def __len__(self) -> int:
-        n = len(self.names)
-        return n // self.B if self.drop_last else (n + self.B - 1) // self.B
+        return len(batch_ids(len(self.names), self.B, self.drop_last))
 
-    def _staging(self, k: int, b: int, image_shape) -> tuple:
-        st = self._stage[k]
-        if st is None or st[0].shape[0] != b:
-            mk = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=self.pin)
-            parts = {"spec": mk((b,) + FBANK_SHAPE, torch.float32), "token": mk((b,) + TOKEN_SHAPE, torch.int64),
-                     "pm": mk((b,) + TOKEN_SHAPE, torch.float32), "image": mk((b,) + tuple(image_shape), torch.float32),
-                     "label": mk((b,), torch.int64), "idx": mk((b, 1), torch.int64)}
+    def _staging(self, k: int, b: int, image_shape) -> dict:
+        st = self._ring.slots[k]
+        if st is None or st["label"].shape[0] != b:
+            rows = {"spec": (FBANK_SHAPE, torch.float32), "token": (TOKEN_SHAPE, torch.int64), "pm": (TOKEN_SHAPE, torch.float32),
+                    "image": (tuple(image_shape), torch.float32), "label": ((), torch.int64), "idx": ((1,), torch.int64)}
             keys = {"av": ("spec", "image", "label", "idx"), "tv": ("token", "pm", "image", "label", "idx"),
                     "tva": ("token", "pm", "image", "spec", "label", "idx")}[self.order]
-            st = tuple(parts[k_] for k_ in keys) + (keys,)
-            self._stage[k] = st
+            st = self._ring.slots[k] = {f: self._ring.empty((b,) + rows[f][0], rows[f][1]) for f in keys}
         return st
 
     def copied(self, event) -> None:
-        """Consumer hook: `event` (anything with .synchronize(), e.g. torch.cuda.Event) completes when the asynchronous copies
-        out of the OLDEST batch not yet reported have finished.  DeviceFeeder calls it once per batch, in order."""
-        if self._unfenced:
-            self._fence[self._unfenced.pop(0)] = event
+        """DeviceFeeder hook (see StagingRing.copied)."""
+        self._ring.copied(event)
 
     def __iter__(self) -> Iterator[tuple]:
-        k = 0
-        self._unfenced = []
-        for b0 in range(0, len(self.names), self.B):
-            ids = range(b0, min(b0 + self.B, len(self.names)))
-            if self.drop_last and len(ids) < self.B:
-                return
-            if self._fence[k] is not None:             # the DMA out of this staging tuple must have run before it is refilled
-                self._fence[k].synchronize()
-                self._fence[k] = None
-            if k in self._unfenced:                    # consumer without copied(): it has consumed the batch by now
-                self._unfenced.remove(k)
+        self._ring.restart()
+        for ids in batch_ids(len(self.names), self.B, self.drop_last):
+            k = self._ring.acquire()                   # the DMA out of this staging tuple must have run before it is refilled
             first_img = self.image_fn(self.names[ids[0]])
-            *tensors, keys = self._staging(k, len(ids), first_img.shape)
-            out = dict(zip(keys, tensors))
+            out = self._staging(k, len(ids), first_img.shape)
             for j, i in enumerate(ids):
                 name = self.names[i]
                 if "spec" in out:
@@ -130,6 +156,5 @@ class NpyBatcher:
                 out["image"][j].copy_(img)
                 out["label"][j] = self.labels[i]
                 out["idx"][j, 0] = i
-            self._unfenced.append(k)
-            yield tuple(tensors)
-            k = (k + 1) % self.ring
+            self._ring.yielded(k)
+            yield tuple(out.values())

@@ -34,11 +34,9 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import ops
-from .cav_feed import BICUBIC, image_descriptors, resize_center_crop
-from .data import TOKEN_SHAPE, load_token
-from .frames import (MAX_THREADS, MEAN, RATIO, SCALE, STD, FrameBatcher, _cache_path, decode_jpeg, load_cached_frame, sample_crop,
-                     sample_flip, sample_generator)
+from .cav_feed import ResizeCenterCrop
+from .frames import (MAX_THREADS, MEAN, RATIO, SCALE, STD, Batcher, ImagePart, Placement, SampleKey, _cache_path, decode_jpeg,
+                     sample_crop, sample_flip, sample_generator, token_part)
 
 OUT_SIZE = 256                                        # dataset.py:402, 415-416
 BRIGHTNESS, CONTRAST, SATURATION = 0, 1, 2            # operation ids of mla_image_augment = torchvision ColorJitter's fn_id
@@ -65,11 +63,12 @@ def sample_jitter(g: torch.Generator, brightness: float = 1.0, contrast: float =
     return order, tuple(1.0 if f is None else f for f in factors)
 
 
-def jitter_descriptors(jitters: Sequence[Jitter]) -> np.ndarray:
-    """int64 (N, 7) rows (n_ops, op0, op1, op2, brightness bits, contrast bits, saturation bits) from sample_jitter results;
-    unused operation slots hold -1, the bits are the patterns of fp32(factor) (Pillow's blend takes a C float)."""
+def jitter_descriptors(jitters: Sequence[Optional[Jitter]]) -> np.ndarray:
+    """int64 (N, 7) rows (n_ops, op0, op1, op2, brightness bits, contrast bits, saturation bits) from sample_jitter results
+    (None, the image of a transform that draws no jitter, counts as NO_JITTER); unused operation slots hold -1, the bits are the
+    patterns of fp32(factor) (Pillow's blend takes a C float)."""
     desc = np.zeros((len(jitters), JITTER_COLS), dtype=np.int64)
-    for n, (order, factors) in enumerate(jitters):
+    for n, (order, factors) in enumerate(j or NO_JITTER for j in jitters):
         desc[n, 0] = len(order)
         desc[n, 1:4] = tuple(order) + (-1,) * (3 - len(order))
         desc[n, 4:7] = np.asarray(factors, dtype=np.float32).view(np.uint32)
@@ -88,85 +87,53 @@ def decode_images(visual_feature_path: str, out_path: str, names: Sequence[str],
         return sum(pool.map(one, names))
 
 
-class M3AEBatcher(FrameBatcher):
-    DESC_COLS = 12
+def image_path(visual: str, name: str, T: int = 1) -> List[str]:
+    """Frame source of M3AEDataset for frames.ImagePart: the flat file <visual>/<name>.jpg."""
+    return [os.path.join(visual, name + ".jpg")]
 
+
+class TimmTrain:
+    """Transform for frames.ImagePart: timm's train transform on one image.  Crop, flip and jitter draws in the transform's
+    order, the crop resized to size x size (so the CenterCrop window is the whole resize); mla_image_augment."""
+    cols, kernel, table = 12, "image_augment", staticmethod(ResizeCenterCrop.table)
+
+    def __init__(self, size: int, scale: Sequence[float], ratio: Sequence[float], jitter: Sequence[float]):
+        self.size, self.scale, self.ratio, self.jitter = int(size), tuple(scale), tuple(ratio), tuple(jitter)
+
+    def place(self, shapes: Sequence[Tuple[int, int]], key: SampleKey) -> List[Placement]:
+        (H, W), = shapes
+        g = sample_generator(*key)
+        crop = sample_crop(H, W, g, self.scale, self.ratio) + (int(sample_flip(g)),)
+        return [Placement(crop, (self.size, self.size, 0, 0), sample_jitter(g, *self.jitter))]
+
+
+def timm_image_part(visual_feature_path: Optional[str], frame_cache: Optional[str], paths, train: bool, out_size: int, scale, ratio,
+                    color_jitter, mean, std, present=None) -> ImagePart:
+    """The image part of M3AEDataset and Modal3Dataset: TimmTrain when `train`, else Resize(out) + CenterCrop(out); the jitter
+    table is part of the host tuple either way."""
+    cj = tuple(color_jitter) if isinstance(color_jitter, (list, tuple)) else (float(color_jitter),) * 3
+    if len(cj) != 3 or min(cj) < 0:
+        raise ValueError("color_jitter: one non-negative strength, or three (brightness, contrast, saturation)")
+    transform = TimmTrain(out_size, scale, ratio, [float(v) for v in cj]) if train else ResizeCenterCrop(out_size)
+    return ImagePart(visual_feature_path, frame_cache, paths, 1, transform, out_size, mean, std, jitter_table=jitter_descriptors,
+                     present=present)
+
+
+class M3AEBatcher(Batcher):
     def __init__(self, names: Sequence[str], labels: Sequence[int], batch_size: int, text_feature_path: str,
                  visual_feature_path: Optional[str] = None, frame_cache: Optional[str] = None, train: bool = True, seed: int = 0,
                  epoch: int = 0, threads: int = 8, ring: int = 4, out_size: int = OUT_SIZE, scale: Sequence[float] = SCALE,
                  ratio: Sequence[float] = RATIO, color_jitter=1.0, mean: Sequence[float] = MEAN, std: Sequence[float] = STD,
                  drop_last: bool = False, pin: Optional[bool] = None):
         """M3AEDataset batches from the token / padding-mask .npy files and either the JPEG images (`visual_feature_path`) or a
-        decode_images cache (`frame_cache`), on FrameBatcher's staging ring, `copied()` fence and `device_step()` hook.
+        decode_images cache (`frame_cache`), on frames.Batcher's loop, staging ring, `copied()` fence and `device_step()` hook.
         Yields host tuples (token, padding_mask, frames uint8 (capacity,), image_desc int64 (B, 12), jitter_desc int64 (B, 7),
         label, idx); through a DeviceFeeder the device tuple is (token (B, 1, 256) int64, padding_mask (B, 1, 256) fp32,
         image (B, 3, out, out) fp32, label, idx): M3AEDataset.__getitem__'s tuple, what M3AEClassifier / MLATrainer take.
         `color_jitter`: one strength for brightness, contrast and saturation, or three (timm's convention); 0 drops the
         operation.  train=False: Resize(out) + CenterCrop(out), no draws, no jitter."""
-        super().__init__(names, labels, batch_size, text_feature_path, visual_feature_path=visual_feature_path,
-                         frame_cache=frame_cache, train=train, seed=seed, epoch=epoch, threads=threads, ring=ring, pin=pin,
-                         drop_last=drop_last, out_size=out_size, pick_num=1, mean=mean, std=std)
-        cj = tuple(color_jitter) if isinstance(color_jitter, (list, tuple)) else (float(color_jitter),) * 3
-        if len(cj) != 3 or min(cj) < 0:
-            raise ValueError("color_jitter: one non-negative strength, or three (brightness, contrast, saturation)")
-        self.scale, self.ratio, self.jitter = tuple(scale), tuple(ratio), tuple(float(v) for v in cj)
-
-    def sample_frames(self, i: int) -> List[np.ndarray]:
-        """[the decoded uint8 (H, W, 3) image of dataset index i], from <visual>/<name>.jpg or the cache."""
-        name = self.names[i]
-        if self.cache is not None:
-            return [load_cached_frame(self.cache, name, 0)]
-        return [decode_jpeg(os.path.join(self.visual, name + ".jpg"))]
-
-    def sample_boxes(self, i: int, shapes: Sequence[Tuple[int, int]]) -> List[tuple]:
-        """[(top, left, h, w, flip, full_h, full_w, win_top, win_left, jitter)] of dataset index i for the current epoch.
-        train: crop, flip and jitter draws in the transform's order, the crop resized to out x out; eval: the whole image
-        through Resize + CenterCrop, no draws."""
-        (H, W), = shapes
-        if not self.train:
-            return [(0, 0, H, W, 0) + resize_center_crop(H, W, self.size) + (NO_JITTER,)]
-        g = sample_generator(self.seed, self.epoch, i)
-        box = sample_crop(H, W, g, self.scale, self.ratio)
-        flip = int(sample_flip(g))
-        return [box + (flip, self.size, self.size, 0, 0, sample_jitter(g, *self.jitter))]
-
-    def _load_side(self, i: int):
-        return load_token(self.audio, self.names[i])
-
-    def _side_staging(self, mk) -> dict:
-        return {"token": mk((self.B,) + TOKEN_SHAPE, torch.int64), "pm": mk((self.B,) + TOKEN_SHAPE, torch.float32)}
-
-    def _fill_side(self, st, j, side) -> None:
-        np.copyto(st["token"][j].numpy(), side[0])
-        np.copyto(st["pm"][j].numpy(), side[1])
-
-    def _descriptors(self, shapes, boxes):
-        return image_descriptors(shapes, [b[:5] for b in boxes], [b[5:9] for b in boxes])
-
-    def _extra_staging(self, mk) -> dict:
-        return {"jdesc": mk((self.B, JITTER_COLS), torch.int64)}
-
-    def _fill_extra(self, st, ids, loaded) -> None:
-        st["jdesc"][:len(ids)].numpy()[...] = jitter_descriptors([l[2][0][9] for l in loaded])
-
-    def _host_tuple(self, st, b):
-        return st["token"][:b], st["pm"][:b], st["frames"], st["desc"][:b], st["jdesc"][:b], st["label"][:b], st["idx"][:b]
-
-    def device_step(self, host: Sequence[torch.Tensor], dev: Sequence[torch.Tensor], scratch: dict) -> tuple:
-        """DeviceFeeder hook, run on its copy stream behind the copies of `dev` (= `host` on the device): the train or the eval
-        kernel into the slot's image buffer; returns (token, padding_mask, image, label, idx)."""
-        token, pm, frames, desc, jdesc, label, idx = dev
-        b, S = label.shape[0], self.size
-        if "image" not in scratch or scratch["image"].shape[0] < b:
-            n = max(b, self.B)
-            scratch["image"] = torch.empty((n, 3, 1, S, S), dtype=torch.float32, device=token.device)
-            scratch["staging"] = torch.empty(n * S * S * 3, dtype=torch.uint8, device=token.device)
-            scratch["partials"] = torch.empty(n * S, dtype=torch.int64, device=token.device)
-        if "lut" not in scratch:
-            scratch["lut"] = self.lut.to(token.device)
-        if self.train:
-            img = ops.image_augment(frames, desc, host[3], jdesc, host[4], scratch["lut"], scratch["image"][:b], scratch["staging"],
-                                    scratch["partials"])
-        else:
-            img = ops.image_resample(frames, desc, host[3], scratch["lut"], scratch["image"][:b], 1, BICUBIC)
-        return token, pm, img.view(b, 3, S, S), label, idx
+        self.text = text_feature_path
+        images = timm_image_part(visual_feature_path, frame_cache, image_path, train, out_size, scale, ratio, color_jitter, mean, std)
+        super().__init__(names, labels, batch_size, [images, token_part(text_feature_path)],
+                         ("token", "pm", "frames", "desc", "jdesc", "label", "idx"), ("token", "pm", "image", "label", "idx"),
+                         seed=seed, epoch=epoch, threads=threads, ring=ring, pin=pin, drop_last=drop_last)

@@ -26,18 +26,16 @@ draws only.
 """
 from __future__ import annotations
 
-import os
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import ops
 from ._lib import MLAHipError
-from .cav_feed import BICUBIC, pick_middle_frame
-from .data import FBANK_SHAPE, TOKEN_SHAPE, load_fbank, load_token
-from .frames import MEAN, RATIO, SCALE, STD, decode_jpeg, load_cached_frame
-from .m3ae_feed import JITTER_COLS, OUT_SIZE, M3AEBatcher, jitter_descriptors
+from .cav_feed import middle_frame_path
+from .frames import MEAN, RATIO, SCALE, STD, Batcher, Part, SampleKey, fbank_part, slot_buffer, token_part
+from .m3ae_feed import OUT_SIZE, timm_image_part
 
 AUDIO, IMAGE, TEXT = 0, 1, 2                   # columns of the mask matrix (dataset.py:798-801)
 MASK_TOLERANCE = 0.005                         # dataset.py:619
@@ -86,7 +84,29 @@ def mask_descriptors(rows: np.ndarray) -> np.ndarray:
     return desc
 
 
-class Modal3Batcher(M3AEBatcher):
+class MaskPart(Part):
+    """Modal3Batcher's own part, last in its list: the batch's mask rows as "mdesc" (B, 4), and the one extra device step,
+    mla_modal3_assemble, over what the parts before it left in `out`: the compact images become "image" (B, 3, size, size)
+    and the rows of absent spectrograms, tokens and padding masks are zeroed."""
+    tensors = {"mdesc": (1, (4,), torch.int64)}
+
+    def __init__(self, mask: np.ndarray, size: int):
+        self.mask, self.size = mask, int(size)
+
+    def load(self, name: str, key: SampleKey) -> np.ndarray:
+        return self.mask[key.index]
+
+    def pack(self, st: dict, recs: Sequence[np.ndarray], b: int, empty) -> dict:
+        st["mdesc"][:b].numpy()[...] = mask_descriptors(np.stack(recs))
+        return {"mdesc": st["mdesc"][:b]}
+
+    def device(self, host: dict, dev: dict, scratch: dict, out: dict, B: int) -> None:
+        mdesc, S = dev["mdesc"], self.size
+        image = slot_buffer(scratch, "assembled", mdesc.shape[0], B, (3, S, S), torch.float32, mdesc.device)
+        out["image"] = ops.modal3_assemble(out["image"], out["spec"], out["token"], out["pm"], mdesc, host["mdesc"], image)
+
+
+class Modal3Batcher(Batcher):
     def __init__(self, names: Sequence[str], labels: Sequence[int], batch_size: int, text_feature_path: str, audio_feature_path: str,
                  visual_feature_path: Optional[str] = None, frame_cache: Optional[str] = None, train: bool = True,
                  mask_percent: float = 0.0, mask_seed: int = 0, mask=None, seed: int = 0, epoch: int = 0, threads: int = 8,
@@ -94,19 +114,15 @@ class Modal3Batcher(M3AEBatcher):
                  color_jitter=1.0, mean: Sequence[float] = MEAN, std: Sequence[float] = STD, drop_last: bool = False,
                  pin: Optional[bool] = None):
         """Modal3Dataset batches from the token / padding-mask and fbank .npy files and either the JPEG frame directories
-        (`visual_feature_path`) or a decode_middle_frames cache (`frame_cache`), on FrameBatcher's staging ring, `copied()` fence
-        and `device_step()` hook.  `self.mask` int64 (n, 3), columns (audio, image, text), is random_mask(3, n, mask_percent,
+        (`visual_feature_path`) or a decode_middle_frames cache (`frame_cache`), on frames.Batcher's loop, staging ring, `copied()`
+        fence and `device_step()` hook.  `self.mask` int64 (n, 3), columns (audio, image, text), is random_mask(3, n, mask_percent,
         RandomState(mask_seed)) unless `mask` gives it (0/1 entries, no all-zero row: the reference keeps one modality per sample).
         Yields host tuples (token, padding_mask, spec, frames uint8 (capacity,), image_desc int64 (P, 12), jitter_desc int64
         (P, 7), mask_desc int64 (B, 4), label, idx), P = the batch's images that are present; rows of token, padding_mask and
         spec whose modality is absent are NOT filled.  Through a DeviceFeeder the device tuple is (token (B, 1, 256) int64,
         padding_mask (B, 1, 256) fp32, image (B, 3, out, out) fp32, spec (B, 1024, 128) fp32, label, idx): Modal3Dataset.__getitem__'s
         tuple, MLATrainer.train_step's argument order, with absent modalities zero.  Image transform and its arguments: M3AEBatcher."""
-        super().__init__(names, labels, batch_size, text_feature_path, visual_feature_path=visual_feature_path,
-                         frame_cache=frame_cache, train=train, seed=seed, epoch=epoch, threads=threads, ring=ring, out_size=out_size,
-                         scale=scale, ratio=ratio, color_jitter=color_jitter, mean=mean, std=std, drop_last=drop_last, pin=pin)
-        self.text, self.audio = text_feature_path, audio_feature_path
-        n = len(self.names)
+        n = len(names)
         if mask is None:
             mask = random_mask(3, n, float(mask_percent), np.random.RandomState(int(mask_seed)))
         mask = np.asarray(mask)
@@ -115,70 +131,13 @@ class Modal3Batcher(M3AEBatcher):
         if n and (mask.sum(axis=1) == 0).any():
             raise ValueError(f"mask: sample {int(np.argmin(mask.sum(axis=1)))} has no modality left (the reference keeps at least one)")
         self.mask = mask.astype(np.int64)
-
-    def sample_frames(self, i: int) -> List[np.ndarray]:
-        """[the decoded uint8 (H, W, 3) middle frame of dataset index i], from the JPEGs or the cache."""
-        name = self.names[i]
-        if self.cache is not None:
-            return [load_cached_frame(self.cache, name, 0)]
-        d = os.path.join(self.visual, name)
-        return [decode_jpeg(os.path.join(d, pick_middle_frame(d)))]
-
-    def _load(self, i: int):
-        if self.mask[i, IMAGE]:
-            return super()._load(i)
-        return self._load_side(i), [], []                   # no listdir, no decode, no frame, no descriptor row
-
-    def _load_side(self, i: int):
-        m, name = self.mask[i], self.names[i]
-        return (load_token(self.text, name) if m[TEXT] else None, load_fbank(self.audio, name) if m[AUDIO] else None)
-
-    def _side_staging(self, mk) -> dict:
-        return {"token": mk((self.B,) + TOKEN_SHAPE, torch.int64), "pm": mk((self.B,) + TOKEN_SHAPE, torch.float32),
-                "spec": mk((self.B,) + FBANK_SHAPE, torch.float32)}
-
-    def _fill_side(self, st, j, side) -> None:
-        text, spec = side
-        if text is not None:
-            np.copyto(st["token"][j].numpy(), text[0])
-            np.copyto(st["pm"][j].numpy(), text[1])
-        if spec is not None:
-            np.copyto(st["spec"][j].numpy(), spec)
-
-    def _extra_staging(self, mk) -> dict:
-        return {"jdesc": mk((self.B, JITTER_COLS), torch.int64), "mdesc": mk((self.B, 4), torch.int64)}
-
-    def _fill_extra(self, st, ids, loaded) -> None:
-        jit = [l[2][0][9] for l in loaded if l[2]]
-        st["images"] = len(jit)
-        if jit:
-            st["jdesc"][:len(jit)].numpy()[...] = jitter_descriptors(jit)
-        st["mdesc"][:len(ids)].numpy()[...] = mask_descriptors(self.mask[list(ids)])
-
-    def _host_tuple(self, st, b):
-        P = st["images"]
-        return (st["token"][:b], st["pm"][:b], st["spec"][:b], st["frames"], st["desc"][:P], st["jdesc"][:P], st["mdesc"][:b],
-                st["label"][:b], st["idx"][:b])
-
-    def device_step(self, host: Sequence[torch.Tensor], dev: Sequence[torch.Tensor], scratch: dict) -> tuple:
-        """DeviceFeeder hook, run on its copy stream behind the copies of `dev` (= `host` on the device): the train or the eval
-        image kernel over the P present images into the slot's compact buffer (skipped when P = 0), then mla_modal3_assemble;
-        returns (token, padding_mask, image, spec, label, idx)."""
-        token, pm, spec, frames, desc, jdesc, mdesc, label, idx = dev
-        b, P, S = label.shape[0], desc.shape[0], self.size
-        if "image" not in scratch or scratch["image"].shape[0] < b:
-            n = max(b, self.B)
-            scratch["image"] = torch.empty((n, 3, S, S), dtype=torch.float32, device=token.device)
-            scratch["compact"] = torch.empty((n, 3, 1, S, S), dtype=torch.float32, device=token.device)
-            scratch["staging"] = torch.empty(n * S * S * 3, dtype=torch.uint8, device=token.device)
-            scratch["partials"] = torch.empty(n * S, dtype=torch.int64, device=token.device)
-        if "lut" not in scratch:
-            scratch["lut"] = self.lut.to(token.device)
-        compact = None
-        if P and self.train:
-            compact = ops.image_augment(frames, desc, host[4], jdesc, host[5], scratch["lut"], scratch["compact"][:P], scratch["staging"],
-                                        scratch["partials"])
-        elif P:
-            compact = ops.image_resample(frames, desc, host[4], scratch["lut"], scratch["compact"][:P], 1, BICUBIC)
-        image = ops.modal3_assemble(compact, spec, token, pm, mdesc, host[6], scratch["image"][:b])
-        return token, pm, image, spec, label, idx
+        self.text, self.audio = text_feature_path, audio_feature_path
+        have = self.mask != 0
+        parts = [timm_image_part(visual_feature_path, frame_cache, middle_frame_path, train, out_size, scale, ratio, color_jitter,
+                                 mean, std, present=have[:, IMAGE]),
+                 token_part(text_feature_path, present=have[:, TEXT]), fbank_part(audio_feature_path, present=have[:, AUDIO]),
+                 MaskPart(self.mask, out_size)]
+        super().__init__(names, labels, batch_size, parts,
+                         ("token", "pm", "spec", "frames", "desc", "jdesc", "mdesc", "label", "idx"),
+                         ("token", "pm", "image", "spec", "label", "idx"), seed=seed, epoch=epoch, threads=threads, ring=ring,
+                         pin=pin, drop_last=drop_last)
