@@ -14,7 +14,7 @@
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------------------
-// LayerNorm: one wave per row, D <= 2048, D % 64 == 0
+// LayerNorm: one wave per row, D in {512, 768, 1024} (the row lives in D / 64 registers per lane)
 // ---------------------------------------------------------------------------------------------------
 template <int PER>   // elements per lane = D / 64 (compile-time so the row lives in registers, not scratch)
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -382,6 +382,7 @@ extern "C" int mla_softmax_fwd(float* S, const float* pad_mask, int B, int H, in
 extern "C" int mla_softmax_bwd(const float* P, float* dP, int B, int H, int n, void* stream) {
   MLA_REQUIRE(P && dP && B > 0 && H > 0 && n > 0 && n <= 1024, "mla_softmax_bwd: bad argument (n <= 1024)");
   const long rows = (long)B * H * n;
+  MLA_REQUIRE(rows < (1L << 31), "mla_softmax_bwd: too many rows");
   softmax_bwd_kernel<<<cdiv(rows, 4), 256, 0, (hipStream_t)stream>>>(P, dP, (int)rows, n);
   MLA_CHECK_LAUNCH("softmax_bwd_kernel");
   return MLA_OK;
@@ -593,13 +594,15 @@ extern "C" int mla_tokens_assemble_bwd(const float* dx0, const float* colsum_all
   MLA_REQUIRE(dx0 && colsum_all && dtype && B > 0 && L > 0 && D > 0 && ((dtable == nullptr) == (ids == nullptr)) && (!dtable || V > 0),
               "mla_tokens_assemble_bwd: bad argument");
   MLA_REQUIRE(dcls || !dtable, "mla_tokens_assemble_bwd: the text path always has a [cls] token");
+  if (dtable) {                                                     // everything is checked before the first launch
+    MLA_REQUIRE(D % 4 == 0 && D <= 256 * EMB_MAXD4, "mla_tokens_assemble_bwd: D=%d must be a multiple of 4, <= %d", D, 256 * EMB_MAXD4);
+    MLA_REQUIRE(L <= EMB_CHUNK && (long)V * EMB_CHUNK <= 0xFFFFFFFFL, "mla_tokens_assemble_bwd: L=%d / V=%d out of range", L, V);
+    MLA_REQUIRE(ws && ws_bytes >= mla_tokens_assemble_bwd_ws_bytes(B, L, D), "mla_tokens_assemble_bwd: workspace too small");
+  }
   hipStream_t st = (hipStream_t)stream;
   assemble_bwd_kernel<<<cdiv(D, 256), 256, 0, st>>>(dx0, colsum_all, dcls, dtype, B, L, D);
   MLA_CHECK_LAUNCH("assemble_bwd_kernel");
   if (!dtable) return MLA_OK;
-  MLA_REQUIRE(D % 4 == 0 && D <= 256 * EMB_MAXD4, "mla_tokens_assemble_bwd: D=%d must be a multiple of 4, <= %d", D, 256 * EMB_MAXD4);
-  MLA_REQUIRE(L <= EMB_CHUNK && (long)V * EMB_CHUNK <= 0xFFFFFFFFL, "mla_tokens_assemble_bwd: L=%d / V=%d out of range", L, V);
-  MLA_REQUIRE(ws && ws_bytes >= mla_tokens_assemble_bwd_ws_bytes(B, L, D), "mla_tokens_assemble_bwd: workspace too small");
   unsigned* sorted = (unsigned*)ws;
   float* part = (float*)(sorted + EMB_CHUNK);
   const int rows_per_chunk = EMB_CHUNK / L;                         // whole sequences per chunk

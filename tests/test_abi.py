@@ -141,6 +141,33 @@ def test_bgemm_rejects_descriptors_that_leave_their_buffers():
     assert call(good_a, L4(n * 3 * D, hd, -1, 3 * D), good_c, qkv_elems, qkv_elems - D, p_elems) == -1    # negative stride
 
 
+def test_token_path_entry_points_reject_before_any_launch():
+    """The transformer token-path entry points validate their sizes before they launch anything: every call below hands over fake
+    (non-null, never dereferenced) pointers, so it must come back as MLA_ERR_INVALID_ARG with the function named in mla_last_error()."""
+    from mla_hip import _lib
+    lib = _lib.load()
+    fake = 0x1000
+
+    def rejected(fn, *args):
+        assert getattr(lib, fn)(*args) == -1, f"{fn}{args} was not rejected"
+        assert fn.encode() in lib.mla_last_error(), (fn, lib.mla_last_error())
+    for fn in ("mla_softmax_fwd", "mla_softmax_bwd"):
+        rejected(fn, fake, fake, 1, 1, 1025, None)                                     # n <= 1024
+        rejected(fn, fake, fake, 2 ** 11, 2 ** 10, 2 ** 10, None)                      # B * H * n == 2^31 rows
+        rejected(fn, fake, fake, 65536, 32, 1024, None)                                # ... and == 2^31 again, other factors
+    rejected("mla_layernorm_fwd", fake, fake, fake, fake, fake, fake, 4, 640, 1e-5, None)
+    rejected("mla_layernorm_bwd", *([fake] * 10), 4, 640, None)
+    assert b"D=640" in lib.mla_last_error()
+    rejected("mla_tokens_assemble", fake, fake, fake, fake, fake, None, 2, 8, 64, 100, None)         # a table but no [cls]
+    ws = lib.mla_tokens_assemble_bwd_ws_bytes(1, 16385, 64)
+    rejected("mla_tokens_assemble_bwd", *([fake] * 6), 1, 16385, 64, 100, fake, ws, None)            # L > 16384
+    assert b"L=16385" in lib.mla_last_error()
+    rejected("mla_tokens_assemble_bwd", *([fake] * 6), 2, 8, 64, 262144, fake, ws, None)             # V * 16384 = 2^32 > 2^32 - 1
+    assert b"V=262144" in lib.mla_last_error()
+    rejected("mla_patchify", fake, fake, 1, 3, 33, 32, 16, 0, None)                                  # H % P != 0
+    rejected("mla_patchify", fake, fake, 1, 3, 32, 33, 16, 1, None)
+
+
 def test_host_side_sizing_and_selection_logic():
     """Host functions of the round-3 kernels that launch nothing: workspaces cover every kernel a shape may be routed to, the folded-BatchNorm
     entry points are offered only for the 64 -> 64 3x3 / 1 / 1 shapes whose grid the persistent patch kernel fills, hooks answer queries."""
