@@ -560,6 +560,30 @@ int mla_modal3_assemble_check(const int64_t* mdesc_host, int B, int P, int S, in
 int mla_modal3_assemble(const float* image_compact, float* spec, int64_t* token, float* pm, const int64_t* mdesc,
                         const int64_t* mdesc_host, float* image_out, int B, int P, int S, int TF, int L, void* stream);
 
+/* ---- Kaldi log-mel filterbank from PCM16 clips (data/extract_fbank.py:8-54) -------------------------------------
+ * For each of B packed mono 16 kHz clips: waveform = s / 32768 - mean, then torchaudio 0.8.1's
+ *     kaldi.fbank(waveform, htk_compat=True, sample_frequency=16000, use_energy=False, window_type='hanning',
+ *                 num_mel_bins=128, dither=0.0, frame_shift=10)
+ * (400-sample frames every 160 with snip_edges, per-frame DC removal, pre-emphasis 0.97, symmetric Hann window, 512-point
+ * power spectrum, 128 mel banks over the bins 0..255, log(max(E, 2^-23))), padded with +0.0 or cut to target_length rows.
+ *     wav        int16, wav_samples of them; a clip may start at any sample (2-byte alignment)
+ *     desc       int64 (B, 4) per clip: offset_samples, n_samples, sample_sum, reserved (0).  n_samples is 0 (an absent clip:
+ *                all rows +0.0) or >= 400; sample_sum is the exact integer sum of the clip's samples, from which the clip mean
+ *                is float(double(sample_sum) / (32768.0 * n_samples))
+ *     window     fp32 (400); twiddle fp32 (512, 2): (cos, -sin)(2 pi j / 512), computed in fp64 and rounded once
+ *     mel_start, mel_len int32 (128), mel_weight fp32 (mel_weights): bank i weighs the bins [mel_start[i], mel_start[i] +
+ *                mel_len[i]) with the next mel_len[i] entries of mel_weight; the runs lie inside [0, 256)
+ *     out        fp32 (B, target_length, 128), 16-byte aligned; every element is written
+ * `desc`, `mel_start`, `mel_len` (device) and their `_host` twins (host, the same values) as for the other feed kernels.
+ * A clip's rows depend on that clip alone (not on B, its neighbours or its offset) and are the same bits in every run: fixed
+ * reduction orders, no atomics.  mla_wav_fbank_check runs the size and table checks alone (no GPU). */
+int mla_wav_fbank_check(const int64_t* desc_host, int B, size_t wav_samples, int target_length, const int32_t* mel_start_host,
+                        const int32_t* mel_len_host, size_t mel_weights);
+int mla_wav_fbank(const int16_t* wav, size_t wav_samples, const int64_t* desc, const int64_t* desc_host, const float* window,
+                  const float* twiddle, const int32_t* mel_start, const int32_t* mel_len, const int32_t* mel_start_host,
+                  const int32_t* mel_len_host, const float* mel_weight, size_t mel_weights, float* out, int B, int target_length,
+                  void* stream);
+
 /* ---- evaluation path (main.py:486-679 `valid`, gs_flag branch) --------------------------------- */
 /* logits = X W^T + b only (main.py:636-639) */
 int mla_head_logits(const float* X, const float* W, const float* b, float* logits, int B, int D, int C, void* stream);

@@ -149,6 +149,8 @@ PROTOTYPES = {
     "mla_fbank_augment": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, ctypes.c_uint64, _P]),
     "mla_modal3_assemble_check": (_I, [_P, _I, _I, _I, _I, _I]),
     "mla_modal3_assemble": (_I, [_P] * 7 + [_I] * 5 + [_P]),
+    "mla_wav_fbank_check": (_I, [_P, _I, _Z, _I, _P, _P, _Z]),
+    "mla_wav_fbank": (_I, [_P, _Z, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _I, _P]),
 }
 
 _lib = None

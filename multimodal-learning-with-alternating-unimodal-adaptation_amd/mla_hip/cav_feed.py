@@ -35,8 +35,9 @@ import torch
 from . import ops
 from ._lib import MLAHipError
 from .data import FBANK_SHAPE
-from .frames import (MEAN, STD, Batcher, ImagePart, Part, Placement, SampleKey, decode_frames, fbank_part, list_frames,
-                     sample_generator, slot_buffer)
+from .frames import (MEAN, STD, Batcher, ImagePart, Part, Placement, SampleKey, decode_frames, list_frames, sample_generator,
+                     slot_buffer)
+from .wav_feed import audio_fields, audio_part
 
 NORM_MEAN, NORM_STD = -5.081, 4.4849           # dataset.py:259-260
 FREQM, TIMEM = 48, 192                         # dataset.py:281
@@ -160,22 +161,24 @@ class SpecAugPart(Part):
 
 
 class CAVBatcher(Batcher):
-    def __init__(self, names: Sequence[str], labels: Sequence[int], batch_size: int, audio_feature_path: str,
+    def __init__(self, names: Sequence[str], labels: Sequence[int], batch_size: int, audio_feature_path: Optional[str] = None,
                  visual_feature_path: Optional[str] = None, frame_cache: Optional[str] = None, train: bool = True,
                  augnois: bool = False, seed: int = 0, epoch: int = 0, threads: int = 8, ring: int = 4, pin: Optional[bool] = None,
                  drop_last: bool = False, out_size: int = 224, mean: Sequence[float] = MEAN, std: Sequence[float] = STD,
-                 norm_mean: float = NORM_MEAN, norm_std: float = NORM_STD):
+                 norm_mean: float = NORM_MEAN, norm_std: float = NORM_STD, audio_wav_path: Optional[str] = None):
         """CAVDataset batches from the fbank .npy files and either the JPEG frame directories (`visual_feature_path`) or a
         decode_middle_frames cache (`frame_cache`), on frames.Batcher's loop, staging ring, `copied()` fence and `device_step()` hook.
         Yields host tuples (spec_raw, frames uint8 (capacity,), image_desc int64 (B, 12), fbank_desc int64 (B, 8), label, idx);
         through a DeviceFeeder the device tuple is (spec (B, 1024, 128), image (B, 3, out, out), label, idx), the shapes
         CAVClassifier.forward takes.  The spectrogram is augmented only when `train and augnois` and always normalised; the
-        image transform is the same in train and eval.  out_size=256 gives the M3AE / Food-101 eval transform."""
+        image transform is the same in train and eval.  out_size=256 gives the M3AE / Food-101 eval transform.
+        Audio: exactly one of `audio_feature_path` (fbank .npy files) and `audio_wav_path` (.wav files: wav_feed); with the latter
+        the host tuple carries wav int16 (capacity,) and wdesc int64 (B, 4) where it carried spec_raw."""
         images = ImagePart(visual_feature_path, frame_cache, middle_frame_path, 1, ResizeCenterCrop(out_size), out_size, mean, std)
         if float(norm_std) == 0.0:
             raise ValueError("norm_std must not be 0")
-        self.audio = audio_feature_path
-        parts = [images, fbank_part(audio_feature_path), SpecAugPart(train and augnois, norm_mean, norm_std, seed)]
-        super().__init__(names, labels, batch_size, parts, ("spec", "frames", "desc", "fdesc", "label", "idx"),
+        self.audio, self.audio_wav = audio_feature_path, audio_wav_path
+        parts = [images, audio_part(audio_feature_path, audio_wav_path), SpecAugPart(train and augnois, norm_mean, norm_std, seed)]
+        super().__init__(names, labels, batch_size, parts, audio_fields(("spec", "frames", "desc", "fdesc", "label", "idx"), audio_wav_path),
                          ("spec", "image", "label", "idx"), seed=seed, epoch=epoch, threads=threads, ring=ring, pin=pin,
                          drop_last=drop_last)

@@ -30,6 +30,8 @@ tuples; none overrides the loop.  The sibling modules add frame sources and tran
     m3ae_feed     M3AEBatcher: <name>.jpg through the timm TRAIN transform (dataset.py:401-412: bicubic random crop, flip,
                   color jitter), token pair
     modal3_feed   Modal3Batcher: Modal3Dataset's three modalities with its missing-modality masks (dataset.py:596-803)
+    wav_feed      WavPart: <name>.wav in place of the fbank <name>.npy (`audio_wav_path=` of FrameBatcher, CAVBatcher and
+                  Modal3Batcher), the Kaldi fbank computed on the device
 Out of scope: QMF's masking.
 """
 from __future__ import annotations
@@ -487,23 +489,27 @@ class Batcher:
 
 
 class FrameBatcher(Batcher):
-    def __init__(self, names: Sequence[str], labels: Sequence[int], batch_size: int, audio_feature_path: str,
+    def __init__(self, names: Sequence[str], labels: Sequence[int], batch_size: int, audio_feature_path: Optional[str] = None,
                  visual_feature_path: Optional[str] = None, frame_cache: Optional[str] = None, train: bool = True,
                  seed: int = 0, epoch: int = 0, threads: int = 8, ring: int = 4, pin: Optional[bool] = None,
                  drop_last: bool = False, out_size: int = OUT_SIZE, pick_num: int = PICK_NUM,
-                 mean: Sequence[float] = MEAN, std: Sequence[float] = STD):
+                 mean: Sequence[float] = MEAN, std: Sequence[float] = STD, audio_wav_path: Optional[str] = None):
         """AVDataset batches (dataset.py:111-161) from the fbank .npy files and either the JPEG frame directories
         (`visual_feature_path`, decoded with PIL in a pool of `threads` <= 16 threads) or a decode_frames cache
         (`frame_cache`).  Yields host tuples (spec, frames uint8 (capacity,), desc int64 (B*T, 8), label, idx); through a
         DeviceFeeder the device tuple is (spec, image (B, 3, T, out, out) fp32, label, idx).  `set_epoch` reseeds the draws.
         Threads: the cache source is fastest with threads=1 (a memcpy per frame; more threads contend for the GIL), the
-        JPEG source gains up to about 8."""
-        self.audio = audio_feature_path
+        JPEG source gains up to about 8.
+        Audio: exactly one of `audio_feature_path` (fbank .npy files) and `audio_wav_path` (16 kHz mono PCM16 .wav files, whose
+        fbank mla_wav_fbank computes on the device: wav_feed); with the latter the host tuple carries wav int16 (capacity,) and
+        wdesc int64 (B, 4) where it carried spec, and the device tuple is the same."""
+        from .wav_feed import audio_fields, audio_part           # wav_feed builds on this module
+        self.audio, self.audio_wav = audio_feature_path, audio_wav_path
         self.images = ImagePart(visual_feature_path, frame_cache, frame_paths, pick_num, RandomCropFlip(bool(train)), out_size,
                                 mean, std, keep_time=True)
-        super().__init__(names, labels, batch_size, [self.images, fbank_part(audio_feature_path)],
-                         ("spec", "frames", "desc", "label", "idx"), ("spec", "image", "label", "idx"), seed=seed, epoch=epoch,
-                         threads=threads, ring=ring, pin=pin, drop_last=drop_last)
+        super().__init__(names, labels, batch_size, [self.images, audio_part(audio_feature_path, audio_wav_path)],
+                         audio_fields(("spec", "frames", "desc", "label", "idx"), audio_wav_path), ("spec", "image", "label", "idx"),
+                         seed=seed, epoch=epoch, threads=threads, ring=ring, pin=pin, drop_last=drop_last)
 
     def sample_frames(self, i: int) -> List[np.ndarray]:
         """The T decoded uint8 (H, W, 3) frames of dataset index i, from the JPEGs or the cache."""

@@ -34,7 +34,8 @@ import torch
 from . import ops
 from ._lib import MLAHipError
 from .cav_feed import middle_frame_path
-from .frames import MEAN, RATIO, SCALE, STD, Batcher, Part, SampleKey, fbank_part, slot_buffer, token_part
+from .frames import MEAN, RATIO, SCALE, STD, Batcher, Part, SampleKey, slot_buffer, token_part
+from .wav_feed import audio_fields, audio_part
 from .m3ae_feed import OUT_SIZE, timm_image_part
 
 AUDIO, IMAGE, TEXT = 0, 1, 2                   # columns of the mask matrix (dataset.py:798-801)
@@ -107,12 +108,12 @@ class MaskPart(Part):
 
 
 class Modal3Batcher(Batcher):
-    def __init__(self, names: Sequence[str], labels: Sequence[int], batch_size: int, text_feature_path: str, audio_feature_path: str,
+    def __init__(self, names: Sequence[str], labels: Sequence[int], batch_size: int, text_feature_path: str, audio_feature_path: Optional[str] = None,
                  visual_feature_path: Optional[str] = None, frame_cache: Optional[str] = None, train: bool = True,
                  mask_percent: float = 0.0, mask_seed: int = 0, mask=None, seed: int = 0, epoch: int = 0, threads: int = 8,
                  ring: int = 4, out_size: int = OUT_SIZE, scale: Sequence[float] = SCALE, ratio: Sequence[float] = RATIO,
                  color_jitter=1.0, mean: Sequence[float] = MEAN, std: Sequence[float] = STD, drop_last: bool = False,
-                 pin: Optional[bool] = None):
+                 pin: Optional[bool] = None, audio_wav_path: Optional[str] = None):
         """Modal3Dataset batches from the token / padding-mask and fbank .npy files and either the JPEG frame directories
         (`visual_feature_path`) or a decode_middle_frames cache (`frame_cache`), on frames.Batcher's loop, staging ring, `copied()`
         fence and `device_step()` hook.  `self.mask` int64 (n, 3), columns (audio, image, text), is random_mask(3, n, mask_percent,
@@ -121,7 +122,10 @@ class Modal3Batcher(Batcher):
         (P, 7), mask_desc int64 (B, 4), label, idx), P = the batch's images that are present; rows of token, padding_mask and
         spec whose modality is absent are NOT filled.  Through a DeviceFeeder the device tuple is (token (B, 1, 256) int64,
         padding_mask (B, 1, 256) fp32, image (B, 3, out, out) fp32, spec (B, 1024, 128) fp32, label, idx): Modal3Dataset.__getitem__'s
-        tuple, MLATrainer.train_step's argument order, with absent modalities zero.  Image transform and its arguments: M3AEBatcher."""
+        tuple, MLATrainer.train_step's argument order, with absent modalities zero.  Image transform and its arguments: M3AEBatcher.
+        Audio: exactly one of `audio_feature_path` (fbank .npy files) and `audio_wav_path` (.wav files: wav_feed); with the latter
+        the host tuple carries wav int16 (capacity,) and wdesc int64 (B, 4) where it carried spec, an absent spectrogram is a
+        wdesc row with n_samples = 0, and no .wav is opened for it."""
         n = len(names)
         if mask is None:
             mask = random_mask(3, n, float(mask_percent), np.random.RandomState(int(mask_seed)))
@@ -131,13 +135,14 @@ class Modal3Batcher(Batcher):
         if n and (mask.sum(axis=1) == 0).any():
             raise ValueError(f"mask: sample {int(np.argmin(mask.sum(axis=1)))} has no modality left (the reference keeps at least one)")
         self.mask = mask.astype(np.int64)
-        self.text, self.audio = text_feature_path, audio_feature_path
+        self.text, self.audio, self.audio_wav = text_feature_path, audio_feature_path, audio_wav_path
         have = self.mask != 0
         parts = [timm_image_part(visual_feature_path, frame_cache, middle_frame_path, train, out_size, scale, ratio, color_jitter,
                                  mean, std, present=have[:, IMAGE]),
-                 token_part(text_feature_path, present=have[:, TEXT]), fbank_part(audio_feature_path, present=have[:, AUDIO]),
+                 token_part(text_feature_path, present=have[:, TEXT]),
+                 audio_part(audio_feature_path, audio_wav_path, present=have[:, AUDIO]),
                  MaskPart(self.mask, out_size)]
         super().__init__(names, labels, batch_size, parts,
-                         ("token", "pm", "spec", "frames", "desc", "jdesc", "mdesc", "label", "idx"),
+                         audio_fields(("token", "pm", "spec", "frames", "desc", "jdesc", "mdesc", "label", "idx"), audio_wav_path),
                          ("token", "pm", "image", "spec", "label", "idx"), seed=seed, epoch=epoch, threads=threads, ring=ring,
                          pin=pin, drop_last=drop_last)

@@ -1031,3 +1031,40 @@ def modal3_assemble(image_compact: Optional[torch.Tensor], spec: torch.Tensor, t
     _call("mla_modal3_assemble", _p(image_compact) if P else None, _p(spec), _p(token, torch.int64), _p(pm), _p(mask_desc, torch.int64),
           d.data_ptr(), _p(image_out), B, P, image_out.shape[2], spec[0].numel(), token[0].numel(), stream or cur_stream())
     return image_out
+
+
+# ---- Kaldi log-mel filterbank from PCM16 clips (data/extract_fbank.py:8-54) ------------------------------------------------------
+def _mel_runs_host(tables) -> Tuple[torch.Tensor, torch.Tensor]:
+    s, l = tables.mel_start_host, tables.mel_len_host
+    for t in (s, l):
+        if t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != (128,) or not t.is_contiguous():
+            raise MLAHipError(f"mel runs: expected contiguous host int32 (128,) tensors, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return s, l
+
+
+def wav_fbank_check(desc_host: torch.Tensor, wav_samples: int, tables, target_length: int = 1024) -> None:
+    """The size and table checks of wav_fbank alone (no GPU): raises MLAHipError on a clip table or mel runs the kernel must not run."""
+    d = _table_host(desc_host, 4, "clip descriptors")
+    s, l = _mel_runs_host(tables)
+    _call("mla_wav_fbank_check", d.data_ptr(), d.shape[0], wav_samples, target_length, s.data_ptr(), l.data_ptr(), tables.mel_weight.numel())
+
+
+def wav_fbank(wav: torch.Tensor, desc: torch.Tensor, desc_host: torch.Tensor, tables, out: torch.Tensor,
+              stream: Optional[int] = None) -> torch.Tensor:
+    """wav int16 (device, packed mono 16 kHz clips), desc int64 (B, 4) rows (offset_samples, n_samples, sample_sum, 0) on the device
+    and the same table on the host, tables = wav_feed.fbank_tables() moved to the device (window, twiddle, mel_start, mel_len,
+    mel_weight there; mel_start_host, mel_len_host here) -> out fp32 (B, target_length, 128): each clip's Kaldi log-mel filterbank,
+    zero rows beyond its frames (see include/mla_hip.h, mla_wav_fbank)."""
+    d = _table_host(desc_host, 4, "clip descriptors")
+    s, l = _mel_runs_host(tables)
+    if tuple(desc.shape) != tuple(d.shape):
+        raise MLAHipError(f"clip descriptors: device table {tuple(desc.shape)} and host table {tuple(d.shape)} differ")
+    if wav.dim() != 1 or out.dim() != 3 or out.shape[0] != d.shape[0] or out.shape[2] != 128 or tuple(tables.window.shape) != (400,) \
+            or tuple(tables.twiddle.shape) != (512, 2) or tuple(tables.mel_start.shape) != (128,) or tuple(tables.mel_len.shape) != (128,) \
+            or tables.mel_weight.dim() != 1:
+        raise MLAHipError(f"wav_fbank: wav {tuple(wav.shape)} / out {tuple(out.shape)} / window {tuple(tables.window.shape)} / twiddle "
+                          f"{tuple(tables.twiddle.shape)} do not match (n,) / ({d.shape[0]}, target_length, 128) / (400,) / (512, 2)")
+    _call("mla_wav_fbank", _p(wav, torch.int16) if wav.numel() else None, wav.numel(), _p(desc, torch.int64), d.data_ptr(),
+          _p(tables.window), _p(tables.twiddle), _p(tables.mel_start, torch.int32), _p(tables.mel_len, torch.int32), s.data_ptr(),
+          l.data_ptr(), _p(tables.mel_weight), tables.mel_weight.numel(), _p(out), d.shape[0], out.shape[1], stream or cur_stream())
+    return out

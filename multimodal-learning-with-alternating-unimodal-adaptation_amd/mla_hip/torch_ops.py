@@ -462,3 +462,15 @@ def modal3_assemble(image_compact, spec, token, pm, mask_desc, size=256):
     out = _f32((desc_host.shape[0], 3, size, size), spec)
     ops.modal3_assemble(image_compact if image_compact.shape[0] else None, spec, token, pm, desc_host.to(spec.device), desc_host, out)
     return out
+
+
+# ---- Kaldi log-mel filterbank from PCM16 clips (data/extract_fbank.py:8-54) -------------------------------------------------
+@_op("wav_fbank(Tensor wav, Tensor desc, int target_length=1024) -> Tensor")
+def wav_fbank(wav, desc, target_length=1024):
+    """Packed int16 mono 16 kHz clips (device) + clip descriptors int64 (B, 4) (host; validated there, then copied to the device)
+    -> a new (B, target_length, 128) fp32: each clip's Kaldi log-mel filterbank, zero rows beyond its frames (mla_hip.wav_feed)."""
+    from .wav_feed import device_tables
+    desc_host = desc.cpu().contiguous()
+    out = _f32((desc_host.shape[0], target_length, 128), wav)
+    ops.wav_fbank(wav, desc_host.to(wav.device), desc_host, device_tables(wav.device), out)
+    return out
