@@ -698,11 +698,13 @@ extern "C" int mla_conv2d_dgrad_merge(int on) { return g_dgrad_merge.hook(on); }
 
 extern "C" int mla_conv2d_fwd_split(const float* x, const void* wsplit_t, float* y, int N, int H, int W, int Cin, int Cout,
                                     int KH, int KW, int stride, int pad, float* bn_partial, int* bn_tiles, void* stream) {
-  if (int rc = check_conv("mla_conv2d_fwd_split", N, H, W, Cin, Cout, KH, KW, stride, pad)) return rc;
-  MLA_REQUIRE(Cin % 64 == 0, "mla_conv2d_fwd_split: Cin=%d must be a multiple of 64 (the stem runs on mla_conv2d_fwd)", Cin);
+  if (int rc = check_conv("mla_conv2d_fwd_split", N, H, W, Cin, Cout, KH, KW, stride, pad, 32)) return rc;
   MLA_REQUIRE(x && wsplit_t && y, "mla_conv2d_fwd_split: null pointer");
   IGemmGeom g;
   make_fwd_geom(g, N, H, W, Cin, Cout, KH, KW, stride, pad);
+  // (an odd number of 32-channel chunks: only where the LDS-patch kernel, whose K stage is one chunk, takes the layer)
+  MLA_REQUIRE(Cin % 64 == 0 || (Cin % 32 == 0 && use_patch(g)),
+              "mla_conv2d_fwd_split: Cin=%d must be a multiple of 64 (of 32 for a layer the LDS-patch kernel serves; the stem runs on mla_conv2d_fwd)", Cin);
   MLA_REQUIRE(g.OH > 0 && g.OW > 0, "mla_conv2d_fwd_split: empty output");
   if (use_patch(g)) return mla_patch_launch(x, wsplit_t, y, nullptr, nullptr, bn_partial, g, bn_tiles, (hipStream_t)stream);
   const int cfg = pick_scfg(g.M, Cout, KH * KW * Cin);

@@ -10,10 +10,11 @@
 //     right) are loaded ONCE, split ONCE and kept in LDS as three bf16 planes [pixel][32 channels] (64-B rows, the XOR
 //     chunk swizzle of igemm_split_kernel): a tap is a row offset into that patch, and all nine taps read their A fragments
 //     from it with the same conflict-free ds_read_b128 -- 9x fewer gathers and operand splits;
-//   * the pre-split weight planes of a (tap, chunk) stage are register-staged one stage ahead into a two-slot ring (three
-//     16-B loads and three ds_write_b128 per thread: the B side was never the cost);
-//   * a K stage is then fragment reads + 48 MFMAs per wave, one barrier per stage as before; the next chunk's patch is in
-//     flight in registers during the nine stages of this chunk.
+//   * the pre-split weight planes of a (tap, chunk) stage are register-staged into a two-slot ring (three 16-B loads and three
+//     ds_write_b128 per thread: the B side was never the cost), loaded two stages and stored one stage ahead of their use;
+//   * a K stage is then fragment reads + 48 MFMAs per wave, one barrier per stage as before; the stages of a chunk are unrolled,
+//     the fragments of a half-step are read during the MFMAs of the one before it, the barrier stands in the middle of a stage's
+//     last MFMA group and the next chunk's patch is loaded a slot at a time over the stages of this one (see the main loop).
 // Geometry, tap tables (forward: (kh - 1, kw - 1); input gradient: (1 - kh, 1 - kw) on the transposed weights) and the whole
 // epilogue (BatchNorm statistics, residual, ReLU mask, fused BatchNorm-backward reductions) are those of igemm_split_kernel.
 #include "split_common.h"
@@ -97,27 +98,33 @@ __global__ __launch_bounds__(512, 2) void patch_split_kernel(const float* __rest
   const rsrc_t xr = make_rsrc(X, g.x_bytes), wr = make_rsrc(Wsp, 3 * plane_bytes);
 
   // ---- patch staging: slot s = tid + 512 u -> (patch pixel s >> 3, float4 s & 7 of the chunk's 32 channels)
+  // One slot is one 16-B load: the main loop issues them a few per K stage (see there), so a slot's address is formed where it
+  // is issued (the `zero` keeps the eight chunk-invariant addresses from being hoisted out of the chunk loop: 16+ VGPRs).
+  // Chunks past the last one are masked off (the load returns zeros and is never stored).
   f32x4 pre[PT_NPRE];
-  auto patch_load = [&](int c0) {
-#pragma unroll
-    for (int u = 0; u < PT_NPRE; ++u) {
-      const int s = tid + 512 * u, pp = s >> 3, c4 = s & 7;
-      const int pr = pp / prow, pc = pp - pr * prow;
-      const int gr = r0 - 1 + pr, x = pc - 1;
-      const int ok = (int)(pp < npx) & (int)((unsigned)gr < (unsigned)(g.N * gH)) & (int)((unsigned)x < (unsigned)gW);
-      const unsigned off = ((unsigned)(gr * gW + x) * (unsigned)gC + (unsigned)(c0 + 4 * c4)) * 4u;
-      pre[u] = buf_load4(xr, off | ((unsigned)ok - 1u), 0);
-    }
+  const unsigned prow_inv = (65536u + (unsigned)prow - 1u) / (unsigned)prow;      // pp / prow == (pp * prow_inv) >> 16 for pp < 512, prow < 64
+  const int nimg_rows = g.N * gH;
+  auto patch_load1 = [&](int u, int c0) {
+    int zero = 0;
+    asm volatile("" : "+v"(zero));
+    const int s = tid + 512 * u + zero, pp = s >> 3, c4 = s & 7;
+    const int pr = (int)(((unsigned)pp * prow_inv) >> 16), pc = pp - pr * prow;
+    const int gr = r0 - 1 + pr, x = pc - 1;
+    const int ok = (int)(pp < npx) & (int)((unsigned)gr < (unsigned)nimg_rows) & (int)((unsigned)x < (unsigned)gW) & (int)(c0 < gC);
+    const unsigned off = ((unsigned)(gr * gW + x) * (unsigned)gC + (unsigned)(c0 + 4 * c4)) * 4u;
+    pre[u] = buf_load4(xr, off | ((unsigned)ok - 1u), 0);
   };
-  auto patch_store = [&]() {
+  auto patch_store = [&](int u0, int u1) {       // slots [u0, u1)
 #pragma unroll
-    for (int u = 0; u < PT_NPRE; ++u) {
-      const int s = tid + 512 * u, pp = s >> 3, c4 = s & 7;
-      if (pp >= PT_ZP) continue;                               // (never the zero pixel; pixels in [npx, ZP) receive zeros: harmless)
+    for (int u = u0; u < u1; ++u) {
+      const int s = tid + 512 * u, c4 = s & 7;
+      // (never the zero pixel: the last slots are redirected, branch-free, onto pixel ZP - 1, the right padding column of the
+      // largest patch's last row at most, which receives zeros from them as from its own slot; pixels in [npx, ZP) receive zeros)
+      const int pp = (s >> 3) < PT_ZP ? (s >> 3) : PT_ZP - 1;
+      unsigned* dst = P + pp * 16 + ((((c4 >> 1) ^ ((pp >> 2) & 3)) << 2) + (c4 & 1) * 2);
       unsigned h0, m0_, l0, h1, m1, l1;
       split_pair<true>(pre[u][0], pre[u][1], h0, m0_, l0);
       split_pair<true>(pre[u][2], pre[u][3], h1, m1, l1);
-      unsigned* dst = P + pp * 16 + ((((c4 >> 1) ^ ((pp >> 2) & 3)) << 2) + (c4 & 1) * 2);
       *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
       *reinterpret_cast<u32x2*>(dst + PT_PPL) = u32x2{m0_, m1};
       *reinterpret_cast<u32x2*>(dst + 2 * PT_PPL) = u32x2{l0, l1};
@@ -127,87 +134,177 @@ __global__ __launch_bounds__(512, 2) void patch_split_kernel(const float* __rest
   // tid & 3) of each plane, 16 B each (the swizzle is applied on the source side); 128 rows = TPS taps x BN output columns.
   // (LDS-DMA -- buffer_load ... lds -- was tried first: hipcc serialises the DMA instructions with vmcnt(0) and waits for all
   // of them before the first fragment read of every stage, which exposes the whole load latency: register staging it is.)
+  //
+  // The nine tap words are read once: (patch offset dy * prow + dx) << 8 | weight tap << 4 | row-validity bits the tap needs;
+  // the stages below index the table statically, so the loop holds no scalar memory load.
+  int tapw[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    const int tp = g.tap[t];
+    const int dy = tap_dy(tp), dx = tap_dx(tp);
+    tapw[t] = (dy * prow + dx) * 256 + ((tap_wt(tp) << 4) | 4 | (dy < 0 ? 1 : 0) | (dy > 0 ? 2 : 0));
+  }
+  const unsigned wtap_bytes = (unsigned)(gCO * gC * 2);       // one tap of a weight plane
   u32x4 breg[3];
-  auto b_load = [&](int t0, int c0) {
-    const int row = tid >> 2;
-    const int tt = row / BN, n = row - tt * BN;
-    const int t = t0 + tt;
-    const int q = (tid & 3) ^ ((row >> 2) & 3);
-    const int tp = g.tap[t < g.T ? t : g.T - 1];
-    const unsigned off = (unsigned)(((tap_wt(tp) * gCO + tn * BN + n) * gC + c0) * 2 + q * 16) | ((unsigned)(t < g.T) - 1u);
+  const int b_row = tid >> 2, b_tt = b_row / BN, b_n = b_row - b_tt * BN;
+  const unsigned b_base = (unsigned)((tn * BN + b_n) * gC * 2 + ((tid & 3) ^ ((b_row >> 2) & 3)) * 16);
+  auto b_load = [&](int t0, int c0, bool valid) {            // t0: static; valid: wave-uniform (false: past the last stage, nothing is fetched)
+    int tw = tapw[t0];
+    if constexpr (TPS == 2) tw = b_tt ? tapw[t0 + 1 < 9 ? t0 + 1 : 8] : tw;
+    const bool ok = valid && t0 + b_tt < 9;
+    const unsigned off = (b_base + (unsigned)((tw >> 4) & 15) * wtap_bytes + (unsigned)c0 * 2u) | ((unsigned)ok - 1u);
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) breg[pl] = buf_load4u(wr, off, pl * plane_bytes);
   };
-  auto b_store = [&](int slot) {
-    unsigned* dst = Bs + slot * BSLOT + tid * 4;            // row (tid >> 2) * 16 dwords + slot (tid & 3) * 4 = tid * 4
+  auto b_store = [&](int slot_off) {
+    unsigned* dst = Bs + slot_off + tid * 4;                // row (tid >> 2) * 16 dwords + slot (tid & 3) * 4 = tid * 4
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + pl * 128 * 16) = breg[pl];
   };
 
+  // ---- main loop.  A chunk is 18 half-steps j = (tap j >> 1, 16-deep k half j & 1), fully unrolled; a half-step is the six product
+  // groups of split_mma<6> (same order: K runs chunk, tap, kk, product; within a product mi, ni), MI * NI MFMAs each.  The whole
+  // fragment set Fy of the NEXT half-step is read during the groups of this one (Fx), so no MFMA waits for a read issued
+  // less than four groups before it:
+  //   inside a K stage        group 0: Fy.a0 Fy.b0   group 1: Fy.b1 Fy.a1                                        group 4: Fy.b2 Fy.a2
+  //   last half-step of one   group 0: Fy.a0 Fy.a1   BARRIER           group 2: Fy.b0 Fy.b1 + global loads   group 4: Fy.b2 Fy.a2
+  // (the third planes are needed last -- products 4 and 5 -- and take the registers Fx.a1 / Fx.b1 leave after group 3.)
+  // The stage's barrier stands in front of group 2 of its last half-step: every read of the stage's B slot (and, in the chunk's
+  // last stage, of the patch) is in registers by then, the A fragments of the next stage (the patch does not change inside a
+  // chunk) are read in front of it, only the B reads of the new slot behind it, and groups 2 ... 5 (16 MFMAs on fragments that
+  // are already there) keep the matrix pipes fed across it.
+  // Global loads: behind the barrier of stage S go the three weight loads of stage S + 2, then PPS of the next chunk's eight
+  // patch loads.  The weights are stored one stage later (group 5 of the stage's last but one half-step) with vmcnt(PPS): that
+  // wait leaves the youngest patch loads in flight and covers only patch loads that are a whole stage old.  Only the patch store
+  // at the chunk's end waits for everything; it rides beside the last 16 MFMAs of the chunk, behind the barrier that ends the
+  // reads of the old patch, and the half-step after it starts cold.
   typedef SplitFrags<MI, NI> Frags;
-  auto load_frags = [&](int slot, int tt, int ppv[MI], int kk, Frags& f) {
-    const unsigned* Br = Bs + slot * BSLOT + tt * BN * 16 + b_rd + frag_koff(kk, h, swz);
+  constexpr int SPC = (9 + TPS - 1) / TPS;       // K stages per chunk
+  constexpr int PPS = PT_NPRE / (SPC - 1);       // patch loads issued in each of the first SPC - 1 stages
+  static_assert(SPC % 2 == 1 && PPS * (SPC - 1) == PT_NPRE, "slot parity flips per chunk; the patch loads divide over the stages");
+  const int NC = gC / 32;                        // channel chunks
+  const int brd[2] = {b_rd + frag_koff(0, h, swz), b_rd + frag_koff(1, h, swz)};
+  auto a_addr = [&](int j, int (&ad)[MI]) {      // dword offsets of this lane's two A rows in plane 0 for half-step j
+    const int tw = tapw[j >> 1], need = tw & 7;
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) {
-        const unsigned* Ar = P + pl * PT_PPL + ppv[mi] * 16 + frag_koff(kk, h, (ppv[mi] >> 2) & 3);
-        f.a[pl][mi] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(Ar));
-      }
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-        f.b[pl][ni] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(Br + (pl * 128 + ni * 32) * 16));
+    for (int mi = 0; mi < MI; ++mi) {
+      const int ppv = (pv[mi] & need) == need ? pb[mi] + (tw >> 8) : PT_ZP;
+      ad[mi] = ppv * 16 + frag_koff(j & 1, h, (ppv >> 2) & 3);
     }
   };
-  auto mma_frags = [&](const Frags& f) { split_mma<6>(f.a, f.b, acc); };
+  auto rd_a = [&](Frags& f, int pl, const int (&ad)[MI]) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) f.a[pl][mi] = lds_frag(P + pl * PT_PPL + ad[mi]);
+  };
+  auto rd_b = [&](Frags& f, int pl, const unsigned* Br) {
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) f.b[pl][ni] = lds_frag(Br + (pl * 128 + ni * 32) * 16);
+  };
+  auto mma_group = [&](int term, const Frags& f) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni)
+        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[TERM_A[term]][mi], f.b[TERM_B[term]][ni], acc[mi][ni], 0, 0, 0);
+  };
 
-  const int NC = gC / 32;                        // channel chunks
-  constexpr int SPC = (9 + TPS - 1) / TPS;       // K stages per chunk
-  const int NS = NC * SPC;
-  patch_load(0);
-  b_load(0, 0);
-  patch_store();
+  constexpr auto closes_stage = [](int j) { return (j & 1) == 1 && ((j >> 1) % TPS == TPS - 1 || j == 17); };
+#pragma unroll
+  for (int u = 0; u < PT_NPRE; ++u) patch_load1(u, 0);
+  b_load(0, 0, true);
+  patch_store(0, PT_NPRE);
   b_store(0);
+  b_load(TPS, 0, true);                          // stage 1 (in registers until stage 0 stores it)
+#pragma unroll
+  for (int u = 0; u < PPS; ++u) patch_load1(u, 32);
   __syncthreads();
-  Frags f0, f1;
-  int c = 0, st = 0;                             // chunk, stage within the chunk
-  for (int s = 0; s < NS; ++s) {
-    const int cur = s & 1;
-    {                                            // next stage's weights -> registers (stored into the other slot mid-stage)
-      int st1 = st + 1, c1 = c;
-      if (st1 == SPC) { st1 = 0; ++c1; }
-      if (s + 1 < NS) b_load(st1 * TPS, c1 * 32);
-    }
-    if (st == 0 && c + 1 < NC) patch_load((c + 1) * 32);       // next chunk's patch: in flight for the nine taps of this one
+  Frags F[2];
+  int off_e = 0, off_o = BSLOT;                  // B slot of this chunk's even / odd stages (SPC is odd: they swap per chunk)
+  for (int c = 0;; ++c) {
+    asm volatile("" : "+v"(pb[0]), "+v"(pb[1]));                // (keeps the 18 chunk-invariant A addresses out of registers)
+    {                                            // cold start: the first half-step's operands
+      int ad[MI];
+      a_addr(0, ad);
+      const unsigned* Br = Bs + off_e + brd[0];
 #pragma unroll
-    for (int tt = 0; tt < TPS; ++tt) {
-      const int t = st * TPS + tt;
-      if (t < 9) {
-        const int tp = g.tap[t];
-        const int dy = tap_dy(tp), dx = tap_dx(tp);
-        const int toff = dy * prow + dx;                        // wave-uniform
-        const int need = 4 | (dy < 0 ? 1 : 0) | (dy > 0 ? 2 : 0);
-        int ppv[MI];
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) ppv[mi] = (pv[mi] & need) == need ? pb[mi] + toff : PT_ZP;
-        load_frags(cur, tt, ppv, 0, f0);
-        load_frags(cur, tt, ppv, 1, f1);
-        mma_frags(f0);
-        if (tt == 0 && s + 1 < NS) b_store(cur ^ 1);           // that slot's readers passed the previous barrier
-        mma_frags(f1);
+      for (int pl = 0; pl < 3; ++pl) {
+        rd_a(F[0], pl, ad);
+        rd_b(F[0], pl, Br);
       }
     }
-    ++st;
-    if (st == SPC) {
-      st = 0;
-      ++c;
-      if (c < NC) {
-        __syncthreads();                         // every wave is done with this chunk's patch
-        patch_store();
+#pragma unroll
+    for (int j = 0; j < 18; ++j) {
+      const Frags& Fx = F[j & 1];
+      Frags& Fy = F[(j + 1) & 1];
+      const int st = (j >> 1) / TPS;
+      const bool last = closes_stage(j);
+      const int t1 = (j + 1) >> 1, st1 = t1 / TPS;
+      int ay[MI];
+      const unsigned* by = Bs + ((st1 & 1) ? off_o : off_e) + (t1 % TPS) * BN * 16 + brd[(j + 1) & 1];
+      if (j < 17) {
+        a_addr(j + 1, ay);
+        rd_a(Fy, 0, ay);
+        if (last) rd_a(Fy, 1, ay);
+        else rd_b(Fy, 0, by);
+      }
+      mma_group(0, Fx);
+      __builtin_amdgcn_sched_barrier(0);
+      if (j < 17 && !last) {
+        rd_b(Fy, 1, by);
+        rd_a(Fy, 1, ay);
+      }
+      mma_group(1, Fx);
+      __builtin_amdgcn_sched_barrier(0);
+      if (last) {
+        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (j == 17) {
+        // chunk end: every wave is done with this chunk's patch and with both B slots' earlier stages.  The next chunk's first
+        // stage (loaded behind the previous barrier), then its patch, beside the last four groups; then the loads that run ahead.
+        // (Unconditional, so that the split arithmetic shares a basic block with the MFMAs and is scheduled between them: behind
+        // the last chunk the masked loads delivered zeros, which land in a slot and a patch nobody reads again.)
+        b_store(off_o);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          patch_store(2 * q, 2 * q + 2);
+          mma_group(2 + q, Fx);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        b_load(TPS, (c + 1) * 32, c + 1 < NC);
+#pragma unroll
+        for (int u = 0; u < PPS; ++u) patch_load1(u, (c + 2) * 32);
+      } else {
+        if (last) {                              // behind the stage's barrier: the new slot, and the loads that run ahead
+          rd_b(Fy, 0, by);
+          rd_b(Fy, 1, by);
+          if (st + 2 < SPC) b_load((st + 2) * TPS, c * 32, true);
+          else b_load((st + 2 - SPC) * TPS, (c + 1) * 32, c + 1 < NC);
+          if (st + 2 < SPC) {
+#pragma unroll
+            for (int u = 0; u < PPS; ++u) patch_load1((st + 1) * PPS + u, (c + 1) * 32);
+          }
+        }
+        mma_group(2, Fx);
+        __builtin_amdgcn_sched_barrier(0);
+        mma_group(3, Fx);
+        __builtin_amdgcn_sched_barrier(0);
+        rd_b(Fy, 2, by);                          // (into the registers Fx.a1 / Fx.b1 have just left)
+        rd_a(Fy, 2, ay);
+        mma_group(4, Fx);
+        __builtin_amdgcn_sched_barrier(0);
+        if (j < 16 && closes_stage(j + 1)) b_store((st & 1) ? off_e : off_o);  // stage st + 1: that slot's readers passed the previous barrier
+        mma_group(5, Fx);
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
+    if (c + 1 >= NC) break;
     __syncthreads();
+    const int o = off_e;
+    off_e = off_o;
+    off_o = o;
   }
+  __syncthreads();                               // (the epilogue stages through P)
   igemm_epilogue<PT_BM, BN, WM, WN>(acc, rowinfo, reinterpret_cast<float*>(P), Y, R, MASK, part, nullptr, nullptr, g, tm, tn);
 }
 

@@ -245,12 +245,13 @@ __device__ __forceinline__ void igemm_epilogue(f32x16 (&acc)[BM / WM / 32][BN / 
 // ---------------------------------------------------------------------------------------------
 static inline int conv_out(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
 
-static inline int check_conv(const char* who, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+// cin_granule: 64 everywhere but the split forward, whose LDS-patch kernel works in 32-channel chunks
+static inline int check_conv(const char* who, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int cin_granule = 64) {
   MLA_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "%s: non-positive dims", who);
   MLA_REQUIRE(KH * KW <= MAX_TAPS && KH > 0 && KW > 0, "%s: kernel %dx%d unsupported (max %d taps)", who, KH, KW, MAX_TAPS);
   MLA_REQUIRE(stride == 1 || stride == 2, "%s: stride %d unsupported", who, stride);
   MLA_REQUIRE(Cout % 64 == 0 && Cout <= 1024 && Cin <= 1024, "%s: Cout=%d must be a multiple of 64; channels <= 1024", who, Cout);
-  MLA_REQUIRE(Cin % 64 == 0 || Cin <= 4, "%s: Cin=%d must be a multiple of 64 or <= 4 (stem)", who, Cin);
+  MLA_REQUIRE(Cin % cin_granule == 0 || Cin <= 4, "%s: Cin=%d must be a multiple of %d or <= 4 (stem)", who, Cin, cin_granule);
   MLA_REQUIRE(pad >= 0 && pad < 64 && H < 32768 && W < 32768, "%s: pad/size out of range", who);
   MLA_REQUIRE((long)N * H * W < (1L << 31) / 4, "%s: too many pixels for 32-bit pixel indices", who);
   {   // both tensors of the convolution are addressed with 32-bit byte offsets
