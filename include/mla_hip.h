@@ -584,6 +584,39 @@ int mla_wav_fbank(const int16_t* wav, size_t wav_samples, const int64_t* desc, c
                   const int32_t* mel_len_host, const float* mel_weight, size_t mel_weights, float* out, int B, int target_length,
                   void* stream);
 
+/* ---- HBM-resident CREMA-D feed (dataset/dataset.py:111-161 from device memory) ---------------------------------
+ * The decoded dataset stays on the device: `frames` (uint8 HWC frames at the byte offsets of `table`), `table` int64 (N*T, 3) rows
+ * (byte offset, H, W) of frame t of sample i at row i*T + t, `spec_table` fp32 (N, 1024*128) or NULL, `labels` int64 (N), and the
+ * epoch's visiting `order` int64 (N).  mla_resident_batch makes batch slots j = 0..b-1 from the samples i = order[pos + j] with three
+ * launches and nothing else -- no allocation, no synchronisation, no host read of device memory:
+ *   draw      desc_out int64 (b*T, 8): one mla_frames_resample descriptor row per frame, label_out[j] = labels[i], idx_out[j] = i.
+ *             train == 0: (offset, H, W, 0, 0, H, W, 0).  train != 0: torchvision RandomResizedCrop(scale (0.08, 1), ratio
+ *             (3/4, 4/3)).get_params with its central-crop fallback, and RandomHorizontalFlip, on Philox4x32-10 in fp64:
+ *               block(k) = philox4x32(counter = (t << 4) | k, stream_id = i, key = (epoch << 32) | seed), words a, b, c, d
+ *               try k = 0..9:  target_area = H*W*(0.08 + 0.92*a*2^-32);  aspect = exp(L0 + (L1 - L0)*b*2^-32), L0 = log(3/4),
+ *                              L1 = log(4/3);  w = rint(sqrt(target_area*aspect)), h = rint(sqrt(target_area/aspect));
+ *                              accepted when 0 < w <= W and 0 < h <= H: top = (c*(H-h+1)) >> 32, left = (d*(W-w+1)) >> 32
+ *               flip = word a of block(10) < 2^31
+ *             so a frame's row depends on (seed, epoch, i, t) and its size alone; seed, epoch < 2^32.
+ *   resample  image_out fp32 (b, 3, T, out_h, out_w): mla_frames_resample's kernel body over desc_out, the same bits.
+ *   gather    spec_out fp32 (b, 1024, 128) = the rows i of spec_table (skipped when spec_table is NULL), 16-byte accesses.
+ * mla_resident_plan runs once, on the host copy of the table (no GPU): 0 < H, W <= 65536, offset >= 0 and offset + H*W*3 <=
+ * frames_bytes in 64-bit arithmetic, rows = N*T; then plan5 = (band, rows_cap, kh, kv, lds), the resample kernel's LDS plan maximised
+ * over every crop the draw can make (every height 1..H and width 1..W of every frame shape; train == 0: the whole frames only).
+ * A dataset for which no band fits 64 KB of LDS is refused with the frame size named.  A plan made with train != 0 also serves
+ * train == 0.  A larger plan than a batch needs changes no bit of the result.
+ * mla_resident_batch refuses on the host: pos + b > N, b*T >= 65536, seed or epoch >= 2^32, null or misaligned buffers (the int64
+ * buffers 8-byte, lut / image_out 4-byte, spec_table / spec_out 16-byte), and a plan5 that is not of mla_resident_plan's making for
+ * out_h, out_w (band a power of two <= 16, odd filter sizes >= 3, lds recomputed from the rest and <= 64 KB).  The order vector
+ * is validated where it is made, with mla_gather_index_check; on the device an entry is clamped to [0, N) and a table row that
+ * leaves the buffer becomes the 1x1 frame at offset 0, so no kernel reads out of bounds. */
+int mla_resident_plan(const int64_t* table_host, int64_t rows, int T, size_t frames_bytes, int out_h, int out_w, int train,
+                      int* plan5);
+int mla_resident_batch(const uint8_t* frames, size_t frames_bytes, const int64_t* table, const float* spec_table,
+                       const int64_t* labels, const int64_t* order, int N, int T, int pos, int b, uint64_t seed, uint64_t epoch,
+                       int train, const int* plan5, const float* lut, int64_t* desc_out, float* image_out, float* spec_out,
+                       int64_t* label_out, int64_t* idx_out, int out_h, int out_w, void* stream);
+
 /* ---- evaluation path (main.py:486-679 `valid`, gs_flag branch) --------------------------------- */
 /* logits = X W^T + b only (main.py:636-639) */
 int mla_head_logits(const float* X, const float* W, const float* b, float* logits, int B, int D, int C, void* stream);

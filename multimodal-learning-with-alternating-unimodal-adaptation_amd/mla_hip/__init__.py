@@ -15,6 +15,7 @@ from .cav_feed import (CAVBatcher, decode_middle_frames, fbank_descriptors, imag
 from .m3ae_feed import M3AEBatcher, decode_images, jitter_descriptors, sample_jitter  # noqa: F401
 from .modal3_feed import Modal3Batcher, mask_descriptors, random_mask  # noqa: F401
 from .wav_feed import WavPart, clip_descriptors, extract_fbank, fbank_tables, read_wav, wav_part  # noqa: F401
+from .resident_feed import ResidentFrameBatcher, ResidentStore, frame_table  # noqa: F401
 from .model import AVClassifier, ConcatFusion, SharedHead  # noqa: F401
 from .m3ae import CAVClassifier, ConcatFusion3, M3AEClassifier, M3AEEncoder, Modal3Classifier  # noqa: F401
 from .clip import CLIPClassifier  # noqa: F401

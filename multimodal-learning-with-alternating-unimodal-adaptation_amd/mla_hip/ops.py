@@ -7,7 +7,7 @@ Activations are NHWC, conv weights HWIO.  No fallbacks: errors raise MLAHipError
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -1068,3 +1068,52 @@ def wav_fbank(wav: torch.Tensor, desc: torch.Tensor, desc_host: torch.Tensor, ta
           _p(tables.window), _p(tables.twiddle), _p(tables.mel_start, torch.int32), _p(tables.mel_len, torch.int32), s.data_ptr(),
           l.data_ptr(), _p(tables.mel_weight), tables.mel_weight.numel(), _p(out), d.shape[0], out.shape[1], stream or cur_stream())
     return out
+
+
+# ---- HBM-resident CREMA-D feed (csrc/resident.hip) ------------------------------------------------------------------------------
+class ResidentPlan(NamedTuple):
+    """mla_resident_plan's result: plan5 = host int32 (band, rows_cap, kh, kv, lds) for one output size; a plan made with `train`
+    holds for eval batches too, one made without holds for those only."""
+    plan5: torch.Tensor
+    out_h: int
+    out_w: int
+    train: bool
+
+
+def resident_plan(table_host: torch.Tensor, T: int, frames_bytes: int, out_h: int = 224, out_w: int = 224, train: bool = True) -> ResidentPlan:
+    """Validate the host frame table int64 (N * T, 3) rows (byte offset, H, W) against a buffer of `frames_bytes` and plan the
+    resample launch for every crop the device draw can make of it (no GPU; see include/mla_hip.h, mla_resident_plan)."""
+    t = _table_host(table_host, 3, "frame table")
+    plan5 = torch.zeros(5, dtype=torch.int32)
+    _call("mla_resident_plan", t.data_ptr(), t.shape[0], T, frames_bytes, out_h, out_w, int(bool(train)), plan5.data_ptr())
+    return ResidentPlan(plan5, int(out_h), int(out_w), bool(train))
+
+
+def resident_batch(frames: torch.Tensor, table: torch.Tensor, spec_table: Optional[torch.Tensor], labels: torch.Tensor, order: torch.Tensor,
+                   T: int, pos: int, b: int, seed: int, epoch: int, train: bool, plan: ResidentPlan, lut: torch.Tensor, desc_out: torch.Tensor,
+                   image_out: torch.Tensor, spec_out: Optional[torch.Tensor], label_out: torch.Tensor, idx_out: torch.Tensor,
+                   stream: Optional[int] = None) -> None:
+    """Batch slots 0..b-1 from the samples order[pos : pos + b] of a device-resident dataset: frames uint8, table int64 (N * T, 3),
+    spec_table fp32 (N, 1024, 128) or None, labels / order int64 (N) -> desc_out int64 (b * T, 8), image_out fp32 (b, 3, T, out_h,
+    out_w), spec_out fp32 (b, 1024, 128), label_out int64 (b), idx_out int64 (b, 1); three launches on the stream, nothing else (see
+    include/mla_hip.h, mla_resident_batch).  The order vector is checked where it is made (gather_index_check)."""
+    N = labels.numel()
+    if frames.dim() != 1 or table.dim() != 2 or tuple(table.shape) != (N * T, 3) or order.numel() != N:
+        raise MLAHipError(f"resident_batch: frames {tuple(frames.shape)} / table {tuple(table.shape)} / labels {tuple(labels.shape)} / order "
+                          f"{tuple(order.shape)} do not match (bytes,) / (N * {T}, 3) / (N,) / (N,)")
+    if seed < 0 or epoch < 0:
+        raise MLAHipError(f"resident_batch: seed {seed} and epoch {epoch} must lie in [0, 2^32)")
+    if train and not plan.train:
+        raise MLAHipError("resident_batch: a plan made for whole frames (train=False) does not hold for drawn crops")
+    if tuple(lut.shape) != (3, 256) or tuple(desc_out.shape) != (b * T, 8) or tuple(image_out.shape) != (b, 3, T, plan.out_h, plan.out_w) \
+            or label_out.numel() != b or idx_out.numel() != b:
+        raise MLAHipError(f"resident_batch: lut {tuple(lut.shape)} / desc_out {tuple(desc_out.shape)} / image_out {tuple(image_out.shape)} / "
+                          f"label_out {tuple(label_out.shape)} / idx_out {tuple(idx_out.shape)} do not match (3, 256) / ({b * T}, 8) / "
+                          f"({b}, 3, {T}, {plan.out_h}, {plan.out_w}) / ({b},) / ({b}, 1)")
+    if spec_table is not None and (tuple(spec_table.shape) != (N, 1024, 128) or spec_out is None or tuple(spec_out.shape) != (b, 1024, 128)):
+        raise MLAHipError(f"resident_batch: spec_table {tuple(spec_table.shape)} / spec_out "
+                          f"{None if spec_out is None else tuple(spec_out.shape)} do not match ({N}, 1024, 128) / ({b}, 1024, 128)")
+    _call("mla_resident_batch", _p(frames, torch.uint8), frames.numel(), _p(table, torch.int64), _p(spec_table), _p(labels, torch.int64),
+          _p(order, torch.int64), N, T, pos, b, seed, epoch, int(bool(train)), plan.plan5.data_ptr(), _p(lut), _p(desc_out, torch.int64),
+          _p(image_out), _p(spec_out) if spec_table is not None else None, _p(label_out, torch.int64), _p(idx_out, torch.int64), plan.out_h,
+          plan.out_w, stream or cur_stream())

@@ -474,3 +474,20 @@ def wav_fbank(wav, desc, target_length=1024):
     out = _f32((desc_host.shape[0], target_length, 128), wav)
     ops.wav_fbank(wav, desc_host.to(wav.device), desc_host, device_tables(wav.device), out)
     return out
+
+
+# ---- HBM-resident CREMA-D feed (mla_hip.resident_feed) --------------------------------------------------------------------------
+@_op("resident_batch(Tensor frames, Tensor table, Tensor? spec_table, Tensor labels, Tensor order, int T, int pos, int b, int seed, "
+     "int epoch, bool train, Tensor lut, int out_h=224, int out_w=224) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
+def resident_batch(frames, table, spec_table, labels, order, T, pos, b, seed, epoch, train, lut, out_h=224, out_w=224):
+    """Batch slots 0..b-1 from the samples order[pos : pos + b] of a device-resident dataset (every tensor on the device; the frame
+    table is read back once for the plan and its checks) -> new (spec (b, 1024, 128) -- (0, 1024, 128) without a spec table --,
+    image (b, 3, T, out_h, out_w), label (b,), idx (b, 1), desc (b * T, 8)): the crops drawn, resampled and gathered on the device."""
+    plan = ops.resident_plan(table.cpu().contiguous(), T, frames.numel(), out_h, out_w, train)
+    i64 = dict(device=frames.device, dtype=torch.int64)
+    spec = _f32((b if spec_table is not None else 0, 1024, 128), frames)
+    image = _f32((b, 3, T, out_h, out_w), frames)
+    label, idx, desc = torch.empty(b, **i64), torch.empty((b, 1), **i64), torch.empty((b * T, 8), **i64)
+    ops.resident_batch(frames, table, spec_table, labels, order, T, pos, b, seed, epoch, train, plan, lut, desc, image,
+                       spec if spec_table is not None else None, label, idx)
+    return spec, image, label, idx, desc
