@@ -633,7 +633,11 @@ int mla_bn_invstd(const float* var, float* invstd, int n, float eps, void* strea
 
 /* ---- torch.optim.SGD(momentum, weight_decay) (main.py:749, 439, 451) ------------------------- */
 /* d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf.  g == NULL means zero gradient
- * (torch-1.8.1 zero_grad semantics).  One flat launch over n contiguous elements. */
+ * (torch-1.8.1 zero_grad semantics).  One flat launch over n contiguous elements; p, g and buf may
+ * start at any 4-byte-aligned address (a slice flat[o:o+n] of a flat buffer): 16-byte accesses from p's first
+ * 16-byte boundary on, scalar before it and after the last whole float4; all scalar when buf does not share p's
+ * misalignment, dword gradient loads when only g is off.  An element's result does not depend on where the
+ * range starts.  n == 0 is a no-op; a null p / buf or a pointer off a 4-byte boundary: MLA_ERR_INVALID_ARG. */
 int mla_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd,
                  int first, void* stream);
 

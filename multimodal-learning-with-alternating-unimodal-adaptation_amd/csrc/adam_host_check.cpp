@@ -51,6 +51,18 @@ int main() {
   // m off p's alignment: the all-scalar launch
   EXPECT(adam_plan(p + 1, g + 1, m + 2, v + 1, 9, 1e-3f, 0.9f, 0.999f, 1, &pl) == MLA_OK);
   EXPECT(pl.vec == 0 && pl.gvec == 0 && pl.head == 0 && pl.n4 == 0);
+  // mla_sgd_step's use of the same split: one state tensor (s1 null), a nullable gradient
+  RangePlan rp;
+  for (int o = 0; o < 4; ++o)
+    for (int og = 0; og < 4; ++og)
+      for (size_t n = 1; n <= 40; ++n) {
+        EXPECT(range_plan(p + o, g + og, m + o, nullptr, n, &rp));
+        EXPECT(rp.vec == 1 && rp.gvec == (o == og) && rp.head <= 3 && rp.head <= n && n - rp.head - 4 * rp.n4 <= 3);
+        EXPECT(rp.n4 == 0 || ((uintptr_t)(p + o + rp.head) & 15) == 0);
+      }
+  EXPECT(range_plan(p + 1, nullptr, m + 1, nullptr, 9, &rp) && rp.vec == 1 && rp.gvec == 1 && rp.head == 3 && rp.n4 == 1);
+  EXPECT(range_plan(p + 1, g + 1, m + 3, nullptr, 9, &rp) && rp.vec == 0 && rp.gvec == 0 && rp.head == 0 && rp.n4 == 0);
+  EXPECT(!range_plan((float*)((char*)p + 2), g, m, nullptr, 9, &rp) && !range_plan(p, g, (float*)((char*)m + 1), nullptr, 9, &rp));
   if (failures) return 1;
   printf("adam host check ok\n");
   return 0;

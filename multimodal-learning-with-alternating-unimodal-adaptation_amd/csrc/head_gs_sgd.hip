@@ -4,6 +4,7 @@
 //   head-gradient projection      GSPlugin.before_update (utils/utils.py:24-41), literal
 //   SGD momentum + weight decay   torch.optim.SGD.step (main.py:749, 439, 451), one flat launch per group
 // Wave-per-row kernels with 64-lane shuffle reductions; no atomics (bitwise reproducible).
+#include "adam_args.h"
 #include "head_common.h"
 
 // ---- head: one workgroup per sample ------------------------------------------------------------
@@ -259,19 +260,34 @@ extern "C" int mla_gs_project(float* Pl, const float* r, float* G, int D, int C,
 }
 
 // ---- SGD -------------------------------------------------------------------------------------------
+// The float4 body starts at p's first 16-byte boundary (`head` elements in) and covers n4 groups; the elements before it and after
+// its last whole float4 are scalar (adam_args.h: range_plan; p and buf of a slice flat[o:o+n] share their misalignment).  GVEC:
+// the gradient is aligned with p too; otherwise it takes four dword loads per float4.  On the all-scalar launch n4 is 0.
+template <bool GVEC>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                   size_t n, float lr, float momentum, float wd, int first) {
-  const size_t n4 = n >> 2;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+                                                   size_t n, size_t head, size_t n4, float lr, float momentum, float wd, int first) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
+  f32x4* p4 = reinterpret_cast<f32x4*>(p + head);
+  f32x4* b4 = reinterpret_cast<f32x4*>(buf + head);
+  for (size_t i = tid; i < n4; i += nthr) {
+    f32x4 pv = p4[i];
     f32x4 d = pv * wd;
-    if (g) d += reinterpret_cast<const f32x4*>(g)[i];
-    f32x4 b = first ? d : reinterpret_cast<f32x4*>(buf)[i] * momentum + d;
-    reinterpret_cast<f32x4*>(buf)[i] = b;
-    reinterpret_cast<f32x4*>(p)[i] = pv - b * lr;
+    if (g) {
+      if constexpr (GVEC) {
+        d += reinterpret_cast<const f32x4*>(g + head)[i];
+      } else {
+        const float* gs = g + head + 4 * i;
+        d += f32x4{gs[0], gs[1], gs[2], gs[3]};
+      }
+    }
+    f32x4 b = first ? d : b4[i] * momentum + d;
+    b4[i] = b;
+    p4[i] = pv - b * lr;
   }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {     // sgd_elem's expression (head_common.h), with g == nullptr as a zero gradient
-    const size_t i = (n4 << 2) + threadIdx.x;
+  // everything outside the float4 body: [0, head) and [head + 4 n4, n) (at most 6 elements; all of n on the scalar launch)
+  const size_t rest = n - 4 * n4;
+  for (size_t r = tid; r < rest; r += nthr) {         // sgd_elem's expression (head_common.h), with g == nullptr as a zero gradient
+    const size_t i = r < head ? r : r + 4 * n4;
     const float pv = p[i];
     const float d = (g ? g[i] : 0.f) + wd * pv;
     const float b = first ? d : momentum * buf[i] + d;
@@ -284,12 +300,15 @@ extern "C" int mla_sgd_step(float* p, const float* g, float* buf, size_t n, floa
                             void* stream) {
   MLA_REQUIRE(p && buf, "mla_sgd_step: null pointer");
   if (n == 0) return MLA_OK;
-  MLA_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)buf % 16 == 0) && (!g || (uintptr_t)g % 16 == 0),
-              "mla_sgd_step: buffers must be 16-byte aligned");
-  size_t blocks = (n / 4 + 255) / 256;
+  RangePlan pl;
+  MLA_REQUIRE(range_plan(p, g, buf, nullptr, n, &pl), "mla_sgd_step: buffers must be 4-byte aligned");
+  size_t blocks = ((pl.vec ? pl.n4 : n) + 255) / 256;         // threads' worth of grid-stride work
   if (blocks < 1) blocks = 1;
   if (blocks > 4096) blocks = 4096;
-  sgd_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p, g, buf, n, lr, momentum, wd, first);
+  if (pl.gvec)
+    sgd_kernel<true><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p, g, buf, n, pl.head, pl.n4, lr, momentum, wd, first);
+  else
+    sgd_kernel<false><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p, g, buf, n, pl.head, pl.n4, lr, momentum, wd, first);
   MLA_CHECK_LAUNCH("sgd_kernel");
   return MLA_OK;
 }
@@ -373,6 +392,7 @@ __global__ __launch_bounds__(256) void eval_fuse_kernel(const EvalFuseArgs a, co
   }
   __syncthreads();
   if (tid < a.M && weights_out) weights_out[tid] = wgt[tid];
+  __syncthreads();                                     // a bad label's NaN (below, any wave) lands after thread 0's weights_out[0]
   for (int r = tid; r < a.B; r += 256) {               // one sample per thread: arg-max (first maximum, like np.argmax)
     const long lab_raw = (long)labels[r];
     if (lab_raw < 0 || lab_raw >= a.C) {               // never index the counters with a bad label; poison the weights instead

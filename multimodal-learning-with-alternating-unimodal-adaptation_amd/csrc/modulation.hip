@@ -23,6 +23,9 @@ struct OgmArgs {
   float alpha;
 };
 
+// nn.ReLU on a scalar: a NaN ratio (bad label) stays NaN, as in torch; fmaxf would return the 0
+__device__ __forceinline__ float relu_nan(float x) { return x < 0.f ? 0.f : x; }
+
 // one workgroup; thread m < M accumulates score_m over the rows IN ROW ORDER (the reference's python sum())
 __global__ __launch_bounds__(64) void ogm_coeff_kernel(const OgmArgs a, const int64_t* __restrict__ labels, float* __restrict__ coeff,
                                                         float* __restrict__ info) {
@@ -47,15 +50,15 @@ __global__ __launch_bounds__(64) void ogm_coeff_kernel(const OgmArgs a, const in
     if (a.M == 2) {                                          // index 0 = audio, 1 = visual (main.py:376-384)
       ratio[1] = score[1] / score[0];
       ratio[0] = 1.f / ratio[1];
-      if (ratio[1] > 1.f) cf[1] = 1.f - tanhf(a.alpha * fmaxf(ratio[1], 0.f));
-      else cf[0] = 1.f - tanhf(a.alpha * fmaxf(ratio[0], 0.f));
+      if (ratio[1] > 1.f) cf[1] = 1.f - tanhf(a.alpha * relu_nan(ratio[1]));
+      else cf[0] = 1.f - tanhf(a.alpha * relu_nan(ratio[0]));
     } else {                                                 // index 0 = audio, 1 = visual, 2 = text (main.py:319-337)
       ratio[0] = score[0] / (score[1] + score[2]);
       ratio[1] = score[1] / (score[0] + score[2]);
       ratio[2] = score[2] / (score[1] + score[0]);
-      if (ratio[1] > 1.f) cf[1] = 1.f - tanhf(a.alpha * fmaxf(ratio[1], 0.f));
-      else if (ratio[2] > 1.f) cf[2] = 1.f - tanhf(a.alpha * fmaxf(ratio[2], 0.f));
-      else cf[0] = 1.f - tanhf(a.alpha * fmaxf(ratio[0], 0.f));
+      if (ratio[1] > 1.f) cf[1] = 1.f - tanhf(a.alpha * relu_nan(ratio[1]));
+      else if (ratio[2] > 1.f) cf[2] = 1.f - tanhf(a.alpha * relu_nan(ratio[2]));
+      else cf[0] = 1.f - tanhf(a.alpha * relu_nan(ratio[0]));
     }
     for (int m2 = 0; m2 < a.M; ++m2) {
       coeff[m2] = cf[m2];
