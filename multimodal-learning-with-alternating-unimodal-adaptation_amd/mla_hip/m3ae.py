@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import math
 import os
+from collections import namedtuple
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -51,15 +52,34 @@ def sincos_pos_embed(embed_dim: int, length: int, two_d: bool) -> torch.Tensor:
 # measurement switch (same-box A/B): 0 = bias gradients by separate column-reduction launches
 FUSE_BIAS_GRAD = os.environ.get("MLA_FUSE_BIAS_GRAD", "1") != "0"
 
+
+# One row of an encoder's parameter table, all that is known about a trained parameter: internal name (key of layout / p / g),
+# internal shape (Linear weights [in][out]), init rule ((shape, generator) -> initial value, drawn in table order), the
+# reference-shaped VIEW of the internal tensor (no copy), and the reference state_dict key
+_Param = namedtuple("_Param", "name shape init view ref")
+_same = lambda t: t
+_t = lambda t: t.t()                              # nn.Linear.weight is (out, in)
+_row = lambda t: t.view(1, 1, -1)                 # type / modality embeddings and cls are (1, 1, D)
+_lead = lambda t: t.view(1, *t.shape)             # learned position embedding (1, L, D)
+# Conv2d(1 | 3, D, 16, 16) weight (cav_mae.py:80): patchify emits a patch as (c, p1, p2), the order of the conv weight's
+# trailing dimensions, so splitting the transposed view's second dimension is all it takes
+_conv16 = lambda t: t.t().view(t.shape[1], -1, 16, 16)
+
+# The layers as forward / backward_from_pooled read them, bound once: parameter and gradient views (b / gb None without a
+# bias), for a Linear also its [K][N] dims and the bf16 images its forward / input-gradient GEMMs read (None under "f32")
+_Norm = namedtuple("_Norm", "w b gw gb")
+_Linear = namedtuple("_Linear", "w b gw gb K N img_fwd img_dgrad")
+_Block = namedtuple("_Block", "ln1 qkv fc ln2 fc1 fc2")
+# ... and a block's layers in layout order: a LayerNorm, or a Linear with its (K, N) in units of D
+_BLOCK_LAYERS = (("layer_norm1", None), ("attention.qkv_linear", (1, 3)), ("attention.fc", (1, 1)), ("layer_norm2", None),
+                 ("transformer_mlp.fc1", (1, 4)), ("transformer_mlp.fc2", (4, 1)))
+
+
 class M3AEEncoder(FlatEncoder):
     """nn.Module face (module.py): parameters under the reference's names, order and layouts -- nn.Linear weights
     (out, in) as transposed views of the [in][out] GEMM operands, type embeddings / cls as (1,1,D) -- registered as
     MaskedMultimodalAutoencoder does (direct parameters, text_embedding, image_embedding, encoder: m3ae.py:305-331)
     resp. the audio ("audio") or the visual ("cav_visual") branch of CAVMAEFT (cav_mae.py:116-145)."""
-    BLOCK_PARAMS = [("layer_norm1.weight", "D"), ("layer_norm1.bias", "D"), ("attention.qkv_linear.weight", "D,3D"),
-                    ("attention.qkv_linear.bias", "3D"), ("attention.fc.weight", "D,D"), ("attention.fc.bias", "D"),
-                    ("layer_norm2.weight", "D"), ("layer_norm2.bias", "D"), ("transformer_mlp.fc1.weight", "D,4D"),
-                    ("transformer_mlp.fc1.bias", "4D"), ("transformer_mlp.fc2.weight", "4D,D"), ("transformer_mlp.fc2.bias", "D")]
 
     def __init__(self, kind: str, device="cuda", depth: int = 12, emb_dim: int = 768, num_heads: int = 12,
                  text_vocab_size: int = 30522, patch_dim: int = 768, seed: Optional[int] = None, conv_math: Optional[str] = None):
@@ -85,22 +105,9 @@ class M3AEEncoder(FlatEncoder):
         self.cav_tokens = {"audio": self.audio_tokens, "cav_visual": 196}.get(kind)      # 224 / 16 squared (cav_mae.py:75)
         self.depth, self.D, self.H, self.V, self.PD = depth, emb_dim, num_heads, text_vocab_size, patch_dim
         D = emb_dim
-        dims = {"D": (D,), "3D": (3 * D,), "4D": (4 * D,), "D,3D": (D, 3 * D), "D,D": (D, D), "D,4D": (D, 4 * D), "4D,D": (4 * D, D)}
-        # ---- flat layout of the parameters this modality trains (Linear weights as [in][out])
-        lay: List[Tuple[str, Tuple[int, ...]]] = []
-        if kind == "text":
-            lay += [("text_embedding.weight", (text_vocab_size, D)), ("encoder_text_type_embedding", (D,)), ("cls_token", (D,))]
-        elif kind == "image":
-            lay += [("image_embedding.weight", (patch_dim, D)), ("image_embedding.bias", (D,)), ("encoder_image_type_embedding", (D,)),
-                    ("cls_token", (D,))]
-        else:   # CAV-MAE: conv patch embed (as [256 | 768][D]), modality embedding, LEARNED position embedding (tr_pos=True)
-            x = self.sfx
-            lay += [(f"patch_embed_{x}.proj.weight", (patch_dim, D)), (f"patch_embed_{x}.proj.bias", (D,)), (f"modality_{x}", (D,)),
-                    (f"pos_embed_{x}", (self.cav_tokens, D))]
-        for i in range(depth):
-            lay += [(f"encoder.blocks.{i}.{n}", dims[s]) for n, s in self.BLOCK_PARAMS]
-        lay += [("encoder.layer_norm.weight", (D,)), ("encoder.layer_norm.bias", (D,))]
-        self._alloc_flat(lay)
+        # ---- the parameters this modality trains, in flat-buffer order
+        self._table: Dict[str, _Param] = {r.name: r for r in self._param_table()}
+        self._alloc_flat([(r.name, r.shape) for r in self._table.values()])
         # ---- parameters of the other modality's input path: never used, never receive a gradient (grad stays None, so
         # SGD skips them, like the reference); registered below with their own storage, reference shapes
         if kind == "text":
@@ -112,34 +119,65 @@ class M3AEEncoder(FlatEncoder):
             unused_shapes = {}   # CAVMAEFT's other branch / unused norms are not materialised (never touched by forward_feat)
         self.unused: Dict[str, nn.Parameter] = {}
         self._register_reference_tree(unused_shapes)
-        self._pos: Dict[int, torch.Tensor] = {}
         self._ws: dict = {}
         self._key = None
         # split-bf16 images of every Linear weight ([K][N] = a 1-tap conv weight)
         self._build_wsplit([(k, k, 1) + shp for k, (_o, shp) in self.layout.items()
                             if len(shp) == 2 and k.endswith(".weight") and k != "text_embedding.weight"])
+        # ---- every layer bound once: what one launch needs of it, as forward / backward_from_pooled read it
+        self.embed = None if kind == "text" else self._bind(f"patch_embed_{self.sfx}.proj" if self.cav else "image_embedding")
+        self._blocks = tuple(_Block(*(self._bind(f"encoder.blocks.{i}.{n}") for n, _kn in _BLOCK_LAYERS)) for i in range(depth))
+        self._norm = self._bind("encoder.layer_norm")
         self.reset_parameters(seed)
 
-    def _w(self, name: str, which: int):
-        """split image of Linear `name` (0: forward, 1: input gradient) or None in f32 mode"""
-        e = self.wsp.get(name)
-        return None if e is None else e[which]
+    def _param_table(self) -> List[_Param]:
+        """The per-kind parameter table.  Initialisation is the reference's module defaults (m3ae.py:306-324; nn.Linear /
+        nn.LayerNorm defaults); reset_parameters draws in table order."""
+        D, PD, x = self.D, self.PD, self.sfx
+        uniform = lambda shp, gen: torch.rand(shp, generator=gen) * 2 - 1
+        normal = lambda shp, gen: torch.randn(shp, generator=gen)
+
+        def linear(name, K, N, bound=None, bias_fan=None, view=_t):   # nn.Linear default: weight and bias U(+-1/sqrt(fan_in))
+            bound, bias_fan = bound or 1.0 / math.sqrt(K), bias_fan or K
+            return [(name + ".weight", (K, N), lambda shp, gen: uniform(shp, gen) * bound, view),
+                    (name + ".bias", (N,), lambda shp, gen: uniform(shp, gen) / math.sqrt(bias_fan), _same)]
+
+        def layer_norm(name):
+            return [(name + ".weight", (D,), lambda shp, gen: torch.ones(shp), _same),
+                    (name + ".bias", (D,), lambda shp, gen: torch.zeros(shp), _same)]
+
+        def type_embedding(name):                                     # torch.empty().normal_(0.02): mean .02, std 1
+            return [(name, (D,), lambda shp, gen: normal(shp, gen) + 0.02, _row)]
+
+        if self.kind == "text":
+            rows = [("text_embedding.weight", (self.V, D), normal, _same)]                                   # normal_(0, 1)
+            rows += type_embedding("encoder_text_type_embedding") + type_embedding("cls_token")
+        elif self.kind == "image":
+            rows = linear("image_embedding", PD, D, bound=math.sqrt(6.0 / (PD + D)))                         # xavier_uniform_
+            rows += type_embedding("encoder_image_type_embedding") + type_embedding("cls_token")
+        else:   # CAV-MAE: conv patch embed (as [256 | 768][D]), modality embedding, LEARNED position embedding (tr_pos=True)
+            # (the conv bias is drawn with the block Linears' bound 1/sqrt(D), not 1/sqrt(PD): seeded weights depend on it)
+            rows = linear(f"patch_embed_{x}.proj", PD, D, bias_fan=D, view=_conv16)
+            rows += [(f"modality_{x}", (D,), lambda shp, gen: normal(shp, gen) * 0.02, _row),               # cav_mae.py:172-173
+                     (f"pos_embed_{x}", (self.cav_tokens, D), lambda shp, gen: self._cav_pos_embed(), _lead)]   # :161-165
+        for i in range(self.depth):
+            for n, kn in _BLOCK_LAYERS:
+                name = f"encoder.blocks.{i}.{n}"
+                rows += layer_norm(name) if kn is None else linear(name, kn[0] * D, kn[1] * D)
+        rows += layer_norm("encoder.layer_norm")
+        return [_Param(*r, self._ref_name(r[0])) for r in rows]
+
+    def _bind(self, name: str):
+        """The layer `name` as the launches read it: a _Norm, or for a 2-D weight a _Linear."""
+        w, b = name + ".weight", name + ".bias"
+        if len(self.layout[w][1]) == 1:
+            return _Norm(self.p[w], self.p[b], self.g[w], self.g[b])
+        return _Linear(self.p[w], self.p.get(b), self.g[w], self.g.get(b), *self.layout[w][1], *self.wsp.get(w, (None, None)))
 
     # ---- reference-named parameter tree -----------------------------------------------------------
     def _to_ref(self, name: str):
         """internal flat view -> reference-shaped VIEW (no copy)."""
-        D = self.D
-        if name in ("patch_embed_a.proj.weight", "patch_embed_v.proj.weight"):
-            # Conv2d(1 | 3, D, 16, 16) weight (cav_mae.py:80): patchify emits a patch as (c, p1, p2), the order of the conv
-            # weight's trailing dimensions, so splitting the transposed view's second dimension is all it takes
-            return lambda t: t.t().view(D, self.PD // 256, 16, 16)
-        if name in ("cls_token", "encoder_text_type_embedding", "encoder_image_type_embedding", "modality_a", "modality_v"):
-            return lambda t: t.view(1, 1, -1)
-        if name in ("pos_embed_a", "pos_embed_v"):
-            return lambda t: t.view(1, *t.shape)
-        if len(self.layout[name][1]) == 2 and name != "text_embedding.weight":
-            return lambda t: t.t()                                                       # nn.Linear.weight is (out, in)
-        return lambda t: t
+        return self._table[name].view
 
     def _register_reference_tree(self, unused_shapes: Dict[str, Tuple[int, ...]]) -> None:
         if self.cav:
@@ -150,8 +188,9 @@ class M3AEEncoder(FlatEncoder):
                      "image_embedding.weight", "image_embedding.bias"]
         order += [k for k in self.layout if k.startswith("encoder.")]
         for name in order:
-            if name in self.layout:
-                p = self._param_view(self.p[name], self.g[name], self._to_ref(name), self._ref_name(name))
+            row = self._table.get(name)
+            if row is not None:
+                p = self._param_view(self.p[name], self.g[name], row.view, row.ref)
             else:
                 p = nn.Parameter(torch.zeros(unused_shapes[name], device=self.device, dtype=torch.float32))
                 p._mla_owner = self
@@ -162,27 +201,11 @@ class M3AEEncoder(FlatEncoder):
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def reset_parameters(self, seed: Optional[int] = None) -> None:
-        """Module-default initialisation of the reference (m3ae.py:306-324; nn.Linear / nn.LayerNorm defaults)."""
+        """Module-default initialisation of the reference, as the parameter table states it."""
         gen = torch.Generator(device="cpu")
         gen.manual_seed(seed) if seed is not None else gen.seed()
-        for name, (_o, shp) in self.layout.items():
-            t = self.p[name]
-            if name == "text_embedding.weight":
-                t.copy_(torch.randn(shp, generator=gen))                                   # normal_(0, 1)
-            elif name in ("cls_token", "encoder_text_type_embedding", "encoder_image_type_embedding"):
-                t.copy_(torch.randn(shp, generator=gen) + 0.02)                            # torch.empty().normal_(0.02): mean .02, std 1
-            elif name in ("modality_a", "modality_v"):
-                t.copy_(torch.randn(shp, generator=gen) * 0.02)                            # cav_mae.py:172-173
-            elif name in ("pos_embed_a", "pos_embed_v"):
-                t.copy_(self._cav_pos_embed())                                             # cav_mae.py:161-165 (sin-cos init, then trained)
-            elif "layer_norm" in name:
-                t.fill_(1.0 if name.endswith("weight") else 0.0)
-            elif len(shp) == 2:
-                bound = math.sqrt(6.0 / (shp[0] + shp[1])) if name == "image_embedding.weight" else 1.0 / math.sqrt(shp[0])
-                t.copy_((torch.rand(shp, generator=gen) * 2 - 1) * bound)
-            else:   # nn.Linear bias: U(-1/sqrt(fan_in), 1/sqrt(fan_in))
-                fan_in = 4 * self.D if name.endswith("fc2.bias") else (self.PD if name == "image_embedding.bias" else self.D)
-                t.copy_((torch.rand(shp, generator=gen) * 2 - 1) / math.sqrt(fan_in))
+        for r in self._table.values():
+            self.p[r.name].copy_(r.init(r.shape, gen))
 
     def _cav_pos_embed(self) -> torch.Tensor:
         """get_2d_sincos_pos_embed(D, 8, L/8) (audio) / (D, 14, 14) (visual) of cav_mae.py:51-66, 161-165 ('w goes first')."""
@@ -201,7 +224,7 @@ class M3AEEncoder(FlatEncoder):
             return name.replace("encoder.layer_norm.", f"norm_{x}.")                       # cav_mae.py:142-143, 350, 363
         _e, _b, i, rest = name.split(".", 3)
         i = int(i)
-        shared = i >= self.depth - 1                                                       # 11 blocks_a|v + 1 blocks_u (cav_mae.py:138-140)
+        shared = i >= self.depth - 1                                             # 11 blocks_a|v + 1 blocks_u (cav_mae.py:138-140)
         pre = f"blocks_u.{i - (self.depth - 1)}." if shared else f"blocks_{x}.{i}."
         sub = {"layer_norm1": f"norm1_{x}" if shared else "norm1", "layer_norm2": f"norm2_{x}" if shared else "norm2",
                "attention.qkv_linear": "attn.qkv", "attention.fc": "attn.proj", "transformer_mlp.fc1": "mlp.fc1",
@@ -212,27 +235,7 @@ class M3AEEncoder(FlatEncoder):
         raise KeyError(name)
 
     def grads_as_reference(self) -> Dict[str, torch.Tensor]:
-        out = {}
-        for name in self.layout:
-            t = self.g[name]
-            if self.cav:
-                key = self._ref_name(name)
-                if name.endswith(".proj.weight"):
-                    out[key] = t.t().contiguous().view(self.D, self.PD // 256, 16, 16)
-                elif name.startswith("modality_"):
-                    out[key] = t.clone().view(1, 1, -1)
-                elif name.startswith("pos_embed_"):
-                    out[key] = t.clone().view(1, *t.shape)
-                else:
-                    out[key] = t.t().contiguous() if t.dim() == 2 else t.clone()
-                continue
-            if name in ("cls_token", "encoder_text_type_embedding", "encoder_image_type_embedding"):
-                out[name] = t.clone().view(1, 1, -1)
-            elif t.dim() == 2 and name != "text_embedding.weight":
-                out[name] = t.t().contiguous()
-            else:
-                out[name] = t.clone()
-        return out
+        return {r.ref: r.view(self.g[r.name]).clone(memory_format=torch.contiguous_format) for r in self._table.values()}
 
     # ------------------------------------------------------------------------------------------
     def _plan(self, B: int, L: int) -> dict:
@@ -278,17 +281,43 @@ class M3AEEncoder(FlatEncoder):
         else:
             ws["dP"] = torch.empty((B, H, n, n), **f32)
         ws["wt_ws"] = torch.empty(4 * D * D, **f32)
-        wb = max(ops.linear_wgrad_ws_bytes(m_, k_, n_, sp, sp and self.bf16) for sp in ((False, True) if self.split else (False,))
-                 for (m_, k_, n_) in ((M, D, 3 * D), (M, D, 4 * D), (M, 4 * D, D), (M, D, D), (B * ws["L"], self.PD, D)))
+        # one weight-gradient workspace: the largest any bound Linear asks for at the rows it really runs on
+        gemms = {(M, lin.K, lin.N) for blk in self._blocks for lin in (blk.qkv, blk.fc, blk.fc1, blk.fc2)}
+        if self.embed is not None:
+            gemms.add((B * ws["L"], self.embed.K, self.embed.N))
+        wb = max(ops.linear_wgrad_ws_bytes(*mkn, sp, sp and self.bf16) for sp in ((False, True) if self.split else (False,))
+                 for mkn in gemms)
         ws["wgrad_ws"] = torch.empty((wb + 3) // 4, **f32)
         ws["red_ws"] = torch.empty(ops.colreduce_ws_elems(M, 4 * D), **f32)
         ws["colsum"] = torch.empty(D, **f32)
 
+    # ---- the Linear launches: the only callers of ops.linear_* here; arithmetic flags and weight image come from the encoder
+    def _lin_fwd(self, lin: _Linear, x, y, rows: int, st, groups: int = 1, y_group_rows: Optional[int] = None, y_off: int = 0,
+                 residual=None, y_gelu=None) -> None:
+        ops.linear_fwd(x, lin.w, lin.b, y, groups, rows, lin.K, lin.N, y_group_rows=y_group_rows, y_off=y_off, residual=residual,
+                       y_gelu=y_gelu, stream=st, bf16=self.bf16, wsplit=lin.img_fwd)
+
+    def _lin_dgrad(self, lin: _Linear, dy, dx, rows: int, ws: dict, st, gelu_src=None) -> None:
+        ops.linear_dgrad(dy, lin.w, dx, ws["wt_ws"], 1, rows, lin.K, lin.N, gelu_src=gelu_src, stream=st, bf16=self.bf16,
+                         wsplit=lin.img_dgrad)
+
+    def _lin_wgrad(self, lin: _Linear, x, dy, rows: int, ws: dict, st, bias: bool = True) -> None:
+        """Weight gradient of one Linear (dw = x^T dy) and, with `bias`, its bias gradient (db = column sums of dy).  On the
+        weight-image arithmetics the bias gradient comes out of the weight-gradient kernel's own pass over dy; otherwise
+        (fp32, or FUSE_BIAS_GRAD off) from a column reduction launched first."""
+        fused = bias and self.split and FUSE_BIAS_GRAD
+        if bias and not fused:
+            ops.colsum_rows(dy, lin.gb, ws["red_ws"], rows, lin.N, stream=st)
+        ops.linear_wgrad(x, dy, lin.gw, ws["wgrad_ws"], 1, rows, lin.K, lin.N, stream=st, split=self.split,
+                         dbias=lin.gb if fused else None, bf16=self.bf16)
+
     # ------------------------------------------------------------------------------------------
-    def forward(self, inp: torch.Tensor, padding_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, inp: torch.Tensor, padding_mask: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """text: inp = token ids (B,1,L) or (B,L) int64, padding_mask (B,1,L)/(B,L) float (1 = padded);
-        image: inp = (B,3,256,256) fp32; audio: inp = (B,1024,128) fp32; cav_visual: inp = (B,3,224,224) fp32.  Returns the (B, D) token-mean feature (basic_model.py:182-200), written into
-        `out` if given (else into the reused workspace buffer)."""
+        image: inp = (B,3,256,256) fp32; audio: inp = (B,1024,128) fp32; cav_visual: inp = (B,3,224,224) fp32.
+        Returns the (B, D) token-mean feature (basic_model.py:182-200), written into `out` if given (else into the reused
+        workspace buffer)."""
         self._await_tail()
         st = ops.cur_stream()
         D, H = self.D, self.H
@@ -302,84 +331,69 @@ class M3AEEncoder(FlatEncoder):
             pm = padding_mask.reshape(B, -1).to(torch.float32)
             if "ids" not in ws:
                 ws["ids"] = torch.empty_like(ids)
-            ws["ids"].copy_(ids)          # owned copy: tokens_assemble_bwd reads it after forward() returned (feeder slots are reused)
+            ws["ids"].copy_(ids)     # owned copy: tokens_assemble_bwd reads it after forward() returned (feeder slots are reused)
             ids = ws["ids"]
-            ws["pm"] = torch.cat([torch.zeros((B, 1), device=self.device), pm], dim=1).contiguous()   # cls is never masked (m3ae.py:347)
+            # cls is never masked (m3ae.py:347)
+            ws["pm"] = torch.cat([torch.zeros((B, 1), device=self.device), pm], dim=1).contiguous()
             ops.tokens_assemble(ws["x0"], self.p["text_embedding.weight"], ids, ws["pos"], self.p["encoder_text_type_embedding"],
                                 self.p["cls_token"], B, L, D, stream=st)
-        elif self.kind == "audio":
-            # cav_mae.py:337-343: (B, time, freq) -> unsqueeze, transpose -> conv16x16/16 -> (B, 8*64, D) + pos + modality
-            B, T_, F_ = inp.shape
-            L = (F_ // 16) * (T_ // 16)
-            if L != self.audio_tokens:
-                raise MLAHipError(f"audio encoder expects {self.audio_tokens} patches, got {L}")
-            ws = self._plan(B, L)
-            ws["pm"] = None
-            ops.patchify(inp.contiguous().float(), ws["patches"], 16, transposed_hw=(F_, T_), stream=st)
-            ops.linear_fwd(ws["patches"], self.p["patch_embed_a.proj.weight"], self.p["patch_embed_a.proj.bias"], ws["x0"], 1, B * L,
-                           self.PD, D, stream=st, bf16=self.bf16, wsplit=self._w("patch_embed_a.proj.weight", 0))
-            ops.tokens_assemble(ws["x0"], None, None, self.p["pos_embed_a"], self.p["modality_a"], None, B, L, D, stream=st)
-        elif self.kind == "cav_visual":
-            # cav_mae.py:352-355: conv16x16/16 over (B, 3, 224, 224) -> (B, 14*14, D) + pos_embed_v + modality_v
-            if inp.dim() != 4 or inp.shape[1] != 3 or (inp.shape[2] // 16) * (inp.shape[3] // 16) != self.cav_tokens:
-                raise MLAHipError(f"cav_visual encoder expects (B, 3, 224, 224), got {tuple(inp.shape)}")
-            B, L = inp.shape[0], self.cav_tokens
-            ws = self._plan(B, L)
-            ws["pm"] = None
-            ops.patchify(inp.contiguous().float(), ws["patches"], 16, stream=st)
-            ops.linear_fwd(ws["patches"], self.p["patch_embed_v.proj.weight"], self.p["patch_embed_v.proj.bias"], ws["x0"], 1, B * L,
-                           self.PD, D, stream=st, bf16=self.bf16, wsplit=self._w("patch_embed_v.proj.weight", 0))
-            ops.tokens_assemble(ws["x0"], None, None, self.p["pos_embed_v"], self.p["modality_v"], None, B, L, D, stream=st)
         else:
-            B = inp.shape[0]
-            L = (inp.shape[2] // 16) * (inp.shape[3] // 16)
+            transposed_hw = None
+            if self.kind == "audio":
+                # cav_mae.py:337-343: (B, time, freq) -> unsqueeze, transpose -> conv16x16/16 -> (B, 8*64, D) + pos + modality
+                B, T_, F_ = inp.shape
+                L = (F_ // 16) * (T_ // 16)
+                if L != self.audio_tokens:
+                    raise MLAHipError(f"audio encoder expects {self.audio_tokens} patches, got {L}")
+                transposed_hw = (F_, T_)
+            elif self.kind == "cav_visual":
+                # cav_mae.py:352-355: conv16x16/16 over (B, 3, 224, 224) -> (B, 14*14, D) + pos_embed_v + modality_v
+                if inp.dim() != 4 or inp.shape[1] != 3 or (inp.shape[2] // 16) * (inp.shape[3] // 16) != self.cav_tokens:
+                    raise MLAHipError(f"cav_visual encoder expects (B, 3, 224, 224), got {tuple(inp.shape)}")
+                B, L = inp.shape[0], self.cav_tokens
+            else:
+                B = inp.shape[0]
+                L = (inp.shape[2] // 16) * (inp.shape[3] // 16)
             ws = self._plan(B, L)
             ws["pm"] = None
-            ops.patchify(inp.contiguous(), ws["patches"], 16, stream=st)                     # basic_model.py:184-186
-            ops.linear_fwd(ws["patches"], self.p["image_embedding.weight"], self.p["image_embedding.bias"], ws["x0"], B, L,
-                           self.PD, D, y_group_rows=L + 1, y_off=1, stream=st, bf16=self.bf16, wsplit=self._w("image_embedding.weight", 0))               # m3ae.py:353
-            ops.tokens_assemble(ws["x0"], None, None, ws["pos"], self.p["encoder_image_type_embedding"], self.p["cls_token"],
-                                B, L, D, stream=st)
+            img = inp.contiguous().float() if self.cav else inp.contiguous()
+            ops.patchify(img, ws["patches"], 16, transposed_hw=transposed_hw, stream=st)     # basic_model.py:184-186
+            if self.cav:
+                self._lin_fwd(self.embed, ws["patches"], ws["x0"], B * L, st)
+                ops.tokens_assemble(ws["x0"], None, None, self.p[f"pos_embed_{self.sfx}"], self.p[f"modality_{self.sfx}"], None,
+                                    B, L, D, stream=st)
+            else:   # the patch rows land behind each sample's [cls] row (m3ae.py:353)
+                self._lin_fwd(self.embed, ws["patches"], ws["x0"], L, st, groups=B, y_group_rows=L + 1, y_off=1)
+                ops.tokens_assemble(ws["x0"], None, None, ws["pos"], self.p["encoder_image_type_embedding"], self.p["cls_token"],
+                                    B, L, D, stream=st)
         n, M = ws["n"], ws["M"]
         scale = hd ** -0.5
         x = ws["x0"]
-        for i, bk in enumerate(ws["blocks"]):
-            P_ = lambda nm: self.p[f"encoder.blocks.{i}.{nm}"]
+        for blk, bk in zip(self._blocks, ws["blocks"]):
             bk["x"] = x
-            ops.layernorm_fwd(x, P_("layer_norm1.weight"), P_("layer_norm1.bias"), bk["h1"], bk["st"][0], bk["st"][1], M, D, stream=st)
-            ops.linear_fwd(bk["h1"], P_("attention.qkv_linear.weight"), P_("attention.qkv_linear.bias"), bk["qkv"], 1, M, D, 3 * D, stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.attention.qkv_linear.weight", 0))
+            ops.layernorm_fwd(x, blk.ln1.w, blk.ln1.b, bk["h1"], bk["st"][0], bk["st"][1], M, D, stream=st)
+            self._lin_fwd(blk.qkv, bk["h1"], bk["qkv"], M, st)
             if self.attention == "fused":
-                ops.attention_fwd(bk["qkv"], ws["pm"], bk["o"], bk["lse"], B, H, n, hd, stream=st)                                   # m3ae.py:109-122
-            else:
-                qs, ss, os_ = (n * 3 * D, hd, 3 * D, 1), (H * n * n, n * n, n, 1), (n * D, hd, D, 1)
-                ops.bgemm(bk["qkv"], bk["qkv"], bk["P"], B, H, n, n, hd, qs, (n * 3 * D, hd, 1, 3 * D), ss, scale, b_off=D, stream=st)   # m3ae.py:109
-                ops.softmax_fwd(bk["P"], ws["pm"], B, H, n, stream=st)                                                                    # :111-118
-                ops.bgemm(bk["P"], bk["qkv"], bk["o"], B, H, n, hd, n, ss, (n * 3 * D, hd, 3 * D, 1), os_, 1.0, b_off=2 * D, stream=st)   # :121-122
-            ops.linear_fwd(bk["o"], P_("attention.fc.weight"), P_("attention.fc.bias"), bk["xmid"], 1, M, D, D, residual=x, stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.attention.fc.weight", 0))  # :123,149
-            ops.layernorm_fwd(bk["xmid"], P_("layer_norm2.weight"), P_("layer_norm2.bias"), bk["h2"], bk["st"][2], bk["st"][3], M, D, stream=st)
-            ops.linear_fwd(bk["h2"], P_("transformer_mlp.fc1.weight"), P_("transformer_mlp.fc1.bias"), bk["u"], 1, M, D, 4 * D,
-                           y_gelu=bk["gl"], stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc1.weight", 0))                                                                               # :76-77
-            ops.linear_fwd(bk["gl"], P_("transformer_mlp.fc2.weight"), P_("transformer_mlp.fc2.bias"), bk["xout"], 1, M, 4 * D, D,
-                           residual=bk["xmid"], stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc2.weight", 0))                                                                            # :79,154
+                ops.attention_fwd(bk["qkv"], ws["pm"], bk["o"], bk["lse"], B, H, n, hd, stream=st)            # m3ae.py:109-122
+            else:   # element strides (batch, head, row, col) of q | k | v inside qkv, of k^T, of the scores, of o
+                qs, kt, os_ = (n * 3 * D, hd, 3 * D, 1), (n * 3 * D, hd, 1, 3 * D), (n * D, hd, D, 1)
+                ss = (H * n * n, n * n, n, 1)
+                ops.bgemm(bk["qkv"], bk["qkv"], bk["P"], B, H, n, n, hd, qs, kt, ss, scale, b_off=D, stream=st)   # m3ae.py:109
+                ops.softmax_fwd(bk["P"], ws["pm"], B, H, n, stream=st)                                            # :111-118
+                ops.bgemm(bk["P"], bk["qkv"], bk["o"], B, H, n, hd, n, ss, qs, os_, 1.0, b_off=2 * D, stream=st)  # :121-122
+            self._lin_fwd(blk.fc, bk["o"], bk["xmid"], M, st, residual=x)                                     # :123,149
+            ops.layernorm_fwd(bk["xmid"], blk.ln2.w, blk.ln2.b, bk["h2"], bk["st"][2], bk["st"][3], M, D, stream=st)
+            self._lin_fwd(blk.fc1, bk["h2"], bk["u"], M, st, y_gelu=bk["gl"])                                 # :76-77
+            self._lin_fwd(blk.fc2, bk["gl"], bk["xout"], M, st, residual=bk["xmid"])                          # :79,154
             x = bk["xout"]
         ws["xlast"] = x
-        ops.layernorm_fwd(x, self.p["encoder.layer_norm.weight"], self.p["encoder.layer_norm.bias"], ws["y"], ws["stf"][0], ws["stf"][1],
-                          M, D, stream=st)                                                                                            # m3ae.py:176
+        ops.layernorm_fwd(x, self._norm.w, self._norm.b, ws["y"], ws["stf"][0], ws["stf"][1], M, D, stream=st)   # m3ae.py:176
         feat = ws["feat"] if out is None else out
         ops.avgpool_fwd(ws["y"], feat, B, n, D, stream=st)                                    # .mean(dim=1) over all 1+L tokens
         self._pa = n
         return feat
 
     # ------------------------------------------------------------------------------------------
-    def _wgrad_bias(self, x, dy, dw, db, wgw, red, M: int, K: int, N: int, st) -> None:
-        """Weight and bias gradient of one Linear (dw = x^T dy, db = column sums of dy).  On the split arithmetic the bias
-        gradient comes out of the weight-gradient kernel's own pass over dy (no separate column-reduction launches)."""
-        if self.split and FUSE_BIAS_GRAD:
-            ops.linear_wgrad(x, dy, dw, wgw, 1, M, K, N, stream=st, split=True, dbias=db, bf16=self.bf16)
-        else:
-            ops.colsum_rows(dy, db, red, M, N, stream=st)
-            ops.linear_wgrad(x, dy, dw, wgw, 1, M, K, N, stream=st, split=self.split, bf16=self.bf16)
-
     def backward_from_pooled(self, dfeat: torch.Tensor, P: Optional[int] = None) -> None:
         ws = self._ws
         self._bwd_ws(ws)
@@ -388,39 +402,36 @@ class M3AEEncoder(FlatEncoder):
         hd = D // H
         scale = hd ** -0.5
         dA, dB_, dC = ws["dA"], ws["dB"], ws["dC"]
-        red, wtw, wgw = ws["red_ws"], ws["wt_ws"], ws["wgrad_ws"]
+        red = ws["red_ws"]
         ops.avgpool_bwd(dfeat.contiguous(), dA, B, n, D, stream=st)                                             # d y
-        ops.layernorm_bwd(dA, ws["xlast"], self.p["encoder.layer_norm.weight"], ws["stf"][0], ws["stf"][1], dA,
-                          self.g["encoder.layer_norm.weight"], self.g["encoder.layer_norm.bias"], red, M, D, stream=st)
-        dx = dA                                                                                                 # grad wrt block output
-        for i in reversed(range(self.depth)):
-            bk = ws["blocks"][i]
-            P_ = lambda nm: self.p[f"encoder.blocks.{i}.{nm}"]
-            G_ = lambda nm: self.g[f"encoder.blocks.{i}.{nm}"]
+        ops.layernorm_bwd(dA, ws["xlast"], self._norm.w, ws["stf"][0], ws["stf"][1], dA, self._norm.gw, self._norm.gb, red, M, D,
+                          stream=st)
+        dx = dA                                                                                            # grad wrt block output
+        for blk, bk in zip(reversed(self._blocks), reversed(ws["blocks"])):
             # ---- MLP: xout = xmid + fc2(gelu(fc1(LN2(xmid))))
-            self._wgrad_bias(bk["gl"], dx, G_("transformer_mlp.fc2.weight"), G_("transformer_mlp.fc2.bias"), wgw, red, M, 4 * D, D, st)
-            ops.linear_dgrad(dx, P_("transformer_mlp.fc2.weight"), ws["du"], wtw, 1, M, 4 * D, D, gelu_src=bk["u"], stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc2.weight", 1))
-            self._wgrad_bias(bk["h2"], ws["du"], G_("transformer_mlp.fc1.weight"), G_("transformer_mlp.fc1.bias"), wgw, red, M, D, 4 * D, st)
-            ops.linear_dgrad(ws["du"], P_("transformer_mlp.fc1.weight"), dB_, wtw, 1, M, D, 4 * D, stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.transformer_mlp.fc1.weight", 1))   # d h2
-            ops.layernorm_bwd(dB_, bk["xmid"], P_("layer_norm2.weight"), bk["st"][2], bk["st"][3], dB_, G_("layer_norm2.weight"),
-                              G_("layer_norm2.bias"), red, M, D, add=dx, stream=st)                             # d xmid -> dB_
+            self._lin_wgrad(blk.fc2, bk["gl"], dx, M, ws, st)
+            self._lin_dgrad(blk.fc2, dx, ws["du"], M, ws, st, gelu_src=bk["u"])
+            self._lin_wgrad(blk.fc1, bk["h2"], ws["du"], M, ws, st)
+            self._lin_dgrad(blk.fc1, ws["du"], dB_, M, ws, st)                                                  # d h2
+            ops.layernorm_bwd(dB_, bk["xmid"], blk.ln2.w, bk["st"][2], bk["st"][3], dB_, blk.ln2.gw, blk.ln2.gb, red, M, D,
+                              add=dx, stream=st)                                                                # d xmid -> dB_
             # ---- attention: xmid = x + fc(PV)
-            self._wgrad_bias(bk["o"], dB_, G_("attention.fc.weight"), G_("attention.fc.bias"), wgw, red, M, D, D, st)
-            ops.linear_dgrad(dB_, P_("attention.fc.weight"), dC, wtw, 1, M, D, D, stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.attention.fc.weight", 1))                    # d o (B,n,D)
+            self._lin_wgrad(blk.fc, bk["o"], dB_, M, ws, st)
+            self._lin_dgrad(blk.fc, dB_, dC, M, ws, st)                                                         # d o (B,n,D)
             if self.attention == "fused":
                 ops.attention_bwd(dC, bk["qkv"], bk["o"], bk["lse"], ws["pm"], ws["dqkv"], ws["dvec"], B, H, n, hd, stream=st)
             else:
-                qs, ss, os_ = (n * 3 * D, hd, 3 * D, 1), (H * n * n, n * n, n, 1), (n * D, hd, D, 1)
-                ops.bgemm(dC, bk["qkv"], ws["dP"], B, H, n, n, hd, os_, (n * 3 * D, hd, 1, 3 * D), ss, 1.0, b_off=2 * D, stream=st)          # dP = dO V^T
-                ops.bgemm(bk["P"], dC, ws["dqkv"], B, H, n, hd, n, (H * n * n, n * n, 1, n), (n * D, hd, D, 1), qs, 1.0, c_off=2 * D, stream=st)   # dV = P^T dO
-                ops.softmax_bwd(bk["P"], ws["dP"], B, H, n, stream=st)                                                                       # dS
-                ops.bgemm(ws["dP"], bk["qkv"], ws["dqkv"], B, H, n, hd, n, ss, (n * 3 * D, hd, 3 * D, 1), qs, scale, b_off=D, stream=st)     # dQ = s dS K
-                ops.bgemm(ws["dP"], bk["qkv"], ws["dqkv"], B, H, n, hd, n, (H * n * n, n * n, 1, n), (n * 3 * D, hd, 3 * D, 1), qs, scale,
-                          c_off=D, stream=st)                                                                                                # dK = s dS^T Q
-            self._wgrad_bias(bk["h1"], ws["dqkv"], G_("attention.qkv_linear.weight"), G_("attention.qkv_linear.bias"), wgw, red, M, D, 3 * D, st)
-            ops.linear_dgrad(ws["dqkv"], P_("attention.qkv_linear.weight"), dC, wtw, 1, M, D, 3 * D, stream=st, bf16=self.bf16, wsplit=self._w(f"encoder.blocks.{i}.attention.qkv_linear.weight", 1))  # d h1
-            ops.layernorm_bwd(dC, bk["x"], P_("layer_norm1.weight"), bk["st"][0], bk["st"][1], dC, G_("layer_norm1.weight"),
-                              G_("layer_norm1.bias"), red, M, D, add=dB_, stream=st)                            # d x -> dC
+                qs, kt, os_ = (n * 3 * D, hd, 3 * D, 1), (n * 3 * D, hd, 1, 3 * D), (n * D, hd, D, 1)       # as in forward
+                ss, sT = (H * n * n, n * n, n, 1), (H * n * n, n * n, 1, n)                                  # scores, scores^T
+                ops.bgemm(dC, bk["qkv"], ws["dP"], B, H, n, n, hd, os_, kt, ss, 1.0, b_off=2 * D, stream=st)        # dP = dO V^T
+                ops.bgemm(bk["P"], dC, ws["dqkv"], B, H, n, hd, n, sT, os_, qs, 1.0, c_off=2 * D, stream=st)        # dV = P^T dO
+                ops.softmax_bwd(bk["P"], ws["dP"], B, H, n, stream=st)                                              # dS
+                ops.bgemm(ws["dP"], bk["qkv"], ws["dqkv"], B, H, n, hd, n, ss, qs, qs, scale, b_off=D, stream=st)   # dQ = s dS K
+                ops.bgemm(ws["dP"], bk["qkv"], ws["dqkv"], B, H, n, hd, n, sT, qs, qs, scale, c_off=D, stream=st)  # dK = s dS^T Q
+            self._lin_wgrad(blk.qkv, bk["h1"], ws["dqkv"], M, ws, st)
+            self._lin_dgrad(blk.qkv, ws["dqkv"], dC, M, ws, st)                                                 # d h1
+            ops.layernorm_bwd(dC, bk["x"], blk.ln1.w, bk["st"][0], bk["st"][1], dC, blk.ln1.gw, blk.ln1.gb, red, M, D,
+                              add=dB_, stream=st)                                                               # d x -> dC
             dx, dC = dC, dx                                                                                     # rotate buffers
             ws["dA"], ws["dC"] = dx, dC
         # ---- token assembly (m3ae.py:342-366)
@@ -428,13 +439,12 @@ class M3AEEncoder(FlatEncoder):
         if self.cav:
             # x0 = conv(patches) + pos_embed + modality: d modality = d conv-bias = sum over all tokens,
             # d pos[i] = sum over the batch, d conv-weight = patches^T dx
-            x = self.sfx
-            self.g[f"modality_{x}"].copy_(ws["colsum"])
-            self.g[f"patch_embed_{x}.proj.bias"].copy_(ws["colsum"])
+            self.g[f"modality_{self.sfx}"].copy_(ws["colsum"])
+            self.embed.gb.copy_(ws["colsum"])
             if "red_pos" not in ws:
                 ws["red_pos"] = torch.empty(ops.colreduce_ws_elems(B, L * D), device=self.device, dtype=torch.float32)
-            ops.colsum_rows(dx, self.g[f"pos_embed_{x}"], ws["red_pos"], B, L * D, stream=st)
-            ops.linear_wgrad(ws["patches"], dx, self.g[f"patch_embed_{x}.proj.weight"], wgw, 1, B * L, self.PD, D, stream=st, split=self.split, bf16=self.bf16)
+            ops.colsum_rows(dx, self.g[f"pos_embed_{self.sfx}"], ws["red_pos"], B, L * D, stream=st)
+            self._lin_wgrad(self.embed, ws["patches"], dx, B * L, ws, st, bias=False)
         elif self.kind == "text":
             self.g["text_embedding.weight"].zero_()
             if "emb_ws" not in ws:
@@ -444,9 +454,10 @@ class M3AEEncoder(FlatEncoder):
         else:
             ops.tokens_assemble_bwd(dx, ws["colsum"], None, self.g["cls_token"], self.g["encoder_image_type_embedding"], None,
                                     B, L, D, stream=st)
+            # the embed's bias gradient sums the patch rows only, so it is reduced here and not inside the weight gradient
             dimg = dx.view(B, n, D)[:, 1:, :].contiguous().view(B * L, D)       # memory plumbing: drop the cls rows
-            ops.colsum_rows(dimg, self.g["image_embedding.bias"], red, B * L, D, stream=st)
-            ops.linear_wgrad(ws["patches"], dimg, self.g["image_embedding.weight"], wgw, 1, B * L, self.PD, D, stream=st, split=self.split, bf16=self.bf16)
+            ops.colsum_rows(dimg, self.embed.gb, red, B * L, D, stream=st)
+            self._lin_wgrad(self.embed, ws["patches"], dimg, B * L, ws, st, bias=False)
 
 
 class M3AEClassifier(_Classifier):
