@@ -453,6 +453,18 @@ int mla_softmax_bwd(const float* P, float* dP, int B, int H, int n, void* stream
 int mla_attention_fwd(const float* qkv, const float* pad_mask, float* o, float* lse, int B, int H, int n, int hd, void* stream);
 int mla_attention_bwd(const float* d_o, const float* qkv, const float* o, const float* lse, const float* pad_mask,
                       float* dqkv, float* dvec, int B, int H, int n, int hd, void* stream);
+/* The same attention (models/m3ae.py:102-125; cav_mae.py:93) on the split-bf16 arithmetic: fp32 in, out and accumulate, the five
+ * products (S = Q K^T, O = P V, dP = dO V^T, dQ = dS K, dK = dS^T Q, dV = P^T dO) from the exact three-way bf16 split of both
+ * operands, six kept products on the 32x32x16 bf16 MFMA (the arithmetic of mla_conv2d_*_split and the split Linear).  Arguments,
+ * layouts, the rejections (hd != 64, n <= 0, B * n * 3 * H * hd >= 2^31: MLA_ERR_INVALID_ARG before any launch), the mask rule
+ * and the bitwise reproducibility are mla_attention_fwd / _bwd's; n <= 3 runs their vector kernels.  Same accuracy against fp64
+ * (profiles/attention_split_score_range.json).  Time of forward + backward relative to mla_attention_fwd / _bwd, same process, three
+ * runs each, B = 64, H = 12 (larger (max - min) / median of the two in brackets; profiles/r07_attention_math.txt):
+ * faster at tile-aligned lengths -- n = 256: 0.70 masked [0.017], 0.72 [0.016]; 288: 0.70 [0.006]; 512 (B = 32): 0.68 [0.037] --, level
+ * at n = 257 (0.955 masked [0.073], 0.950 [0.005]), slower with two or three remainder rows (n = 258: 1.16 [0.002]). */
+int mla_attention_fwd_split(const float* qkv, const float* pad_mask, float* o, float* lse, int B, int H, int n, int hd, void* stream);
+int mla_attention_bwd_split(const float* d_o, const float* qkv, const float* o, const float* lse, const float* pad_mask,
+                            float* dqkv, float* dvec, int B, int H, int n, int hd, void* stream);
 /* forward_representation token assembly (m3ae.py:342-366): x0[b][0] = cls; x0[b][1+i] = (table[ids[b][i]] if
  * table else x0[b][1+i]) + pos[i] + type.  x0 is (B, L+1, D).  cls == NULL (CAV-MAE, cav_mae.py:341-343): no
  * [cls] row, x0 is (B, L, D) and x0[b][i] += pos[i] + type.  V = rows of `table`; a token id outside [0, V) makes its row

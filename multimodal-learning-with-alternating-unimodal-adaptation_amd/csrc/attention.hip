@@ -26,59 +26,11 @@
 // Masking: keys beyond n do not exist (-inf, probability exactly 0); padded keys (mask > 0) have their score REPLACED by
 // -1e7 like the reference, which underflows to probability exactly 0 in fp32 unless a whole row is padded (never: the
 // [cls] key is always present, m3ae.py:347).
-#include "common.h"
-
-#define ATT_HD 64          // head dim (ViT-B: 768 / 12)
-#define ATT_LD 68          // padded LDS row (floats): 17 x 16 B -> conflict-free ds_read_b128 across 32 rows
-#define ATT_TAIL_MAX 3     // n % 32 <= this: the remainder rows take the vector path
-#define ATT_TAIL_N 4096    // longest sequence the one-wave tail kernels hold in LDS
+// The geometry, the tile loads, the accumulator-layout helpers, the mask rule and the host-side kernel selection live in
+// attention_common.h, shared with attention_split.hip (the same kernels on the split-bf16 arithmetic).
+#include "attention_common.h"
 
 namespace {
-
-// exp via v_exp_f32 (2^x): the accurate expf expands to ~20 VALU instructions, 16 of them per lane and key tile were a
-// quarter of the forward's issue slots.  Relative error <= |x| 2^-23 (the rounding of x * log2 e), i.e. < 3e-6 for the
-// score range a softmax row can hold before the result underflows anyway; arguments of -inf / -1e7 give exactly 0.
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-
-__device__ __forceinline__ int acc_row(int e, int half) { return (e & 3) + 8 * (e >> 2) + 4 * half; }
-
-struct AttGeom {
-  const float* qkv;        // (B, n, 3, H, 64)
-  const float* pm;         // (B, n) or null
-  int B, H, n;
-  int nm;                  // rows [0, nm) are handled by the MFMA kernels (nm % 32 == 0 or nm == n); rows [nm, n) -- at most
-                           // ATT_TAIL_MAX of them -- by vector code: the [cls] token makes n = 257 = 8 tiles + 1, and a ninth
-                           // 32-wide tile / a ninth wave block for that one row cost 60 % more time than n = 256
-  float scale;
-};
-
-// byte-free helpers: element offset of (b, t, which, h, 0)
-__device__ __forceinline__ size_t qkv_off(const AttGeom& g, int b, int t, int which, int h) {
-  return (((size_t)b * g.n + t) * 3 + which) * (size_t)(g.H * ATT_HD) + (size_t)h * ATT_HD;
-}
-
-// One 32 x 64 tile (rows t0.., zero-filled beyond n) from global into registers / from registers into padded LDS.
-// NT threads: float4 slot idx = tid + NT p of the 512 (row = idx / 16, float4 column idx % 16).
-template <int NT>
-struct TileRegs {
-  static constexpr int P = (512 + NT - 1) / NT;
-  f32x4 r[P];
-  __device__ __forceinline__ void load(const float* base, size_t row_stride, int t0, int n, int tid) {
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-      const int idx = tid + NT * p, row = idx >> 4;
-      r[p] = (idx < 512 && t0 + row < n) ? *reinterpret_cast<const f32x4*>(base + (size_t)(t0 + row) * row_stride + (idx & 15) * 4)
-                                         : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
-  __device__ __forceinline__ void store(float* lds, int tid) const {
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-      const int idx = tid + NT * p;
-      if (idx < 512) *reinterpret_cast<f32x4*>(&lds[(idx >> 4) * ATT_LD + (idx & 15) * 4]) = r[p];
-    }
-  }
-};
 
 // 32 registers of the B operand of a wave-owned row block: lane (row = lane % 32, half) holds X[row][half * 32 + kk]
 __device__ __forceinline__ void own_rows_load(float (&x)[32], const float* base, size_t row_stride, int row, int n, int half) {
@@ -117,31 +69,6 @@ __device__ __forceinline__ void mma_tileT_acc(f32x16& o0, f32x16& o1, const floa
   }
 }
 
-// Write a wave's transposed 64 x 32 result (o0 / o1: row = feature, column = own row) to global rows of 64 floats.
-// stage: this wave's 32 x ATT_LD floats of LDS.
-__device__ __forceinline__ void store_ownT(float* stage, const f32x16& o0, const f32x16& o1, float* dst, size_t row_stride,
-                                            int row0, int n, int lane, float mul) {
-  const int half = lane >> 5, c = lane & 31;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    stage[c * ATT_LD + acc_row(e, half)] = o0[e] * mul;
-    stage[c * ATT_LD + 32 + acc_row(e, half)] = o1[e] * mul;
-  }
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int p = 0; p < 8; ++p) {
-    const int idx = p * 64 + lane, r = idx >> 4, c4 = idx & 15;
-    if (row0 + r < n)
-      *reinterpret_cast<f32x4*>(dst + (size_t)(row0 + r) * row_stride + c4 * 4) = *reinterpret_cast<const f32x4*>(&stage[r * ATT_LD + c4 * 4]);
-  }
-}
-
-// key state of a tile: 0 = attend, 1 = padded (score := -1e7), 2 = beyond n
-__device__ __forceinline__ float key_state(const AttGeom& g, int b, int key, int limit) {
-  if (key >= limit) return 2.f;
-  return (g.pm && g.pm[(size_t)b * g.n + key] > 0.f) ? 1.f : 0.f;
-}
-
 // dot product of a wave-owned row (lane: row lane % 32, dims half * 32 ..) with one broadcast row of 64 floats
 __device__ __forceinline__ float own_dot(const float (&own)[32], const float* __restrict__ row, int half) {
   const f32x4* p = reinterpret_cast<const f32x4*>(row + half * 32);
@@ -152,14 +79,6 @@ __device__ __forceinline__ float own_dot(const float (&own)[32], const float* __
     d += own[4 * c] * v[0] + own[4 * c + 1] * v[1] + own[4 * c + 2] * v[2] + own[4 * c + 3] * v[3];
   }
   return d + __shfl_xor(d, 32, 64);
-}
-// out^T (+)= row (x) w : rank-1 update of a transposed 64 x 32 accumulator pair with one broadcast row and a per-lane weight
-__device__ __forceinline__ void own_axpy(f32x16& o0, f32x16& o1, const float* __restrict__ row, float w, int half) {
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    o0[e] += row[acc_row(e, half)] * w;
-    o1[e] += row[32 + acc_row(e, half)] * w;
-  }
 }
 
 // ---- vector code for OWNED remainder rows, run by one wave per (b, h) on the tiles in LDS: a dot product per tile row (lane = row,
@@ -844,32 +763,6 @@ __global__ __launch_bounds__(64 * ATT_TW) void attn_bwd_dkv_tail_kernel(const At
     dqkv[qkv_off(g, b, key, 1, h) + tid] = dk;
     dqkv[qkv_off(g, b, key, 2, h) + tid] = dv;
   }
-}
-
-// rows the MFMA kernels own: everything, unless the last partial tile holds <= ATT_TAIL_MAX rows
-int att_main_rows(int n) {
-  const int r = n % 32;
-  return (r > 0 && r <= ATT_TAIL_MAX && n <= ATT_TAIL_N) ? n - r : n;
-}
-
-// Waves (= blocks of 32 owned rows) per workgroup: the sequence is cut into ceil(n / 32) wave blocks and a workgroup whose
-// last waves have no rows keeps its CU slot for the whole key loop, so pick the width that leaves the fewest idle waves
-// (n = 257 = cls + 256: nine blocks -> three workgroups of three waves instead of 4 + 4 + 1; n = 512: four).
-int att_waves(int n) {
-  const int blocks = (n + 31) / 32;
-  int best = 4, best_idle = 1 << 30;
-  for (int w = 4; w >= 2; --w) {
-    const int idle = ((blocks + w - 1) / w) * w - blocks;
-    if (idle < best_idle) { best = w; best_idle = idle; }
-  }
-  return best;
-}
-
-int check_att(const char* who, int B, int H, int n, int hd) {
-  MLA_REQUIRE(B > 0 && H > 0 && n > 0, "%s: non-positive dims", who);
-  MLA_REQUIRE(hd == ATT_HD, "%s: head dim %d unsupported (64)", who, hd);
-  MLA_REQUIRE((long)B * H < 65536 && (long)B * n * 3 * H * hd < (1L << 31), "%s: problem too large", who);
-  return MLA_OK;
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// Pieces shared by the split-bf16 kernels (conv_igemm_split.hip, conv_patch_split.hip, wgrad_tr_split.hip, stem_split.hip):
+// Pieces shared by the split-bf16 kernels (conv_igemm_split.hip, conv_patch_split.hip, wgrad_tr_split.hip, stem_split.hip, attention_split.hip):
 // fp32 -> three bf16 terms, the product set, and the MFMA / LDS idioms every one of those kernels is built from.
 #pragma once
 #include "igemm_common.h"
@@ -8,6 +8,14 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+// ds_read_b64_tr_b16, gfx950's transposing LDS read: a 16-lane group reads 4 rows x 16 columns of 16-bit elements (lane 4q + p
+// supplies the 8-byte-aligned address of row q, columns 4p .. 4p+3) and lane c of the group receives column c of the 4 rows.
+// EXEC must be all ones.
+__device__ __forceinline__ s16x4 lds_tr(const unsigned* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)p);
+}
 
 __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {   // low half = bf16(a), high half = bf16(b), RNE
   f32x2 v = {a, b};

@@ -18,8 +18,6 @@
 
 namespace {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int WT_TH = 8, WT_TW = 8;                      // output tile
 constexpr int WT_SW = WT_TW + 2, WT_SH = WT_TH + 2;      // input patch (halo 1)
 constexpr int WT_SPX = WT_SW * WT_SH;                    // 100 patch pixels
@@ -39,10 +37,6 @@ struct WtGeom {
 };
 
 __device__ __forceinline__ unsigned wt_off_or_oob(int ok, unsigned off) { return off | ((unsigned)ok - 1u); }
-
-__device__ __forceinline__ s16x4 lds_tr(const unsigned* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)p);
-}
 
 template <bool BNIN>
 __global__ __launch_bounds__(512, 2) void wgrad_tr_split_kernel(const float* __restrict__ X, const float* __restrict__ dY,

@@ -82,7 +82,8 @@ class M3AEEncoder(FlatEncoder):
     resp. the audio ("audio") or the visual ("cav_visual") branch of CAVMAEFT (cav_mae.py:116-145)."""
 
     def __init__(self, kind: str, device="cuda", depth: int = 12, emb_dim: int = 768, num_heads: int = 12,
-                 text_vocab_size: int = 30522, patch_dim: int = 768, seed: Optional[int] = None, conv_math: Optional[str] = None):
+                 text_vocab_size: int = 30522, patch_dim: int = 768, seed: Optional[int] = None, conv_math: Optional[str] = None,
+                 attention_math: Optional[str] = None):
         if kind not in ("text", "image", "audio", "cav_visual"):
             raise ValueError("kind must be 'text', 'image', 'audio' or 'cav_visual'")
         super().__init__(device, conv_math)                  # conv_math: here the arithmetic of the Linear GEMMs
@@ -93,6 +94,13 @@ class M3AEEncoder(FlatEncoder):
         self.attention = os.environ.get("MLA_ATTENTION", "fused")
         if self.attention not in ("fused", "materialized"):
             raise MLAHipError(f"MLA_ATTENTION must be 'fused' or 'materialized', got {self.attention!r}")
+        # arithmetic of the fused kernels' five products: "f32" (fp32 MFMA, csrc/attention.hip) or "split" (exact three-way bf16
+        # split, six products on the bf16 MFMA, csrc/attention_split.hip; same accuracy).  Independent of conv_math.
+        self.attention_math = attention_math or os.environ.get("MLA_ATTENTION_MATH", "f32")
+        if self.attention_math not in ops.ATTENTION_MATHS:
+            raise MLAHipError(f"attention_math must be 'f32' or 'split', got {self.attention_math!r}")
+        if self.attention_math == "split" and self.attention == "materialized":
+            raise MLAHipError("attention_math='split' needs the fused attention kernels (MLA_ATTENTION=materialized is set)")
         self.kind = kind
         self.cav = kind in ("audio", "cav_visual")
         self.sfx = {"audio": "a", "cav_visual": "v"}.get(kind)       # CAVMAEFT's per-modality name suffix
@@ -374,7 +382,7 @@ class M3AEEncoder(FlatEncoder):
             ops.layernorm_fwd(x, blk.ln1.w, blk.ln1.b, bk["h1"], bk["st"][0], bk["st"][1], M, D, stream=st)
             self._lin_fwd(blk.qkv, bk["h1"], bk["qkv"], M, st)
             if self.attention == "fused":
-                ops.attention_fwd(bk["qkv"], ws["pm"], bk["o"], bk["lse"], B, H, n, hd, stream=st)            # m3ae.py:109-122
+                ops.attention_fwd(bk["qkv"], ws["pm"], bk["o"], bk["lse"], B, H, n, hd, stream=st, math=self.attention_math)   # m3ae.py:109-122
             else:   # element strides (batch, head, row, col) of q | k | v inside qkv, of k^T, of the scores, of o
                 qs, kt, os_ = (n * 3 * D, hd, 3 * D, 1), (n * 3 * D, hd, 1, 3 * D), (n * D, hd, D, 1)
                 ss = (H * n * n, n * n, n, 1)
@@ -419,7 +427,8 @@ class M3AEEncoder(FlatEncoder):
             self._lin_wgrad(blk.fc, bk["o"], dB_, M, ws, st)
             self._lin_dgrad(blk.fc, dB_, dC, M, ws, st)                                                         # d o (B,n,D)
             if self.attention == "fused":
-                ops.attention_bwd(dC, bk["qkv"], bk["o"], bk["lse"], ws["pm"], ws["dqkv"], ws["dvec"], B, H, n, hd, stream=st)
+                ops.attention_bwd(dC, bk["qkv"], bk["o"], bk["lse"], ws["pm"], ws["dqkv"], ws["dvec"], B, H, n, hd, stream=st,
+                                  math=self.attention_math)
             else:
                 qs, kt, os_ = (n * 3 * D, hd, 3 * D, 1), (n * 3 * D, hd, 1, 3 * D), (n * D, hd, D, 1)       # as in forward
                 ss, sT = (H * n * n, n * n, n, 1), (H * n * n, n * n, 1, n)                                  # scores, scores^T
@@ -466,9 +475,9 @@ class M3AEClassifier(_Classifier):
     fusion_module(a, v) itself (main.py:236-237)."""
 
     def __init__(self, args, device="cuda", depth: int = 12, text_vocab_size: int = 30522, seed: Optional[int] = None,
-                 conv_math: Optional[str] = None):
+                 conv_math: Optional[str] = None, attention_math: Optional[str] = None):
         super().__init__(args, device, seed, ("Food101", "MVSA", "CREMAD"), ConcatFusion, 768, 2)             # :132-163
-        kw = dict(depth=depth, text_vocab_size=text_vocab_size, conv_math=conv_math)
+        kw = dict(depth=depth, text_vocab_size=text_vocab_size, conv_math=conv_math, attention_math=attention_math)
         self.mae_a = M3AEEncoder("text", device, seed=self._seed(0), **kw)                                    # :166
         self.mae_v = M3AEEncoder("image", device, seed=self._seed(1), **kw)                                   # :167
 
@@ -500,10 +509,11 @@ class Modal3Classifier(_Classifier):
     shared (--gs_flag) or Linear(2304, 4) on cat(a, v, t) (:218-221); MLA alternates a -> v -> t (main.py:432-466)."""
 
     def __init__(self, args, device="cuda", depth: int = 12, text_vocab_size: int = 30522, seed: Optional[int] = None,
-                 conv_math: Optional[str] = None):
+                 conv_math: Optional[str] = None, attention_math: Optional[str] = None):
         super().__init__(args, device, seed, ("IEMOCAP",), ConcatFusion3, 768, 3)                             # :208-229
-        kw = dict(depth=depth, text_vocab_size=text_vocab_size, conv_math=conv_math)
-        self.mae_a = M3AEEncoder("audio", device, depth=depth, seed=self._seed(0), conv_math=conv_math)       # :231 CAVMAEFT
+        kw = dict(depth=depth, text_vocab_size=text_vocab_size, conv_math=conv_math, attention_math=attention_math)
+        self.mae_a = M3AEEncoder("audio", device, depth=depth, seed=self._seed(0), conv_math=conv_math,       # :231 CAVMAEFT
+                                 attention_math=attention_math)
         self.mae_v = M3AEEncoder("image", device, seed=self._seed(1), **kw)                                   # :232
         self.mae_t = M3AEEncoder("text", device, seed=self._seed(2), **kw)                                    # :233
 
@@ -530,10 +540,11 @@ class CAVClassifier(_Classifier):
     lorb_large = True
 
     def __init__(self, args, device="cuda", depth: int = 12, seed: Optional[int] = None, conv_math: Optional[str] = None,
-                 audio_ckpt: Optional[str] = None, visual_ckpt: Optional[str] = None):
+                 audio_ckpt: Optional[str] = None, visual_ckpt: Optional[str] = None, attention_math: Optional[str] = None):
         super().__init__(args, device, seed, ("CREMAD",), ConcatFusion, 768, 2)                               # :82-104
-        self.mae_a = M3AEEncoder("audio", device, depth=depth, seed=self._seed(0), conv_math=conv_math)       # :106
-        self.mae_v = M3AEEncoder("cav_visual", device, depth=depth, seed=self._seed(1), conv_math=conv_math)  # :107
+        kw = dict(depth=depth, conv_math=conv_math, attention_math=attention_math)
+        self.mae_a = M3AEEncoder("audio", device, seed=self._seed(0), **kw)                                   # :106
+        self.mae_v = M3AEEncoder("cav_visual", device, seed=self._seed(1), **kw)                              # :107
         for enc, path in ((self.mae_a, audio_ckpt), (self.mae_v, visual_ckpt)):                               # :109-117
             if path is not None:
                 enc.load_state_dict(torch.load(path, map_location="cpu"), strict=False)   # other-branch keys: unexpected, ignored

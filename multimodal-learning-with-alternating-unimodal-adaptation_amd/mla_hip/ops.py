@@ -810,13 +810,26 @@ def softmax_bwd(P, dP, B: int, H: int, n: int, stream: Optional[int] = None):
     _call("mla_softmax_bwd", _p(P), _p(dP), B, H, n, stream or cur_stream())
 
 
-def attention_fwd(qkv, pad_mask, o, lse, B: int, H: int, n: int, hd: int, stream: Optional[int] = None):
+ATTENTION_MATHS = ("f32", "split")
+
+
+def _attention_symbol(base: str, math: str) -> str:
+    """math "f32": the fp32-MFMA kernels (attention.hip); "split": the same kernels on the exact three-way bf16 split
+    (attention_split.hip), fp32-equivalent."""
+    if math not in ATTENTION_MATHS:
+        raise MLAHipError(f"attention math must be 'f32' or 'split', got {math!r}")
+    return base if math == "f32" else base + "_split"
+
+
+def attention_fwd(qkv, pad_mask, o, lse, B: int, H: int, n: int, hd: int, stream: Optional[int] = None, math: str = "f32"):
     """o = softmax(mask(q k^T * hd^-0.5)) v, fused (models/m3ae.py:102-125); lse (B, H, n) is kept for the backward."""
-    _call("mla_attention_fwd", _p(qkv), _p(pad_mask), _p(o), _p(lse), B, H, n, hd, stream or cur_stream())
+    _call(_attention_symbol("mla_attention_fwd", math), _p(qkv), _p(pad_mask), _p(o), _p(lse), B, H, n, hd, stream or cur_stream())
 
 
-def attention_bwd(do, qkv, o, lse, pad_mask, dqkv, dvec, B: int, H: int, n: int, hd: int, stream: Optional[int] = None):
-    _call("mla_attention_bwd", _p(do), _p(qkv), _p(o), _p(lse), _p(pad_mask), _p(dqkv), _p(dvec), B, H, n, hd, stream or cur_stream())
+def attention_bwd(do, qkv, o, lse, pad_mask, dqkv, dvec, B: int, H: int, n: int, hd: int, stream: Optional[int] = None,
+                  math: str = "f32"):
+    _call(_attention_symbol("mla_attention_bwd", math), _p(do), _p(qkv), _p(o), _p(lse), _p(pad_mask), _p(dqkv), _p(dvec), B, H, n, hd,
+          stream or cur_stream())
 
 
 def tokens_assemble(x0, table, ids, pos, type_emb, cls, B: int, L: int, D: int, stream: Optional[int] = None):

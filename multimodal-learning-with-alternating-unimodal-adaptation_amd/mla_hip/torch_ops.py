@@ -400,6 +400,25 @@ def attention_bwd(do, qkv, o, lse, pad_mask, heads):
     return dqkv
 
 
+# ---- the same attention on the split-bf16 arithmetic (attention_math "split") ---------------------------------------------------
+@_op("attention_fwd_split(Tensor qkv, Tensor? pad_mask, int heads) -> (Tensor, Tensor)")
+def attention_fwd_split(qkv, pad_mask, heads):
+    B, n, D3 = qkv.shape
+    D = D3 // 3
+    o, lse = _f32((B, n, D), qkv), _f32((B, heads, n), qkv)
+    ops.attention_fwd(qkv, pad_mask, o, lse, B, heads, n, D // heads, math="split")
+    return o, lse
+
+
+@_op("attention_bwd_split(Tensor do, Tensor qkv, Tensor o, Tensor lse, Tensor? pad_mask, int heads) -> Tensor")
+def attention_bwd_split(do, qkv, o, lse, pad_mask, heads):
+    B, n, D3 = qkv.shape
+    D = D3 // 3
+    dqkv = torch.empty_like(qkv)
+    ops.attention_bwd(do, qkv, o, lse, pad_mask, dqkv, _f32((B, heads, n), qkv), B, heads, n, D // heads, math="split")
+    return dqkv
+
+
 # ---- CREMA-D frame augmentation (dataset/dataset.py:128-153) --------------------------------------------------------
 @_op("frames_resample(Tensor frames, Tensor desc, Tensor lut, int T, int out_h=224, int out_w=224) -> Tensor")
 def frames_resample(frames, desc, lut, T, out_h=224, out_w=224):
