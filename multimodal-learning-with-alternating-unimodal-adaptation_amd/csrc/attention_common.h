@@ -1,7 +1,8 @@
-// Pieces shared by the fused-attention kernels of both arithmetics (attention.hip: fp32 MFMA, attention_split.hip: split bf16):
-// the geometry, the global -> register tile loads, the accumulator-layout helpers, the mask rule, fast_exp and the host-side
-// kernel selection.  Everything here is independent of how a product is formed.
+// Pieces the fused-attention kernels (attention_kernels.h) and their arithmetics (attention.hip: fp32 MFMA, attention_split.hip: split
+// bf16) share: the geometry, the global -> register tile loads, the accumulator-layout helpers, the mask rule, fast_exp and the
+// host-side kernel selection.  Everything here is independent of how a product is formed.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 #define ATT_HD 64          // head dim (ViT-B: 768 / 12)
@@ -17,6 +18,10 @@ namespace {
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
 __device__ __forceinline__ int acc_row(int e, int half) { return (e & 3) + 8 * (e >> 2) + 4 * half; }
+__device__ __forceinline__ void att_zero(f32x16& acc) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+}
 
 struct AttGeom {
   const float* qkv;        // (B, n, 3, H, 64)
@@ -107,6 +112,23 @@ inline int att_waves(int n) {
     if (idle < best_idle) { best = w; best_idle = idle; }
   }
   return best;
+}
+
+// The one place that maps a length to an instantiation, nm = att_main_rows(n) > 0: W = att_waves(nm) waves; TAIL = 1 for [cls] + 32 m
+// (one remainder row: 3 instead of 9 state registers), ATT_TAIL_MAX for any other remainder, 0 for none.
+// launch(W, TAIL, grid, block) receives both as std::integral_constant and starts its kernel<.., W, TAIL>.
+template <class Launch>
+inline void att_launch(int nm, int n, int BH, Launch&& launch) {
+  const int W = att_waves(nm);
+  const dim3 grid(cdiv(nm, 32 * W), BH), block(64 * W);
+  auto with_tail = [&](auto w) {
+    if (nm + 1 == n) launch(w, std::integral_constant<int, 1>{}, grid, block);
+    else if (nm < n) launch(w, std::integral_constant<int, ATT_TAIL_MAX>{}, grid, block);
+    else launch(w, std::integral_constant<int, 0>{}, grid, block);
+  };
+  if (W == 4) with_tail(std::integral_constant<int, 4>{});
+  else if (W == 3) with_tail(std::integral_constant<int, 3>{});
+  else with_tail(std::integral_constant<int, 2>{});
 }
 
 inline int check_att(const char* who, int B, int H, int n, int hd) {

@@ -1,7 +1,7 @@
-"""CPU side of the fused-attention tests (csrc/attention.hip): the kernel-selection logic restated, the case table, the
+"""CPU side of the fused-attention tests (csrc/attention_kernels.h, attention.hip): the kernel-selection logic restated, the case table, the
 padding-mask layouts and a plain autograd reference in fp32 / fp64.
 
-  att_main_rows, att_waves   the two host functions of attention.hip:849-866, restated line for line
+  att_main_rows, att_waves   the two host functions of csrc/attention_common.h, restated line for line
   att_path                   which kernel a length n is routed to: ("tail", rows) or (W, TAIL, workgroups per (b, h))
   CASES                      every (W, TAIL) instantiation and the tail-only kernels at the smallest n that reaches them
   mask_layout                the padding-mask layouts "a" .. "f"
@@ -16,18 +16,18 @@ import torch.nn.functional as F
 from oracle import mla_oracle as O
 
 HD = 64
-ATT_TAIL_MAX = 3          # attention.hip:33
-ATT_TAIL_N = 4096         # attention.hip:34
+ATT_TAIL_MAX = 3          # attention_common.h
+ATT_TAIL_N = 4096         # attention_common.h
 
 
 def att_main_rows(n):
-    """attention.hip:850-853: rows the MFMA kernels own."""
+    """attention_common.h, att_main_rows: rows the MFMA kernels own."""
     r = n % 32
     return n - r if (0 < r <= ATT_TAIL_MAX and n <= ATT_TAIL_N) else n
 
 
 def att_waves(n):
-    """attention.hip:858-866: waves per workgroup, the width that leaves the fewest idle waves (ties: the widest)."""
+    """attention_common.h, att_waves: waves per workgroup, the width that leaves the fewest idle waves (ties: the widest)."""
     blocks = (n + 31) // 32
     best, best_idle = 4, 1 << 30
     for w in (4, 3, 2):
@@ -38,7 +38,7 @@ def att_waves(n):
 
 
 def att_path(n):
-    """The launch mla_attention_fwd / mla_attention_bwd make for n tokens (attention.hip:881-902, 911-947)."""
+    """The launch mla_attention_fwd / mla_attention_bwd make for n tokens (att_launch in attention_common.h; the nm == 0 branches of attention.hip)."""
     nm = att_main_rows(n)
     if nm == 0:
         return ("tail", n)

@@ -1,6 +1,6 @@
 """CPU: the case table of tests/test_attention_gpu.py reaches every fused-attention instantiation (csrc/attention.hip), and the
 reference helper / mask layouts it uses are what they claim to be.  att_main_rows / att_waves are restated in
-tests/attention_model.py from attention.hip:849-866: when someone retunes them, the first test says which shapes to re-pick."""
+tests/attention_model.py from csrc/attention_common.h: when someone retunes them, the first test says which shapes to re-pick."""
 import pytest
 import torch
 
