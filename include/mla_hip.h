@@ -264,7 +264,11 @@ int mla_avgpool_bwd(const float* dy, const float* relu_src, float* dx, int NB, i
 /* logits = X W^T + b; loss = -sum_i log softmax(logits_i)[label_i] * inv_batch (rank-local part);
  * dlogits = (softmax - onehot) * inv_batch; dW = dlogits^T X; db = sum dlogits; dX = dlogits W.
  * Two launches (wave per sample, then the BxD contraction).  X [B][D], W [C][D], labels int64 [B];
- * C <= 128.  ws: mla_head_ws_elems(B, C) floats. */
+ * C <= 128.  ws: mla_head_ws_elems(B, C) floats: dlogits [B][C], then the row losses [B].
+ * A label outside [0, C) yields a NaN loss and a zero dlogits row: that sample adds nothing to dW and db and its dX row is zero
+ * (the policy of mla_ce_fwd_bwd, the concat head and the QMF heads; the fused call is the mla_head_logits -> mla_ce_fwd_bwd ->
+ * mla_head_bwd chain bit for bit, bad labels included).  The logits do not depend on the labels.
+ * Every loss of this family is formed per row as log(sum exp(l - max)) - (l[label] - max), the two terms of log_softmax. */
 size_t mla_head_ws_elems(int B, int C);
 int mla_head_ce_fwd_bwd(const float* X, const float* W, const float* b, const int64_t* labels,
                         float* logits, float* loss, float* dW, float* db, float* dX, float* ws,
@@ -273,7 +277,8 @@ int mla_head_ce_fwd_bwd(const float* X, const float* W, const float* b, const in
 /* The same head where autograd splits it, for the nn.Module / autograd.Function protocol (main.py:432-435 executed
  * literally: `out = fc_out(a)`; `loss = criterion(out, label)`; `loss.backward()`):
  *   mla_ce_fwd_bwd   nn.CrossEntropyLoss() (main.py:130), mean reduction: loss and dlogits = (softmax - onehot) * inv_batch
- *                    in one pass; ws: B floats.  A label outside [0, C) yields a NaN loss (the reference asserts).
+ *                    in one pass; ws: B floats (the row losses).  A label outside [0, C) yields a NaN loss (the reference
+ *                    asserts) and a zero dlogits row.  Any C.
  *   mla_head_bwd     autograd of nn.Linear (fusion_modules.py:19) for a given dlogits: dW = s dlogits^T X, db = s sum dlogits,
  *                    dX = s dlogits W  (s = 1/world under data parallel, else 1).
  *   mla_scale_by_device_scalar   x *= *scalar, the scalar read on the device (gradient flowing into a loss node). */
@@ -349,8 +354,9 @@ int mla_gs_project(float* Pl, const float* r, float* G, int D, int C, float alph
  * torch.optim.SGD(momentum, weight decay) on weight and bias (:439), in place.  No dX is formed: nothing lies behind the features.
  * X (B, D), labels int64 (B); W (C, D), b (C) and buf (C*D + C: the momentum of [W | b], `first` != 0: it becomes g + wd p);
  * Pl (D, D), read and updated only when `project`; logits (B, C) and loss[1] out; ws: mla_feature_ws_elems(B, D, C) floats.
- * 4 kernel launches and no copy when projecting, 2 otherwise; no atomics, bit-reproducible.  An out-of-range label poisons the loss
- * with NaN.  C <= 128, D <= 4096; X, W, buf, Pl, logits and ws 16-byte aligned.  Any D and C*D (nothing here needs a multiple of 4). */
+ * 4 kernel launches and no copy when projecting, 2 otherwise; no atomics, bit-reproducible.  A label outside [0, C) poisons the loss
+ * with NaN and gives a zero dlogits row: that sample adds nothing to the gradient, the momentum or the update (mla_head_ce_fwd_bwd's
+ * policy).  C <= 128, D <= 4096; X, W, buf, Pl, logits and ws 16-byte aligned.  Any D and C*D (nothing here needs a multiple of 4). */
 size_t mla_feature_ws_elems(int B, int D, int C);
 int mla_feature_phase(const float* X, const int64_t* labels, float* W, float* b, float* buf, float* Pl, float* logits,
                       float* loss, float* ws, int B, int D, int C, float inv_batch, int project, double alpha, float lr,

@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void concat_head_fwd_kernel(const ConcatPtrs p
     // wave 0: the trained logits `out`; wave 1 + m: out_m (loss value only)
     const float* l = wave == 0 ? lg : lgm[wave - 1];
     const Softmax2 q = head_softmax2(l, C, lane);
-    if (lane == 0) rowloss[(size_t)wave * B + row] = lab_ok ? (q.lse - l[lab]) * inv_batch : NAN;
+    if (lane == 0) rowloss[(size_t)wave * B + row] = lab_ok ? head_ce_loss(q.logs, q.mx, l[lab]) * inv_batch : NAN;
     if (wave == 0) {
       __builtin_amdgcn_wave_barrier();              // every lane has read lg before it is overwritten with dlogits
       const float d0 = lab_ok ? head_ce_grad(q.e0, q.s, lane == lab, inv_batch) : 0.f;

@@ -41,11 +41,11 @@ __global__ __launch_bounds__(64 * FEAT_WAVES) void feat_fwd_kernel(const float* 
   if (wave != 0) return;
   const Softmax2 p = head_softmax2(lg, C, lane);
   const long lab_raw = (long)labels[row];
-  const bool lab_ok = lab_raw >= 0 && lab_raw < C;   // out of range: NaN loss, no out-of-bounds LDS read
+  const bool lab_ok = lab_raw >= 0 && lab_raw < C;   // out of range: NaN loss, a zero dlogits row, no out-of-bounds LDS read
   const int lab = lab_ok ? (int)lab_raw : 0;
-  if (lane == 0) rowloss[row] = lab_ok ? (p.lse - lg[lab]) * inv_batch : NAN;
-  const float d0 = head_ce_grad(p.e0, p.s, lane == lab, inv_batch);
-  const float d1 = head_ce_grad(p.e1, p.s, lane + 64 == lab, inv_batch);
+  if (lane == 0) rowloss[row] = lab_ok ? head_ce_loss(p.logs, p.mx, lg[lab]) * inv_batch : NAN;
+  const float d0 = lab_ok ? head_ce_grad(p.e0, p.s, lane == lab, inv_batch) : 0.f;
+  const float d1 = lab_ok ? head_ce_grad(p.e1, p.s, lane + 64 == lab, inv_batch) : 0.f;
   if (lane < C) {
     logits[(size_t)row * C + lane] = p.l0;
     dlogits[(size_t)row * C + lane] = d0;

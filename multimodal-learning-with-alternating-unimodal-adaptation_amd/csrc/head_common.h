@@ -23,19 +23,24 @@ __device__ __forceinline__ float head_row_dot(const float* x, const float* w, in
 
 // Softmax of a row of C <= MLA_HEAD_MAXC logits by one wave: lane holds the slots lane and lane + 64 (-inf / 0 past C).
 struct Softmax2 {
-  float l0, l1, e0, e1, s, lse;
+  float l0, l1, e0, e1, s, mx, logs;      // mx: the row maximum; s = sum exp(l - mx); logs = logf(s)
 };
 __device__ __forceinline__ Softmax2 head_softmax2(const float* l, int C, int lane) {
   Softmax2 r;
   r.l0 = lane < C ? l[lane] : -INFINITY;
   r.l1 = lane + 64 < C ? l[lane + 64] : -INFINITY;
-  const float mx = wave_max(fmaxf(r.l0, r.l1));
-  r.e0 = lane < C ? expf(r.l0 - mx) : 0.f;
-  r.e1 = lane + 64 < C ? expf(r.l1 - mx) : 0.f;
+  r.mx = wave_max(fmaxf(r.l0, r.l1));
+  r.e0 = lane < C ? expf(r.l0 - r.mx) : 0.f;
+  r.e1 = lane + 64 < C ? expf(r.l1 - r.mx) : 0.f;
   r.s = wave_sum(r.e0 + r.e1);
-  r.lse = mx + logf(r.s);
+  r.logs = logf(r.s);
   return r;
 }
+
+// -log softmax(l)[label] of a row with maximum mx and logs = log sum exp(l - mx), as log_softmax forms it: both terms are of the
+// size of the loss.  (mx + logs) - l_label rounds at the size of the LOGITS instead: at logits near -1e4 and a loss near 1 that is
+// an error of 1e-4 of the loss (tests/test_head_exact_gpu.py, the `low` family).
+__device__ __forceinline__ float head_ce_loss(float logs, float mx, float l_label) { return logs - (l_label - mx); }
 
 // d CE / d logit of one slot (mean reduction).  What a bad label does to the row is the caller's policy.
 __device__ __forceinline__ float head_ce_grad(float e, float s, bool hit, float inv_batch) {

@@ -29,14 +29,15 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
   if (wave == 0) {
     const Softmax2 p = head_softmax2(lg, C, lane);
     const long lab_raw = (long)labels[row];
-    const bool lab_ok = lab_raw >= 0 && lab_raw < C;   // out of range: NaN loss (the reference's CE kernel asserts), no OOB LDS read
+    // out of range: NaN loss (the reference's CE kernel asserts), a zero dlogits row (ce_fwd_bwd_kernel's policy), no OOB LDS read
+    const bool lab_ok = lab_raw >= 0 && lab_raw < C;
     const int lab = lab_ok ? (int)lab_raw : 0;
     if (lane < C) logits[(size_t)row * C + lane] = p.l0;
     if (lane + 64 < C) logits[(size_t)row * C + lane + 64] = p.l1;
-    if (lane == 0) rowloss[row] = lab_ok ? (p.lse - lg[lab]) * inv_batch : NAN;
+    if (lane == 0) rowloss[row] = lab_ok ? head_ce_loss(p.logs, p.mx, lg[lab]) * inv_batch : NAN;
     __builtin_amdgcn_wave_barrier();
-    const float d0 = head_ce_grad(p.e0, p.s, lane == lab, inv_batch);
-    const float d1 = head_ce_grad(p.e1, p.s, lane + 64 == lab, inv_batch);
+    const float d0 = lab_ok ? head_ce_grad(p.e0, p.s, lane == lab, inv_batch) : 0.f;
+    const float d1 = lab_ok ? head_ce_grad(p.e1, p.s, lane + 64 == lab, inv_batch) : 0.f;
     if (lane < C) {
       lg[lane] = d0;
       dlogits[(size_t)row * C + lane] = d0;
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(const float* __restrict
   s = wave_sum(s);
   const long lab = (long)labels[row];
   const bool ok = lab >= 0 && lab < C;
-  if (lane == 0) rowloss[row] = ok ? (m + logf(s) - l[lab]) * inv_batch : NAN;
+  if (lane == 0) rowloss[row] = ok ? head_ce_loss(logf(s), m, l[lab]) * inv_batch : NAN;
   for (int c = lane; c < C; c += 64)
     dlogits[(size_t)row * C + c] = ok ? (expf(l[c] - m) / s - (c == lab ? 1.f : 0.f)) * inv_batch : 0.f;
 }

@@ -68,14 +68,15 @@ __global__ __launch_bounds__(256) void qmf_head_fwd_kernel(const QmfPtrs p, cons
     const float mx = wave_max(fmaxf(l0, l1));
     const float e0 = lane < C ? expf(l0 - mx) : 0.f, e1 = lane + 64 < C ? expf(l1 - mx) : 0.f;
     const float s = wave_sum(e0 + e1);
-    const float E = mx + logf(s);
+    const float logs = logf(s);
+    const float E = mx + logs;
     const float cm = E / 10.f;                                          // main.py:245-246
     if (lane == 0) {
       conf[(size_t)m * B + row] = cm;
       cl[m] = cm;
     }
     if (TRAIN) {
-      const float lm = ok ? E - zl[m][lab] : NAN;                       // CrossEntropyLoss(reduction='none'), main.py:255-256
+      const float lm = ok ? head_ce_loss(logs, mx, zl[m][lab]) : NAN;         // CrossEntropyLoss(reduction='none'), main.py:255-256
       if (lane < C) prob[((size_t)m * B + row) * C + lane] = e0 / s;
       if (lane + 64 < C) prob[((size_t)m * B + row) * C + lane + 64] = e1 / s;
       // last occurrence of this index inside the batch writes (utils/utils.py:57-58)
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(256) void qmf_head_fwd_kernel(const QmfPtrs p, cons
   __syncthreads();
   if (wave == 0) {
     const Softmax2 q = head_softmax2(ol, C, lane);
-    if (lane == 0) rowcml[row] = ok ? (q.lse - ol[lab]) * inv_batch : NAN;
+    if (lane == 0) rowcml[row] = ok ? head_ce_loss(q.logs, q.mx, ol[lab]) * inv_batch : NAN;
     if (lane < C) dfused[(size_t)row * C + lane] = ok ? head_ce_grad(q.e0, q.s, lane == lab, inv_batch) : 0.f;
     if (lane + 64 < C) dfused[(size_t)row * C + lane + 64] = ok ? head_ce_grad(q.e1, q.s, lane + 64 == lab, inv_batch) : 0.f;
   }

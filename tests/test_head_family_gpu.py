@@ -8,7 +8,9 @@
       ce_fwd_bwd's loss of out_m[m].
 
 Shapes: B = 70 crosses the 64-row stride of the bias-gradient and loss sums; D = 70 is no multiple of 64 or 4, D = 320 more than one
-256-column block; C = 3, 64, 65, 128: one softmax slot, the slot boundary, the second slot, the limit.  Labels are valid."""
+256-column block; C = 3, 64, 65, 128: one softmax slot, the slot boundary, the second slot, the limit.  Labels are valid, except in
+the two bad-label cases of (b) and (c): labels -1 and C at rows 0 and B - 1 of BAD_SHAPE give a NaN loss on both sides and, with the
+zero dlogits rows every family writes for them, the same gradients bit for bit."""
 import functools
 
 import pytest
@@ -19,6 +21,7 @@ pytestmark = pytest.mark.gpu
 from oracle import mla_oracle as O  # noqa: E402
 
 SHAPES = [(B, D, C) for B in (1, 5, 70) for D in (70, 320) for C in (3, 64, 65, 128)]
+BAD_SHAPE = (70, 70, 65)
 F32 = dict(device="cuda", dtype=torch.float32)
 
 
@@ -47,6 +50,12 @@ def _ce(logits, labels):
     loss, dl, ws = torch.empty(1, **F32), torch.empty_like(logits), torch.empty(B, **F32)
     ops.ce_fwd_bwd(logits, labels, loss, dl, ws, 1.0 / B)
     return loss, dl
+
+
+def _bad_labels(labels, C):
+    bad = labels.clone()
+    bad[0], bad[-1] = -1, C
+    return bad
 
 
 def _same(a, b, what):
@@ -86,23 +95,45 @@ def test_logits_agree_across_families(B, D, C):
 
 @pytest.mark.parametrize("B,D,C", SHAPES)
 def test_shared_head_fused_equals_split(B, D, C):
+    _shared_head_fused_equals_split(B, D, C, _inputs(B, D, C)[5], bad=False)
+
+
+def test_shared_head_fused_equals_split_bad_labels():
+    B, D, C = BAD_SHAPE
+    _shared_head_fused_equals_split(B, D, C, _bad_labels(_inputs(B, D, C)[5], C), bad=True)
+
+
+def _shared_head_fused_equals_split(B, D, C, labels, bad):
     from mla_hip import ops
-    xs, Ws, bs, _, _, labels = _inputs(B, D, C)
+    xs, Ws, bs = _inputs(B, D, C)[:3]
     X, W, b = xs[0], Ws[0], bs[0]
     logits, loss, dW, db, dX = (torch.empty(s, **F32) for s in ((B, C), (1,), (C, D), (C,), (B, D)))
     ops.head_ce_fwd_bwd(X, W, b, labels, logits, loss, dW, db, dX, torch.empty(ops.head_ws_elems(B, C), **F32), 1.0 / B)
     loss2, dl = _ce(_head_logits(X, W, b), labels)
     dW2, db2, dX2 = torch.empty_like(dW), torch.empty_like(db), torch.empty_like(dX)
     ops.head_bwd(X, W, dl, dW2, db2, dX2, 1.0)
+    if bad:
+        assert torch.isnan(loss).all() and torch.isnan(loss2).all() and bool((dl[0] == 0).all()) and bool((dl[-1] == 0).all())
+        assert torch.isfinite(dW).all() and torch.isfinite(db).all() and torch.isfinite(dX).all()
     for name, a, c in (("loss", loss, loss2), ("dW", dW, dW2), ("db", db, db2), ("dX", dX, dX2)):
-        _same(a, c, f"head_ce_fwd_bwd {name} vs head_logits -> ce_fwd_bwd -> head_bwd")
+        if not (bad and name == "loss"):
+            _same(a, c, f"head_ce_fwd_bwd {name} vs head_logits -> ce_fwd_bwd -> head_bwd")
 
 
 @pytest.mark.parametrize("M", [2, 3])
 @pytest.mark.parametrize("B,D,C", SHAPES)
 def test_concat_head_fused_equals_split(B, D, C, M):
+    _concat_head_fused_equals_split(B, D, C, M, _inputs(B, D, C)[5], bad=False)
+
+
+def test_concat_head_fused_equals_split_bad_labels():
+    B, D, C = BAD_SHAPE
+    _concat_head_fused_equals_split(B, D, C, 3, _bad_labels(_inputs(B, D, C)[5], C), bad=True)
+
+
+def _concat_head_fused_equals_split(B, D, C, M, labels, bad):
     from mla_hip import ops
-    xs, _, _, Wcat, b, labels = _inputs(B, D, C)
+    xs, _, _, Wcat, b, _ = _inputs(B, D, C)
     xs, W = xs[:M], Wcat[M]
     out, out_m, loss, loss_m, dW, db = (torch.empty(s, **F32) for s in ((B, C), (M, B, C), (1,), (M,), (C, M * D), (C,)))
     dxs = [torch.empty((B, D), **F32) for _ in range(M)]
@@ -115,7 +146,15 @@ def test_concat_head_fused_equals_split(B, D, C, M):
     ops.concat_head_bwd(xs, W, dl, dW2, db2, dxs2, 1.0)
     pairs = [("out", out, out2), ("out_m", out_m, out_m2), ("loss", loss, loss2), ("dW", dW, dW2), ("db", db, db2)]
     pairs += [(f"dx[{m}]", dxs[m], dxs2[m]) for m in range(M)]
+    if bad:
+        assert torch.isnan(loss).all() and torch.isnan(loss2).all() and torch.isnan(loss_m).all()
+        assert bool((dl[0] == 0).all()) and bool((dl[-1] == 0).all()) and torch.isfinite(dW).all() and torch.isfinite(db).all()
+        pairs = [p for p in pairs if p[0] != "loss"]
     for name, a, c in pairs:
         _same(a, c, f"concat_head_ce_fwd_bwd {name} vs concat_head_fwd -> ce_fwd_bwd -> concat_head_bwd")
     for m in range(M):
-        _same(loss_m[m:m + 1], _ce(out_m2[m].contiguous(), labels)[0], f"loss_m[{m}] vs ce_fwd_bwd(out_m[{m}])")
+        lm = _ce(out_m2[m].contiguous(), labels)[0]
+        if bad:
+            assert torch.isnan(lm).all()
+        else:
+            _same(loss_m[m:m + 1], lm, f"loss_m[{m}] vs ce_fwd_bwd(out_m[{m}])")
