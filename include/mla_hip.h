@@ -635,6 +635,31 @@ int mla_resident_batch(const uint8_t* frames, size_t frames_bytes, const int64_t
                        int train, const int* plan5, const float* lut, int64_t* desc_out, float* image_out, float* spec_out,
                        int64_t* label_out, int64_t* idx_out, int out_h, int out_w, void* stream);
 
+/* ---- rows of a batch: gather, expand, compact-and-sum (Modal3Classifier(..., present=)) ------------------------
+ * A transformer encoder treats every sample on its own, so the samples of a batch whose modality is absent (all-zero input) share
+ * one feature f(0), and their feature gradients reach the parameters only through their sum.  These three move the rows:
+ *   mla_rows_gather       dst[j] = src[idx[j]] for j < P, then zero_tail_rows rows with every bit clear (+0.0 / token id 0).  src has
+ *                         B rows of row_elems elements of elem_bytes (4 or 8) bytes; dst has P + zero_tail_rows >= 1 rows.
+ *   mla_rows_expand       dst[b] = src[map[b]] for b < B: `map` int64 (B) names, for every destination row, its source row among the
+ *                         src_rows rows of src (a present sample's compact row, or the row that holds f(0)); elements as for
+ *                         mla_rows_gather.  The caller builds the
+ *                         map on the host, so every destination row is written exactly once: no fill pass, no overwrite.
+ *   mla_rows_compact_sum  dst[j] = src[idx[j]] for j < P; dst[P] = src[absent_idx[0]] + src[absent_idx[1]] + ... (A terms) in fp32,
+ *                         added in that order starting from +0.0 (A == 0: +0.0).  src has B rows, dst P + 1.
+ * Copies move bits (NaN payloads and -0.0 survive).  16-byte accesses when src, dst and the row size are multiples of 16 bytes,
+ * 4-byte words otherwise; fixed order, no atomics, the same bits in every run.
+ * Every index table comes twice, as mla_modal3_assemble's does: on the device (int64, 8-byte aligned) and the same entries on the
+ * host.  The host copy is checked before anything is launched -- every entry inside [0, B) resp. [0, src_rows) -- together with:
+ * null pointers, B <= 0, P outside [0, B], A < 0, row_elems == 0, no destination row or more than 65535, src / dst off a 4-byte
+ * boundary, dst overlapping src: MLA_ERR_INVALID_ARG, nothing launched.  On the device an entry outside the source is never read
+ * through: its row is written as zeros (resp. skipped in the sum). */
+int mla_rows_gather(const void* src, const int64_t* idx, const int64_t* idx_host, void* dst, int B, int P, size_t row_elems,
+                    int elem_bytes, int zero_tail_rows, void* stream);
+int mla_rows_expand(const void* src, const int64_t* map, const int64_t* map_host, void* dst, int B, int src_rows,
+                    size_t row_elems, int elem_bytes, void* stream);
+int mla_rows_compact_sum(const float* src, const int64_t* idx, const int64_t* idx_host, const int64_t* absent_idx,
+                         const int64_t* absent_host, float* dst, int B, int P, int A, size_t row_elems, void* stream);
+
 /* ---- evaluation path (main.py:486-679 `valid`, gs_flag branch) --------------------------------- */
 /* logits = X W^T + b only (main.py:636-639) */
 int mla_head_logits(const float* X, const float* W, const float* b, float* logits, int B, int D, int C, void* stream);

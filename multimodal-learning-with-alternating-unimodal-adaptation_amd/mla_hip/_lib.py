@@ -151,6 +151,9 @@ PROTOTYPES = {
     "mla_fbank_augment": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, ctypes.c_uint64, _P]),
     "mla_modal3_assemble_check": (_I, [_P, _I, _I, _I, _I, _I]),
     "mla_modal3_assemble": (_I, [_P] * 7 + [_I] * 5 + [_P]),
+    "mla_rows_gather": (_I, [_P, _P, _P, _P, _I, _I, _Z, _I, _I, _P]),
+    "mla_rows_expand": (_I, [_P, _P, _P, _P, _I, _I, _Z, _I, _P]),
+    "mla_rows_compact_sum": (_I, [_P] * 6 + [_I, _I, _I, _Z, _P]),
     "mla_wav_fbank_check": (_I, [_P, _I, _Z, _I, _P, _P, _Z]),
     "mla_wav_fbank": (_I, [_P, _Z, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _I, _P]),
     "mla_resident_plan": (_I, [_P, ctypes.c_int64, _I, _Z, _I, _I, _I, _P]),

@@ -6,6 +6,7 @@ head and on ONE encoder.  Each Function below is a thin shell over the same laun
 
   EncoderFeature   forward  = encoder forward + global pooling  -> (B, D) feature (fresh tensor)
                    backward = encoder.backward_from_pooled(d feature) -> flat gradient buffer -> p.grad views
+                   (after a forward on the present rows only, Modal3Classifier(present=): d feature compacted to those rows first)
   HeadLinear       forward  = mla_head_logits; backward = mla_head_bwd (dW, db, dX in one launch pair)
   ConcatHeadLinear forward  = mla_concat_head_fwd; backward = mla_concat_head_bwd (dW, db, every dX_m; joint step)
   SoftmaxCE        forward  = mla_ce_fwd_bwd (loss + d logits in one launch); backward = scale by the incoming grad
@@ -25,6 +26,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from .rows import compact_feature_grad
 
 
 def make_anchor(device) -> torch.Tensor:
@@ -48,7 +50,7 @@ class EncoderFeature(torch.autograd.Function):
                                "most recent forward only; retain_graph / double backward are not supported)")
         comm = enc.comm        # data parallel: d feature already is this rank's share of the global-batch mean (HeadLinear.backward
         pending = enc.grads_pending()          # scales by 1 / world), so the flat encoder gradient only needs the SUM over ranks
-        enc.backward_from_pooled(dfeat.contiguous(), enc._pa)
+        enc.backward_from_pooled(compact_feature_grad(enc, dfeat.contiguous()), enc._pa)
         if comm is not None and comm.active:
             enc._grad_works = comm.allreduce_flat_async(enc.grad)      # waited for by FusedSGD.step()
             if pending is not None:                                    # accumulation: add the older gradient after the exchange

@@ -25,6 +25,7 @@ from . import ops
 from ._lib import MLAHipError
 from .model import ConcatFusion, SharedHead, _Classifier, concat_fusion_forward
 from .module import FlatEncoder
+from .rows import RowPlan, check_present
 
 
 def _sincos_1d(embed_dim: int, pos: np.ndarray) -> np.ndarray:                      # m3ae.py:181-194
@@ -127,8 +128,10 @@ class M3AEEncoder(FlatEncoder):
             unused_shapes = {}   # CAVMAEFT's other branch / unused norms are not materialised (never touched by forward_feat)
         self.unused: Dict[str, nn.Parameter] = {}
         self._register_reference_tree(unused_shapes)
-        self._ws: dict = {}
+        self._ws: dict = {}                  # the workspace of the last forward: the planned one (_cap) or a prefix view of it
         self._key = None
+        self._cap: Optional[dict] = None
+        self._views: Dict[int, dict] = {}
         # split-bf16 images of every Linear weight ([K][N] = a 1-tap conv weight)
         self._build_wsplit([(k, k, 1) + shp for k, (_o, shp) in self.layout.items()
                             if len(shp) == 2 and k.endswith(".weight") and k != "text_embedding.weight"])
@@ -247,8 +250,77 @@ class M3AEEncoder(FlatEncoder):
 
     # ------------------------------------------------------------------------------------------
     def _plan(self, B: int, L: int) -> dict:
+        """The workspace of a forward on B samples of L tokens.  Buffers are allocated once, at the largest batch seen so far (or
+        at reserve()'s): every one is row-major in M = B n or (B, H, n), so a smaller batch runs in a prefix of the same
+        memory, through views that are made once per B.  Only a batch larger than any before (or another L) allocates again."""
         if self._key == (B, L):
             return self._ws
+        cap = self._cap
+        if cap is None or cap["L"] != L or B > cap["B"]:
+            cap, self._views = self._alloc_ws(B, L), {}
+            self._cap = cap
+        if B == cap["B"]:
+            ws = cap
+        else:
+            ws = self._views.get(B)
+            if ws is None:
+                ws = self._views[B] = self._prefix_ws(cap, B)
+        self._ws, self._key = ws, (B, L)
+        return ws
+
+    def reserve(self, B: int, L: int, backward: bool = True) -> None:
+        """Allocate the workspace for batches of up to B samples of L tokens now (and, with `backward`, the backward's), so that no
+        later batch of at most B samples allocates any of it."""
+        cap = self._cap
+        if cap is None or cap["L"] != L or B > cap["B"]:
+            self._plan(B, L)
+        if backward:
+            self._bwd_ws(self._cap)
+
+    def workspace_tensors(self) -> Dict[str, torch.Tensor]:
+        """path -> buffer of the planned workspace (the allocation that batches up to its size run in), without what a forward
+        leaves beside them: the padding mask it builds and the aliases "x" / "xlast"."""
+        def walk(path, v):
+            if isinstance(v, torch.Tensor):
+                yield path, v
+            elif isinstance(v, dict):
+                for k, x in v.items():
+                    if k not in ("pm", "x", "xlast"):
+                        yield from walk(f"{path}.{k}", x)
+            elif isinstance(v, (list, tuple)):
+                for i, x in enumerate(v):
+                    yield from walk(f"{path}[{i}]", x)
+        return dict(walk("ws", self._cap or {}))
+
+    def _prefix_ws(self, cap: dict, B: int) -> dict:
+        """The planned workspace `cap` cut to its first B samples: views, no memory of its own."""
+        L, n = cap["L"], cap["n"]
+        M = B * n
+        ws: dict = {"B": B, "L": L, "n": n, "M": M, "cap": cap, "x0": cap["x0"][:M], "y": cap["y"][:M], "feat": cap["feat"][:B],
+                    "stf": [r[:M] for r in cap["stf"]], "blocks": []}
+        for bk in cap["blocks"]:
+            v = {k: bk[k][:M] for k in ("h1", "qkv", "o", "xmid", "h2", "u", "gl", "xout")}
+            v["st"] = [r[:M] for r in bk["st"]]
+            for k in ("P", "lse"):
+                if k in bk:
+                    v[k] = bk[k][:B]
+            ws["blocks"].append(v)
+        if "patches" in cap:
+            ws["patches"] = cap["patches"][:B * L]
+        if "pos" in cap:
+            ws["pos"] = cap["pos"]
+        if "ids" in cap:
+            ws["ids"] = cap["ids"][:B]
+        return ws
+
+    def _scratch(self, ws: dict, name: str, elems: int, dtype=torch.float32) -> torch.Tensor:
+        """ws[name], a scratch buffer of at least `elems` elements: the planned workspace's where that one is large enough."""
+        if name not in ws:
+            have = ws["cap"].get(name) if "cap" in ws else None
+            ws[name] = have if have is not None and have.numel() >= elems else torch.empty(elems, device=self.device, dtype=dtype)
+        return ws[name]
+
+    def _alloc_ws(self, B: int, L: int) -> dict:
         D, H, n = self.D, self.H, L + (1 if self.has_cls else 0)
         M = B * n
         f32 = dict(device=self.device, dtype=torch.float32)
@@ -267,13 +339,14 @@ class M3AEEncoder(FlatEncoder):
         ws["feat"] = torch.empty((B, D), **f32)
         if self.kind != "text":
             ws["patches"] = torch.empty((B * L, self.PD), **f32)
+        else:   # owned copy of the token ids: tokens_assemble_bwd reads it after forward() returned (feeder slots are reused)
+            ws["ids"] = torch.empty((B, L), device=self.device, dtype=torch.int64)
         if not self.cav:
             ws["pos"] = sincos_pos_embed(D, L, two_d=(self.kind == "image")).to(self.device)
         if self.attention == "fused":
             for bk in ws["blocks"]:
                 del bk["P"]
                 bk["lse"] = torch.empty((B, H, n), **f32)
-        self._ws, self._key = ws, (B, L)
         return ws
 
     def _bwd_ws(self, ws: dict) -> None:
@@ -281,23 +354,33 @@ class M3AEEncoder(FlatEncoder):
             return
         D, H, n, M, B = self.D, self.H, ws["n"], ws["M"], ws["B"]
         f32 = dict(device=self.device, dtype=torch.float32)
-        ws["dA"], ws["dB"], ws["dC"] = (torch.empty((M, D), **f32) for _ in range(3))
-        ws["du"] = torch.empty((M, 4 * D), **f32)
-        ws["dqkv"] = torch.empty((M, 3 * D), **f32)
-        if self.attention == "fused":
-            ws["dvec"] = torch.empty((B, H, n), **f32)
-        else:
-            ws["dP"] = torch.empty((B, H, n, n), **f32)
-        ws["wt_ws"] = torch.empty(4 * D * D, **f32)
+        cap = ws.get("cap")
+        if cap is None:
+            ws["dA"], ws["dB"], ws["dC"] = (torch.empty((M, D), **f32) for _ in range(3))
+            ws["du"] = torch.empty((M, 4 * D), **f32)
+            ws["dqkv"] = torch.empty((M, 3 * D), **f32)
+            if self.attention == "fused":
+                ws["dvec"] = torch.empty((B, H, n), **f32)
+            else:
+                ws["dP"] = torch.empty((B, H, n, n), **f32)
+            ws["wt_ws"] = torch.empty(4 * D * D, **f32)
+            ws["colsum"] = torch.empty(D, **f32)
+        else:   # a prefix of the planned workspace's (sizes that do not depend on the batch: the buffers themselves)
+            self._bwd_ws(cap)
+            for k in ("dA", "dB", "dC", "du", "dqkv"):
+                ws[k] = cap[k][:M]
+            for k in ("dvec", "dP"):
+                if k in cap:
+                    ws[k] = cap[k][:B]
+            ws["wt_ws"], ws["colsum"] = cap["wt_ws"], cap["colsum"]
         # one weight-gradient workspace: the largest any bound Linear asks for at the rows it really runs on
         gemms = {(M, lin.K, lin.N) for blk in self._blocks for lin in (blk.qkv, blk.fc, blk.fc1, blk.fc2)}
         if self.embed is not None:
             gemms.add((B * ws["L"], self.embed.K, self.embed.N))
         wb = max(ops.linear_wgrad_ws_bytes(*mkn, sp, sp and self.bf16) for sp in ((False, True) if self.split else (False,))
                  for mkn in gemms)
-        ws["wgrad_ws"] = torch.empty((wb + 3) // 4, **f32)
-        ws["red_ws"] = torch.empty(ops.colreduce_ws_elems(M, 4 * D), **f32)
-        ws["colsum"] = torch.empty(D, **f32)
+        self._scratch(ws, "wgrad_ws", (wb + 3) // 4)
+        self._scratch(ws, "red_ws", ops.colreduce_ws_elems(M, 4 * D))
 
     # ---- the Linear launches: the only callers of ops.linear_* here; arithmetic flags and weight image come from the encoder
     def _lin_fwd(self, lin: _Linear, x, y, rows: int, st, groups: int = 1, y_group_rows: Optional[int] = None, y_off: int = 0,
@@ -319,6 +402,14 @@ class M3AEEncoder(FlatEncoder):
         ops.linear_wgrad(x, dy, lin.gw, ws["wgrad_ws"], 1, rows, lin.K, lin.N, stream=st, split=self.split,
                          dbias=lin.gb if fused else None, bf16=self.bf16)
 
+    def tokens(self, inp: torch.Tensor) -> int:
+        """L, the tokens per sample (without [cls]) that forward() makes of `inp`: what reserve() is told."""
+        if self.kind == "text":
+            return inp[0].numel()
+        if self.kind == "audio":
+            return (inp.shape[2] // 16) * (inp.shape[1] // 16)
+        return (inp.shape[2] // 16) * (inp.shape[3] // 16)
+
     # ------------------------------------------------------------------------------------------
     def forward(self, inp: torch.Tensor, padding_mask: Optional[torch.Tensor] = None,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -337,8 +428,6 @@ class M3AEEncoder(FlatEncoder):
             B, L = ids.shape
             ws = self._plan(B, L)
             pm = padding_mask.reshape(B, -1).to(torch.float32)
-            if "ids" not in ws:
-                ws["ids"] = torch.empty_like(ids)
             ws["ids"].copy_(ids)     # owned copy: tokens_assemble_bwd reads it after forward() returned (feeder slots are reused)
             ids = ws["ids"]
             # cls is never masked (m3ae.py:347)
@@ -450,16 +539,14 @@ class M3AEEncoder(FlatEncoder):
             # d pos[i] = sum over the batch, d conv-weight = patches^T dx
             self.g[f"modality_{self.sfx}"].copy_(ws["colsum"])
             self.embed.gb.copy_(ws["colsum"])
-            if "red_pos" not in ws:
-                ws["red_pos"] = torch.empty(ops.colreduce_ws_elems(B, L * D), device=self.device, dtype=torch.float32)
-            ops.colsum_rows(dx, self.g[f"pos_embed_{self.sfx}"], ws["red_pos"], B, L * D, stream=st)
+            ops.colsum_rows(dx, self.g[f"pos_embed_{self.sfx}"], self._scratch(ws, "red_pos", ops.colreduce_ws_elems(B, L * D)), B, L * D,
+                            stream=st)
             self._lin_wgrad(self.embed, ws["patches"], dx, B * L, ws, st, bias=False)
         elif self.kind == "text":
             self.g["text_embedding.weight"].zero_()
-            if "emb_ws" not in ws:
-                ws["emb_ws"] = torch.empty(ops.tokens_assemble_bwd_ws_bytes(B, L, D), device=self.device, dtype=torch.uint8)
+            emb_ws = self._scratch(ws, "emb_ws", ops.tokens_assemble_bwd_ws_bytes(B, L, D), torch.uint8)
             ops.tokens_assemble_bwd(dx, ws["colsum"], ws["ids"], self.g["cls_token"], self.g["encoder_text_type_embedding"],
-                                    self.g["text_embedding.weight"], B, L, D, stream=st, ws=ws["emb_ws"])
+                                    self.g["text_embedding.weight"], B, L, D, stream=st, ws=emb_ws)
         else:
             ops.tokens_assemble_bwd(dx, ws["colsum"], None, self.g["cls_token"], self.g["encoder_image_type_embedding"], None,
                                     B, L, D, stream=st)
@@ -506,11 +593,22 @@ class ConcatFusion3(nn.Module):
 
 class Modal3Classifier(_Classifier):
     """models/basic_model.py:202-275: CAV-MAE audio (mae_a) + M3AE image (mae_v) + M3AE text (mae_t), head Linear(768, 4)
-    shared (--gs_flag) or Linear(2304, 4) on cat(a, v, t) (:218-221); MLA alternates a -> v -> t (main.py:432-466)."""
+    shared (--gs_flag) or Linear(2304, 4) on cat(a, v, t) (:218-221); MLA alternates a -> v -> t (main.py:432-466).
+
+    `present=` (forward, forward_raw, forward_split; MLATrainer.train_step and Evaluator.update pass it on): a HOST bool / uint8
+    tensor (B, 3), columns (audio, image, text) as in Modal3Batcher(mask=) -- Modal3Batcher.present(step) -- that says which
+    modalities each sample has; the inputs of the others must be what the batcher leaves there, zeros.  Each encoder then runs on
+    its modality's P present rows plus one zero row instead of all B (mla_hip.rows), which in exact arithmetic is the same step:
+    these encoders have no BatchNorm and no dropout, so every absent sample has the feature f(0).  The result differs from the
+    call without `present` in the order of floating-point sums only.  A modality that every sample has takes the path without
+    `present`, launch for launch.  Not offered by JointTrainer / QMFTrainer, nor by M3AEClassifier, CAVClassifier and
+    AVClassifier: the reference masks modalities for IEMOCAP only, and AVClassifier's ResNets have BatchNorm, whose batch
+    statistics make a sample's feature depend on every other row, zeros included."""
 
     def __init__(self, args, device="cuda", depth: int = 12, text_vocab_size: int = 30522, seed: Optional[int] = None,
                  conv_math: Optional[str] = None, attention_math: Optional[str] = None):
         super().__init__(args, device, seed, ("IEMOCAP",), ConcatFusion3, 768, 3)                             # :208-229
+        self._row_bufs: Dict[tuple, torch.Tensor] = {}
         kw = dict(depth=depth, text_vocab_size=text_vocab_size, conv_math=conv_math, attention_math=attention_math)
         self.mae_a = M3AEEncoder("audio", device, depth=depth, seed=self._seed(0), conv_math=conv_math,       # :231 CAVMAEFT
                                  attention_math=attention_math)
@@ -520,11 +618,54 @@ class Modal3Classifier(_Classifier):
     def mla_encoders(self):
         return [("a", "audio", self.mae_a), ("v", "image", self.mae_v), ("t", "text", self.mae_t)]
 
-    def _calls(self, token, padding_mask, visual, audio):
-        """a, v, t = model(token, padding_mask, image, spec)  (main.py:424; basic_model.py:252-275)"""
-        return visual.shape[0], [lambda out=None: self.mae_a.forward(audio, None, out),
-                                 lambda out=None: self.mae_v.forward(visual, None, out),
-                                 lambda out=None: self.mae_t.forward(token, padding_mask, out)]
+    def _calls(self, token, padding_mask, visual, audio, present=None):
+        """a, v, t = model(token, padding_mask, image, spec)  (main.py:424; basic_model.py:252-275); with `present`, each encoder
+        on the rows that have its modality (class docstring)."""
+        B = visual.shape[0]
+        inputs = (("a", self.mae_a, (audio,)), ("v", self.mae_v, (visual,)), ("t", self.mae_t, (token, padding_mask)))
+        have = None if present is None else check_present(present, B, len(inputs))
+        runs = []
+        for k, (tag, enc, xs) in enumerate(inputs):
+            if have is None or bool(have[:, k].all()):
+                runs.append(self._run_all(enc, xs))
+            else:
+                runs.append(self._run_present(tag, enc, xs, RowPlan(have[:, k])))
+        return B, runs
+
+    @staticmethod
+    def _run_all(enc, xs):
+        def run(out=None):
+            enc._row_grad = None                         # the backward takes the (B, D) feature gradient as it is
+            return enc.forward(xs[0], xs[1] if len(xs) > 1 else None, out)
+        return run
+
+    def _row_buf(self, tag: str, name, shape, dtype=torch.float32) -> torch.Tensor:
+        key = (tag, name, tuple(shape), dtype)
+        if key not in self._row_bufs:
+            self._row_bufs[key] = torch.empty(tuple(shape), device=self.device, dtype=dtype)
+        return self._row_bufs[key]
+
+    def _run_present(self, tag: str, enc, xs, plan: RowPlan):
+        """The forward of one encoder on its plan.P present rows and one zero row; leaves the matching compaction of the feature
+        gradient on the encoder (rows.compact_feature_grad).  Everything is enqueued on the stream run() is called on."""
+        def run(out=None):
+            B, rows, D = plan.B, plan.rows, self.feat_dim
+            plan.upload(self._row_buf(tag, "tables", (2 * B,), torch.int64))
+            packed = []
+            for j, x in enumerate(xs):
+                x = (x if x.dtype in (torch.float32, torch.int64) else x.float()).contiguous()
+                dst = self._row_buf(tag, j, x.shape, x.dtype)[:rows]
+                packed.append(ops.rows_gather(x, plan.idx, plan.idx_host, dst, zero_tail_rows=1))
+            enc.reserve(B, enc.tokens(packed[0]), backward=False)        # the workspace every later batch of <= B rows runs in
+            feat = enc.forward(packed[0], packed[1] if len(packed) > 1 else None, self._row_buf(tag, "feat", (B, D))[:rows])
+            if out is None:
+                out = self._row_buf(tag, "out", (B, D))
+            ops.rows_expand(feat, plan.map, plan.map_host, out)
+            dfeat_rows = self._row_buf(tag, "dfeat", (B, D))[:rows]
+            enc._row_grad = lambda dfeat: ops.rows_compact_sum(dfeat.contiguous(), plan.idx, plan.idx_host, plan.absent, plan.absent_host,
+                                                               dfeat_rows)
+            return out
+        return run
 
 
 class CAVClassifier(_Classifier):

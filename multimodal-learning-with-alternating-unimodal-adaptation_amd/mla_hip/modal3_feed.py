@@ -19,6 +19,8 @@ buffer and no descriptor row.  The image kernels (csrc/frames.hip) run over the 
 (P, 3, S, S) buffer; csrc/modal3.hip's mla_modal3_assemble then places them, writes zeros for the others and zeroes the staged rows
 of absent spectrograms, tokens and padding masks (which hold whatever the pinned ring held before) in one launch behind the
 batch's copies.  The zeros are +0.0 where the reference's x * 0 gives -0.0 for negative x: equal values, torch.equal holds.
+On the device the encoders run on those zeros unless the step is told which rows are there: Modal3Batcher.present(step) gives the
+batch's mask rows for MLATrainer.train_step(..., present=) / Evaluator.update(..., present=) (mla_hip.rows).
 
 Every image draw is a function of (seed, epoch, dataset index), as in M3AEBatcher: a sample's crop, flip and jitter do not depend
 on whether its neighbours are masked.  The mask is fixed for the batcher's life, as in the reference; set_epoch reseeds the image
@@ -34,6 +36,7 @@ import torch
 from . import ops
 from ._lib import MLAHipError
 from .cav_feed import middle_frame_path
+from .data import batch_ids
 from .frames import MEAN, RATIO, SCALE, STD, Batcher, Part, SampleKey, slot_buffer, token_part
 from .wav_feed import audio_fields, audio_part
 from .m3ae_feed import OUT_SIZE, timm_image_part
@@ -146,3 +149,8 @@ class Modal3Batcher(Batcher):
                          audio_fields(("token", "pm", "spec", "frames", "desc", "jdesc", "mdesc", "label", "idx"), audio_wav_path),
                          ("token", "pm", "image", "spec", "label", "idx"), seed=seed, epoch=epoch, threads=threads, ring=ring,
                          pin=pin, drop_last=drop_last)
+
+    def present(self, step: int) -> torch.Tensor:
+        """Host bool (b, 3), columns (audio, image, text): the mask rows of the batch the iterator yields at position `step` (batches
+        are in dataset order), as Modal3Classifier / MLATrainer.train_step / Evaluator.update take them under `present=`."""
+        return torch.from_numpy(self.mask[batch_ids(len(self.names), self.B, self.drop_last)[step]] != 0)

@@ -217,19 +217,20 @@ class _Classifier(nn.Module):
         run(out)
         return out
 
-    def forward_split(self, *inputs):
+    def forward_split(self, *inputs, **options):
         """Per-encoder forward closures in alternation order, so the trainer may run each encoder's forward on a stream of
-        its own: no encoder forward depends on the head or on another encoder."""
-        return self._calls(*inputs)[1]
+        its own: no encoder forward depends on the head or on another encoder.  `options`: what the subclass's
+        `_calls` takes by keyword beside its inputs (Modal3Classifier: present=)."""
+        return self._calls(*inputs, **options)[1]
 
-    def forward_raw(self, *inputs):
+    def forward_raw(self, *inputs, **options):
         """Kernel-level joint forward into the reused feature buffers (trainers / evaluators; no autograd)."""
-        return tuple(run() for run in self._calls(*inputs)[1])
+        return tuple(run() for run in self._calls(*inputs, **options)[1])
 
-    def forward(self, *inputs):
+    def forward(self, *inputs, **options):
         """The features as fresh (B, D) tensors that carry autograd history to their encoder when grad mode is on and the
         model is training."""
-        B, runs = self._calls(*inputs)
+        B, runs = self._calls(*inputs, **options)
         feats = tuple(self._feature(enc, run, B) for (_t, _g, enc), run in zip(self.mla_encoders(), runs))
         if self.qmf_heads is not None:      # QMF: (audio_fc(a), visual_fc(v)[, txtual_fc(t)]), basic_model.py:67-71, 196-200, 269-273
             return tuple(head(f) for head, f in zip(self.qmf_heads, feats))

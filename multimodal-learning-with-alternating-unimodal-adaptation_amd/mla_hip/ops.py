@@ -1046,6 +1046,85 @@ def modal3_assemble(image_compact: Optional[torch.Tensor], spec: torch.Tensor, t
     return image_out
 
 
+# ---- rows of a batch: gather, expand, compact-and-sum (csrc/rows.hip; Modal3Classifier(..., present=)) --------------------------
+def _index_host(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.is_cuda or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+        raise MLAHipError(f"{what}: expected a contiguous host int64 vector, got "
+                          f"{(t.dtype, tuple(t.shape), str(t.device)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    return t
+
+
+def _index_pair(dev: torch.Tensor, host: torch.Tensor, what: str) -> Tuple[Optional[int], Optional[int], int]:
+    """(device pointer, host pointer, entries) of an index table handed over on both sides; (None, None, 0) when it is empty."""
+    h = _index_host(host, what)
+    if dev.dim() != 1 or dev.numel() != h.numel():
+        raise MLAHipError(f"{what}: device table {tuple(dev.shape)} and host table {tuple(h.shape)} differ")
+    n = h.numel()
+    return (_p(dev, torch.int64), h.data_ptr(), n) if n else (None, None, 0)
+
+
+def _rows2d(t: torch.Tensor, what: str) -> Tuple[int, int]:
+    if t.dim() < 1 or t.shape[0] == 0 or t.numel() == 0 or not t.is_contiguous():
+        raise MLAHipError(f"{what}: expected a contiguous tensor of at least one non-empty row, got {tuple(t.shape)}")
+    return t.shape[0], t.numel() // t.shape[0]
+
+
+def rows_gather(src: torch.Tensor, idx: torch.Tensor, idx_host: torch.Tensor, dst: torch.Tensor, zero_tail_rows: int = 0,
+                stream: Optional[int] = None) -> torch.Tensor:
+    """src (B, ...) fp32 or int64, idx int64 (P) on the device and the same entries on the host -> dst (P + zero_tail_rows, ...):
+    dst[j] = src[idx[j]], then `zero_tail_rows` rows of zeros (see include/mla_hip.h, mla_rows_gather)."""
+    ip, hp, P = _index_pair(idx, idx_host, "rows_gather: idx")
+    B, row = _rows2d(src, "rows_gather: src")
+    if src.dtype not in (torch.float32, torch.int64) or dst.dtype != src.dtype:
+        raise MLAHipError(f"rows_gather: src {src.dtype} / dst {dst.dtype} must both be float32 or both int64")
+    if zero_tail_rows < 0 or dst.dim() < 1 or dst.shape[0] != P + zero_tail_rows or dst.numel() != dst.shape[0] * row:
+        raise MLAHipError(f"rows_gather: dst {tuple(dst.shape)} does not hold P + zero_tail_rows = {P} + {zero_tail_rows} rows of {row} elements")
+    _call("mla_rows_gather", _p(src, src.dtype), ip, hp, _p(dst, dst.dtype), B, P, row, src.element_size(), int(zero_tail_rows),
+          stream or cur_stream())
+    return dst
+
+
+def rows_expand_map(idx_host: torch.Tensor, fill_row: int, B: int, src_rows: int) -> torch.Tensor:
+    """The per-destination-row source map of rows_expand, host int64 (B): map[idx[j]] = j, every other row `fill_row`.  Refuses an
+    index outside [0, B), one named twice, more indices than source rows and a fill row outside the source (no GPU)."""
+    h = _index_host(idx_host, "rows_expand: idx")
+    P = h.numel()
+    if B <= 0 or P > B or P > src_rows or not 0 <= fill_row < src_rows:
+        raise MLAHipError(f"rows_expand: need 0 <= P <= B, P <= src_rows and 0 <= fill_row < src_rows (got P={P}, B={B}, src_rows={src_rows}, "
+                          f"fill_row={fill_row})")
+    if P and (int(h.min()) < 0 or int(h.max()) >= B or torch.unique(h).numel() != P):
+        raise MLAHipError(f"rows_expand: idx {h.tolist()} must name {P} different rows of [0, {B})")
+    m = torch.full((B,), int(fill_row), dtype=torch.int64)
+    m[h] = torch.arange(P, dtype=torch.int64)
+    return m
+
+
+def rows_expand(src: torch.Tensor, map: torch.Tensor, map_host: torch.Tensor, dst: torch.Tensor, stream: Optional[int] = None) -> torch.Tensor:
+    """src fp32 or int64 (S, ...), map int64 (B) on the device and the same entries on the host (rows_expand_map) -> dst (B, ...):
+    dst[b] = src[map[b]], every row written once (see include/mla_hip.h, mla_rows_expand)."""
+    mp, hp, B = _index_pair(map, map_host, "rows_expand: map")
+    S, row = _rows2d(src, "rows_expand: src")
+    if src.dtype not in (torch.float32, torch.int64) or dst.dtype != src.dtype:
+        raise MLAHipError(f"rows_expand: src {src.dtype} / dst {dst.dtype} must both be float32 or both int64")
+    if dst.dim() < 1 or dst.shape[0] != B or dst.numel() != B * row:
+        raise MLAHipError(f"rows_expand: dst {tuple(dst.shape)} does not hold {B} rows of {row} elements")
+    _call("mla_rows_expand", _p(src, src.dtype), mp, hp, _p(dst, dst.dtype), B, S, row, src.element_size(), stream or cur_stream())
+    return dst
+
+
+def rows_compact_sum(src: torch.Tensor, idx: torch.Tensor, idx_host: torch.Tensor, absent: torch.Tensor, absent_host: torch.Tensor,
+                     dst: torch.Tensor, stream: Optional[int] = None) -> torch.Tensor:
+    """src fp32 (B, ...), idx int64 (P) and absent int64 (A), each on the device and on the host -> dst (P + 1, ...):
+    dst[j] = src[idx[j]]; dst[P] = the fp32 sum of the rows src[absent[a]] in that order (see include/mla_hip.h, mla_rows_compact_sum)."""
+    ip, ihp, P = _index_pair(idx, idx_host, "rows_compact_sum: idx")
+    ap, ahp, A = _index_pair(absent, absent_host, "rows_compact_sum: absent")
+    B, row = _rows2d(src, "rows_compact_sum: src")
+    if dst.dim() < 1 or dst.shape[0] != P + 1 or dst.numel() != (P + 1) * row:
+        raise MLAHipError(f"rows_compact_sum: dst {tuple(dst.shape)} does not hold P + 1 = {P + 1} rows of {row} elements")
+    _call("mla_rows_compact_sum", _p(src), ip, ihp, ap, ahp, _p(dst), B, P, A, row, stream or cur_stream())
+    return dst
+
+
 # ---- Kaldi log-mel filterbank from PCM16 clips (data/extract_fbank.py:8-54) ------------------------------------------------------
 def _mel_runs_host(tables) -> Tuple[torch.Tensor, torch.Tensor]:
     s, l = tables.mel_start_host, tables.mel_len_host

@@ -483,6 +483,38 @@ def modal3_assemble(image_compact, spec, token, pm, mask_desc, size=256):
     return out
 
 
+# ---- rows of a batch: gather, expand, compact-and-sum (Modal3Classifier(..., present=)) ------------------------------------
+def _idx_host(idx: torch.Tensor) -> torch.Tensor:
+    return idx.cpu().to(torch.int64).reshape(-1).contiguous()
+
+
+@_op("rows_gather(Tensor src, Tensor idx, int zero_tail_rows=0) -> Tensor")
+def rows_gather(src, idx, zero_tail_rows=0):
+    """src (B, ...) fp32 or int64 (device) + row indices int64 (P) (host; validated there, then copied to the device) -> a new
+    (P + zero_tail_rows, ...): the rows src[idx[j]], then rows of zeros."""
+    h = _idx_host(idx)
+    out = torch.empty((h.numel() + zero_tail_rows,) + tuple(src.shape[1:]), device=src.device, dtype=src.dtype)
+    return ops.rows_gather(src, h.to(src.device), h, out, zero_tail_rows)
+
+
+@_op("rows_expand(Tensor src, Tensor idx, int fill_row, int rows) -> Tensor")
+def rows_expand(src, idx, fill_row, rows):
+    """src fp32 (S, ...) (device) + row indices int64 (P) (host) -> a new (rows, ...): out[idx[j]] = src[j], every other row
+    src[fill_row]; the per-row source map is built and validated on the host, then copied to the device."""
+    m = ops.rows_expand_map(_idx_host(idx), fill_row, rows, src.shape[0])
+    out = torch.empty((rows,) + tuple(src.shape[1:]), device=src.device, dtype=src.dtype)
+    return ops.rows_expand(src, m.to(src.device), m, out)
+
+
+@_op("rows_compact_sum(Tensor src, Tensor idx, Tensor absent_idx) -> Tensor")
+def rows_compact_sum(src, idx, absent_idx):
+    """src fp32 (B, ...) (device) + row indices int64 (P) and (A) (host; validated there, then copied to the device) -> a new
+    (P + 1, ...): the rows src[idx[j]], then the fp32 sum of the rows src[absent_idx[a]] in that order."""
+    h, a = _idx_host(idx), _idx_host(absent_idx)
+    out = torch.empty((h.numel() + 1,) + tuple(src.shape[1:]), device=src.device, dtype=src.dtype)
+    return ops.rows_compact_sum(src, h.to(src.device), h, a.to(src.device), a, out)
+
+
 # ---- Kaldi log-mel filterbank from PCM16 clips (data/extract_fbank.py:8-54) -------------------------------------------------
 @_op("wav_fbank(Tensor wav, Tensor desc, int target_length=1024) -> Tensor")
 def wav_fbank(wav, desc, target_length=1024):

@@ -26,6 +26,7 @@ from . import ops
 from .dist import Comm
 from .optim import FusedAdam, FusedSGD
 from .plugin import GSPlugin
+from .rows import compact_feature_grad
 
 
 class StreamTrainer:
@@ -94,14 +95,15 @@ class StreamTrainer:
     def _on(self, stream):
         return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
 
-    def _forwards(self, inputs):
+    def _forwards(self, inputs, **options):
         """The joint forward (main.py:424-431, 273): (features, their completion events).  Under the pipeline each encoder's
-        forward is enqueued on its own stream and the caller decides when to wait for which event; else the events are None."""
+        forward is enqueued on its own stream and the caller decides when to wait for which event; else the events are None.
+        `options`: the model's forward keywords (Modal3Classifier: present=)."""
         if not self.overlap_forward:
-            return self.model.forward_raw(*inputs), None
+            return self.model.forward_raw(*inputs, **options), None
         main = torch.cuda.current_stream()
         feats, done = [], []
-        for es, f in zip(self._estreams, self.model.forward_split(*inputs)):
+        for es, f in zip(self._estreams, self.model.forward_split(*inputs, **options)):
             es.wait_stream(main)       # inputs are ready; the previous step's head has read this encoder's features
             with torch.cuda.stream(es):
                 feats.append(f())      # stream order on `es`: after this encoder's SGD of the previous step
@@ -184,12 +186,12 @@ class MLATrainer(StreamTrainer):
         if enc is None:
             works = []                                                                        # stored features: nothing behind dX
         elif bstream is None:
-            enc.backward_from_pooled(dX, enc._pa)                                             # loss.backward()
+            enc.backward_from_pooled(compact_feature_grad(enc, dX), enc._pa)                  # loss.backward()
             works = self.comm.allreduce_flat_async(enc.grad)                                 # overlaps what follows
         else:
             bstream.wait_stream(torch.cuda.current_stream())                                  # dX (and the forward) are ready
             with torch.cuda.stream(bstream):
-                enc.backward_from_pooled(dX, enc._pa)
+                enc.backward_from_pooled(compact_feature_grad(enc, dX), enc._pa)
                 works = self.comm.allreduce_flat_async(enc.grad)
         fires = self.gs_plugin.mode == "as_intended" and self.gs_plugin.exp_count != 0
         r_mean = None
@@ -237,20 +239,24 @@ class MLATrainer(StreamTrainer):
             self.dist_events = {}
         return out
 
-    def train_step(self, *batch):
+    def train_step(self, *batch, present=None):
         """AVClassifier:     train_step(spec, image, label, batch_step, len_dataloader)
         M3AEClassifier:   train_step(token, padding_mask, image, label, batch_step, len_dataloader)
-        Modal3Classifier: train_step(token, padding_mask, image, spec, label, batch_step, len_dataloader)
+        Modal3Classifier: train_step(token, padding_mask, image, spec, label, batch_step, len_dataloader, present=None)
         spec (B,H,W) or (B,1,H,W); image (B,3,T,H,W) / (B,3,256,256); label int64 (B,).  Returns device scalars
-        {'loss','loss_a','loss_v'[,'loss_t']} (no host sync; call .item() when needed, main.py:472-476)."""
+        {'loss','loss_a','loss_v'[,'loss_t']} (no host sync; call .item() when needed, main.py:472-476).
+        present (Modal3Classifier only): host bool / uint8 (B, 3), columns (audio, image, text) -- Modal3Batcher.present(step): each
+        encoder runs forward and backward on the rows that have its modality plus one zero row; the head, the loss, the projection
+        and the optimiser see all B features, as without it."""
         *inputs, label, batch_step, len_dataloader = batch
+        options = {} if present is None else {"present": present}
         m, opt = self.model, self.optimizer
         if not getattr(m, "training", True):
             m.train()                                                                         # main.py:135 model.train()
         B = label.shape[0]
         inv_batch = 1.0 / (B * self.comm.world)
         opt.zero_grad()                                                                       # main.py:164
-        feats, fwd_done = self._forwards(inputs)                                              # main.py:424-431 (joint forward, Q7)
+        feats, fwd_done = self._forwards(inputs, **options)                                   # main.py:424-431 (joint forward, Q7)
         if self.feature_only:                                                                 # main.py:428-429, 432-454: head phases only
             for (tag, _g, _e), feat in zip(self.encoders, feats):
                 self.last[tag] = feat
@@ -311,10 +317,11 @@ class Evaluator:
     def reset(self) -> None:
         self.counts.zero_()
 
-    def update(self, *batch):
-        """update(spec, image, label) | update(token, padding_mask, image, label) | update(token, pm, image, spec, label)."""
+    def update(self, *batch, present=None):
+        """update(spec, image, label) | update(token, padding_mask, image, label) | update(token, pm, image, spec, label, present=None).
+        present (Modal3Classifier only): host bool / uint8 (B, 3) as in MLATrainer.train_step."""
         *inputs, label = batch
-        feats = self.model.forward_raw(*inputs)
+        feats = self.model.forward_raw(*inputs, **({} if present is None else {"present": present}))
         outs = [self.head.logits(f, slot="eval_" + str(k)) for k, f in enumerate(feats)]
         if self.comm.active:                                         # global batch (Q9): (world * B_local, C) in rank order
             g_outs = [self.comm.allgather_rows(o) for o in outs]
