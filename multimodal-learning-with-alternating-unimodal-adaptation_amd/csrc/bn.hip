@@ -7,9 +7,14 @@
 //
 // HBM-bound: every pass is float4-vectorised with channels on the fast axis, so a wave reads
 // whole 256-B..1-KiB pixel rows; per-channel reductions are thread-private over a row stripe,
-// then LDS across row lanes, then fp64 across tiles (mla_bn_finalize) -- no atomics, results are
-// bitwise reproducible.  Statistics normally arrive pre-reduced from the conv epilogue
-// (conv_igemm.hip), saving one full read of the activation.
+// then LDS across row lanes, then fp64 across tiles -- no atomics, results are bitwise reproducible.
+// Statistics normally arrive pre-reduced from the conv epilogue (conv_igemm.hip), saving one full
+// read of the activation.
+//
+// The fp64 step over the tile partials [tiles][2][C] is one family for both directions
+// (bn_finalize_partials picks the regime): bn_finalize_tiles_kernel<PT, FWD, CL, KL> in one launch
+// (<16, 16> or <4, 64>), or bn_tiles_stage1_kernel + bn_finalize_chunks_kernel<FWD>; the closing
+// arithmetic is written once (bn_close_fwd, bn_close_bwd).
 #include "common.h"
 
 static size_t bn_red_scratch_floats(int C);
@@ -31,23 +36,37 @@ extern "C" size_t mla_bn_stats_partial_elems(int M, int C) {
 }
 extern "C" size_t mla_bn_bwd_ws_elems(int M, int C) { return (size_t)cdiv(M, bn_tile_rows(M)) * 2 * C + bn_red_scratch_floats(C); }
 
-// Reduce two per-channel quantities over a tile of rows.  MODE 0: (x, x^2).  MODE 1: (g, g*xhat).
+// one per-channel float4 (mean, invstd, gamma, beta, dgamma, dbeta) of column group cg
+__device__ __forceinline__ f32x4 chan4(const float* __restrict__ p, int cg) { return reinterpret_cast<const f32x4*>(p)[cg]; }
+
+// The tail of the fp32 tile reductions (bn_reduce_kernel<1>, bn_bwd_pooled_reduce_kernel): row lane 0 of every column group adds
+// the sums of lanes 1..nrl-1 in that order through LDS and stores the partial row partial[tile][0|1][C] of this workgroup.
+__device__ __forceinline__ void bn_store_tile_sums(f32x4 s0, f32x4 s1, float* __restrict__ partial, int C, int cg, int rl, int nrl) {
+  __shared__ f32x4 red[2][256];
+  const int c4n = C >> 2;
+  red[0][threadIdx.x] = s0;
+  red[1][threadIdx.x] = s1;
+  __syncthreads();
+  if (rl == 0) {
+    for (int k = 1; k < nrl; ++k) {
+      s0 += red[0][k * c4n + cg];
+      s1 += red[1][k * c4n + cg];
+    }
+    reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 0) * C)[cg] = s0;
+    reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 1) * C)[cg] = s1;
+  }
+}
+
+// Reduce two per-channel quantities over a tile of rows.  MODE 0: (x, x^2), fp64 partials.  MODE 1: (g, g*xhat), fp32 partials.
 // Block: 256 threads = (C/4 column groups) x (row lanes); C/4 <= 256 and divides 256.
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dout,
                                                          const float* __restrict__ relu_out,
                                                          const float* __restrict__ mean, const float* __restrict__ invstd,
                                                          float* __restrict__ partial, int M, int C, int tile_rows) {
-  __shared__ f32x4 red[2][256];
   const int c4n = C >> 2;
   const int cg = threadIdx.x % c4n, rl = threadIdx.x / c4n, nrl = 256 / c4n;
   const int r0 = blockIdx.x * tile_rows, r1 = min(M, r0 + tile_rows);
-  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is = {1.f, 1.f, 1.f, 1.f};
-  if (MODE == 1) {
-    mu = reinterpret_cast<const f32x4*>(mean)[cg];
-    is = reinterpret_cast<const f32x4*>(invstd)[cg];
-  }
   if (MODE == 0) {   // forward statistics: everything in fp64 (x * x is exact there), see the conv epilogue in igemm_common.h
     double d0[4] = {0.0, 0.0, 0.0, 0.0}, d1[4] = {0.0, 0.0, 0.0, 0.0};
     for (int r = r0 + rl; r < r1; r += nrl) {
@@ -81,34 +100,21 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
     }
     return;
   }
+  const f32x4 mu = chan4(mean, cg), is = chan4(invstd, cg);
+  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
   for (int r = r0 + rl; r < r1; r += nrl) {
     const size_t idx = (size_t)r * c4n + cg;
     const f32x4 xv = reinterpret_cast<const f32x4*>(x)[idx];
-    if (MODE == 0) {
-      s0 += xv;
-      s1 += xv * xv;
-    } else {
-      f32x4 g = reinterpret_cast<const f32x4*>(dout)[idx];
-      if (relu_out) {
-        const f32x4 o = reinterpret_cast<const f32x4*>(relu_out)[idx];
+    f32x4 g = reinterpret_cast<const f32x4*>(dout)[idx];
+    if (relu_out) {
+      const f32x4 o = reinterpret_cast<const f32x4*>(relu_out)[idx];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) g[e] = o[e] > 0.f ? g[e] : 0.f;
-      }
-      s0 += g;
-      s1 += g * ((xv - mu) * is);
+      for (int e = 0; e < 4; ++e) g[e] = o[e] > 0.f ? g[e] : 0.f;
     }
+    s0 += g;
+    s1 += g * ((xv - mu) * is);
   }
-  red[0][threadIdx.x] = s0;
-  red[1][threadIdx.x] = s1;
-  __syncthreads();
-  if (rl == 0) {
-    for (int k = 1; k < nrl; ++k) {
-      s0 += red[0][k * c4n + cg];
-      s1 += red[1][k * c4n + cg];
-    }
-    reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 0) * C)[cg] = s0;
-    reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 1) * C)[cg] = s1;
-  }
+  bn_store_tile_sums(s0, s1, partial, C, cg, rl, nrl);
 }
 
 // Two-stage fp64 reduction of the per-tile partials partial[t][0|1][c] (up to 9408 tiles at the 64x64 conv tile).
@@ -177,13 +183,10 @@ __device__ __forceinline__ void chunk_sums(const double* __restrict__ scratch, i
     }
 }
 
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restrict__ scratch, int S, int M, int C, float eps,
-                                                           float momentum, float* __restrict__ mean, float* __restrict__ invstd,
-                                                           float* running_mean, float* running_var) {
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  double s, q;
-  chunk_sums(scratch, S, C, s, q);
-  if ((threadIdx.x >> 6) != 0 || c >= C) return;
+// The closing arithmetic of every finalize regime, from the fp64 channel totals s (slot 0) and q (slot 1).
+// Forward: mean, invstd from the clamped biased variance, running statistics with the unbiased one.
+__device__ __forceinline__ void bn_close_fwd(double s, double q, int M, float eps, float momentum, int c, float* __restrict__ mean,
+                                             float* __restrict__ invstd, float* running_mean, float* running_var) {
   const double m = s / M;
   double var = q / M - m * m;
   if (var < 0.0) var = 0.0;
@@ -195,41 +198,51 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restri
     running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unb);
   }
 }
-
-__global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const double* __restrict__ scratch, int S, int C,
-                                                               float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  double s, q;
-  chunk_sums(scratch, S, C, s, q);
-  if ((threadIdx.x >> 6) != 0 || c >= C) return;
+// Backward: slot 0 is sum g = dbeta, slot 1 is sum g * xhat = dgamma.
+__device__ __forceinline__ void bn_close_bwd(double s, double q, int c, float* __restrict__ dgamma, float* __restrict__ dbeta) {
   dbeta[c] = (float)s;
   dgamma[c] = (float)q;
 }
 
-// One-launch finalize for tile counts <= BN_ONE_MAXT (every layer but the stem and layer1 forward): a block owns 16
-// channels x 16 tile lanes; lane k sums tiles k, k+16, ... (four loads in flight), the 16 lanes are combined through LDS
-// in a fixed order, then the statistics are formed exactly as in bn_finalize_kernel / bn_bwd_finalize_kernel.  Replaces
-// the stage-1 + finalize pair (two dependent 5-8 us launches on the serial conv -> statistics -> apply chain) by one.
-#define BN_ONE_MAXT 1024
-template <typename PT, int FWD>
+// Stage 2.  FWD 1: out0 = mean, out1 = invstd.  FWD 0: out0 = dgamma, out1 = dbeta (the other arguments are unused).
+template <int FWD>
+__global__ __launch_bounds__(256) void bn_finalize_chunks_kernel(const double* __restrict__ scratch, int S, int M, int C, float eps,
+                                                                  float momentum, float* __restrict__ out0, float* __restrict__ out1,
+                                                                  float* running_mean, float* running_var) {
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  double s, q;
+  chunk_sums(scratch, S, C, s, q);
+  if ((threadIdx.x >> 6) != 0 || c >= C) return;
+  if (FWD) bn_close_fwd(s, q, M, eps, momentum, c, out0, out1, running_mean, running_var);
+  else bn_close_bwd(s, q, c, out0, out1);
+}
+
+// One-launch finalize, instead of the stage-1 + stage-2 pair (two dependent 5-8 us launches on the serial conv -> statistics ->
+// apply chain): a block owns CL channels x KL tile lanes; lane k sums tiles k, k + KL, ... (four loads in flight, then a tail of
+// single tiles), lane 0 adds the other lanes through LDS in ascending order, then the closing arithmetic above.  Two shapes:
+//   <16, 16>  up to BN_ONE_MAXT tiles (every layer but the stem and layer1 forward);
+//   <4, 64>   up to BN_WIDE_MAXT (layer1: 2048 / 2352 conv tiles, the pooled stem backward: <= 37 values per lane at 2352 tiles).
+// The order of the fp64 additions is part of the contract: tests/exact.py restates it and test_finalize_order holds every regime to it.
+template <typename PT, int FWD, int CL, int KL>
 __global__ __launch_bounds__(256) void bn_finalize_tiles_kernel(const PT* __restrict__ partial, int tiles, int M, int C, float eps,
                                                                  float momentum, float* __restrict__ out0, float* __restrict__ out1,
                                                                  float* running_mean, float* running_var) {
-  __shared__ double red[2][16][16];
-  const int cl = threadIdx.x & 15, kl = threadIdx.x >> 4;
-  const int c = blockIdx.x * 16 + cl;
+  static_assert(CL * KL == 256, "a block is CL channels x KL tile lanes");
+  __shared__ double red[2][KL][CL];
+  const int cl = threadIdx.x % CL, kl = threadIdx.x / CL;
+  const int c = blockIdx.x * CL + cl;
   double s = 0.0, q = 0.0;
   if (c < C) {
     int t = kl;
-    for (; t + 48 < tiles; t += 64) {
+    for (; t + 3 * KL < tiles; t += 4 * KL) {
       const double a0 = (double)partial[((size_t)t * 2 + 0) * C + c], b0 = (double)partial[((size_t)t * 2 + 1) * C + c];
-      const double a1 = (double)partial[((size_t)(t + 16) * 2 + 0) * C + c], b1 = (double)partial[((size_t)(t + 16) * 2 + 1) * C + c];
-      const double a2 = (double)partial[((size_t)(t + 32) * 2 + 0) * C + c], b2 = (double)partial[((size_t)(t + 32) * 2 + 1) * C + c];
-      const double a3 = (double)partial[((size_t)(t + 48) * 2 + 0) * C + c], b3 = (double)partial[((size_t)(t + 48) * 2 + 1) * C + c];
+      const double a1 = (double)partial[((size_t)(t + KL) * 2 + 0) * C + c], b1 = (double)partial[((size_t)(t + KL) * 2 + 1) * C + c];
+      const double a2 = (double)partial[((size_t)(t + 2 * KL) * 2 + 0) * C + c], b2 = (double)partial[((size_t)(t + 2 * KL) * 2 + 1) * C + c];
+      const double a3 = (double)partial[((size_t)(t + 3 * KL) * 2 + 0) * C + c], b3 = (double)partial[((size_t)(t + 3 * KL) * 2 + 1) * C + c];
       s += (a0 + a1) + (a2 + a3);
       q += (b0 + b1) + (b2 + b3);
     }
-    for (; t < tiles; t += 16) {
+    for (; t < tiles; t += KL) {
       s += (double)partial[((size_t)t * 2 + 0) * C + c];
       q += (double)partial[((size_t)t * 2 + 1) * C + c];
     }
@@ -238,78 +251,36 @@ __global__ __launch_bounds__(256) void bn_finalize_tiles_kernel(const PT* __rest
   red[1][kl][cl] = q;
   __syncthreads();
   if (kl != 0 || c >= C) return;
-  for (int k = 1; k < 16; ++k) {
+  for (int k = 1; k < KL; ++k) {
     s += red[0][k][cl];
     q += red[1][k][cl];
   }
-  if (FWD) {
-    const double m = s / M;
-    double var = q / M - m * m;
-    if (var < 0.0) var = 0.0;
-    out0[c] = (float)m;                                           // mean
-    out1[c] = (float)(1.0 / sqrt(var + (double)eps));             // invstd
-    if (running_mean) {
-      const double unb = var * ((double)M / (double)(M > 1 ? M - 1 : 1));
-      running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * m);
-      running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unb);
-    }
-  } else {
-    out1[c] = (float)s;                                           // dbeta
-    out0[c] = (float)q;                                           // dgamma
-  }
+  if (FWD) bn_close_fwd(s, q, M, eps, momentum, c, out0, out1, running_mean, running_var);
+  else bn_close_bwd(s, q, c, out0, out1);
 }
 
-// ... and for MORE than BN_ONE_MAXT tiles (layer1: 2048 / 2352 conv tiles, the pooled stem backward): a block owns 4 channels x 64
-// tile lanes (lane k sums tiles k, k + 64, ...: <= 37 values at 2352 tiles, four loads in flight), combined through LDS in a fixed
-// order.  One launch instead of the stage-1 + finalize pair of round 2 (two dependent launches on the serial conv ->
-// statistics -> apply chain); bn_tiles_stage1_kernel / bn_finalize_kernel stay for tile counts beyond BN_WIDE_MAXT.
-#define BN_WIDE_MAXT 16384
+// The one place that picks the finalize regime for `tiles` partial rows partial[tiles][2][C] (PT = double, FWD = 1: forward
+// statistics -> out0 = mean, out1 = invstd and the running statistics; PT = float, FWD = 0: backward sums -> out0 = dgamma,
+// out1 = dbeta).  Beyond BN_WIDE_MAXT tiles the two-stage pair runs through the scratch tail that follows the tiles.
+constexpr int BN_ONE_MAXT = 1024, BN_WIDE_MAXT = 16384;
 template <typename PT, int FWD>
-__global__ __launch_bounds__(256) void bn_finalize_tiles_wide_kernel(const PT* __restrict__ partial, int tiles, int M, int C, float eps,
-                                                                      float momentum, float* __restrict__ out0, float* __restrict__ out1,
-                                                                      float* running_mean, float* running_var) {
-  __shared__ double red[2][64][4];
-  const int cl = threadIdx.x & 3, kl = threadIdx.x >> 2;
-  const int c = blockIdx.x * 4 + cl;
-  double s = 0.0, q = 0.0;
-  if (c < C) {
-    int t = kl;
-    for (; t + 192 < tiles; t += 256) {
-      const double a0 = (double)partial[((size_t)t * 2 + 0) * C + c], b0 = (double)partial[((size_t)t * 2 + 1) * C + c];
-      const double a1 = (double)partial[((size_t)(t + 64) * 2 + 0) * C + c], b1 = (double)partial[((size_t)(t + 64) * 2 + 1) * C + c];
-      const double a2 = (double)partial[((size_t)(t + 128) * 2 + 0) * C + c], b2 = (double)partial[((size_t)(t + 128) * 2 + 1) * C + c];
-      const double a3 = (double)partial[((size_t)(t + 192) * 2 + 0) * C + c], b3 = (double)partial[((size_t)(t + 192) * 2 + 1) * C + c];
-      s += (a0 + a1) + (a2 + a3);
-      q += (b0 + b1) + (b2 + b3);
-    }
-    for (; t < tiles; t += 64) {
-      s += (double)partial[((size_t)t * 2 + 0) * C + c];
-      q += (double)partial[((size_t)t * 2 + 1) * C + c];
-    }
-  }
-  red[0][kl][cl] = s;
-  red[1][kl][cl] = q;
-  __syncthreads();
-  if (kl != 0 || c >= C) return;
-  for (int k = 1; k < 64; ++k) {
-    s += red[0][k][cl];
-    q += red[1][k][cl];
-  }
-  if (FWD) {
-    const double m = s / M;
-    double var = q / M - m * m;
-    if (var < 0.0) var = 0.0;
-    out0[c] = (float)m;                                           // mean
-    out1[c] = (float)(1.0 / sqrt(var + (double)eps));             // invstd
-    if (running_mean) {
-      const double unb = var * ((double)M / (double)(M > 1 ? M - 1 : 1));
-      running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * m);
-      running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unb);
-    }
+static int bn_finalize_partials(const PT* partial, int tiles, int M, int C, float eps, float momentum, float* out0, float* out1,
+                                float* running_mean, float* running_var, hipStream_t st) {
+  if (tiles <= BN_ONE_MAXT) {
+    bn_finalize_tiles_kernel<PT, FWD, 16, 16><<<cdiv(C, 16), 256, 0, st>>>(partial, tiles, M, C, eps, momentum, out0, out1, running_mean, running_var);
+    MLA_CHECK_LAUNCH("bn_finalize_tiles_kernel<16, 16>");
+  } else if (tiles <= BN_WIDE_MAXT) {
+    bn_finalize_tiles_kernel<PT, FWD, 4, 64><<<cdiv(C, 4), 256, 0, st>>>(partial, tiles, M, C, eps, momentum, out0, out1, running_mean, running_var);
+    MLA_CHECK_LAUNCH("bn_finalize_tiles_kernel<4, 64>");
   } else {
-    out1[c] = (float)s;                                           // dbeta
-    out0[c] = (float)q;                                           // dgamma
+    double* scratch = reinterpret_cast<double*>(const_cast<PT*>(partial) + (size_t)tiles * 2 * C);
+    const int S = bn_red_chunks(tiles);
+    bn_tiles_stage1_kernel<PT><<<dim3(cdiv(C, 64), S), 256, 0, st>>>(partial, tiles, C, scratch);
+    MLA_CHECK_LAUNCH("bn_tiles_stage1_kernel");
+    bn_finalize_chunks_kernel<FWD><<<cdiv(C, 64), 256, 0, st>>>(scratch, S, M, C, eps, momentum, out0, out1, running_mean, running_var);
+    MLA_CHECK_LAUNCH("bn_finalize_chunks_kernel");
   }
+  return MLA_OK;
 }
 
 // the one BN expression (explicit fma) every kernel that forms or re-forms bn(x) uses: identical rounding everywhere
@@ -326,8 +297,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
                                                         const float* residual, float* out, size_t n4, int c4n, int relu) {
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n4; idx += (size_t)gridDim.x * blockDim.x) {
     const int cg = (int)(idx % c4n);
-    const f32x4 mu = reinterpret_cast<const f32x4*>(mean)[cg], is = reinterpret_cast<const f32x4*>(invstd)[cg];
-    const f32x4 ga = reinterpret_cast<const f32x4*>(gamma)[cg], be = reinterpret_cast<const f32x4*>(beta)[cg];
+    const f32x4 mu = chan4(mean, cg), is = chan4(invstd, cg), ga = chan4(gamma, cg), be = chan4(beta, cg);
     f32x4 v = bn_val(reinterpret_cast<const f32x4*>(x)[idx], mu, is, ga, be);
     if (residual) v += reinterpret_cast<const f32x4*>(residual)[idx];
     if (relu) {
@@ -348,9 +318,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dout, co
                                                             size_t n4, int c4n, float invM) {
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n4; idx += (size_t)gridDim.x * blockDim.x) {
     const int cg = (int)(idx % c4n);
-    const f32x4 mu = reinterpret_cast<const f32x4*>(mean)[cg], is = reinterpret_cast<const f32x4*>(invstd)[cg];
-    const f32x4 ga = reinterpret_cast<const f32x4*>(gamma)[cg];
-    const f32x4 dg = reinterpret_cast<const f32x4*>(dgamma)[cg] * invM, db = reinterpret_cast<const f32x4*>(dbeta)[cg] * invM;
+    const f32x4 mu = chan4(mean, cg), is = chan4(invstd, cg), ga = chan4(gamma, cg);
+    const f32x4 dg = chan4(dgamma, cg) * invM, db = chan4(dbeta, cg) * invM;
     f32x4 g = reinterpret_cast<const f32x4*>(dout)[idx];
     if (relu_out) {
       const f32x4 o = reinterpret_cast<const f32x4*>(relu_out)[idx];
@@ -391,8 +360,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(const float* _
     const int oxq = (int)(p % QW); p /= QW;
     const int oyq = (int)(p % QH);
     const int n = (int)(p / QH);
-    const f32x4 mu = reinterpret_cast<const f32x4*>(mean)[cg], is = reinterpret_cast<const f32x4*>(invstd)[cg];
-    const f32x4 ga = reinterpret_cast<const f32x4*>(gamma)[cg], be = reinterpret_cast<const f32x4*>(beta)[cg];
+    const f32x4 mu = chan4(mean, cg), is = chan4(invstd, cg), ga = chan4(gamma, cg), be = chan4(beta, cg);
     f32x4 best[2][2];
     int bi[2][2][4];
     bool first[2][2];
@@ -467,12 +435,10 @@ __global__ __launch_bounds__(256) void bn_bwd_pooled_reduce_kernel(const float* 
                                                                     const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                                     const float* __restrict__ beta, float* __restrict__ out, int N, int H,
                                                                     int W, int C, int OH, int OW, int tile_rows) {
-  __shared__ f32x4 red[2][256];
   const int c4n = C >> 2, MP = N * OH * OW;
   const int cg = threadIdx.x % c4n, rl = threadIdx.x / c4n, nrl = 256 / c4n;
   const int r0 = blockIdx.x * tile_rows, r1 = min(MP, r0 + tile_rows);
-  const f32x4 mu = reinterpret_cast<const f32x4*>(mean)[cg], is = reinterpret_cast<const f32x4*>(invstd)[cg];
-  const f32x4 ga = reinterpret_cast<const f32x4*>(gamma)[cg], be = reinterpret_cast<const f32x4*>(beta)[cg];
+  const f32x4 mu = chan4(mean, cg), is = chan4(invstd, cg), ga = chan4(gamma, cg), be = chan4(beta, cg);
   f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
   for (int r = r0 + rl; r < r1; r += nrl) {
     const int ox = r % OW, t = r / OW, oy = t % OH, n = t / OH;
@@ -495,17 +461,7 @@ __global__ __launch_bounds__(256) void bn_bwd_pooled_reduce_kernel(const float* 
       s1[e] += ge * xhat[e];
     }
   }
-  red[0][threadIdx.x] = s0;
-  red[1][threadIdx.x] = s1;
-  __syncthreads();
-  if (rl == 0) {
-    for (int k = 1; k < nrl; ++k) {
-      s0 += red[0][k * c4n + cg];
-      s1 += red[1][k * c4n + cg];
-    }
-    reinterpret_cast<f32x4*>(out + ((size_t)blockIdx.x * 2 + 0) * C)[cg] = s0;
-    reinterpret_cast<f32x4*>(out + ((size_t)blockIdx.x * 2 + 1) * C)[cg] = s1;
-  }
+  bn_store_tile_sums(s0, s1, out, C, cg, rl, nrl);
 }
 
 // The apply pass: dy = gamma * invstd * (g - db/M - xhat * dg/M).  A thread owns the 2x2 pixel quad (2a + py, 2b + px): its
@@ -528,9 +484,8 @@ __global__ __launch_bounds__(256) void bn_bwd_pooled_apply_kernel(const float* _
     const int b = (int)(p % QW); p /= QW;
     const int a = (int)(p % QH);
     const int n = (int)(p / QH);
-    const f32x4 mu = reinterpret_cast<const f32x4*>(mean)[cg], is = reinterpret_cast<const f32x4*>(invstd)[cg];
-    const f32x4 ga = reinterpret_cast<const f32x4*>(gamma)[cg], be = reinterpret_cast<const f32x4*>(beta)[cg];
-    const f32x4 dgs = reinterpret_cast<const f32x4*>(dgamma)[cg], dbs = reinterpret_cast<const f32x4*>(dbeta)[cg];
+    const f32x4 mu = chan4(mean, cg), is = chan4(invstd, cg), ga = chan4(gamma, cg), be = chan4(beta, cg);
+    const f32x4 dgs = chan4(dgamma, cg), dbs = chan4(dbeta, cg);
     f32x4 dg, db;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { dg[e] = bn_bwd_scale(dgs[e], invM); db[e] = bn_bwd_scale(dbs[e], invM); }
@@ -587,6 +542,22 @@ static int ew_grid(size_t n4) {
   return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
+// the backward sums partial[tiles][2][C] (fp32, scratch tail behind them) -> dgamma, dbeta
+static int bn_bwd_finalize(const float* partial, int tiles, int M, int C, float* dgamma, float* dbeta, hipStream_t st) {
+  return bn_finalize_partials<float, 0>(partial, tiles, M, C, 0.f, 0.f, dgamma, dbeta, nullptr, nullptr, st);
+}
+
+// the apply pass of the two plain backward entry points
+static int bn_bwd_apply(const float* dout, const float* relu_out, const float* x, const float* mean, const float* invstd,
+                        const float* gamma, const float* dgamma, const float* dbeta, float* dx, float* g_out, int M, int C,
+                        hipStream_t st) {
+  const size_t n4 = (size_t)M * C / 4;
+  bn_bwd_apply_kernel<<<ew_grid(n4), 256, 0, st>>>(dout, relu_out, x, mean, invstd, gamma, dgamma, dbeta, dx, g_out, n4, C / 4,
+                                                   1.0f / (float)M);
+  MLA_CHECK_LAUNCH("bn_bwd_apply_kernel");
+  return MLA_OK;
+}
+
 extern "C" int mla_bn_stats_partial(const float* x, int M, int C, float* partial, int* tiles, void* stream) {
   if (int rc = bn_check("mla_bn_stats_partial", M, C)) return rc;
   MLA_REQUIRE(x && partial, "mla_bn_stats_partial: null pointer");
@@ -602,26 +573,8 @@ extern "C" int mla_bn_finalize(const float* partial, int tiles, int M, int C, fl
   MLA_REQUIRE(partial && mean && invstd && tiles > 0 && M > 0 && C > 0, "mla_bn_finalize: bad argument");
   MLA_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "mla_bn_finalize: running stats must come in pairs");
   MLA_REQUIRE(((uintptr_t)partial % 8) == 0, "mla_bn_finalize: partial must be 8-byte aligned");
-  // scratch tail: right after the tiles
-  hipStream_t st = (hipStream_t)stream;
   const double* pd = reinterpret_cast<const double*>(partial);                     // fp64 [tiles][2][C] (conv epilogue / bn_stats_partial)
-  if (tiles <= BN_ONE_MAXT) {
-    bn_finalize_tiles_kernel<double, 1><<<cdiv(C, 16), 256, 0, st>>>(pd, tiles, M, C, eps, momentum, mean, invstd, running_mean, running_var);
-    MLA_CHECK_LAUNCH("bn_finalize_tiles_kernel");
-    return MLA_OK;
-  }
-  if (tiles <= BN_WIDE_MAXT) {
-    bn_finalize_tiles_wide_kernel<double, 1><<<cdiv(C, 4), 256, 0, st>>>(pd, tiles, M, C, eps, momentum, mean, invstd, running_mean, running_var);
-    MLA_CHECK_LAUNCH("bn_finalize_tiles_wide_kernel");
-    return MLA_OK;
-  }
-  double* scratch = const_cast<double*>(pd) + (size_t)tiles * 2 * C;
-  const int S = bn_red_chunks(tiles);
-  bn_tiles_stage1_kernel<double><<<dim3(cdiv(C, 64), S), 256, 0, st>>>(pd, tiles, C, scratch);
-  MLA_CHECK_LAUNCH("bn_tiles_stage1_kernel");
-  bn_finalize_kernel<<<cdiv(C, 64), 256, 0, st>>>(scratch, S, M, C, eps, momentum, mean, invstd, running_mean, running_var);
-  MLA_CHECK_LAUNCH("bn_finalize_kernel");
-  return MLA_OK;
+  return bn_finalize_partials<double, 1>(pd, tiles, M, C, eps, momentum, mean, invstd, running_mean, running_var, (hipStream_t)stream);
 }
 
 extern "C" int mla_bn_apply(const float* x, const float* mean, const float* invstd, const float* gamma,
@@ -643,25 +596,8 @@ extern "C" int mla_bn_bwd(const float* dout, const float* relu_out, const float*
   const int tr = bn_tile_rows(M), nt = cdiv(M, tr);
   bn_reduce_kernel<1><<<nt, 256, 0, st>>>(x, dout, relu_out, mean, invstd, ws, M, C, tr);
   MLA_CHECK_LAUNCH("bn_reduce_kernel<1>");
-  if (nt <= BN_ONE_MAXT) {
-    bn_finalize_tiles_kernel<float, 0><<<cdiv(C, 16), 256, 0, st>>>(ws, nt, M, C, 0.f, 0.f, dgamma, dbeta, nullptr, nullptr);
-    MLA_CHECK_LAUNCH("bn_finalize_tiles_kernel");
-  } else if (nt <= BN_WIDE_MAXT) {
-    bn_finalize_tiles_wide_kernel<float, 0><<<cdiv(C, 4), 256, 0, st>>>(ws, nt, M, C, 0.f, 0.f, dgamma, dbeta, nullptr, nullptr);
-    MLA_CHECK_LAUNCH("bn_finalize_tiles_wide_kernel");
-  } else {
-    double* scratch = reinterpret_cast<double*>(ws + (size_t)nt * 2 * C);
-    const int S = bn_red_chunks(nt);
-    bn_tiles_stage1_kernel<float><<<dim3(cdiv(C, 64), S), 256, 0, st>>>(ws, nt, C, scratch);
-    MLA_CHECK_LAUNCH("bn_tiles_stage1_kernel");
-    bn_bwd_finalize_kernel<<<cdiv(C, 64), 256, 0, st>>>(scratch, S, C, dgamma, dbeta);
-    MLA_CHECK_LAUNCH("bn_bwd_finalize_kernel");
-  }
-  const size_t n4 = (size_t)M * C / 4;
-  bn_bwd_apply_kernel<<<ew_grid(n4), 256, 0, st>>>(dout, relu_out, x, mean, invstd, gamma, dgamma, dbeta, dx, g_out, n4,
-                                                   C / 4, 1.0f / (float)M);
-  MLA_CHECK_LAUNCH("bn_bwd_apply_kernel");
-  return MLA_OK;
+  if (int rc = bn_bwd_finalize(ws, nt, M, C, dgamma, dbeta, st)) return rc;
+  return bn_bwd_apply(dout, relu_out, x, mean, invstd, gamma, dgamma, dbeta, dx, g_out, M, C, st);
 }
 
 // BatchNorm backward whose reduction pass was done by the producer of dout (mla_conv2d_dgrad[_split]_bn): finalize the
@@ -673,25 +609,8 @@ extern "C" int mla_bn_bwd_from_partial(const float* dout, const float* x, const 
   MLA_REQUIRE(dout && x && mean && invstd && gamma && dx && dgamma && dbeta && partial && tiles > 0,
               "mla_bn_bwd_from_partial: null pointer or no tiles");
   hipStream_t st = (hipStream_t)stream;
-  if (tiles <= BN_ONE_MAXT) {
-    bn_finalize_tiles_kernel<float, 0><<<cdiv(C, 16), 256, 0, st>>>(partial, tiles, M, C, 0.f, 0.f, dgamma, dbeta, nullptr, nullptr);
-    MLA_CHECK_LAUNCH("bn_finalize_tiles_kernel");
-  } else if (tiles <= BN_WIDE_MAXT) {
-    bn_finalize_tiles_wide_kernel<float, 0><<<cdiv(C, 4), 256, 0, st>>>(partial, tiles, M, C, 0.f, 0.f, dgamma, dbeta, nullptr, nullptr);
-    MLA_CHECK_LAUNCH("bn_finalize_tiles_wide_kernel");
-  } else {
-    double* scratch = reinterpret_cast<double*>(partial + (size_t)tiles * 2 * C);
-    const int S = bn_red_chunks(tiles);
-    bn_tiles_stage1_kernel<float><<<dim3(cdiv(C, 64), S), 256, 0, st>>>(partial, tiles, C, scratch);
-    MLA_CHECK_LAUNCH("bn_tiles_stage1_kernel");
-    bn_bwd_finalize_kernel<<<cdiv(C, 64), 256, 0, st>>>(scratch, S, C, dgamma, dbeta);
-    MLA_CHECK_LAUNCH("bn_bwd_finalize_kernel");
-  }
-  const size_t n4 = (size_t)M * C / 4;
-  bn_bwd_apply_kernel<<<ew_grid(n4), 256, 0, st>>>(dout, nullptr, x, mean, invstd, gamma, dgamma, dbeta, dx, nullptr, n4, C / 4,
-                                                   1.0f / (float)M);
-  MLA_CHECK_LAUNCH("bn_bwd_apply_kernel");
-  return MLA_OK;
+  if (int rc = bn_bwd_finalize(partial, tiles, M, C, dgamma, dbeta, st)) return rc;
+  return bn_bwd_apply(dout, nullptr, x, mean, invstd, gamma, dgamma, dbeta, dx, nullptr, M, C, st);
 }
 
 extern "C" int mla_bn_relu_maxpool_fwd(const float* y, const float* mean, const float* invstd, const float* gamma, const float* beta,
@@ -719,20 +638,7 @@ extern "C" int mla_bn_bwd_pooled(const float* dpool, const uint8_t* idx, const f
   const int trp = bn_tile_rows(MP), nt = cdiv(MP, trp);     // reduction: tiles of pooled pixels (<= the tiles of M the workspace holds)
   bn_bwd_pooled_reduce_kernel<<<nt, 256, 0, st>>>(dpool, idx, y, mean, invstd, gamma, beta, ws, N, H, W, C, OH, OW, trp);
   MLA_CHECK_LAUNCH("bn_bwd_pooled_reduce_kernel");
-  if (nt <= BN_ONE_MAXT) {
-    bn_finalize_tiles_kernel<float, 0><<<cdiv(C, 16), 256, 0, st>>>(ws, nt, M, C, 0.f, 0.f, dgamma, dbeta, nullptr, nullptr);
-    MLA_CHECK_LAUNCH("bn_finalize_tiles_kernel");
-  } else if (nt <= BN_WIDE_MAXT) {
-    bn_finalize_tiles_wide_kernel<float, 0><<<cdiv(C, 4), 256, 0, st>>>(ws, nt, M, C, 0.f, 0.f, dgamma, dbeta, nullptr, nullptr);
-    MLA_CHECK_LAUNCH("bn_finalize_tiles_wide_kernel");
-  } else {
-    double* scratch = reinterpret_cast<double*>(ws + (size_t)nt * 2 * C);
-    const int S = bn_red_chunks(nt);
-    bn_tiles_stage1_kernel<float><<<dim3(cdiv(C, 64), S), 256, 0, st>>>(ws, nt, C, scratch);
-    MLA_CHECK_LAUNCH("bn_tiles_stage1_kernel");
-    bn_bwd_finalize_kernel<<<cdiv(C, 64), 256, 0, st>>>(scratch, S, C, dgamma, dbeta);
-    MLA_CHECK_LAUNCH("bn_bwd_finalize_kernel");
-  }
+  if (int rc = bn_bwd_finalize(ws, nt, M, C, dgamma, dbeta, st)) return rc;
   if (!dy) return MLA_OK;            // reduction half only: the consumer of dy forms it itself (mla_conv2d_stem_wgrad_split_bnpool)
   const size_t nq = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);     // one thread per 2x2 pixel quad and 4 channels
   bn_bwd_pooled_apply_kernel<<<ew_grid(nq), 256, 0, st>>>(dpool, idx, y, mean, invstd, gamma, beta, dgamma, dbeta, dy, N, H, W, C, OH, OW);

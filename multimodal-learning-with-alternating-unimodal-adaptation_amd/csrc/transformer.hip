@@ -106,35 +106,23 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_kernel(const float* __restrict_
   }
 }
 
-// Column reductions over rows.  MODE 0: s0 = sum x.  MODE 1 (LayerNorm affine grads): s0 = sum dy, s1 = sum dy*xhat.
+// Column sums over rows: partial[tile][0][c] = sum of the tile's rows of a.  Slot 1 of the row is written as zeros: the rows have
+// the two-slot layout of ln_bwd_dx_kernel's, because colreduce_finalize_kernel (shared with it) reads both slots.
 // grid (C/64, row tiles); 256 threads = 16 float4 column groups x 16 row lanes.
-template <int MODE>
-__global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict__ a, const float* __restrict__ x,
-                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                         float* __restrict__ partial, int M, int C, int tile_rows) {
-  __shared__ f32x4 red[2][256];
+__global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict__ a, float* __restrict__ partial, int M, int C,
+                                                         int tile_rows) {
+  __shared__ f32x4 red[256];
   const int cg = threadIdx.x & 15, rl = threadIdx.x >> 4;
   const int c4 = blockIdx.x * 16 + cg, c4n = C >> 2;
   const int r0 = blockIdx.y * tile_rows, r1 = min(M, r0 + tile_rows);
-  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-  for (int r = r0 + rl; r < r1; r += 16) {
-    const f32x4 av = reinterpret_cast<const f32x4*>(a)[(size_t)r * c4n + c4];
-    s0 += av;
-    if (MODE == 1) {
-      const f32x4 xv = reinterpret_cast<const f32x4*>(x)[(size_t)r * c4n + c4];
-      s1 += av * ((xv - mean[r]) * rstd[r]);
-    }
-  }
-  red[0][threadIdx.x] = s0;
-  red[1][threadIdx.x] = s1;
+  f32x4 s0 = {0.f, 0.f, 0.f, 0.f};
+  for (int r = r0 + rl; r < r1; r += 16) s0 += reinterpret_cast<const f32x4*>(a)[(size_t)r * c4n + c4];
+  red[threadIdx.x] = s0;
   __syncthreads();
   if (rl == 0) {
-    for (int k = 1; k < 16; ++k) {
-      s0 += red[0][k * 16 + cg];
-      s1 += red[1][k * 16 + cg];
-    }
+    for (int k = 1; k < 16; ++k) s0 += red[k * 16 + cg];
     reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.y * 2 + 0) * C)[c4] = s0;
-    reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.y * 2 + 1) * C)[c4] = s1;
+    reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.y * 2 + 1) * C)[c4] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 }
 
@@ -171,8 +159,8 @@ extern "C" int mla_colsum_rows(const float* x, float* out, float* ws, int M, int
   MLA_REQUIRE(x && out && ws && M > 0 && C > 0 && C % 64 == 0, "mla_colsum_rows: bad argument (C %% 64 == 0)");
   hipStream_t st = (hipStream_t)stream;
   const int tr = colreduce_tile_rows(M), nt = cdiv(M, tr);
-  colreduce_kernel<0><<<dim3(C / 64, nt), 256, 0, st>>>(x, nullptr, nullptr, nullptr, ws, M, C, tr);
-  MLA_CHECK_LAUNCH("colreduce_kernel<0>");
+  colreduce_kernel<<<dim3(C / 64, nt), 256, 0, st>>>(x, ws, M, C, tr);
+  MLA_CHECK_LAUNCH("colreduce_kernel");
   colreduce_finalize_kernel<<<cdiv(C, 4), 256, 0, st>>>(ws, nt, C, out, nullptr);
   MLA_CHECK_LAUNCH("colreduce_finalize_kernel");
   return MLA_OK;

@@ -362,13 +362,18 @@ def bwd_partials(tiles, C, seed):
     return SimpleNamespace(tiles=tiles, C=C, ints=p, partial=p.float(), dbeta=exact_f32(tot[0], 1.0), dgamma=exact_f32(tot[1], 1.0))
 
 
+def fwd_rows(tiles):
+    """The row count M = 2^k the forward cases pair with `tiles` tiles: about 32 to 64 rows per tile."""
+    return 1 << (32 * tiles - 1).bit_length()
+
+
 def fwd_partials(tiles, C, seed):
     """fp64 [tiles][2][C] per-tile (sum x, sum x^2) rows as the conv epilogue / bn_reduce_kernel<0> write them, for M = 2^k rows (about
     32 to 64 per tile): sum x in [-32, 96] without 0, sum x^2 in [1024, 4095].  Then |mean| <= 3 and E[x^2] > 16, so the variance is
     above 7 -- far from the cancellation of E[x^2] - E[x]^2 -- and s / M is exact in fp64 AND in fp32 (s < 2^24).
     The running mean starts at multiples of 1/4: (1 - momentum) * rm + momentum * mean is then exact in fp64 whether the compiler
     contracts it or not (running_units), so after the one rounding to fp32 the kernel's value must equal the reference bit for bit."""
-    M = 1 << (32 * tiles - 1).bit_length()
+    M = fwd_rows(tiles)
     s = rand_ints((tiles, 1, C), -32, 96, seed, nonzero=True)
     q = rand_ints((tiles, 1, C), 1024, 4095, seed + 1)
     p = torch.cat([s, q], 1)
@@ -399,6 +404,113 @@ def running_units(S, rm4, M):
     u = (2 ** 27 - a) * rm4 * M + 4 * a * S
     assert int(u.abs().max()) < 2 ** 53
     return u, 2.0 ** -29 / M
+
+
+# ---- 1b. the ORDER in which each finalize regime adds the tiles of one channel ---------------------------------------------------------
+# On the integer data above every order gives the same bits, so those cases cannot see a change of the fp64 summation order -- which
+# decides the last bit of every mean, dgamma and dbeta in training.  Here the order of csrc/bn.hip is restated in torch fp64 (IEEE
+# addition, like the device's v_add_f64: no fast-math on either side) and run on CANCELLING partials, whose channel total is rounding
+# residue and nothing else.  p is [tiles][...] (any trailing shape: slots and channels are carried along), widened to fp64 first.
+BN_ONE_MAXT, BN_WIDE_MAXT = 1024, 16384          # the regime thresholds of csrc/bn.hip
+ORDER_REGIMES = ("narrow", "wide", "two_stage")
+
+
+def finalize_regime(tiles):
+    return "narrow" if tiles <= BN_ONE_MAXT else "wide" if tiles <= BN_WIDE_MAXT else "two_stage"
+
+
+def lane_order_total(p, KL):
+    """bn_finalize_tiles_kernel with KL tile lanes (narrow: 16, wide: 64).  Lane k starts at tile k; while t + 3 KL < tiles it adds
+    (p[t] + p[t+KL]) + (p[t+2KL] + p[t+3KL]) and steps 4 KL, then it adds p[t] singly in steps of KL; lane 0 adds lanes 1..KL-1 in
+    ascending order.  One loop trip here is one block of 4 KL tiles: the first `full` lanes take the unrolled form, the others are
+    in their tail (a lane that left the unrolled loop never re-enters it, and its tail ends inside the same block)."""
+    p = p.double()
+    tiles = p.shape[0]
+    s = torch.zeros((KL,) + p.shape[1:], dtype=torch.float64)
+    for t in range(0, tiles, 4 * KL):
+        full = min(max(tiles - t - 3 * KL, 0), KL)
+        if full:
+            a = [p[t + j * KL:t + j * KL + full] for j in range(4)]
+            s[:full] += (a[0] + a[1]) + (a[2] + a[3])
+        for j in range(4):
+            lo, hi = t + j * KL + full, min(t + (j + 1) * KL, tiles)
+            if lo < hi:
+                s[full:full + hi - lo] += p[lo:hi]
+    tot = s[0].clone()
+    for k in range(1, KL):
+        tot += s[k]
+    return tot
+
+
+def two_stage_order_total(p):
+    """bn_tiles_stage1_kernel + chunk_sums.  S = clamp(cdiv(tiles, 64), 1, 64) chunks of per = cdiv(tiles, S) tiles; in a chunk wave w
+    of 4 adds tiles t0 + w, t0 + w + 4, ... one by one, wave 0 then adds waves 1..3; stage 2: lane kl of 4 adds the chunk sums kl,
+    kl + 4, ... in ascending order (absent chunks count as 0.0), lane 0 then adds lanes 1..3.  Tiles past the end of a chunk are
+    zero-padded here: a running sum that starts at +0.0 is never -0.0, so adding +0.0 leaves its bits alone."""
+    p = p.double()
+    tiles, rest = p.shape[0], p.shape[1:]
+    S = min(max(-(-tiles // 64), 1), 64)
+    per = -(-tiles // S)
+    trips = -(-per // 4)
+    pad = torch.zeros((S, trips * 4) + rest, dtype=torch.float64)
+    for y in range(S):
+        n = max(min(tiles, (y + 1) * per) - y * per, 0)
+        pad[y, :n] = p[y * per:y * per + n]
+    pad = pad.view((S, trips, 4) + rest)
+    w = torch.zeros((S, 4) + rest, dtype=torch.float64)
+    for i in range(trips):
+        w += pad[:, i]
+    chunk = torch.zeros((64,) + rest, dtype=torch.float64)
+    chunk[:S] = ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+    chunk = chunk.view((16, 4) + rest)
+    lane = torch.zeros((4,) + rest, dtype=torch.float64)
+    for j in range(16):
+        lane += chunk[j]
+    return ((lane[0] + lane[1]) + lane[2]) + lane[3]
+
+
+def sequential_total(p):
+    """Plain tile-by-tile fp64 sum (no kernel's order: what the cancelling tile is built from, and a fourth order to tell apart)."""
+    p = p.double()
+    tot = torch.zeros(p.shape[1:], dtype=torch.float64)
+    for t in range(p.shape[0]):
+        tot += p[t]
+    return tot
+
+
+def order_total(p, regime=None):
+    """The fp64 total of every channel of p, added in the order of `regime` (default: the regime this tile count lands in)."""
+    regime = regime or finalize_regime(p.shape[0])
+    return lane_order_total(p, 16) if regime == "narrow" else lane_order_total(p, 64) if regime == "wide" else two_stage_order_total(p)
+
+
+def _cancel_tail(p, n_split):
+    """Replace the last min(n_split, tiles - 1) tiles of p by minus the sequential fp64 sum of the tiles before them, split into
+    that many values of p's dtype (the value itself last, before it what its rounding left, ...).  One fp64 value, or three fp32 values (72 >= 53
+    bits), hold that sum exactly, so the mathematical total of every channel is zero.  A single tile stays as drawn."""
+    k = min(n_split, p.shape[0] - 1)
+    if k:
+        r = -sequential_total(p[:-k])
+        for i in range(1, k + 1):                # the leading part goes last: the closing tile is never a zero
+            p[-i] = r.to(p.dtype)
+            r = r - p[-i].double()
+        assert (r == 0).all(), "the split must hold the sum exactly"
+    return p
+
+
+def cancelling_partials(tiles, C, seed):
+    """[tiles][2][C] partial rows whose channel totals are pure rounding residue: non-integers with a wide exponent spread,
+    randn * 2^randint(-20, 20) per element, closed by tiles that cancel the sequential fp64 sum of the others (_cancel_tail).
+    The bits of a total then depend on the order of the additions and on nothing else.  `fwd`: fp64, as the forward statistics
+    arrive; `bwd`: generated in fp32 (a product of an fp32 value and a power of two), so that the kernel's widening is exact --
+    there the sum of the others needs three fp32 tiles to cancel to the last fp64 bit: with one, its fp32 rounding (2^-24 of
+    the sum) would bury the order's residue (2^-53) beyond what an fp32 result resolves."""
+    g = torch.Generator().manual_seed(int(seed) + 1)     # (+ 1: with + 0 the case 1216 x 4 misses test_cancelling_partials_tell_orders_apart)
+
+    def draw(dtype):
+        v = torch.randn((tiles, 2, C), generator=g, dtype=dtype)
+        return v * (2.0 ** torch.randint(-20, 21, (tiles, 2, C), generator=g).double()).to(dtype)
+    return SimpleNamespace(tiles=tiles, C=C, M=fwd_rows(tiles), fwd=_cancel_tail(draw(torch.float64), 1), bwd=_cancel_tail(draw(torch.float32), 3))
 
 
 # ---- 2. producer kernels over [M][C] rows -------------------------------------------------------------------------------------------
@@ -597,7 +709,7 @@ def case_seed(*v):
     return sum((i + 1) * int(x) for i, x in enumerate(v)) % 100003
 
 
-_REDUCE_BUILDERS = {"fwd_partials": fwd_partials, "bwd_partials": bwd_partials, "bn_rows": bn_rows_case, "dgrad_bn": dgrad_bn_case,
+_REDUCE_BUILDERS = {"fwd_partials": fwd_partials, "bwd_partials": bwd_partials, "cancelling": cancelling_partials, "bn_rows": bn_rows_case, "dgrad_bn": dgrad_bn_case,
                     "pooled": pooled_case, "colsum": colsum_case, "ln": ln_case}
 
 

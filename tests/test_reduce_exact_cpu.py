@@ -4,7 +4,10 @@ test_reduce_exact_gpu.py.
 For every builder and every case that file runs: the 2^24 budget holds (the builders assert it, no case is skipped or relaxed), the
 int64 reference equals an fp64 evaluation of the same sums (in fp32 too, in more than one order, where that is cheap), the tile
 contributions are non-zero and distinct, and the two slots of a partial row have different totals -- so that a dropped, doubled or
-swapped tile, row or slot moves a result by at least one unit."""
+swapped tile, row or slot moves a result by at least one unit.
+
+For the order pin (test_finalize_order): the vectorised restatement of the kernels' summation order equals a tile-by-tile loop, and
+the cancelling partials give different bits for every pair of orders."""
 import pytest
 import torch
 
@@ -47,6 +50,78 @@ def test_finalize_cases_cover_the_regimes():
     wide = [x for x in t if 1024 < x <= 16384]
     assert any((x - 1) % 256 >= 192 for x in wide) and any((x - 1) % 256 < 192 for x in wide)
     assert {C for C, _ in X.FINALIZE_CASES} == {4, 64, 1024} and all(tl <= 1025 for C, tl in X.FINALIZE_CASES if C == 1024)
+
+
+def _lane_loop(p, KL):
+    """The lane regimes tile by tile, as the kernel text reads (p: [tiles][...] fp64)."""
+    tiles, lanes = p.shape[0], []
+    for k in range(KL):
+        s, t = torch.zeros_like(p[0]), k
+        while t + 3 * KL < tiles:
+            s = s + ((p[t] + p[t + KL]) + (p[t + 2 * KL] + p[t + 3 * KL]))
+            t += 4 * KL
+        while t < tiles:
+            s = s + p[t]
+            t += KL
+        lanes.append(s)
+    tot = lanes[0]
+    for k in range(1, KL):
+        tot = tot + lanes[k]
+    return tot
+
+
+def _two_stage_loop(p):
+    """Stage 1 + chunk sums tile by tile."""
+    tiles = p.shape[0]
+    S = min(max((tiles + 63) // 64, 1), 64)
+    per = (tiles + S - 1) // S
+    chunks = []
+    for y in range(S):
+        t0, t1 = y * per, min(tiles, (y + 1) * per)
+        waves = []
+        for w in range(4):
+            s = torch.zeros_like(p[0])
+            for t in range(t0 + w, t1, 4):
+                s = s + p[t]
+            waves.append(s)
+        chunks.append(((waves[0] + waves[1]) + waves[2]) + waves[3])
+    lanes = []
+    for kl in range(4):
+        s = torch.zeros_like(p[0])
+        for j in range(16):
+            s = s + (chunks[kl + 4 * j] if kl + 4 * j < S else 0.0)
+        lanes.append(s)
+    return ((lanes[0] + lanes[1]) + lanes[2]) + lanes[3]
+
+
+@pytest.mark.parametrize("tiles", [17, 1025 + 191])
+def test_order_restatement_is_the_per_tile_loop(tiles):
+    """exact.order_total (vectorised over lanes, one trip per step) against the direct per-tile loops above, for all three regimes."""
+    c = X.reduce_case("cancelling", tiles, 4)
+    for p in (c.fwd, c.bwd.double()):
+        assert torch.equal(X.order_total(p, "narrow"), _lane_loop(p, 16))
+        assert torch.equal(X.order_total(p, "wide"), _lane_loop(p, 64))
+        assert torch.equal(X.order_total(p, "two_stage"), _two_stage_loop(p))
+
+
+@pytest.mark.parametrize("C,tiles", [c for c in X.FINALIZE_CASES if c[1] > 64], ids=_ids)
+def test_cancelling_partials_tell_orders_apart(C, tiles):
+    """A condition on the inputs of test_finalize_order: on the cancelling partials the three regimes' orders and the plain sequential
+    order give pairwise different totals in at least half of the channels of each slot, in both layouts -- so a kernel that adds in
+    another regime's order, or tile by tile, cannot pass.  (At or below 64 tiles one or both lane regimes ARE the sequential order.)
+    The totals are what the GPU test compares: float32(total) for the backward layout, float32(total / M) for the forward one."""
+    c = X.reduce_case("cancelling", tiles, C)
+    assert c.bwd.dtype == torch.float32 and c.fwd.dtype == torch.float64 and c.M == X.reduce_case("fwd_partials", tiles, C).M
+    for name, p, scale in (("forward", c.fwd, 1.0 / c.M), ("backward", c.bwd, 1.0)):
+        assert torch.isfinite(p).all()
+        tot = {r: (X.order_total(p, r) * scale).float() for r in X.ORDER_REGIMES}
+        tot["sequential"] = (X.sequential_total(p) * scale).float()
+        assert tot[X.finalize_regime(tiles)].abs().max().item() < 1e-6 * p.abs().max().item() * scale, "the totals must be residue"
+        names = list(tot)
+        for i, a in enumerate(names):
+            for b in names[i + 1:]:
+                differ = (tot[a] != tot[b]).sum(1)
+                assert (2 * differ >= C).all(), f"{name} {tiles} x {C}: {a} and {b} differ in {differ.tolist()} of {C} channels per slot"
 
 
 @pytest.mark.parametrize("M,C", X.BN_ROW_CASES, ids=_ids)

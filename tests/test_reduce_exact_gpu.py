@@ -9,6 +9,9 @@ second trip of the capped elementwise grid).  All sums are required BIT-EQUAL to
 mis-paired row, tile or slot is off by whole units.  Every case asserts its 2^24 budget on the CPU before it launches anything
 (test_reduce_exact_cpu.py proves the same cases without a GPU); no case is skipped or relaxed.
 
+Integer data cannot see the ORDER of the fp64 additions (every order gives the same bits); test_finalize_order pins it, on the same
+finalize cases, with partials whose totals are rounding residue, against the restatement of the kernels' order in tests/exact.py.
+
 What is not exact by nature is held to the formats: invstd and running_var to 2 fp32 ulp of the fp64 evaluation (one correctly rounded
 fp64 divide, sqrt and subtract, possibly fused, then one rounding to fp32); the elementwise passes (bn_apply, the BatchNorm and
 LayerNorm input gradients) to the fp64 formula at the tolerances of test_bn_fwd_bwd / test_layernorm, element by element, on data
@@ -101,6 +104,39 @@ def test_finalize_backward(ops, C, tiles):
     assert_bitwise(dbeta, b.dbeta, name + ": dbeta", 1.0)
     assert_bitwise(dgamma, b.dgamma, name + ": dgamma", 1.0)
     assert_close_each(dx, X.bn_dx_rows(r.g, r.x, r.ch, dgamma.cpu(), dbeta.cpu(), 64), 1e-6, 2e-5, name + ": dx")
+
+
+@pytest.mark.parametrize("C,tiles", X.FINALIZE_CASES, ids=_ids)
+def test_finalize_order(ops, C, tiles):
+    """The fp64 ORDER of the finalize regimes, which the integer cases above cannot see: on the cancelling partials of tests/exact.py
+    (channel totals are rounding residue; test_reduce_exact_cpu.py proves that the regimes' orders and the sequential one give
+    different bits there) the results are bit-equal to exact.order_total, the CPU restatement of the kernels' order of additions.
+    Backward (mla_bn_bwd_from_partial, fp32 partials, apply pass on the 64-row problem): dbeta = float32(total of slot 0), dgamma =
+    float32(total of slot 1).  Forward (mla_bn_finalize, fp64 partials): mean = float32(total of slot 0 / M).  invstd and the
+    running statistics are not asserted here -- slot 1 cancels to noise and the variance clamps; test_finalize_forward holds them --
+    but slot 1 of the double instantiation runs the same template code as slot 0, and the backward half covers slot 1 for the
+    float instantiation."""
+    c = X.reduce_case("cancelling", tiles, C)
+    r = _rows64(C)
+    name = f"finalize order ({X.finalize_regime(tiles)}) {tiles} tiles x {C}"
+
+    want = X.order_total(c.bwd).float()
+    buf = torch.cat([c.bwd.reshape(-1).cuda(), _nan(ops.bn_partial_scratch_elems(C))])
+    mean, invstd, gamma, _ = _dev_channels(r.ch)
+    dx, dgamma, dbeta = _nan(64, C), _nan(C), _nan(C)
+    ops.bn_bwd_from_partial(r.g.cuda(), r.x.cuda(), mean, invstd, gamma, dx, dgamma, dbeta, buf, tiles, 64, C)
+    assert_bitwise(dbeta, want[0], name + ": dbeta")
+    assert_bitwise(dgamma, want[1], name + ": dgamma")
+    assert not torch.isnan(dx).any(), name + ": dx"
+
+    want = (X.order_total(c.fwd[:, 0]) / c.M).float()
+    n = tiles * 2 * C * 2
+    buf = _nan(n + ops.bn_partial_scratch_elems(C))
+    buf[:n].view(torch.float64).copy_(c.fwd.reshape(-1))
+    mean, invstd = _nan(C), _nan(C)
+    ops.bn_finalize(buf, tiles, c.M, C, mean, invstd, None, None)
+    assert_bitwise(mean, want, name + ": mean")
+    assert not torch.isnan(invstd).any(), name + ": invstd"
 
 
 # ---- 2. producer kernels: every legal C and the row edges ---------------------------------------------------------------------------
