@@ -312,6 +312,51 @@ int mla_concat_head_fwd(const float* x0, const float* x1, const float* x2, const
 int mla_concat_head_bwd(const float* x0, const float* x1, const float* x2, const float* W, const float* dlogits, float* dW,
                         float* db, float* dx0, float* dx1, float* dx2, int M, int B, int D, int C, float scale, void* stream);
 
+/* ---- sum / FiLM / gated fusion heads of the joint step (fusion_modules.py:5-13, 38-67, 70-98; main.py:24, 273-310, 610-614) ------
+ * Two features x, y [B][D]; every Linear in the reference's (out, in) row-major layout; D a multiple of 64 (at most 4096), C <= 128.
+ * Anything else is MLA_ERR_INVALID_ARG before any launch.
+ *   sum    out = (x Wx^T + bx) + (y Wy^T + by)  (fusion_modules.py:12);  out_a = x Wx^T + bias_scale bx, out_v = y Wy^T + bias_scale by
+ *          with bias_scale 1 in training (main.py:292-295) and 0.5 in evaluation (main.py:610-614).  Wx, Wy [C][D].
+ *   FiLM   h = film W^T + b [B][2D], gamma = h[:, :D], beta = h[:, D:], z = gamma * t + beta, out = z Wout^T + bout
+ *          (fusion_modules.py:53-67).  W [2D][D], Wout [C][D].  The caller passes (film, t) = (x, y) under x_film, else (y, x).
+ *   gated  hx = x Wx^T + bx, hy = y Wy^T + by [B][D], z = sigmoid(hx) * hy (x_gate) or hx * sigmoid(hy), out = z Wout^T + bout
+ *          (fusion_modules.py:87-98).  Wx, Wy [D][D], Wout [C][D].  sigmoid(h) = 1 / (1 + exp(-h)) in fp32.
+ * mla_fusion_*_ce_fwd_bwd: the training head of main.py:305-310: `out` (sum: out_a, out_v; FiLM: h, z; gated: hx, hy, z),
+ *   loss = -sum_i log softmax(out_i)[label_i] * inv_batch (sum: losses[3] = {loss, the same for out_a, for out_v}: the reported losses of
+ *   main.py:308-309, never differentiated), dlogits = (softmax - onehot) * inv_batch and the gradient of every parameter and of both
+ *   features.  A label outside [0, C) yields a NaN loss and a zero dlogits row.  sum: 2 launches; FiLM / gated: 3.
+ * mla_fusion_*_fwd: the outputs only (valid(); the autograd forward).  sum: 1 launch; FiLM / gated: 2.
+ * mla_fusion_*_bwd: autograd for a given dlogits [B][C], times `scale`, from the h / hx, hy and z of the forward.
+ * ws: mla_fusion_ws_elems(B, D, C) floats.  No atomics; every reduction in a fixed order (bitwise reproducible). */
+size_t mla_fusion_ws_elems(int B, int D, int C);
+int mla_fusion_sum_ce_fwd_bwd(const float* x, const float* y, const float* Wx, const float* bx, const float* Wy, const float* by,
+                              const int64_t* labels, float* out, float* out_a, float* out_v, float* losses, float* dWx, float* dbx,
+                              float* dWy, float* dby, float* dX, float* dY, float* ws, int B, int D, int C, float inv_batch,
+                              float bias_scale, void* stream);
+int mla_fusion_sum_fwd(const float* x, const float* y, const float* Wx, const float* bx, const float* Wy, const float* by, float* out,
+                       float* out_a, float* out_v, int B, int D, int C, float bias_scale, void* stream);
+int mla_fusion_sum_bwd(const float* x, const float* y, const float* Wx, const float* Wy, const float* dlogits, float* dWx, float* dbx,
+                       float* dWy, float* dby, float* dX, float* dY, float* ws, int B, int D, int C, float scale, void* stream);
+int mla_fusion_film_ce_fwd_bwd(const float* film, const float* t, const float* W, const float* b, const float* Wout, const float* bout,
+                               const int64_t* labels, float* out, float* h, float* z, float* loss, float* dW, float* db, float* dWout,
+                               float* dbout, float* dfilm, float* dt, float* ws, int B, int D, int C, float inv_batch, void* stream);
+int mla_fusion_film_fwd(const float* film, const float* t, const float* W, const float* b, const float* Wout, const float* bout,
+                        float* out, float* h, float* z, int B, int D, int C, void* stream);
+int mla_fusion_film_bwd(const float* film, const float* t, const float* W, const float* Wout, const float* h, const float* z,
+                        const float* dlogits, float* dW, float* db, float* dWout, float* dbout, float* dfilm, float* dt, float* ws,
+                        int B, int D, int C, float scale, void* stream);
+int mla_fusion_gated_ce_fwd_bwd(const float* x, const float* y, const float* Wx, const float* bx, const float* Wy, const float* by,
+                                const float* Wout, const float* bout, const int64_t* labels, float* out, float* hx, float* hy, float* z,
+                                float* loss, float* dWx, float* dbx, float* dWy, float* dby, float* dWout, float* dbout, float* dX,
+                                float* dY, float* ws, int B, int D, int C, int x_gate, float inv_batch, void* stream);
+int mla_fusion_gated_fwd(const float* x, const float* y, const float* Wx, const float* bx, const float* Wy, const float* by,
+                         const float* Wout, const float* bout, float* out, float* hx, float* hy, float* z, int B, int D, int C,
+                         int x_gate, void* stream);
+int mla_fusion_gated_bwd(const float* x, const float* y, const float* Wx, const float* Wy, const float* Wout, const float* hx,
+                         const float* hy, const float* z, const float* dlogits, float* dWx, float* dbx, float* dWy, float* dby,
+                         float* dWout, float* dbout, float* dX, float* dY, float* ws, int B, int D, int C, int x_gate, float scale,
+                         void* stream);
+
 /* ---- QMF joint step head (--modulation QMF; main.py:170-268, 544-586; utils/utils.py:44-95; main.py:108-125) --------------
  * One Linear head per modality (audio_fc / visual_fc / txtual_fc): x_m [B][D], W_m [C][D], b_m [C] (x2 / W2 / b2 / dW2 / db2 /
  * dx2 NULL when M = 2), M = 2 or 3, C <= 128.

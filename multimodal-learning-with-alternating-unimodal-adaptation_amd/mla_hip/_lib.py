@@ -93,6 +93,16 @@ PROTOTYPES = {
     "mla_concat_head_ce_fwd_bwd": (_I, [_P] * 16 + [_I, _I, _I, _I, _F, _P]),
     "mla_concat_head_fwd": (_I, [_P] * 7 + [_I, _I, _I, _I, _P]),
     "mla_concat_head_bwd": (_I, [_P] * 10 + [_I, _I, _I, _I, _F, _P]),
+    "mla_fusion_ws_elems": (_Z, [_I, _I, _I]),
+    "mla_fusion_sum_ce_fwd_bwd": (_I, [_P] * 18 + [_I, _I, _I, _F, _F, _P]),
+    "mla_fusion_sum_fwd": (_I, [_P] * 9 + [_I, _I, _I, _F, _P]),
+    "mla_fusion_sum_bwd": (_I, [_P] * 12 + [_I, _I, _I, _F, _P]),
+    "mla_fusion_film_ce_fwd_bwd": (_I, [_P] * 18 + [_I, _I, _I, _F, _P]),
+    "mla_fusion_film_fwd": (_I, [_P] * 9 + [_I, _I, _I, _P]),
+    "mla_fusion_film_bwd": (_I, [_P] * 14 + [_I, _I, _I, _F, _P]),
+    "mla_fusion_gated_ce_fwd_bwd": (_I, [_P] * 23 + [_I, _I, _I, _I, _F, _P]),
+    "mla_fusion_gated_fwd": (_I, [_P] * 12 + [_I, _I, _I, _I, _P]),
+    "mla_fusion_gated_bwd": (_I, [_P] * 18 + [_I, _I, _I, _I, _F, _P]),
     "mla_qmf_head_ws_elems": (_Z, [_I, _I, _I]),
     "mla_qmf_head_fwd_bwd": (_I, [_P] * 13 + [_I] + [_P] * 17 + [_I, _I, _I, _I, _F, _F, _F, _P]),
     "mla_qmf_head_fwd": (_I, [_P] * 12 + [_I, _I, _I, _I, _P]),

@@ -9,6 +9,8 @@ head and on ONE encoder.  Each Function below is a thin shell over the same laun
                    (after a forward on the present rows only, Modal3Classifier(present=): d feature compacted to those rows first)
   HeadLinear       forward  = mla_head_logits; backward = mla_head_bwd (dW, db, dX in one launch pair)
   ConcatHeadLinear forward  = mla_concat_head_fwd; backward = mla_concat_head_bwd (dW, db, every dX_m; joint step)
+  SumFusionHead / FiLMHead / GatedFusionHead   forward = mla_fusion_*_fwd; backward = mla_fusion_*_bwd (every parameter gradient
+                   of the fusion module and both feature gradients; joint step with an attached fusion, mla_hip.fusion)
   SoftmaxCE        forward  = mla_ce_fwd_bwd (loss + d logits in one launch); backward = scale by the incoming grad
 
 Graph recording is triggered by a private 1-element `anchor` tensor (requires_grad, not a Parameter): the encoder's
@@ -112,6 +114,96 @@ class ConcatHeadLinear(torch.autograd.Function):
             comm.allreduce_small(head.grad)                          # critical path: packed dW|db, one message
         head.publish_grads(pending)
         return (None, None) + tuple(dxs)
+
+
+def _fusion_io(fusion, x, y):
+    if fusion.comm is not None and fusion.comm.active:
+        raise NotImplementedError("data-parallel training with an attached sum / film / gated fusion is not implemented")
+    xd, yd = x.detach().contiguous(), y.detach().contiguous()
+    f32 = dict(device=xd.device, dtype=torch.float32)
+    B, D = xd.shape
+    return xd, yd, B, D, fusion.out_features, f32
+
+
+def _fusion_publish(fusion, run):
+    """The backward of an attached fusion module: `run()` overwrites its whole flat gradient; autograd's accumulate rule on top."""
+    pending = fusion.grads_pending()
+    run()
+    fusion.publish_grads(pending)
+
+
+class SumFusionHead(torch.autograd.Function):
+    """fc_x(x) + fc_y(y) (fusion_modules.py:11-13): one `loss.backward()` fills fc_x / fc_y and hands each encoder its feature gradient."""
+
+    @staticmethod
+    def forward(ctx, anchor, fusion, x, y):
+        xd, yd, B, _D, C, f32 = _fusion_io(fusion, x, y)
+        out, out_a, out_v = (torch.empty((B, C), **f32) for _ in range(3))
+        w = fusion.p
+        ops.fusion_sum_fwd(xd, yd, w["fc_x.weight"], w["fc_x.bias"], w["fc_y.weight"], w["fc_y.bias"], out, out_a, out_v)
+        ctx.fusion, ctx.xy = fusion, (xd, yd)
+        return out
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        fusion, (x, y) = ctx.fusion, ctx.xy
+        w, g = fusion.p, fusion.g
+        dX, dY = torch.empty_like(x), torch.empty_like(y)
+        ws = torch.empty(ops.fusion_ws_elems(x.shape[0], x.shape[1], fusion.out_features), device=x.device, dtype=torch.float32)
+        _fusion_publish(fusion, lambda: ops.fusion_sum_bwd(x, y, w["fc_x.weight"], w["fc_y.weight"], dlogits.contiguous(), g["fc_x.weight"],
+                                                           g["fc_x.bias"], g["fc_y.weight"], g["fc_y.bias"], dX, dY, ws))
+        return None, None, dX, dY
+
+
+class FiLMHead(torch.autograd.Function):
+    """fc_out(gamma * t + beta), gamma | beta = fc(film) (fusion_modules.py:53-67); (film, t) = (x, y) under x_film, else (y, x)."""
+
+    @staticmethod
+    def forward(ctx, anchor, fusion, x, y):
+        xd, yd, B, D, C, f32 = _fusion_io(fusion, x, y)
+        film, t = (xd, yd) if fusion.x_film else (yd, xd)
+        out, h, z = torch.empty((B, C), **f32), torch.empty((B, 2 * D), **f32), torch.empty((B, D), **f32)
+        w = fusion.p
+        ops.fusion_film_fwd(film, t, w["fc.weight"], w["fc.bias"], w["fc_out.weight"], w["fc_out.bias"], out, h, z)
+        ctx.fusion, ctx.saved = fusion, (film, t, h, z)
+        return out
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        fusion, (film, t, h, z) = ctx.fusion, ctx.saved
+        w, g = fusion.p, fusion.g
+        dfilm, dt = torch.empty_like(film), torch.empty_like(t)
+        ws = torch.empty(ops.fusion_ws_elems(t.shape[0], t.shape[1], fusion.out_features), device=t.device, dtype=torch.float32)
+        _fusion_publish(fusion, lambda: ops.fusion_film_bwd(film, t, w["fc.weight"], w["fc_out.weight"], h, z, dlogits.contiguous(),
+                                                            g["fc.weight"], g["fc.bias"], g["fc_out.weight"], g["fc_out.bias"], dfilm, dt, ws))
+        return (None, None) + ((dfilm, dt) if fusion.x_film else (dt, dfilm))
+
+
+class GatedFusionHead(torch.autograd.Function):
+    """(fc_x(x), fc_y(y), fc_out(gate * other)) (fusion_modules.py:87-98).  Only `out` carries history: the reference's loop never
+    differentiates out_x / out_y, and they are returned detached."""
+
+    @staticmethod
+    def forward(ctx, anchor, fusion, x, y):
+        xd, yd, B, D, C, f32 = _fusion_io(fusion, x, y)
+        out, hx, hy, z = torch.empty((B, C), **f32), torch.empty((B, D), **f32), torch.empty((B, D), **f32), torch.empty((B, D), **f32)
+        w = fusion.p
+        ops.fusion_gated_fwd(xd, yd, w["fc_x.weight"], w["fc_x.bias"], w["fc_y.weight"], w["fc_y.bias"], w["fc_out.weight"],
+                             w["fc_out.bias"], out, hx, hy, z, fusion.x_gate)
+        ctx.fusion, ctx.saved = fusion, (xd, yd, hx, hy, z)
+        ctx.mark_non_differentiable(hx, hy)
+        return hx, hy, out
+
+    @staticmethod
+    def backward(ctx, _dhx, _dhy, dlogits):
+        fusion, (x, y, hx, hy, z) = ctx.fusion, ctx.saved
+        w, g = fusion.p, fusion.g
+        dX, dY = torch.empty_like(x), torch.empty_like(y)
+        ws = torch.empty(ops.fusion_ws_elems(x.shape[0], x.shape[1], fusion.out_features), device=x.device, dtype=torch.float32)
+        _fusion_publish(fusion, lambda: ops.fusion_gated_bwd(
+            x, y, w["fc_x.weight"], w["fc_y.weight"], w["fc_out.weight"], hx, hy, z, dlogits.contiguous(), g["fc_x.weight"], g["fc_x.bias"],
+            g["fc_y.weight"], g["fc_y.bias"], g["fc_out.weight"], g["fc_out.bias"], dX, dY, ws, fusion.x_gate))
+        return None, None, dX, dY
 
 
 class SoftmaxCE(torch.autograd.Function):

@@ -32,6 +32,7 @@ import torch
 from . import ops
 from ._lib import MLAHipError
 from .dist import Comm
+from .module import is_attached_fusion
 from .modulation import OGM
 from .trainer import StreamTrainer
 
@@ -45,6 +46,19 @@ def _joint_fusion(model):
     return fusion
 
 
+def _attached(fusion, comm: Optional[Comm], modulation: str = "Normal"):
+    """The attached sum / film / gated fusion module (mla_hip.fusion) of a joint model, or None for concat fusion."""
+    if not is_attached_fusion(fusion):
+        return None
+    if comm is not None and comm.world > 1:
+        raise NotImplementedError("data-parallel training / evaluation (comm.world > 1) with an attached sum / film / gated fusion is "
+                                  "not implemented")
+    if modulation != "Normal" and not fusion.per_modality:
+        raise NotImplementedError(f"--modulation {modulation} with --fusion_method {fusion.method}: the reference defines no per-modality "
+                                  "logits out_a / out_v for film / gated fusion (main.py:291-302), so OGM / OGM-GE have no coefficients")
+    return fusion
+
+
 class JointTrainer(StreamTrainer):
     def __init__(self, model, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 1e-4, modulation: str = "Normal",
                  alpha: float = 0.3, modulation_starts: int = 0, modulation_ends: int = 50, seed: int = 0,
@@ -53,8 +67,10 @@ class JointTrainer(StreamTrainer):
         `modulation_starts`, `modulation_ends`: args.* of main.py:312-410; `seed` keys OGM-GE's noise."""
         if modulation not in MODULATIONS:
             raise NotImplementedError(f"JointTrainer implements --modulation {' | '.join(MODULATIONS)}, not {modulation!r}")
-        _joint_fusion(model)
+        self.fusion = _attached(_joint_fusion(model), comm, modulation)
         super().__init__(model, lr, momentum, weight_decay, False, comm)
+        if self.fusion is not None and not self.fusion.per_modality:          # film / gated: no out_a / out_v, no loss_a / loss_v
+            self.losses = {"loss": self.losses["loss"]}
         self.M = len(self.encoders)
         self.modulation = modulation
         self.modulation_starts, self.modulation_ends = modulation_starts, modulation_ends
@@ -86,7 +102,10 @@ class JointTrainer(StreamTrainer):
         for (tag, _g, _e), f in zip(self.encoders, feats):
             self.last[tag] = f
         # 2. the concatenated head (main.py:273-310)
-        out, out_m, L, dX = self.head.concat_forward_backward(list(feats), label, inv_batch)
+        if self.fusion is not None:                           # attached sum / film / gated (out_m None and one loss for film / gated)
+            out, out_m, L, dX = self.fusion.forward_backward(list(feats), label, inv_batch, self.last)
+        else:
+            out, out_m, L, dX = self.head.concat_forward_backward(list(feats), label, inv_batch)
         if self.comm.active:                                  # (dW|db) and the rank-local losses: one message
             n = self.head.numel
             self._msg[:n].copy_(self.head.grad)
@@ -96,7 +115,7 @@ class JointTrainer(StreamTrainer):
             L.copy_(self._msg[n:])
         self.last["out"], self.last["out_m"] = out, out_m
         self.losses["loss"].copy_(L[:1])
-        for k, (tag, _g, _e) in enumerate(self.encoders):
+        for k, (tag, _g, _e) in enumerate(self.encoders if out_m is not None else ()):
             self.losses["loss_" + tag].copy_(L[1 + k:2 + k])
         # 3. OGM coefficients (main.py:314-337 / 373-384), from the global batch
         modulate = self._modulating(epoch)
@@ -143,10 +162,10 @@ class JointEvaluator:
     weights (1, 0, 0): its fused prediction is then exactly arg-max(out); with three modalities a second call counts out_t."""
 
     def __init__(self, model, comm: Optional[Comm] = None):
-        _joint_fusion(model)
+        self.fusion = _attached(_joint_fusion(model), comm)
         self.model = model
         self.comm = comm if comm is not None else Comm()
-        self.head = model.fusion_module.fc_out
+        self.head = self.fusion if self.fusion is not None else model.fusion_module.fc_out
         self.M = len(model.mla_encoders())
         self.C = self.head.out_features
         dev = model.device
@@ -164,8 +183,11 @@ class JointEvaluator:
         Returns (out, out_m) of the local batch."""
         *inputs, label = batch
         feats = self.model.forward_raw(*inputs)
-        out, out_m = self.head.concat_logits(list(feats), slot="eval")
-        outs = [out] + [out_m[k] for k in range(self.M)]
+        if self.fusion is not None:                           # sum: out_m with HALF the bias (main.py:610-614); film / gated: none
+            out, out_m = self.fusion.logits(list(feats), bias_scale=0.5, slot="eval")
+        else:
+            out, out_m = self.head.concat_logits(list(feats), slot="eval")
+        outs = [out] + [out_m[k] if out_m is not None else out for k in range(self.M)]
         if self.comm.active:
             outs = [self.comm.allgather_rows(o) for o in outs]
             label = self.comm.allgather_rows(label.contiguous())
@@ -178,6 +200,8 @@ class JointEvaluator:
         """(acc, acc_a, acc_v[, acc_t]) = sum(acc) / sum(num) (main.py:677-679; one host sync)."""
         c = self.counts.view(5, self.C).sum(dim=1).cpu().tolist()
         num = max(c[0], 1)
+        if self.fusion is not None and not self.fusion.per_modality:
+            return (c[1] / num,)                              # film / gated: the reference defines no out_a / out_v
         res = [c[1] / num, c[3] / num, c[4] / num]
         if self.M == 3:
             res.append(self.counts_t.view(4, self.C).sum(dim=1)[1].item() / num)

@@ -51,6 +51,12 @@ def _alias(view: torch.Tensor) -> torch.Tensor:
     return t
 
 
+def is_attached_fusion(fusion) -> bool:
+    """True for a sum / film / gated fusion module put in place by mla_hip.fusion.attach_fusion (it owns its Linears in one flat
+    buffer and has no shared `fc_out` head), False for ConcatFusion / ConcatFusion3."""
+    return bool(getattr(fusion, "attached_fusion", False))
+
+
 def _bare_init(self) -> None:
     nn.Module.__init__(self)
 

@@ -608,6 +608,114 @@ def concat_head_bwd(xs, W, dlogits, dW, db, dxs, scale: float = 1.0, stream: Opt
     _call("mla_concat_head_bwd", x[0], x[1], x[2], _p(W), _p(dlogits), _p(dW), _p(db), dx[0], dx[1], dx[2], M, B, D, C, scale, stream or cur_stream())
 
 
+# ---- sum / FiLM / gated fusion heads (csrc/fusion_head.hip) ---------------------------------------------------------------------------
+def fusion_ws_elems(B: int, D: int, C: int) -> int:
+    return int(_lib.load().mla_fusion_ws_elems(B, D, C))
+
+
+def _fusion_dims(who: str, x, y, Wout, hidden=(), ws=None, labels=None):
+    """(B, D, C) of a fusion head call; `hidden`: (tensor, shape) pairs that must match (biases, bias gradients and loss vectors
+    included: the kernels write them unchecked); `ws` at least fusion_ws_elems(B, D, C) floats; `labels` (B,)."""
+    B, D = x.shape
+    C = Wout.shape[0]
+    if tuple(y.shape) != (B, D) or tuple(Wout.shape) != (C, D):
+        raise MLAHipError(f"{who}: features {tuple(x.shape)} / {tuple(y.shape)} and the output weight {tuple(Wout.shape)} do not match")
+    for t, shp in hidden:
+        if tuple(t.shape) != tuple(shp(B, D, C)):
+            raise MLAHipError(f"{who}: a tensor of shape {tuple(t.shape)} where {tuple(shp(B, D, C))} is expected")
+    if labels is not None and tuple(labels.shape) != (B,):
+        raise MLAHipError(f"{who}: labels of shape {tuple(labels.shape)} where ({B},) is expected")
+    if ws is not None and ws.numel() < fusion_ws_elems(B, D, C):
+        raise MLAHipError(f"{who}: workspace of {ws.numel()} floats, fusion_ws_elems({B}, {D}, {C}) = {fusion_ws_elems(B, D, C)} needed")
+    return B, D, C
+
+
+_BC, _BD, _B2D, _DD, _2DD, _CD = ((lambda B, D, C: (B, C)), (lambda B, D, C: (B, D)), (lambda B, D, C: (B, 2 * D)),
+                                  (lambda B, D, C: (D, D)), (lambda B, D, C: (2 * D, D)), (lambda B, D, C: (C, D)))
+_vC, _vD, _v2D, _v1, _v3 = ((lambda B, D, C: (C,)), (lambda B, D, C: (D,)), (lambda B, D, C: (2 * D,)), (lambda B, D, C: (1,)),
+                            (lambda B, D, C: (3,)))
+
+
+def fusion_sum_ce_fwd_bwd(x, y, Wx, bx, Wy, by, labels, out, out_a, out_v, losses, dWx, dbx, dWy, dby, dX, dY, ws, inv_batch: float,
+                          bias_scale: float = 1.0, stream: Optional[int] = None) -> None:
+    """SumFusion training head (fusion_modules.py:11-13; main.py:292-295, 305-310): out, out_a / out_v (bias times `bias_scale`),
+    losses [loss, loss_a, loss_v] and every gradient."""
+    B, D, C = _fusion_dims("fusion_sum_ce_fwd_bwd", x, y, Wx, [(Wy, _CD), (out, _BC), (out_a, _BC), (out_v, _BC), (dWx, _CD), (dWy, _CD),
+                                                               (dX, _BD), (dY, _BD), (bx, _vC), (by, _vC), (dbx, _vC), (dby, _vC),
+                                                               (losses, _v3)], ws, labels)
+    _call("mla_fusion_sum_ce_fwd_bwd", _p(x), _p(y), _p(Wx), _p(bx), _p(Wy), _p(by), _p(labels, torch.int64), _p(out), _p(out_a), _p(out_v),
+          _p(losses), _p(dWx), _p(dbx), _p(dWy), _p(dby), _p(dX), _p(dY), _p(ws), B, D, C, inv_batch, bias_scale, stream or cur_stream())
+
+
+def fusion_sum_fwd(x, y, Wx, bx, Wy, by, out, out_a, out_v, bias_scale: float = 1.0, stream: Optional[int] = None) -> None:
+    """out = fc_x(x) + fc_y(y) and out_a / out_v with the bias times `bias_scale` (0.5 in valid(), main.py:610-614); no gradients."""
+    B, D, C = _fusion_dims("fusion_sum_fwd", x, y, Wx, [(Wy, _CD), (out, _BC), (out_a, _BC), (out_v, _BC), (bx, _vC), (by, _vC)])
+    _call("mla_fusion_sum_fwd", _p(x), _p(y), _p(Wx), _p(bx), _p(Wy), _p(by), _p(out), _p(out_a), _p(out_v), B, D, C, bias_scale,
+          stream or cur_stream())
+
+
+def fusion_sum_bwd(x, y, Wx, Wy, dlogits, dWx, dbx, dWy, dby, dX, dY, ws, scale: float = 1.0, stream: Optional[int] = None) -> None:
+    """autograd of SumFusion for a given d out (all times `scale`)."""
+    B, D, C = _fusion_dims("fusion_sum_bwd", x, y, Wx, [(Wy, _CD), (dlogits, _BC), (dWx, _CD), (dWy, _CD), (dX, _BD), (dY, _BD), (dbx, _vC),
+                                                        (dby, _vC)], ws)
+    _call("mla_fusion_sum_bwd", _p(x), _p(y), _p(Wx), _p(Wy), _p(dlogits), _p(dWx), _p(dbx), _p(dWy), _p(dby), _p(dX), _p(dY), _p(ws),
+          B, D, C, scale, stream or cur_stream())
+
+
+def fusion_film_ce_fwd_bwd(film, t, W, b, Wout, bout, labels, out, h, z, loss, dW, db, dWout, dbout, dfilm, dt, ws, inv_batch: float,
+                           stream: Optional[int] = None) -> None:
+    """FiLM training head (fusion_modules.py:53-67; main.py:305-310): out, h = fc(film) (gamma | beta), z, the loss and every gradient."""
+    B, D, C = _fusion_dims("fusion_film_ce_fwd_bwd", film, t, Wout, [(W, _2DD), (out, _BC), (h, _B2D), (z, _BD), (dW, _2DD), (dWout, _CD),
+                                                                     (dfilm, _BD), (dt, _BD), (b, _v2D), (bout, _vC), (db, _v2D),
+                                                                     (dbout, _vC), (loss, _v1)], ws, labels)
+    _call("mla_fusion_film_ce_fwd_bwd", _p(film), _p(t), _p(W), _p(b), _p(Wout), _p(bout), _p(labels, torch.int64), _p(out), _p(h), _p(z),
+          _p(loss), _p(dW), _p(db), _p(dWout), _p(dbout), _p(dfilm), _p(dt), _p(ws), B, D, C, inv_batch, stream or cur_stream())
+
+
+def fusion_film_fwd(film, t, W, b, Wout, bout, out, h, z, stream: Optional[int] = None) -> None:
+    B, D, C = _fusion_dims("fusion_film_fwd", film, t, Wout, [(W, _2DD), (out, _BC), (h, _B2D), (z, _BD), (b, _v2D), (bout, _vC)])
+    _call("mla_fusion_film_fwd", _p(film), _p(t), _p(W), _p(b), _p(Wout), _p(bout), _p(out), _p(h), _p(z), B, D, C, stream or cur_stream())
+
+
+def fusion_film_bwd(film, t, W, Wout, h, z, dlogits, dW, db, dWout, dbout, dfilm, dt, ws, scale: float = 1.0,
+                    stream: Optional[int] = None) -> None:
+    """autograd of FiLM for a given d out (all times `scale`), from the forward's h and z."""
+    B, D, C = _fusion_dims("fusion_film_bwd", film, t, Wout, [(W, _2DD), (h, _B2D), (z, _BD), (dlogits, _BC), (dW, _2DD), (dWout, _CD),
+                                                              (dfilm, _BD), (dt, _BD), (db, _v2D), (dbout, _vC)], ws)
+    _call("mla_fusion_film_bwd", _p(film), _p(t), _p(W), _p(Wout), _p(h), _p(z), _p(dlogits), _p(dW), _p(db), _p(dWout), _p(dbout),
+          _p(dfilm), _p(dt), _p(ws), B, D, C, scale, stream or cur_stream())
+
+
+def fusion_gated_ce_fwd_bwd(x, y, Wx, bx, Wy, by, Wout, bout, labels, out, hx, hy, z, loss, dWx, dbx, dWy, dby, dWout, dbout, dX, dY, ws,
+                            x_gate: bool, inv_batch: float, stream: Optional[int] = None) -> None:
+    """GatedFusion training head (fusion_modules.py:87-98; main.py:305-310): out, hx = fc_x(x), hy = fc_y(y), z, the loss and every
+    gradient."""
+    B, D, C = _fusion_dims("fusion_gated_ce_fwd_bwd", x, y, Wout, [(Wx, _DD), (Wy, _DD), (out, _BC), (hx, _BD), (hy, _BD), (z, _BD),
+                                                                   (dWx, _DD), (dWy, _DD), (dWout, _CD), (dX, _BD), (dY, _BD),
+                                                                   (bx, _vD), (by, _vD), (bout, _vC), (dbx, _vD), (dby, _vD), (dbout, _vC),
+                                                                   (loss, _v1)], ws, labels)
+    _call("mla_fusion_gated_ce_fwd_bwd", _p(x), _p(y), _p(Wx), _p(bx), _p(Wy), _p(by), _p(Wout), _p(bout), _p(labels, torch.int64), _p(out),
+          _p(hx), _p(hy), _p(z), _p(loss), _p(dWx), _p(dbx), _p(dWy), _p(dby), _p(dWout), _p(dbout), _p(dX), _p(dY), _p(ws), B, D, C,
+          int(bool(x_gate)), inv_batch, stream or cur_stream())
+
+
+def fusion_gated_fwd(x, y, Wx, bx, Wy, by, Wout, bout, out, hx, hy, z, x_gate: bool, stream: Optional[int] = None) -> None:
+    B, D, C = _fusion_dims("fusion_gated_fwd", x, y, Wout, [(Wx, _DD), (Wy, _DD), (out, _BC), (hx, _BD), (hy, _BD), (z, _BD), (bx, _vD), (by, _vD),
+                                                            (bout, _vC)])
+    _call("mla_fusion_gated_fwd", _p(x), _p(y), _p(Wx), _p(bx), _p(Wy), _p(by), _p(Wout), _p(bout), _p(out), _p(hx), _p(hy), _p(z), B, D, C,
+          int(bool(x_gate)), stream or cur_stream())
+
+
+def fusion_gated_bwd(x, y, Wx, Wy, Wout, hx, hy, z, dlogits, dWx, dbx, dWy, dby, dWout, dbout, dX, dY, ws, x_gate: bool,
+                     scale: float = 1.0, stream: Optional[int] = None) -> None:
+    """autograd of GatedFusion for a given d out (all times `scale`), from the forward's hx, hy and z."""
+    B, D, C = _fusion_dims("fusion_gated_bwd", x, y, Wout, [(Wx, _DD), (Wy, _DD), (hx, _BD), (hy, _BD), (z, _BD), (dlogits, _BC),
+                                                            (dWx, _DD), (dWy, _DD), (dWout, _CD), (dX, _BD), (dY, _BD), (dbx, _vD),
+                                                            (dby, _vD), (dbout, _vC)], ws)
+    _call("mla_fusion_gated_bwd", _p(x), _p(y), _p(Wx), _p(Wy), _p(Wout), _p(hx), _p(hy), _p(z), _p(dlogits), _p(dWx), _p(dbx), _p(dWy),
+          _p(dby), _p(dWout), _p(dbout), _p(dX), _p(dY), _p(ws), B, D, C, int(bool(x_gate)), scale, stream or cur_stream())
+
+
 def qmf_head_ws_elems(B: int, C: int, M: int) -> int:
     return int(_lib.load().mla_qmf_head_ws_elems(B, C, M))
 

@@ -25,6 +25,7 @@ from . import ops
 from ._lib import MLAHipError
 from .dist import Comm
 from .model import SharedHead
+from .module import is_attached_fusion
 from .trainer import StreamTrainer
 
 HEAD_NAMES = ("audio_fc", "visual_fc", "txtual_fc")          # basic_model.py:45-47, 175-177, 244-247
@@ -38,6 +39,8 @@ def attach_qmf_heads(model, seed: Optional[int] = None) -> List[SharedHead]:
         return model.qmf_heads
     if getattr(model, "gs_flag", False):
         raise MLAHipError("QMF needs a classifier built with gs_flag false")
+    if is_attached_fusion(model.fusion_module):
+        raise MLAHipError("QMF heads cannot be attached to a model with an attached sum / film / gated fusion (mla_hip.fusion)")
     C = model.fusion_module.fc_out.out_features
     heads = []
     for k in range(len(model.mla_encoders())):

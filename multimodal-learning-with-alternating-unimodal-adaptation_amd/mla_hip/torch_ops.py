@@ -235,6 +235,108 @@ def concat_head_bwd(xs, W, dlogits, scale=1.0):
     return dW, db, dxs
 
 
+# ---- sum / FiLM / gated fusion heads (fusion_modules.py:5-13, 38-67, 70-98) -------------------------------------------------------
+def _fusion_ws(x, C):
+    return _f32(ops.fusion_ws_elems(x.shape[0], x.shape[1], C), x)
+
+
+@_op("fusion_sum_ce_fwd_bwd(Tensor x, Tensor y, Tensor Wx, Tensor bx, Tensor Wy, Tensor by, Tensor labels, float inv_batch, "
+     "float bias_scale=1.0) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+def fusion_sum_ce_fwd_bwd(x, y, Wx, bx, Wy, by, labels, inv_batch, bias_scale=1.0):
+    """(out, out_a, out_v, losses[3] = [loss, loss_a, loss_v], dWx, dbx, dWy, dby, dX, dY)"""
+    (B, D), C = x.shape, Wx.shape[0]
+    out, out_a, out_v, losses = _f32((B, C), x), _f32((B, C), x), _f32((B, C), x), _f32(3, x)
+    dWx, dbx, dWy, dby, dX, dY = _f32((C, D), x), _f32(C, x), _f32((C, D), x), _f32(C, x), _f32((B, D), x), _f32((B, D), x)
+    ops.fusion_sum_ce_fwd_bwd(x, y, Wx, bx, Wy, by, labels, out, out_a, out_v, losses, dWx, dbx, dWy, dby, dX, dY, _fusion_ws(x, C),
+                              inv_batch, bias_scale)
+    return out, out_a, out_v, losses, dWx, dbx, dWy, dby, dX, dY
+
+
+@_op("fusion_sum_fwd(Tensor x, Tensor y, Tensor Wx, Tensor bx, Tensor Wy, Tensor by, float bias_scale=1.0) -> (Tensor, Tensor, Tensor)")
+def fusion_sum_fwd(x, y, Wx, bx, Wy, by, bias_scale=1.0):
+    """(out, out_a, out_v)"""
+    (B, _D), C = x.shape, Wx.shape[0]
+    out, out_a, out_v = _f32((B, C), x), _f32((B, C), x), _f32((B, C), x)
+    ops.fusion_sum_fwd(x, y, Wx, bx, Wy, by, out, out_a, out_v, bias_scale)
+    return out, out_a, out_v
+
+
+@_op("fusion_sum_bwd(Tensor x, Tensor y, Tensor Wx, Tensor Wy, Tensor dlogits, float scale=1.0) -> "
+     "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+def fusion_sum_bwd(x, y, Wx, Wy, dlogits, scale=1.0):
+    """(dWx, dbx, dWy, dby, dX, dY)"""
+    (B, D), C = x.shape, Wx.shape[0]
+    dWx, dbx, dWy, dby, dX, dY = _f32((C, D), x), _f32(C, x), _f32((C, D), x), _f32(C, x), _f32((B, D), x), _f32((B, D), x)
+    ops.fusion_sum_bwd(x, y, Wx, Wy, dlogits, dWx, dbx, dWy, dby, dX, dY, _fusion_ws(x, C), scale)
+    return dWx, dbx, dWy, dby, dX, dY
+
+
+@_op("fusion_film_ce_fwd_bwd(Tensor film, Tensor t, Tensor W, Tensor b, Tensor Wout, Tensor bout, Tensor labels, float inv_batch) -> "
+     "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+def fusion_film_ce_fwd_bwd(film, t, W, b, Wout, bout, labels, inv_batch):
+    """(out, h (B, 2D), z, loss[1], dW, db, dWout, dbout, dfilm, dt)"""
+    (B, D), C = film.shape, Wout.shape[0]
+    out, h, z, loss = _f32((B, C), t), _f32((B, 2 * D), t), _f32((B, D), t), _f32(1, t)
+    dW, db, dWout, dbout, dfilm, dt = _f32((2 * D, D), t), _f32(2 * D, t), _f32((C, D), t), _f32(C, t), _f32((B, D), t), _f32((B, D), t)
+    ops.fusion_film_ce_fwd_bwd(film, t, W, b, Wout, bout, labels, out, h, z, loss, dW, db, dWout, dbout, dfilm, dt, _fusion_ws(t, C),
+                               inv_batch)
+    return out, h, z, loss, dW, db, dWout, dbout, dfilm, dt
+
+
+@_op("fusion_film_fwd(Tensor film, Tensor t, Tensor W, Tensor b, Tensor Wout, Tensor bout) -> (Tensor, Tensor, Tensor)")
+def fusion_film_fwd(film, t, W, b, Wout, bout):
+    """(out, h (B, 2D), z)"""
+    (B, D), C = film.shape, Wout.shape[0]
+    out, h, z = _f32((B, C), t), _f32((B, 2 * D), t), _f32((B, D), t)
+    ops.fusion_film_fwd(film, t, W, b, Wout, bout, out, h, z)
+    return out, h, z
+
+
+@_op("fusion_film_bwd(Tensor film, Tensor t, Tensor W, Tensor Wout, Tensor h, Tensor z, Tensor dlogits, float scale=1.0) -> "
+     "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+def fusion_film_bwd(film, t, W, Wout, h, z, dlogits, scale=1.0):
+    """(dW, db, dWout, dbout, dfilm, dt)"""
+    (B, D), C = film.shape, Wout.shape[0]
+    dW, db, dWout, dbout, dfilm, dt = _f32((2 * D, D), t), _f32(2 * D, t), _f32((C, D), t), _f32(C, t), _f32((B, D), t), _f32((B, D), t)
+    ops.fusion_film_bwd(film, t, W, Wout, h, z, dlogits, dW, db, dWout, dbout, dfilm, dt, _fusion_ws(t, C), scale)
+    return dW, db, dWout, dbout, dfilm, dt
+
+
+def _gated_grads(x, C):
+    B, D = x.shape
+    return (_f32((D, D), x), _f32(D, x), _f32((D, D), x), _f32(D, x), _f32((C, D), x), _f32(C, x), _f32((B, D), x), _f32((B, D), x))
+
+
+@_op("fusion_gated_ce_fwd_bwd(Tensor x, Tensor y, Tensor Wx, Tensor bx, Tensor Wy, Tensor by, Tensor Wout, Tensor bout, Tensor labels, "
+     "bool x_gate, float inv_batch) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+def fusion_gated_ce_fwd_bwd(x, y, Wx, bx, Wy, by, Wout, bout, labels, x_gate, inv_batch):
+    """(out, hx, hy, z, loss[1], dWx, dbx, dWy, dby, dWout, dbout, dX, dY)"""
+    (B, D), C = x.shape, Wout.shape[0]
+    out, hx, hy, z, loss = _f32((B, C), x), _f32((B, D), x), _f32((B, D), x), _f32((B, D), x), _f32(1, x)
+    g = _gated_grads(x, C)
+    ops.fusion_gated_ce_fwd_bwd(x, y, Wx, bx, Wy, by, Wout, bout, labels, out, hx, hy, z, loss, *g, _fusion_ws(x, C), x_gate, inv_batch)
+    return (out, hx, hy, z, loss) + g
+
+
+@_op("fusion_gated_fwd(Tensor x, Tensor y, Tensor Wx, Tensor bx, Tensor Wy, Tensor by, Tensor Wout, Tensor bout, bool x_gate=True) -> "
+     "(Tensor, Tensor, Tensor, Tensor)")
+def fusion_gated_fwd(x, y, Wx, bx, Wy, by, Wout, bout, x_gate=True):
+    """(out, hx, hy, z)"""
+    (B, D), C = x.shape, Wout.shape[0]
+    out, hx, hy, z = _f32((B, C), x), _f32((B, D), x), _f32((B, D), x), _f32((B, D), x)
+    ops.fusion_gated_fwd(x, y, Wx, bx, Wy, by, Wout, bout, out, hx, hy, z, x_gate)
+    return out, hx, hy, z
+
+
+@_op("fusion_gated_bwd(Tensor x, Tensor y, Tensor Wx, Tensor Wy, Tensor Wout, Tensor hx, Tensor hy, Tensor z, Tensor dlogits, "
+     "bool x_gate=True, float scale=1.0) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+def fusion_gated_bwd(x, y, Wx, Wy, Wout, hx, hy, z, dlogits, x_gate=True, scale=1.0):
+    """(dWx, dbx, dWy, dby, dWout, dbout, dX, dY)"""
+    g = _gated_grads(x, Wout.shape[0])
+    ops.fusion_gated_bwd(x, y, Wx, Wy, Wout, hx, hy, z, dlogits, *g, _fusion_ws(x, Wout.shape[0]), x_gate, scale)
+    return g
+
+
 @_op("qmf_head_fwd_bwd(Tensor[] xs, Tensor[] Ws, Tensor[] bs, Tensor labels, Tensor idx, Tensor(a!) correctness, "
      "Tensor(b!) confidence, float w_cml, float w_crl, float inv_batch) -> "
      "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor[], Tensor[], Tensor[])")

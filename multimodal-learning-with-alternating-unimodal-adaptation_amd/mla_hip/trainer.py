@@ -24,6 +24,7 @@ from .streams import distinct_streams
 
 from . import ops
 from .dist import Comm
+from .module import is_attached_fusion
 from .optim import FusedAdam, FusedSGD
 from .plugin import GSPlugin
 from .rows import compact_feature_grad
@@ -45,7 +46,8 @@ class StreamTrainer:
         optimizer: "sgd" (FusedSGD(lr, momentum, weight_decay)) or "adam" (FusedAdam(lr, weight_decay, **adam); `lr` may then be a
         mapping group name -> lr, and `adam` holds betas / eps / param_groups, e.g. param_groups=cav_param_groups(model, lr))."""
         self.model = model
-        self.head = model.fusion_module.fc_out
+        fusion = model.fusion_module                            # an attached sum / film / gated fusion (mla_hip.fusion) owns its Linears
+        self.head = fusion if is_attached_fusion(fusion) else fusion.fc_out
         self.encoders = model.mla_encoders()                    # [(tag, group, encoder)], alternation / concatenation order
         self.feature_only = bool(getattr(model, "feature_only", False))       # stored features: no encoder, no encoder group
         groups = {grp: enc for _t, grp, enc in self.encoders if enc is not None}

@@ -4,6 +4,7 @@ default) unless MATH=f32.  One JSON line per mode (MLA, Normal, OGM, OGM_GE; QMF
 bench line (bench.py); numbers go to DESIGN.md.
 
     python scripts/bench_joint.py [--steps 20] [--warmup 5] [--batch 64] [--math split] [--serial]
+    python scripts/bench_joint.py --fusion concat,sum,film,gated      # the joint Normal step per fusion head (mla_hip.attach_fusion)
 """
 import argparse
 import json
@@ -15,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-learning-with-alternating-unimodal-adaptation_amd"))
 import torch  # noqa: E402
 
-from mla_hip import AVClassifier, JointTrainer, MLATrainer, QMFTrainer  # noqa: E402
+from mla_hip import AVClassifier, JointTrainer, MLATrainer, QMFTrainer, attach_fusion  # noqa: E402
 
 SPEC_HW, FRAMES, IMG_HW = (1024, 128), 3, (224, 224)
 
@@ -39,6 +40,9 @@ def main():
     ap.add_argument("--math", choices=["f32", "split"], default=os.environ.get("MLA_CONV_MATH", "split"))
     ap.add_argument("--modes", default="MLA,Normal,OGM,OGM_GE", help="comma-separated subset (e.g. one mode per profiler run); QMF is also a mode")
     ap.add_argument("--serial", action="store_true", help="joint modes with set_overlap(False) (A/B of the concurrent backwards)")
+    ap.add_argument("--fusion", default="", help="comma-separated subset of concat,sum,film,gated: instead of the modes, time the joint "
+                    "Normal step per fusion in ONE process, alternating, three runs each; one JSON line per fusion with the median ms/step "
+                    "and (max - min) / median")
     a = ap.parse_args()
     B = a.batch
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -47,6 +51,29 @@ def main():
     label = torch.randint(0, 6, (B,), device="cuda", generator=g)
     base = {"batch": B, "conv_math": a.math, "steps": a.steps, "warmup": a.warmup}
 
+    if a.fusion:
+        fusions = a.fusion.split(",")
+        trainers = {}
+        for f in fusions:
+            class FArgs:
+                fusion_method, dataset, gs_flag, modulation = "concat", "CREMAD", False, "Normal"
+            model = AVClassifier(FArgs(), seed=1, conv_math=a.math)
+            if f != "concat":
+                attach_fusion(model, f, seed=2)
+            trainers[f] = JointTrainer(model)
+            if a.serial:
+                trainers[f].set_overlap(False)
+        runs = {f: [] for f in fusions}
+        for _ in range(3):                                            # alternating: drift of the box hits every fusion alike
+            for f in fusions:
+                jt = trainers[f]
+                runs[f].append(timed(lambda s: jt.train_step(spec, image, label, s), a.steps, a.warmup) * 1e3)
+        for f in fusions:
+            ms = sorted(runs[f])
+            print(json.dumps(dict(base, fusion=f, ms_per_step=round(ms[1], 3), runs_ms=[round(v, 3) for v in runs[f]],
+                                  spread=round((ms[2] - ms[0]) / ms[1], 4), samples_per_s=round(B / ms[1] * 1e3, 1),
+                                  loss=round(trainers[f].losses["loss"].item(), 5))), flush=True)
+        return
     modes = a.modes.split(",")
     mla_ms = None
     if "MLA" in modes:
