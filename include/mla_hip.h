@@ -716,6 +716,29 @@ int mla_head_logits(const float* X, const float* W, const float* b, float* logit
 int mla_eval_fuse(const float* out0, const float* out1, const float* out2, const int64_t* labels, int* counts,
                   float* weights_out, int M, int B, int C, int dynamic, float alpha0, float alpha1, float alpha2,
                   void* stream);
+/* Head + fusion + accuracy of one batch in ONE launch, with the gating taken per SAMPLE (main.py:65-106, 636-676: the rule of
+ * main.py:65-87 applied to each row's own class distribution, the reference's commented-out softmax(dim=1)).  Opt-in: the
+ * published batch-axis form stays mla_eval_fuse.  Per row r:
+ *   l_m    = x_m W^T + b, the sum and the order of mla_head_logits: logits_out[m] (M, B, C) equals it bit for bit
+ *   mode 1   H_m = - sum_c p_c lp_c with p = softmax(l_m), lp = log_softmax(l_m); a class whose exp underflows to 0 contributes
+ *            0, its limit.  g_m = exp(max_k H_k - H_m), w_m = g_m / sum_k g_k over the ELIGIBLE modalities
+ *   mode 0   w_m = alpha_m
+ *   present  (nullable, uint8 (B, M); null = all present): a modality with present[r][m] == 0 is not eligible and gets weight
+ *            +0.0; mode 1 gates over the others, mode 0 gives them alpha_m / (sum of the eligible alphas) -- a row that has every
+ *            modality keeps alpha_m as it is.  The absent modality's own logits, arg-max and counter are still produced.
+ *   fused  = sum_m w_m l_m (modalities in order); arg-max = first maximum, for the fused row and for each modality
+ *   counts   int32, accumulated, the layout of mla_eval_fuse: [0,C) samples per class, [C,2C) fused-correct, [C(2+m), C(3+m))
+ *            modality-m-correct.  Integer atomics only; every float is a function of its row alone (the same bits in every run
+ *            and at every batch size).
+ * fused_out (B, C), weights_out (B, M) and pred_out (B, 1 + M) int32 (fused arg-max, then each modality's) may be null.
+ * A row whose label lies outside [0, C), that has no present modality, or (mode 0) whose eligible alphas do not sum to more than
+ * 0 is counted nowhere: its weights_out and fused_out rows are NaN and its pred_out row is -1; every other row is intact.
+ * Non-finite logits are outside the contract (nothing is indexed with them).
+ * MLA_ERR_INVALID_ARG, nothing launched: M not 2 or 3; a null required pointer (x2 is required when M == 3); B, D, C <= 0;
+ * C > 128 (the two-slot softmax); mode not 0 or 1; a float / int32 buffer off a 4-byte or labels off an 8-byte boundary. */
+int mla_eval_head(const float* x0, const float* x1, const float* x2, const float* W, const float* b, const int64_t* labels,
+                  const uint8_t* present, int* counts, float* logits_out, float* fused_out, float* weights_out, int* pred_out,
+                  int M, int B, int D, int C, int mode, float alpha0, float alpha1, float alpha2, void* stream);
 /* invstd = 1/sqrt(var + eps) (eval-mode BatchNorm on running statistics) */
 int mla_bn_invstd(const float* var, float* invstd, int n, float eps, void* stream);
 

@@ -986,6 +986,33 @@ def eval_fuse(outs, labels, counts, weights_out, dynamic: bool, alphas, stream: 
           al[2], stream or cur_stream())
 
 
+def eval_head(feats, W, b, labels, counts, logits_out, *, mode: int, alphas, present=None, fused_out=None, weights_out=None,
+              pred_out=None, stream: Optional[int] = None):
+    """One batch from features to counters in one launch with per-SAMPLE fusion weights (see include/mla_hip.h, mla_eval_head).
+    feats: M = 2 or 3 (B, D) feature matrices; W (C, D), b (C): the shared head; counts int32 (C * (2 + M)), accumulated;
+    logits_out (M, B, C).  mode 0: the fixed `alphas`; mode 1: entropy gating of each row.  present: device uint8 (B, M) or None.
+    fused_out (B, C), weights_out (B, M), pred_out int32 (B, 1 + M): optional per-row outputs."""
+    M = len(feats)
+    if M < 1 or feats[0].dim() != 2 or W.dim() != 2:
+        raise MLAHipError(f"eval_head: expected M (B, D) feature matrices and a (C, D) head weight, got {M} and {tuple(W.shape)}")
+    B, D = feats[0].shape
+    C = W.shape[0]
+    if any(tuple(f.shape) != (B, D) for f in feats) or W.shape[1] != D or tuple(b.shape) != (C,):
+        raise MLAHipError(f"eval_head: features {[tuple(f.shape) for f in feats]} / bias {tuple(b.shape)} do not match the head weight "
+                          f"{tuple(W.shape)}")
+    want = {"labels": (labels, (B,)), "counts": (counts, (C * (2 + M),)), "logits_out": (logits_out, (M, B, C)),
+            "present": (present, (B, M)), "fused_out": (fused_out, (B, C)), "weights_out": (weights_out, (B, M)),
+            "pred_out": (pred_out, (B, 1 + M))}
+    for name, (t, shape) in want.items():
+        if t is not None and tuple(t.shape) != shape:
+            raise MLAHipError(f"eval_head: {name} {tuple(t.shape)} should be {shape}")
+    x = [_p(f) for f in feats[:3]] + [None] * (3 - min(M, 3))
+    al = [float(v) for v in alphas] + [0.0] * 3
+    _call("mla_eval_head", x[0], x[1], x[2], _p(W), _p(b), _p(labels, torch.int64), _p(present, torch.uint8), _p(counts, torch.int32),
+          _p(logits_out), _p(fused_out), _p(weights_out), _p(pred_out, torch.int32), M, B, D, C, int(mode), al[0], al[1], al[2],
+          stream or cur_stream())
+
+
 def bn_invstd(var, invstd, eps: float = BN_EPS, stream: Optional[int] = None):
     _call("mla_bn_invstd", _p(var), _p(invstd), var.numel(), eps, stream or cur_stream())
 

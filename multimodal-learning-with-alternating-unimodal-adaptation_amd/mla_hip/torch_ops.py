@@ -389,6 +389,19 @@ def feature_phase(X, labels, W, b, buf, Pl, inv_batch, project, alpha, lr, momen
     return logits, loss
 
 
+@_op("eval_head(Tensor[] feats, Tensor W, Tensor b, Tensor labels, Tensor(a!) counts, int mode, float[] alphas, "
+     "Tensor? present=None) -> (Tensor, Tensor, Tensor, Tensor)")
+def eval_head(feats, W, b, labels, counts, mode, alphas, present=None):
+    """One evaluation batch from features to counters with per-sample fusion weights (main.py:65-106, 636-676 per row):
+    (logits (M, B, C), fused (B, C), weights (B, M), pred int32 (B, 1 + M)); `counts` accumulated in place."""
+    M, B, C = len(feats), feats[0].shape[0], W.shape[0]
+    logits, fused, weights = _f32((M, B, C), W), _f32((B, C), W), _f32((B, M), W)
+    pred = torch.empty((B, 1 + M), device=W.device, dtype=torch.int32)
+    ops.eval_head(list(feats), W, b, labels, counts, logits, mode=mode, alphas=list(alphas), present=present, fused_out=fused,
+                  weights_out=weights, pred_out=pred)
+    return logits, fused, weights, pred
+
+
 @_op("gather_rows2(Tensor T0, Tensor T1, Tensor labels, Tensor idx) -> (Tensor, Tensor, Tensor, Tensor)")
 def gather_rows2(T0, T1, labels, idx):
     """(out0 (B, D), out1 (B, D), label (B), idx (B, 1)): rows `idx` of two device-resident feature tables and their labels."""
