@@ -3,11 +3,7 @@
 // with no HIP in it, so adam_host_check.cpp builds it with the host sanitizers.
 #pragma once
 #include <math.h>
-#include <stddef.h>
-#include <stdint.h>
-#include "../../include/mla_hip.h"
-
-void mla_set_error(const char* fmt, ...);
+#include "args_common.h"
 
 // The split of one flat range for a float4 kernel, shared by mla_adam_step and mla_sgd_step: `p` is the written tensor that sets the
 // 16-byte grid, s0 and s1 (s1 nullable) are the state tensors walked with it, g (nullable) the gradient.
@@ -43,23 +39,11 @@ struct AdamPlan {
 
 static inline int adam_plan(const float* p, const float* g, const float* m, const float* v, size_t n, float lr, float beta1,
                             float beta2, int step, AdamPlan* out) {
-  if (!p || !m || !v) {
-    mla_set_error("mla_adam_step: null pointer");
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (n == 0) {
-    mla_set_error("mla_adam_step: n == 0");
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (step < 1) {
-    mla_set_error("mla_adam_step: step must be >= 1 (got %d)", step);
-    return MLA_ERR_INVALID_ARG;
-  }
+  MLA_REQUIRE(p && m && v, "mla_adam_step: null pointer");
+  MLA_REQUIRE(n != 0, "mla_adam_step: n == 0");
+  MLA_REQUIRE(step >= 1, "mla_adam_step: step must be >= 1 (got %d)", step);
   RangePlan r;
-  if (!range_plan(p, g, m, v, n, &r)) {
-    mla_set_error("mla_adam_step: buffers must be 4-byte aligned");
-    return MLA_ERR_INVALID_ARG;
-  }
+  MLA_REQUIRE(range_plan(p, g, m, v, n, &r), "mla_adam_step: buffers must be 4-byte aligned");
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   out->step_size = (float)((double)lr / bc1);

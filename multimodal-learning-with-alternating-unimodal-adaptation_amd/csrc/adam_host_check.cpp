@@ -1,20 +1,8 @@
 // Stand-alone host check of mla_adam_step's argument validation and launch plan (adam_args.h) with util.cpp's error reporting.
 // No GPU, no HIP: `make host-check` builds it with -fsanitize=address,undefined and runs it.
 #include <math.h>
-#include <stdio.h>
-#include <string.h>
 #include "adam_args.h"
-
-extern "C" const char* mla_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                               \
-  do {                                                             \
-    if (!(cond)) {                                                 \
-      fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                  \
-    }                                                              \
-  } while (0)
+#include "host_check.h"
 
 int main() {
   alignas(16) static float buf[4][64];
@@ -63,7 +51,5 @@ int main() {
   EXPECT(range_plan(p + 1, nullptr, m + 1, nullptr, 9, &rp) && rp.vec == 1 && rp.gvec == 1 && rp.head == 3 && rp.n4 == 1);
   EXPECT(range_plan(p + 1, g + 1, m + 3, nullptr, 9, &rp) && rp.vec == 0 && rp.gvec == 0 && rp.head == 0 && rp.n4 == 0);
   EXPECT(!range_plan((float*)((char*)p + 2), g, m, nullptr, 9, &rp) && !range_plan(p, g, (float*)((char*)m + 1), nullptr, 9, &rp));
-  if (failures) return 1;
-  printf("adam host check ok\n");
-  return 0;
+  return host_check_done("adam");
 }

@@ -5,22 +5,12 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include "../../include/mla_hip.h"
+#include "args_common.h"
 
 #define MLA_WAVE 64
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-void mla_set_error(const char* fmt, ...);
-
-#define MLA_REQUIRE(cond, ...)              \
-  do {                                      \
-    if (!(cond)) {                          \
-      mla_set_error(__VA_ARGS__);           \
-      return MLA_ERR_INVALID_ARG;           \
-    }                                       \
-  } while (0)
 
 #define MLA_CHECK_LAUNCH(name)                                             \
   do {                                                                     \

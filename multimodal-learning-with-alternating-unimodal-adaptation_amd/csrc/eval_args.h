@@ -1,12 +1,7 @@
 // Host half of mla_eval_head (eval_head.hip): argument checks and the launch plan.  Plain C++ with no HIP in it, so
 // eval_host_check.cpp builds it with the host sanitizers.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include "../../include/mla_hip.h"
 #include "head_common.h"
-
-void mla_set_error(const char* fmt, ...);
 
 #define EVAL_ROWS 2             // rows per workgroup: one wave per (row, modality), 64 * M * EVAL_ROWS threads
 
@@ -29,33 +24,15 @@ struct EvalPlan {
 };
 
 static inline int eval_head_plan(const EvalHeadArgs* a, EvalPlan* out) {
-  if (a->M != 2 && a->M != 3) {      // first: M says which feature pointers are required
-    mla_set_error("mla_eval_head: need M = 2 or 3 (got %d)", a->M);
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (!a->x[0] || !a->x[1] || (a->M == 3 && !a->x[2]) || !a->W || !a->bias || !a->labels || !a->counts || !a->logits_out) {
-    mla_set_error("mla_eval_head: null pointer");
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (a->B <= 0 || a->D <= 0 || a->C <= 0) {
-    mla_set_error("mla_eval_head: need B, D, C > 0 (got %d, %d, %d)", a->B, a->D, a->C);
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (a->C > MLA_HEAD_MAXC) {
-    mla_set_error("mla_eval_head: need 0 < C <= %d (got %d)", MLA_HEAD_MAXC, a->C);
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (a->mode != 0 && a->mode != 1) {
-    mla_set_error("mla_eval_head: need mode = 0 (fixed alphas) or 1 (per-sample entropy gating) (got %d)", a->mode);
-    return MLA_ERR_INVALID_ARG;
-  }
+  MLA_REQUIRE(a->M == 2 || a->M == 3, "mla_eval_head: need M = 2 or 3 (got %d)", a->M);      // first: M says which x[] are required
+  MLA_REQUIRE(a->x[0] && a->x[1] && (a->M != 3 || a->x[2]) && a->W && a->bias && a->labels && a->counts && a->logits_out,
+              "mla_eval_head: null pointer");
+  MLA_TRY(head_check_shape("mla_eval_head", a->B, a->D, a->C));
+  MLA_REQUIRE(a->mode == 0 || a->mode == 1, "mla_eval_head: need mode = 0 (fixed alphas) or 1 (per-sample entropy gating) (got %d)", a->mode);
   uintptr_t words = (uintptr_t)a->W | (uintptr_t)a->bias | (uintptr_t)a->counts | (uintptr_t)a->logits_out | (uintptr_t)a->fused_out |
                     (uintptr_t)a->weights_out | (uintptr_t)a->pred_out;
   for (int m = 0; m < a->M; ++m) words |= (uintptr_t)a->x[m];
-  if ((words & 3) || ((uintptr_t)a->labels & 7)) {
-    mla_set_error("mla_eval_head: float / int32 buffers must be 4-byte and labels 8-byte aligned");
-    return MLA_ERR_INVALID_ARG;
-  }
+  MLA_REQUIRE(!(words & 3) && !((uintptr_t)a->labels & 7), "mla_eval_head: float / int32 buffers must be 4-byte and labels 8-byte aligned");
   out->threads = 64 * a->M * EVAL_ROWS;
   out->blocks = (int)(((long)a->B + EVAL_ROWS - 1) / EVAL_ROWS);
   return MLA_OK;

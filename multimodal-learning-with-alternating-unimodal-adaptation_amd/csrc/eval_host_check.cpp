@@ -1,20 +1,8 @@
 // Stand-alone host check of mla_eval_head's argument validation and launch plan (eval_args.h) with util.cpp's error reporting.
 // No GPU, no HIP: `make host-check` builds it with -fsanitize=address,undefined and runs it.
-#include <stdio.h>
-#include <string.h>
 #include <initializer_list>
 #include "eval_args.h"
-
-extern "C" const char* mla_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                               \
-  do {                                                             \
-    if (!(cond)) {                                                 \
-      fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                  \
-    }                                                              \
-  } while (0)
+#include "host_check.h"
 
 // op 0: null; 1: two bytes on; 2: four bytes on
 template <class T>
@@ -122,7 +110,5 @@ int main() {
       EXPECT((long)p.blocks * EVAL_ROWS >= B && (long)(p.blocks - 1) * EVAL_ROWS < B);
     }
   EXPECT(sizeof(float) * EVAL_ROWS * MLA_HEAD_MAXM * MLA_HEAD_MAXC <= 6144);
-  if (failures) return 1;
-  printf("eval host check ok\n");
-  return 0;
+  return host_check_done("eval");
 }

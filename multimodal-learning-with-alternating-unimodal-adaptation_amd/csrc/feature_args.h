@@ -1,12 +1,7 @@
 // Host half of mla_feature_phase / mla_gather_rows2 (feature_step.hip): argument checks, the workspace layout and the launch
 // plan.  Plain C++ with no HIP in it, so feature_host_check.cpp builds it with the host sanitizers.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include "../../include/mla_hip.h"
 #include "head_common.h"
-
-void mla_set_error(const char* fmt, ...);
 
 #define FEATURE_MAXD 4096       // the feature mean (fp64) / one row of Pl in LDS: 32 KB
 #define FEATURE_KROWS 8         // rows of Pl one workgroup of the gradient launch forms k for
@@ -29,31 +24,14 @@ static inline size_t feature_ws_elems(int B, int D, int C) {
 static inline int feature_phase_plan(const void* X, const void* labels, const void* W, const void* b, const void* buf,
                                      const void* Pl, const void* logits, const void* loss, const void* ws, int B, int D, int C,
                                      int project, FeaturePlan* out) {
-  if (!X || !labels || !W || !b || !buf || !logits || !loss || !ws || (project && !Pl)) {
-    mla_set_error("mla_feature_phase: null pointer");
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (B <= 0 || D <= 0 || C <= 0) {
-    mla_set_error("mla_feature_phase: need B, D, C > 0 (got %d, %d, %d)", B, D, C);
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (C > MLA_HEAD_MAXC) {
-    mla_set_error("mla_feature_phase: need 0 < C <= %d (got %d)", MLA_HEAD_MAXC, C);
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (D > FEATURE_MAXD) {
-    mla_set_error("mla_feature_phase: need D <= %d (got %d)", FEATURE_MAXD, D);
-    return MLA_ERR_INVALID_ARG;
-  }
+  MLA_REQUIRE(X && labels && W && b && buf && logits && loss && ws && (!project || Pl), "mla_feature_phase: null pointer");
+  MLA_TRY(head_check_shape("mla_feature_phase", B, D, C));
+  MLA_REQUIRE(D <= FEATURE_MAXD, "mla_feature_phase: need D <= %d (got %d)", FEATURE_MAXD, D);
   // the flat bases as the allocator hands them out; b = W + C*D and its momentum only need float alignment (C*D is arbitrary)
-  if (((uintptr_t)X | (uintptr_t)W | (uintptr_t)buf | (uintptr_t)Pl | (uintptr_t)ws | (uintptr_t)logits) & 15) {
-    mla_set_error("mla_feature_phase: buffers must be 16-byte aligned");
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (((uintptr_t)b | (uintptr_t)loss) & 3 || ((uintptr_t)labels & 7)) {
-    mla_set_error("mla_feature_phase: bias / loss must be 4-byte and labels 8-byte aligned");
-    return MLA_ERR_INVALID_ARG;
-  }
+  MLA_REQUIRE(!(((uintptr_t)X | (uintptr_t)W | (uintptr_t)buf | (uintptr_t)Pl | (uintptr_t)ws | (uintptr_t)logits) & 15),
+              "mla_feature_phase: buffers must be 16-byte aligned");
+  MLA_REQUIRE(!(((uintptr_t)b | (uintptr_t)loss) & 3) && !((uintptr_t)labels & 7),
+              "mla_feature_phase: bias / loss must be 4-byte and labels 8-byte aligned");
   out->dlogits = 0;
   out->rowloss = (size_t)B * C;
   out->f64 = (out->rowloss + (size_t)B + 3) & ~(size_t)3;
@@ -69,33 +47,20 @@ static inline int feature_phase_plan(const void* X, const void* labels, const vo
 // vec: 1 when rows move as 16-byte accesses (D % 4 == 0 and every table / output 16-byte aligned), else the scalar path
 static inline int gather_rows2_plan(const void* T0, const void* T1, const void* labels, const void* idx, const void* out0,
                                     const void* out1, const void* out_label, const void* out_idx, long N, int D, int B, int* vec) {
-  if (!T0 || !T1 || !labels || !idx || !out0 || !out1 || !out_label || !out_idx) {
-    mla_set_error("mla_gather_rows2: null pointer");
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (N <= 0 || D <= 0 || B <= 0) {
-    mla_set_error("mla_gather_rows2: need N, D, B > 0 (got %ld, %d, %d)", N, D, B);
-    return MLA_ERR_INVALID_ARG;
-  }
-  if ((((uintptr_t)T0 | (uintptr_t)T1 | (uintptr_t)out0 | (uintptr_t)out1) & 3) ||
-      (((uintptr_t)labels | (uintptr_t)idx | (uintptr_t)out_label | (uintptr_t)out_idx) & 7)) {
-    mla_set_error("mla_gather_rows2: tables must be 4-byte and index / label buffers 8-byte aligned");
-    return MLA_ERR_INVALID_ARG;
-  }
+  MLA_REQUIRE(T0 && T1 && labels && idx && out0 && out1 && out_label && out_idx, "mla_gather_rows2: null pointer");
+  MLA_REQUIRE(N > 0 && D > 0 && B > 0, "mla_gather_rows2: need N, D, B > 0 (got %ld, %d, %d)", N, D, B);
+  MLA_REQUIRE(!(((uintptr_t)T0 | (uintptr_t)T1 | (uintptr_t)out0 | (uintptr_t)out1) & 3) &&
+                  !(((uintptr_t)labels | (uintptr_t)idx | (uintptr_t)out_label | (uintptr_t)out_idx) & 7),
+              "mla_gather_rows2: tables must be 4-byte and index / label buffers 8-byte aligned");
   *vec = (D % 4 == 0) && !(((uintptr_t)T0 | (uintptr_t)T1 | (uintptr_t)out0 | (uintptr_t)out1) & 15);
   return MLA_OK;
 }
 
 // The index vector is produced on the host (the epoch's permutation): refuse anything outside [0, N) before it is uploaded.
 static inline int gather_index_check(const int64_t* idx_host, long n, long N) {
-  if (!idx_host || n <= 0 || N <= 0) {
-    mla_set_error("mla_gather_index_check: bad argument");
-    return MLA_ERR_INVALID_ARG;
-  }
+  MLA_REQUIRE(idx_host && n > 0 && N > 0, "mla_gather_index_check: bad argument");
   for (long i = 0; i < n; ++i)
-    if (idx_host[i] < 0 || idx_host[i] >= N) {
-      mla_set_error("mla_gather_index_check: index %ld at position %ld is outside [0, %ld)", (long)idx_host[i], i, N);
-      return MLA_ERR_INVALID_ARG;
-    }
+    MLA_REQUIRE(idx_host[i] >= 0 && idx_host[i] < N, "mla_gather_index_check: index %ld at position %ld is outside [0, %ld)",
+                (long)idx_host[i], i, N);
   return MLA_OK;
 }

@@ -1,20 +1,8 @@
 // Stand-alone host check of mla_feature_phase's / mla_gather_rows2's argument validation, workspace layout and launch plan
 // (feature_args.h) with util.cpp's error reporting.  No GPU, no HIP: `make host-check` builds it with -fsanitize=address,undefined
 // and runs it.
-#include <stdio.h>
-#include <string.h>
 #include "feature_args.h"
-
-extern "C" const char* mla_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                               \
-  do {                                                             \
-    if (!(cond)) {                                                 \
-      fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                  \
-    }                                                              \
-  } while (0)
+#include "host_check.h"
 
 int main() {
   alignas(16) static float buf[8][64];
@@ -96,7 +84,5 @@ int main() {
   EXPECT(strstr(mla_last_error(), "index -1 at position 3"));
   EXPECT(gather_index_check(nullptr, 16, 16) == MLA_ERR_INVALID_ARG);
   EXPECT(gather_index_check(idx, 0, 16) == MLA_ERR_INVALID_ARG);
-  if (failures) return 1;
-  printf("feature host check ok\n");
-  return 0;
+  return host_check_done("feature");
 }

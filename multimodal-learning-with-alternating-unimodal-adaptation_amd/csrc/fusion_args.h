@@ -1,12 +1,7 @@
 // Host half of the sum / FiLM / gated fusion heads (fusion_head.hip): argument checks, the workspace layout and the block plan of
 // the gradient launch.  Plain C++ with no HIP in it, so fusion_host_check.cpp builds it with the host sanitizers.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include "../../include/mla_hip.h"
 #include "head_common.h"
-
-void mla_set_error(const char* fmt, ...);
 
 #define FUSION_MAXD 4096        // one row of the fused feature z in LDS: 16 KB
 #define FUSION_MAXJOBS 3        // Linear layers of one head: gated has fc_x, fc_y, fc_out
@@ -35,40 +30,21 @@ static inline FusionWs fusion_ws_layout(int B, int D, int C) {
 // Shapes every entry point accepts: D a multiple of 64 (the 64-lane dot products have no tail and a 256-column block never straddles
 // the gamma | beta boundary of FiLM's hidden layer), C within the two-slot softmax.
 static inline int fusion_check_shape(const char* who, int B, int D, int C) {
-  if (B <= 0 || D <= 0 || C <= 0) {
-    mla_set_error("%s: need B, D, C > 0 (got %d, %d, %d)", who, B, D, C);
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (C > MLA_HEAD_MAXC) {
-    mla_set_error("%s: need 0 < C <= %d (got %d)", who, MLA_HEAD_MAXC, C);
-    return MLA_ERR_INVALID_ARG;
-  }
-  if (D % 64 != 0 || D > FUSION_MAXD) {
-    mla_set_error("%s: need D a multiple of 64 and D <= %d (got %d)", who, FUSION_MAXD, D);
-    return MLA_ERR_INVALID_ARG;
-  }
+  MLA_TRY(head_check_shape(who, B, D, C));
+  MLA_REQUIRE(D % 64 == 0 && D <= FUSION_MAXD, "%s: need D a multiple of 64 and D <= %d (got %d)", who, FUSION_MAXD, D);
   return MLA_OK;
 }
 
 static inline int fusion_check_ptrs(const char* who, const void* const* ptrs, int n) {
   for (int i = 0; i < n; ++i) {
-    if (!ptrs[i]) {
-      mla_set_error("%s: null pointer (argument %d)", who, i);
-      return MLA_ERR_INVALID_ARG;
-    }
-    if ((uintptr_t)ptrs[i] & 3) {
-      mla_set_error("%s: argument %d is not 4-byte aligned", who, i);
-      return MLA_ERR_INVALID_ARG;
-    }
+    MLA_REQUIRE(ptrs[i], "%s: null pointer (argument %d)", who, i);
+    MLA_REQUIRE(!((uintptr_t)ptrs[i] & 3), "%s: argument %d is not 4-byte aligned", who, i);
   }
   return MLA_OK;
 }
 
 static inline int fusion_check_labels(const char* who, const void* labels) {
-  if (!labels || ((uintptr_t)labels & 7)) {
-    mla_set_error("%s: labels must be a non-null 8-byte aligned int64 buffer", who);
-    return MLA_ERR_INVALID_ARG;
-  }
+  MLA_REQUIRE(labels && !((uintptr_t)labels & 7), "%s: labels must be a non-null 8-byte aligned int64 buffer", who);
   return MLA_OK;
 }
 
@@ -98,10 +74,7 @@ static inline void fusion_jobs_init(FusionJobs* js) {
 
 static inline int fusion_jobs_add(FusionJobs* js, const float* g, const float* in, const float* W, float* dW, float* db, float* din,
                                   int B, int N, int K) {
-  if (js->n >= FUSION_MAXJOBS || !g || !in || !dW || !db || (din && !W) || B <= 0 || N <= 0 || K <= 0) {
-    mla_set_error("fusion_jobs_add: bad job");
-    return MLA_ERR_INVALID_ARG;
-  }
+  MLA_REQUIRE(js->n < FUSION_MAXJOBS && g && in && dW && db && (!din || W) && B > 0 && N > 0 && K > 0, "fusion_jobs_add: bad job");
   FusionJob* j = &js->job[js->n++];
   j->g = g; j->in = in; j->W = W; j->dW = dW; j->db = db; j->din = din;
   j->N = N; j->K = K;

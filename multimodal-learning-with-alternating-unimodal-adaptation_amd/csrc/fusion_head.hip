@@ -222,16 +222,10 @@ int launch_grad(const FusionJobs& js, const float* rowloss, float* losses, int n
   return MLA_OK;
 }
 
-#define FUSION_TRY(expr)          \
-  do {                            \
-    const int rc__ = (expr);      \
-    if (rc__ != MLA_OK) return rc__; \
-  } while (0)
-
 #define FUSION_PTRS(who, ...)                                              \
   do {                                                                     \
     const void* const ptrs__[] = {__VA_ARGS__};                            \
-    FUSION_TRY(fusion_check_ptrs(who, ptrs__, (int)(sizeof(ptrs__) / sizeof(ptrs__[0])))); \
+    MLA_TRY(fusion_check_ptrs(who, ptrs__, (int)(sizeof(ptrs__) / sizeof(ptrs__[0])))); \
   } while (0)
 
 RowArgs row_args(int B, int D, int C) {
@@ -252,8 +246,8 @@ static int sum_grads(const float* x, const float* y, const float* Wx, const floa
                      float* dby, float* dX, float* dY, const float* rowloss, float* losses, int B, int D, int C, hipStream_t st) {
   FusionJobs js;
   fusion_jobs_init(&js);
-  FUSION_TRY(fusion_jobs_add(&js, dl, x, Wx, dWx, dbx, dX, B, C, D));
-  FUSION_TRY(fusion_jobs_add(&js, dl, y, Wy, dWy, dby, dY, B, C, D));
+  MLA_TRY(fusion_jobs_add(&js, dl, x, Wx, dWx, dbx, dX, B, C, D));
+  MLA_TRY(fusion_jobs_add(&js, dl, y, Wy, dWy, dby, dY, B, C, D));
   return launch_grad(js, rowloss, losses, FUSION_NLOSS, B, st);
 }
 
@@ -263,15 +257,15 @@ extern "C" int mla_fusion_sum_ce_fwd_bwd(const float* x, const float* y, const f
                                          float inv_batch, float bias_scale, void* stream) {
   const char* who = "mla_fusion_sum_ce_fwd_bwd";
   FUSION_PTRS(who, x, y, Wx, bx, Wy, by, out, out_a, out_v, losses, dWx, dbx, dWy, dby, dX, dY, ws);
-  FUSION_TRY(fusion_check_labels(who, labels));
-  FUSION_TRY(fusion_check_shape(who, B, D, C));
+  MLA_TRY(fusion_check_labels(who, labels));
+  MLA_TRY(fusion_check_shape(who, B, D, C));
   hipStream_t st = (hipStream_t)stream;
   const FusionWs w = fusion_ws_layout(B, D, C);
   RowArgs a = row_args(B, D, C);
   a.x = x; a.y = y; a.Wa = Wx; a.ba = bx; a.Wb = Wy; a.bb = by; a.labels = labels;
   a.out = out; a.out_a = out_a; a.out_v = out_v; a.dlogits = ws + w.dlogits; a.rowloss = ws + w.rowloss;
   a.inv_batch = inv_batch; a.bias_scale = bias_scale;
-  FUSION_TRY((launch_row<SUM, TRAIN>(a, st)));
+  MLA_TRY((launch_row<SUM, TRAIN>(a, st)));
   return sum_grads(x, y, Wx, Wy, ws + w.dlogits, dWx, dbx, dWy, dby, dX, dY, ws + w.rowloss, losses, B, D, C, st);
 }
 
@@ -279,7 +273,7 @@ extern "C" int mla_fusion_sum_fwd(const float* x, const float* y, const float* W
                                   float* out, float* out_a, float* out_v, int B, int D, int C, float bias_scale, void* stream) {
   const char* who = "mla_fusion_sum_fwd";
   FUSION_PTRS(who, x, y, Wx, bx, Wy, by, out, out_a, out_v);
-  FUSION_TRY(fusion_check_shape(who, B, D, C));
+  MLA_TRY(fusion_check_shape(who, B, D, C));
   RowArgs a = row_args(B, D, C);
   a.x = x; a.y = y; a.Wa = Wx; a.ba = bx; a.Wb = Wy; a.bb = by;
   a.out = out; a.out_a = out_a; a.out_v = out_v; a.bias_scale = bias_scale;
@@ -291,12 +285,12 @@ extern "C" int mla_fusion_sum_bwd(const float* x, const float* y, const float* W
                                   void* stream) {
   const char* who = "mla_fusion_sum_bwd";
   FUSION_PTRS(who, x, y, Wx, Wy, dlogits, dWx, dbx, dWy, dby, dX, dY, ws);
-  FUSION_TRY(fusion_check_shape(who, B, D, C));
+  MLA_TRY(fusion_check_shape(who, B, D, C));
   hipStream_t st = (hipStream_t)stream;
   const FusionWs w = fusion_ws_layout(B, D, C);
   RowArgs a = row_args(B, D, C);
   a.dl_in = dlogits; a.dlogits = ws + w.dlogits; a.scale = scale;
-  FUSION_TRY((launch_row<SUM, BWD>(a, st)));
+  MLA_TRY((launch_row<SUM, BWD>(a, st)));
   return sum_grads(x, y, Wx, Wy, ws + w.dlogits, dWx, dbx, dWy, dby, dX, dY, nullptr, nullptr, B, D, C, st);
 }
 
@@ -311,8 +305,8 @@ static int film_grads(const float* film, const float* W, const float* z, const f
                       float* dWout, float* dbout, float* dfilm, const float* rowloss, float* loss, int B, int D, int C, hipStream_t st) {
   FusionJobs js;
   fusion_jobs_init(&js);
-  FUSION_TRY(fusion_jobs_add(&js, dl, z, nullptr, dWout, dbout, nullptr, B, C, D));
-  FUSION_TRY(fusion_jobs_add(&js, dh, film, W, dW, db, dfilm, B, 2 * D, D));
+  MLA_TRY(fusion_jobs_add(&js, dl, z, nullptr, dWout, dbout, nullptr, B, C, D));
+  MLA_TRY(fusion_jobs_add(&js, dh, film, W, dW, db, dfilm, B, 2 * D, D));
   return launch_grad(js, rowloss, loss, 1, B, st);
 }
 
@@ -322,15 +316,15 @@ extern "C" int mla_fusion_film_ce_fwd_bwd(const float* film, const float* t, con
                                           float inv_batch, void* stream) {
   const char* who = "mla_fusion_film_ce_fwd_bwd";
   FUSION_PTRS(who, film, t, W, b, Wout, bout, out, h, z, loss, dW, db, dWout, dbout, dfilm, dt, ws);
-  FUSION_TRY(fusion_check_labels(who, labels));
-  FUSION_TRY(fusion_check_shape(who, B, D, C));
+  MLA_TRY(fusion_check_labels(who, labels));
+  MLA_TRY(fusion_check_shape(who, B, D, C));
   hipStream_t st = (hipStream_t)stream;
   const FusionWs w = fusion_ws_layout(B, D, C);
-  FUSION_TRY(film_hidden(film, W, b, h, B, D, st));
+  MLA_TRY(film_hidden(film, W, b, h, B, D, st));
   RowArgs a = row_args(B, D, C);
   a.y = t; a.Wa = Wout; a.ba = bout; a.h0 = h; a.z = z; a.labels = labels; a.out = out;
   a.dlogits = ws + w.dlogits; a.rowloss = ws + w.rowloss; a.dh = ws + w.dh; a.dt = dt; a.inv_batch = inv_batch;
-  FUSION_TRY((launch_row<FILM, TRAIN>(a, st)));
+  MLA_TRY((launch_row<FILM, TRAIN>(a, st)));
   return film_grads(film, W, z, ws + w.dlogits, ws + w.dh, dW, db, dWout, dbout, dfilm, ws + w.rowloss, loss, B, D, C, st);
 }
 
@@ -338,9 +332,9 @@ extern "C" int mla_fusion_film_fwd(const float* film, const float* t, const floa
                                    float* out, float* h, float* z, int B, int D, int C, void* stream) {
   const char* who = "mla_fusion_film_fwd";
   FUSION_PTRS(who, film, t, W, b, Wout, bout, out, h, z);
-  FUSION_TRY(fusion_check_shape(who, B, D, C));
+  MLA_TRY(fusion_check_shape(who, B, D, C));
   hipStream_t st = (hipStream_t)stream;
-  FUSION_TRY(film_hidden(film, W, b, h, B, D, st));
+  MLA_TRY(film_hidden(film, W, b, h, B, D, st));
   RowArgs a = row_args(B, D, C);
   a.y = t; a.Wa = Wout; a.ba = bout; a.h0 = h; a.z = z; a.out = out;
   return launch_row<FILM, FWD>(a, st);
@@ -351,12 +345,12 @@ extern "C" int mla_fusion_film_bwd(const float* film, const float* t, const floa
                                    float* ws, int B, int D, int C, float scale, void* stream) {
   const char* who = "mla_fusion_film_bwd";
   FUSION_PTRS(who, film, t, W, Wout, h, z, dlogits, dW, db, dWout, dbout, dfilm, dt, ws);
-  FUSION_TRY(fusion_check_shape(who, B, D, C));
+  MLA_TRY(fusion_check_shape(who, B, D, C));
   hipStream_t st = (hipStream_t)stream;
   const FusionWs w = fusion_ws_layout(B, D, C);
   RowArgs a = row_args(B, D, C);
   a.y = t; a.Wa = Wout; a.h0 = h; a.dl_in = dlogits; a.dlogits = ws + w.dlogits; a.dh = ws + w.dh; a.dt = dt; a.scale = scale;
-  FUSION_TRY((launch_row<FILM, BWD>(a, st)));
+  MLA_TRY((launch_row<FILM, BWD>(a, st)));
   return film_grads(film, W, z, ws + w.dlogits, ws + w.dh, dW, db, dWout, dbout, dfilm, nullptr, nullptr, B, D, C, st);
 }
 
@@ -374,9 +368,9 @@ static int gated_grads(const float* x, const float* y, const float* Wx, const fl
                        const float* rowloss, float* loss, int B, int D, int C, hipStream_t st) {
   FusionJobs js;
   fusion_jobs_init(&js);
-  FUSION_TRY(fusion_jobs_add(&js, dl, z, nullptr, dWout, dbout, nullptr, B, C, D));
-  FUSION_TRY(fusion_jobs_add(&js, dh, x, Wx, dWx, dbx, dX, B, D, D));
-  FUSION_TRY(fusion_jobs_add(&js, dh + (size_t)B * D, y, Wy, dWy, dby, dY, B, D, D));
+  MLA_TRY(fusion_jobs_add(&js, dl, z, nullptr, dWout, dbout, nullptr, B, C, D));
+  MLA_TRY(fusion_jobs_add(&js, dh, x, Wx, dWx, dbx, dX, B, D, D));
+  MLA_TRY(fusion_jobs_add(&js, dh + (size_t)B * D, y, Wy, dWy, dby, dY, B, D, D));
   return launch_grad(js, rowloss, loss, 1, B, st);
 }
 
@@ -387,15 +381,15 @@ extern "C" int mla_fusion_gated_ce_fwd_bwd(const float* x, const float* y, const
                                            float inv_batch, void* stream) {
   const char* who = "mla_fusion_gated_ce_fwd_bwd";
   FUSION_PTRS(who, x, y, Wx, bx, Wy, by, Wout, bout, out, hx, hy, z, loss, dWx, dbx, dWy, dby, dWout, dbout, dX, dY, ws);
-  FUSION_TRY(fusion_check_labels(who, labels));
-  FUSION_TRY(fusion_check_shape(who, B, D, C));
+  MLA_TRY(fusion_check_labels(who, labels));
+  MLA_TRY(fusion_check_shape(who, B, D, C));
   hipStream_t st = (hipStream_t)stream;
   const FusionWs w = fusion_ws_layout(B, D, C);
-  FUSION_TRY(gated_hidden(x, y, Wx, bx, Wy, by, hx, hy, B, D, st));
+  MLA_TRY(gated_hidden(x, y, Wx, bx, Wy, by, hx, hy, B, D, st));
   RowArgs a = row_args(B, D, C);
   a.Wa = Wout; a.ba = bout; a.h0 = hx; a.h1 = hy; a.z = z; a.labels = labels; a.out = out; a.x_gate = x_gate != 0;
   a.dlogits = ws + w.dlogits; a.rowloss = ws + w.rowloss; a.dh = ws + w.dh; a.inv_batch = inv_batch;
-  FUSION_TRY((launch_row<GATED, TRAIN>(a, st)));
+  MLA_TRY((launch_row<GATED, TRAIN>(a, st)));
   return gated_grads(x, y, Wx, Wy, z, ws + w.dlogits, ws + w.dh, dWx, dbx, dWy, dby, dWout, dbout, dX, dY, ws + w.rowloss, loss, B, D, C,
                      st);
 }
@@ -405,9 +399,9 @@ extern "C" int mla_fusion_gated_fwd(const float* x, const float* y, const float*
                                     int x_gate, void* stream) {
   const char* who = "mla_fusion_gated_fwd";
   FUSION_PTRS(who, x, y, Wx, bx, Wy, by, Wout, bout, out, hx, hy, z);
-  FUSION_TRY(fusion_check_shape(who, B, D, C));
+  MLA_TRY(fusion_check_shape(who, B, D, C));
   hipStream_t st = (hipStream_t)stream;
-  FUSION_TRY(gated_hidden(x, y, Wx, bx, Wy, by, hx, hy, B, D, st));
+  MLA_TRY(gated_hidden(x, y, Wx, bx, Wy, by, hx, hy, B, D, st));
   RowArgs a = row_args(B, D, C);
   a.Wa = Wout; a.ba = bout; a.h0 = hx; a.h1 = hy; a.z = z; a.out = out; a.x_gate = x_gate != 0;
   return launch_row<GATED, FWD>(a, st);
@@ -419,12 +413,12 @@ extern "C" int mla_fusion_gated_bwd(const float* x, const float* y, const float*
                                     float scale, void* stream) {
   const char* who = "mla_fusion_gated_bwd";
   FUSION_PTRS(who, x, y, Wx, Wy, Wout, hx, hy, z, dlogits, dWx, dbx, dWy, dby, dWout, dbout, dX, dY, ws);
-  FUSION_TRY(fusion_check_shape(who, B, D, C));
+  MLA_TRY(fusion_check_shape(who, B, D, C));
   hipStream_t st = (hipStream_t)stream;
   const FusionWs w = fusion_ws_layout(B, D, C);
   RowArgs a = row_args(B, D, C);
   a.Wa = Wout; a.h0 = hx; a.h1 = hy; a.dl_in = dlogits; a.dlogits = ws + w.dlogits; a.dh = ws + w.dh; a.x_gate = x_gate != 0;
   a.scale = scale;
-  FUSION_TRY((launch_row<GATED, BWD>(a, st)));
+  MLA_TRY((launch_row<GATED, BWD>(a, st)));
   return gated_grads(x, y, Wx, Wy, z, ws + w.dlogits, ws + w.dh, dWx, dbx, dWy, dby, dWout, dbout, dX, dY, nullptr, nullptr, B, D, C, st);
 }

@@ -1,19 +1,7 @@
 // Stand-alone host check of the fusion heads' argument validation, workspace layout and gradient-launch block plan (fusion_args.h) with
 // util.cpp's error reporting.  No GPU, no HIP: `make host-check` builds it with -fsanitize=address,undefined and runs it.
-#include <stdio.h>
-#include <string.h>
 #include "fusion_args.h"
-
-extern "C" const char* mla_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                               \
-  do {                                                             \
-    if (!(cond)) {                                                 \
-      fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                  \
-    }                                                              \
-  } while (0)
+#include "host_check.h"
 
 int main() {
   alignas(16) static float buf[8][64];
@@ -101,7 +89,5 @@ int main() {
     EXPECT(strstr(mla_last_error(), "bad job"));
     EXPECT(js.n == 0 && js.blocks == 0);
   }
-  if (failures) return 1;
-  printf("fusion host check ok\n");
-  return 0;
+  return host_check_done("fusion");
 }

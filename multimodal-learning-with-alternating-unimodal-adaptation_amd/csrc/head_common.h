@@ -8,8 +8,17 @@
 #pragma once
 
 // Host-safe part (feature_args.h builds without HIP).
+#include "args_common.h"
+
 #define MLA_HEAD_MAXC 128       // classes: the two-slot softmax holds a row of logits in one wave, two per lane
 #define MLA_HEAD_MAXM 3         // modalities
+
+// the shape rule of every head that holds a row of logits in the two-slot softmax (eval_args.h, feature_args.h, fusion_args.h)
+static inline int head_check_shape(const char* who, int B, int D, int C) {
+  MLA_REQUIRE(B > 0 && D > 0 && C > 0, "%s: need B, D, C > 0 (got %d, %d, %d)", who, B, D, C);
+  MLA_REQUIRE(C <= MLA_HEAD_MAXC, "%s: need 0 < C <= %d (got %d)", who, MLA_HEAD_MAXC, C);
+  return MLA_OK;
+}
 
 #ifdef __HIPCC__
 #include "common.h"

@@ -1,24 +1,7 @@
 // Stand-alone host check of mla_modal3_assemble's argument validation and launch plan (modal3_args.h) with util.cpp's error
 // reporting.  No GPU, no HIP: `make host-check` builds it with -fsanitize=address,undefined and runs it.
-#include <stdio.h>
-#include <string.h>
 #include "modal3_args.h"
-
-extern "C" const char* mla_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                               \
-  do {                                                             \
-    if (!(cond)) {                                                 \
-      fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                  \
-    }                                                              \
-  } while (0)
-#define REFUSED(call, text) \
-  do {                      \
-    EXPECT((call) == MLA_ERR_INVALID_ARG); \
-    EXPECT(strstr(mla_last_error(), text)); \
-  } while (0)
+#include "host_check.h"
 
 int main() {
   // B = 7, S = 2, T*F = 8, L = 4: image rows of 48 B, spectrogram rows of 32 B, token rows of 32 B, padding-mask rows of 16 B
@@ -106,7 +89,5 @@ int main() {
   EXPECT(p.image == 49152 && p.spec == 32768 && p.token == 128 && p.pm == 64 && p.total == 82112);
   EXPECT(p.blocks_x == MODAL3_MAX_BLOCKS / 32 && (long long)p.blocks_x * 32 <= MODAL3_MAX_BLOCKS);
   EXPECT(modal3_shape_plan(5000, 2, 8, 4, &p) == MLA_OK && p.blocks_x == 1);
-  if (failures) return 1;
-  printf("modal3 host check ok\n");
-  return 0;
+  return host_check_done("modal3");
 }

@@ -120,7 +120,7 @@ static_assert((RES_SPEC_ROW / 4) % (RES_GATHER_THREADS * RES_GATHER_UNITS) == 0,
 
 extern "C" int mla_resident_plan(const int64_t* table_host, int64_t rows, int T, size_t frames_bytes, int out_h, int out_w, int train,
                                  int* plan5) {
-  RES_REQUIRE(plan5, "mla_resident_plan: null plan");
+  MLA_REQUIRE(plan5, "mla_resident_plan: null plan");
   FramePlan p;
   const int rc = res_plan(table_host, rows, T, frames_bytes, out_h, out_w, train, &p);
   if (rc != MLA_OK) return rc;

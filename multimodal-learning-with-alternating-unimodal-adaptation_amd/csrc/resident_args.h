@@ -13,15 +13,11 @@
 // after ten refusals the central crop of frames.sample_crop; flip = word 0 of block k = 10 < 2^31.
 #pragma once
 #include <limits.h>
-#include <stddef.h>
-#include <stdint.h>
 #include <algorithm>
 #include <utility>
 #include <vector>
-#include "../../include/mla_hip.h"
+#include "args_common.h"
 #include "frames_common.h"
-
-void mla_set_error(const char* fmt, ...);
 
 #define RES_TABLE_COLS 3                          // frame table row: byte offset, H, W
 #define RES_DESC_COLS 8                           // mla_frames_resample's descriptor row
@@ -41,28 +37,20 @@ void mla_set_error(const char* fmt, ...);
 FR_HD static inline uint64_t res_key(uint64_t seed, uint64_t epoch) { return (epoch << 32) | seed; }
 FR_HD static inline uint64_t res_counter(int t, int k) { return ((uint64_t)(uint32_t)t << 4) | (uint64_t)k; }
 
-#define RES_REQUIRE(cond, ...)    \
-  do {                            \
-    if (!(cond)) {                \
-      mla_set_error(__VA_ARGS__); \
-      return MLA_ERR_INVALID_ARG; \
-    }                             \
-  } while (0)
-
 // table_host int64 (rows, 3): every frame inside the buffer, rows a whole number of samples of T frames
 static inline int res_table_check(const int64_t* table_host, int64_t rows, int T, size_t frames_bytes) {
-  RES_REQUIRE(table_host, "mla_resident_plan: null frame table");
-  RES_REQUIRE(T > 0 && T < 65536, "mla_resident_plan: T=%d frames per sample out of range", T);
-  RES_REQUIRE(rows > 0 && rows % T == 0 && rows / T <= INT_MAX,
+  MLA_REQUIRE(table_host, "mla_resident_plan: null frame table");
+  MLA_REQUIRE(T > 0 && T < 65536, "mla_resident_plan: T=%d frames per sample out of range", T);
+  MLA_REQUIRE(rows > 0 && rows % T == 0 && rows / T <= INT_MAX,
               "mla_resident_plan: %lld table rows are not N * T rows of N <= 2^31 - 1 samples with T=%d", (long long)rows, T);
-  RES_REQUIRE(frames_bytes <= (size_t)INT64_MAX, "mla_resident_plan: a buffer of %zu bytes is too large", frames_bytes);
+  MLA_REQUIRE(frames_bytes <= (size_t)INT64_MAX, "mla_resident_plan: a buffer of %zu bytes is too large", frames_bytes);
   for (int64_t n = 0; n < rows; ++n) {
     const int64_t* d = table_host + (size_t)n * RES_TABLE_COLS;
     const int64_t off = d[0], H = d[1], W = d[2];
-    RES_REQUIRE(H > 0 && W > 0 && H <= FR_DIM_MAX && W <= FR_DIM_MAX, "mla_resident_plan: frame %lld: size %lldx%lld out of range",
+    MLA_REQUIRE(H > 0 && W > 0 && H <= FR_DIM_MAX && W <= FR_DIM_MAX, "mla_resident_plan: frame %lld: size %lldx%lld out of range",
                 (long long)n, (long long)H, (long long)W);
     // H * W * 3 <= 3 * 2^32: no overflow; compared without forming off + size
-    RES_REQUIRE(off >= 0 && H * W * 3 <= (int64_t)frames_bytes && off <= (int64_t)frames_bytes - H * W * 3,
+    MLA_REQUIRE(off >= 0 && H * W * 3 <= (int64_t)frames_bytes && off <= (int64_t)frames_bytes - H * W * 3,
                 "mla_resident_plan: frame %lld: bytes [%lld, %lld + %lld) lie outside the %zu-byte buffer", (long long)n, (long long)off,
                 (long long)off, (long long)(H * W * 3), frames_bytes);
   }
@@ -70,7 +58,7 @@ static inline int res_table_check(const int64_t* table_host, int64_t rows, int T
 }
 
 static inline int res_out_check(const char* who, int out_h, int out_w) {
-  RES_REQUIRE(out_h > 0 && out_w > 0 && out_h <= 4096 && out_w <= 4096, "%s: output size %dx%d out of range", who, out_h, out_w);
+  MLA_REQUIRE(out_h > 0 && out_w > 0 && out_h <= 4096 && out_w <= 4096, "%s: output size %dx%d out of range", who, out_h, out_w);
   return MLA_OK;
 }
 
@@ -92,10 +80,8 @@ static inline int res_band_rows(int ch, int OH, int band) {
 // over every ch, as they need not.
 static inline int res_plan(const int64_t* table_host, int64_t rows, int T, size_t frames_bytes, int OH, int OW, int train,
                            FramePlan* plan) {
-  int rc = res_out_check("mla_resident_plan", OH, OW);
-  if (rc != MLA_OK) return rc;
-  rc = res_table_check(table_host, rows, T, frames_bytes);
-  if (rc != MLA_OK) return rc;
+  MLA_TRY(res_out_check("mla_resident_plan", OH, OW));
+  MLA_TRY(res_table_check(table_host, rows, T, frames_bytes));
   std::vector<std::pair<int, int>> shapes;
   for (int64_t n = 0; n < rows; ++n)
     shapes.emplace_back((int)table_host[(size_t)n * RES_TABLE_COLS + 1], (int)table_host[(size_t)n * RES_TABLE_COLS + 2]);
@@ -136,22 +122,22 @@ static inline int res_plan(const int64_t* table_host, int64_t rows, int T, size_
       return MLA_OK;
     }
   }
-  RES_REQUIRE(false, "mla_resident_plan: a %dx%d frame resized to %dx%d needs more than %d bytes of LDS in every band", worst_h, worst_w,
+  MLA_REQUIRE(false, "mla_resident_plan: a %dx%d frame resized to %dx%d needs more than %d bytes of LDS in every band", worst_h, worst_w,
               OH, OW, FR_LDS_MAX);
   return MLA_ERR_INVALID_ARG;
 }
 
 // a plan5 (band, rows_cap, kh, kv, lds) as res_plan returns them for this output size
 static inline int res_plan5_check(const int* plan5, int OH, int OW, FramePlan* plan) {
-  RES_REQUIRE(plan5, "mla_resident_batch: null plan");
+  MLA_REQUIRE(plan5, "mla_resident_batch: null plan");
   const int band = plan5[0], rows_cap = plan5[1], kh = plan5[2], kv = plan5[3];
-  RES_REQUIRE(band >= 1 && band <= FR_BAND && (band & (band - 1)) == 0, "mla_resident_batch: plan: band %d is not 16, 8, 4, 2 or 1", band);
-  RES_REQUIRE(rows_cap >= 1 && rows_cap <= FR_DIM_MAX, "mla_resident_batch: plan: rows_cap %d out of range", rows_cap);
-  RES_REQUIRE(kh >= 3 && kv >= 3 && (kh & 1) && (kv & 1) && kh <= 2 * FR_DIM_MAX + 1 && kv <= 2 * FR_DIM_MAX + 1,
+  MLA_REQUIRE(band >= 1 && band <= FR_BAND && (band & (band - 1)) == 0, "mla_resident_batch: plan: band %d is not 16, 8, 4, 2 or 1", band);
+  MLA_REQUIRE(rows_cap >= 1 && rows_cap <= FR_DIM_MAX, "mla_resident_batch: plan: rows_cap %d out of range", rows_cap);
+  MLA_REQUIRE(kh >= 3 && kv >= 3 && (kh & 1) && (kv & 1) && kh <= 2 * FR_DIM_MAX + 1 && kv <= 2 * FR_DIM_MAX + 1,
               "mla_resident_batch: plan: %d / %d coefficients per output are not filter sizes", kh, kv);
   const size_t lds = fr_lds(OW, band, rows_cap, kh, kv);
-  RES_REQUIRE(lds <= FR_LDS_MAX, "mla_resident_batch: plan: needs %zu bytes of LDS (max %d)", lds, FR_LDS_MAX);
-  RES_REQUIRE(plan5[4] >= 0 && (size_t)plan5[4] == lds, "mla_resident_batch: plan: says %d bytes of LDS where its sizes need %zu", plan5[4], lds);
+  MLA_REQUIRE(lds <= FR_LDS_MAX, "mla_resident_batch: plan: needs %zu bytes of LDS (max %d)", lds, FR_LDS_MAX);
+  MLA_REQUIRE(plan5[4] >= 0 && (size_t)plan5[4] == lds, "mla_resident_batch: plan: says %d bytes of LDS where its sizes need %zu", plan5[4], lds);
   *plan = FramePlan{band, rows_cap, kh, kv, lds};
   return MLA_OK;
 }
@@ -160,24 +146,22 @@ static inline int res_batch_check(const void* frames, size_t frames_bytes, const
                                   const void* order, int N, int T, int pos, int b, uint64_t seed, uint64_t epoch, const int* plan5,
                                   const void* lut, const void* desc_out, const void* image_out, const void* spec_out,
                                   const void* label_out, const void* idx_out, int OH, int OW, FramePlan* plan) {
-  RES_REQUIRE(frames && table && labels && order && lut && desc_out && image_out && label_out && idx_out,
+  MLA_REQUIRE(frames && table && labels && order && lut && desc_out && image_out && label_out && idx_out,
               "mla_resident_batch: null pointer");
-  RES_REQUIRE(!spec_table || spec_out, "mla_resident_batch: a spec table but no spec_out");
-  RES_REQUIRE(N > 0 && T > 0 && b > 0 && pos >= 0, "mla_resident_batch: need N, T, b > 0 and pos >= 0 (got N=%d T=%d b=%d pos=%d)", N, T, b,
+  MLA_REQUIRE(!spec_table || spec_out, "mla_resident_batch: a spec table but no spec_out");
+  MLA_REQUIRE(N > 0 && T > 0 && b > 0 && pos >= 0, "mla_resident_batch: need N, T, b > 0 and pos >= 0 (got N=%d T=%d b=%d pos=%d)", N, T, b,
               pos);
-  RES_REQUIRE((long long)pos + b <= N, "mla_resident_batch: batch [%d, %d + %d) leaves the order of N=%d", pos, pos, b, N);
-  RES_REQUIRE((long long)b * T < 65536, "mla_resident_batch: b * T = %d * %d frames per launch (max 65535)", b, T);
-  RES_REQUIRE(seed < (1ull << 32) && epoch < (1ull << 32), "mla_resident_batch: seed %llu and epoch %llu must be below 2^32",
+  MLA_REQUIRE((long long)pos + b <= N, "mla_resident_batch: batch [%d, %d + %d) leaves the order of N=%d", pos, pos, b, N);
+  MLA_REQUIRE((long long)b * T < 65536, "mla_resident_batch: b * T = %d * %d frames per launch (max 65535)", b, T);
+  MLA_REQUIRE(seed < (1ull << 32) && epoch < (1ull << 32), "mla_resident_batch: seed %llu and epoch %llu must be below 2^32",
               (unsigned long long)seed, (unsigned long long)epoch);
-  RES_REQUIRE(frames_bytes >= 3 && frames_bytes <= (size_t)INT64_MAX, "mla_resident_batch: a frame buffer of %zu bytes", frames_bytes);
-  int rc = res_out_check("mla_resident_batch", OH, OW);
-  if (rc != MLA_OK) return rc;
-  rc = res_plan5_check(plan5, OH, OW, plan);
-  if (rc != MLA_OK) return rc;
-  RES_REQUIRE(!(((uintptr_t)table | (uintptr_t)labels | (uintptr_t)order | (uintptr_t)desc_out | (uintptr_t)label_out | (uintptr_t)idx_out) & 7),
+  MLA_REQUIRE(frames_bytes >= 3 && frames_bytes <= (size_t)INT64_MAX, "mla_resident_batch: a frame buffer of %zu bytes", frames_bytes);
+  MLA_TRY(res_out_check("mla_resident_batch", OH, OW));
+  MLA_TRY(res_plan5_check(plan5, OH, OW, plan));
+  MLA_REQUIRE(!(((uintptr_t)table | (uintptr_t)labels | (uintptr_t)order | (uintptr_t)desc_out | (uintptr_t)label_out | (uintptr_t)idx_out) & 7),
               "mla_resident_batch: the frame table, labels, order, desc_out, label_out and idx_out must be 8-byte aligned");
-  RES_REQUIRE(!(((uintptr_t)lut | (uintptr_t)image_out) & 3), "mla_resident_batch: lut and image_out must be 4-byte aligned");
-  RES_REQUIRE(!(((uintptr_t)spec_table | (uintptr_t)(spec_table ? spec_out : nullptr)) & 15),
+  MLA_REQUIRE(!(((uintptr_t)lut | (uintptr_t)image_out) & 3), "mla_resident_batch: lut and image_out must be 4-byte aligned");
+  MLA_REQUIRE(!(((uintptr_t)spec_table | (uintptr_t)(spec_table ? spec_out : nullptr)) & 15),
               "mla_resident_batch: spec_table and spec_out must be 16-byte aligned (rows move as 16-byte units)");
   return MLA_OK;
 }

@@ -1,25 +1,8 @@
 // Stand-alone host check of mla_resident_plan's table checks and worst-case plan and of mla_resident_batch's argument validation
 // (resident_args.h) with util.cpp's error reporting.  No GPU, no HIP: `make host-check` builds it with
 // -fsanitize=address,undefined and runs it.
-#include <stdio.h>
-#include <string.h>
 #include "resident_args.h"
-
-extern "C" const char* mla_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                               \
-  do {                                                             \
-    if (!(cond)) {                                                 \
-      fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                  \
-    }                                                              \
-  } while (0)
-#define REFUSED(call, text) \
-  do {                      \
-    EXPECT((call) == MLA_ERR_INVALID_ARG); \
-    EXPECT(strstr(mla_last_error(), text)); \
-  } while (0)
+#include "host_check.h"
 
 int main() {
   // two samples of T = 3 frames, sizes mixed, packed back to back
@@ -118,7 +101,5 @@ int main() {
   REFUSED(forged(1, p.rows_cap + 1, 40), "bytes of LDS where");              // a larger cap with the old byte count
   REFUSED(forged(1, 60000, 40), "bytes of LDS (max");
   REFUSED(forged(4, (int)p.lds, 48), "bytes of LDS where");                  // the same plan at another output width
-  if (failures) return 1;
-  printf("resident host check ok\n");
-  return 0;
+  return host_check_done("resident");
 }

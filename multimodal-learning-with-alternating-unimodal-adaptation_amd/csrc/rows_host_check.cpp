@@ -1,25 +1,8 @@
 // Stand-alone host check of the argument validation and launch plans of mla_rows_gather / mla_rows_expand / mla_rows_compact_sum
 // (rows_args.h) with util.cpp's error reporting.  No GPU, no HIP: `make host-check` builds it with -fsanitize=address,undefined and
 // runs it.
-#include <stdio.h>
-#include <string.h>
 #include "rows_args.h"
-
-extern "C" const char* mla_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                               \
-  do {                                                             \
-    if (!(cond)) {                                                 \
-      fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                  \
-    }                                                              \
-  } while (0)
-#define REFUSED(call, text) \
-  do {                      \
-    EXPECT((call) == MLA_ERR_INVALID_ARG); \
-    EXPECT(strstr(mla_last_error(), text)); \
-  } while (0)
+#include "host_check.h"
 
 int main() {
   enum { B = 5, ROW = 8 };                               // rows of 32 bytes
@@ -96,7 +79,5 @@ int main() {
   EXPECT(gather((const void*)0x1000000, dev, all, (const void*)0x40000000, 32, 5, 196608, 4, 1) == MLA_OK);
   EXPECT(p.vec16 == 1 && p.units == 49152 && p.blocks_x == 192 && (size_t)p.blocks_x * p.rows <= ROWS_MAX_BLOCKS);
   EXPECT(expand((const void*)0x1000000, dev, map, (const void*)0x40000000, 5, 3, 768, 4) == MLA_OK && p.units == 192 && p.blocks_x == 1);
-  if (failures) return 1;
-  printf("rows host check ok\n");
-  return 0;
+  return host_check_done("rows");
 }

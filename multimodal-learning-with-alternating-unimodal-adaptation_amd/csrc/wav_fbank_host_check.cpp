@@ -1,24 +1,7 @@
 // Stand-alone host check of mla_wav_fbank's argument validation and launch plan (wav_fbank_args.h) with util.cpp's error
 // reporting.  No GPU, no HIP: `make host-check` builds it with -fsanitize=address,undefined and runs it.
-#include <stdio.h>
-#include <string.h>
 #include "wav_fbank_args.h"
-
-extern "C" const char* mla_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                               \
-  do {                                                             \
-    if (!(cond)) {                                                 \
-      fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                  \
-    }                                                              \
-  } while (0)
-#define REFUSED(call, text) \
-  do {                      \
-    EXPECT((call) == MLA_ERR_INVALID_ARG); \
-    EXPECT(strstr(mla_last_error(), text)); \
-  } while (0)
+#include "host_check.h"
 
 int main() {
   // three clips in a buffer of 2000 samples: 400 at 0, an absent one, 1599 at the odd offset 401 (to the buffer's last sample)
@@ -121,7 +104,5 @@ int main() {
   EXPECT(mel(3, 0, 256, NW + 254) == MLA_OK);
   REFUSED(mel(-1, 0, 0, NW - 1), "hold 256 weights");
   REFUSED(mel(-1, 0, 0, NW + 1), "hold 256 weights");
-  if (failures) return 1;
-  printf("wav fbank host check ok\n");
-  return 0;
+  return host_check_done("wav fbank");
 }
