@@ -242,7 +242,8 @@ int mla_bn_bwd_from_partial(const float* dout, const float* x, const float* mean
 int mla_bn_relu_maxpool_fwd(const float* y, const float* mean, const float* invstd, const float* gamma,
                             const float* beta, float* out, uint8_t* idx, int N, int H, int W, int C, void* stream);
 /* ... and its backward: BatchNorm backward whose upstream gradient is gathered from the POOLED gradient dpool (N,OH,OW,C)
- * through idx and masked by bn(y) > 0; dy (N,H,W,C) = gradient w.r.t. y, dgamma / dbeta written; ws >= mla_bn_bwd_ws_elems.
+ * through idx and masked by bn(y) > 0; dy (N,H,W,C) = gradient w.r.t. y, dgamma / dbeta written; ws >= mla_bn_bwd_ws_elems(N*H*W, C):
+ * the partial rows of the reduction over the N*OH*OW pooled rows are fitted into that at every admitted shape.
  * dy = NULL: the reduction half alone (dgamma, dbeta) -- for a consumer that forms dy itself
  * (mla_conv2d_stem_wgrad_split_bnpool). */
 int mla_bn_bwd_pooled(const float* dpool, const uint8_t* idx, const float* y, const float* mean, const float* invstd,

@@ -16,25 +16,18 @@
 // (<16, 16> or <4, 64>), or bn_tiles_stage1_kernel + bn_finalize_chunks_kernel<FWD>; the closing
 // arithmetic is written once (bn_close_fwd, bn_close_bwd).
 #include "common.h"
+#include "pool_args.h"
 
 static size_t bn_red_scratch_floats(int C);
 // ---- tiling shared by the stats and backward-reduce kernels --------------------------------
-static int bn_tile_rows(int M) {
-  // aim at ~2048 workgroups for the big activations (stem, layer1: > 256 K rows), ~1024 below (then the statistics are
-  // finalized by ONE launch, bn_finalize_tiles_kernel)
-  long t = M > (1 << 18) ? ((long)M + 2047) / 2048 : ((long)M + 1023) / 1024;
-  t = ((t + 15) / 16) * 16;
-  if (t < 32) t = 32;
-  if (t > 1024) t = 1024;
-  return (int)t;
-}
+// bn_tile_rows / bn_ws_tiles: pool_args.h (the host half the pooled stem entry points share with their host check)
 
 // Every partial buffer carries a scratch tail for the two-stage reduction (declared in bn.hip, used by the conv too).
 extern "C" size_t mla_bn_partial_scratch_elems(int C) { return bn_red_scratch_floats(C); }
 extern "C" size_t mla_bn_stats_partial_elems(int M, int C) {
-  return (size_t)cdiv(M, bn_tile_rows(M)) * 2 * C * 2 + bn_red_scratch_floats(C);     // forward statistics: fp64 partials
+  return (size_t)bn_ws_tiles(M) * 2 * C * 2 + bn_red_scratch_floats(C);     // forward statistics: fp64 partials
 }
-extern "C" size_t mla_bn_bwd_ws_elems(int M, int C) { return (size_t)cdiv(M, bn_tile_rows(M)) * 2 * C + bn_red_scratch_floats(C); }
+extern "C" size_t mla_bn_bwd_ws_elems(int M, int C) { return (size_t)bn_ws_tiles(M) * 2 * C + bn_red_scratch_floats(C); }
 
 // one per-channel float4 (mean, invstd, gamma, beta, dgamma, dbeta) of column group cg
 __device__ __forceinline__ f32x4 chan4(const float* __restrict__ p, int cg) { return reinterpret_cast<const f32x4*>(p)[cg]; }
@@ -300,9 +293,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     const f32x4 mu = chan4(mean, cg), is = chan4(invstd, cg), ga = chan4(gamma, cg), be = chan4(beta, cg);
     f32x4 v = bn_val(reinterpret_cast<const f32x4*>(x)[idx], mu, is, ga, be);
     if (residual) v += reinterpret_cast<const f32x4*>(residual)[idx];
-    if (relu) {
+    if (relu) {   // NaN kept, as torch.relu and bn_relu_maxpool_fwd_kernel keep it (fmaxf alone answers 0)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+      for (int e = 0; e < 4; ++e) v[e] = v[e] != v[e] ? v[e] : fmaxf(v[e], 0.f);
     }
     reinterpret_cast<f32x4*>(out)[idx] = v;
   }
@@ -531,16 +524,8 @@ __global__ __launch_bounds__(256) void bn_bwd_pooled_apply_kernel(const float* _
   }
 }
 
-static int bn_check(const char* who, int M, int C) {
-  MLA_REQUIRE(M > 0 && C > 0, "%s: non-positive dims", who);
-  MLA_REQUIRE(C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0, "%s: C=%d must be 4*2^k, <= 1024", who, C);
-  return MLA_OK;
-}
-
-static int ew_grid(size_t n4) {
-  size_t b = (n4 + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+// bn_check: pool_args.h
+static int ew_grid(size_t n4) { return pool_capped_grid(n4, BN_EW_MAX_BLOCKS); }
 
 // the backward sums partial[tiles][2][C] (fp32, scratch tail behind them) -> dgamma, dbeta
 static int bn_bwd_finalize(const float* partial, int tiles, int M, int C, float* dgamma, float* dbeta, hipStream_t st) {
@@ -615,11 +600,9 @@ extern "C" int mla_bn_bwd_from_partial(const float* dout, const float* x, const 
 
 extern "C" int mla_bn_relu_maxpool_fwd(const float* y, const float* mean, const float* invstd, const float* gamma, const float* beta,
                                        float* out, uint8_t* idx, int N, int H, int W, int C, void* stream) {
-  if (int rc = bn_check("mla_bn_relu_maxpool_fwd", N * H * W, C)) return rc;
-  MLA_REQUIRE(y && mean && invstd && gamma && beta && out && idx && N > 0 && H > 0 && W > 0, "mla_bn_relu_maxpool_fwd: bad argument");
-  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
-  const size_t n4 = (size_t)N * ((OH + 1) / 2) * ((OW + 1) / 2) * (C / 4);     // one thread per 2x2 block of pooled outputs and 4 channels
-  bn_relu_maxpool_fwd_kernel<<<ew_grid(n4), 256, 0, (hipStream_t)stream>>>(y, mean, invstd, gamma, beta, out, idx, N, H, W, C, OH, OW);
+  PoolPlan p;
+  MLA_TRY(bn_relu_maxpool_fwd_plan(y, mean, invstd, gamma, beta, out, idx, N, H, W, C, &p));
+  bn_relu_maxpool_fwd_kernel<<<p.grid, 256, 0, (hipStream_t)stream>>>(y, mean, invstd, gamma, beta, out, idx, N, H, W, C, p.OH, p.OW);
   MLA_CHECK_LAUNCH("bn_relu_maxpool_fwd_kernel");
   return MLA_OK;
 }
@@ -627,21 +610,16 @@ extern "C" int mla_bn_relu_maxpool_fwd(const float* y, const float* mean, const 
 extern "C" int mla_bn_bwd_pooled(const float* dpool, const uint8_t* idx, const float* y, const float* mean, const float* invstd,
                                  const float* gamma, const float* beta, float* dy, float* dgamma, float* dbeta, float* ws, int N,
                                  int H, int W, int C, void* stream) {
-  const long Ml = (long)N * H * W;
-  MLA_REQUIRE(Ml > 0 && Ml < (1L << 31), "mla_bn_bwd_pooled: bad dims");
-  const int M = (int)Ml;
-  if (int rc = bn_check("mla_bn_bwd_pooled", M, C)) return rc;
-  MLA_REQUIRE(dpool && idx && y && mean && invstd && gamma && beta && dgamma && dbeta && ws, "mla_bn_bwd_pooled: null pointer");
+  PooledBwdPlan p;
+  MLA_TRY(bn_bwd_pooled_plan(dpool, idx, y, mean, invstd, gamma, beta, dgamma, dbeta, ws, N, H, W, C, &p));
   hipStream_t st = (hipStream_t)stream;
-  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
-  const int MP = N * OH * OW;
-  const int trp = bn_tile_rows(MP), nt = cdiv(MP, trp);     // reduction: tiles of pooled pixels (<= the tiles of M the workspace holds)
-  bn_bwd_pooled_reduce_kernel<<<nt, 256, 0, st>>>(dpool, idx, y, mean, invstd, gamma, beta, ws, N, H, W, C, OH, OW, trp);
+  // reduction: p.tiles tiles of pooled pixels, one partial row each -- never more than the bn_ws_tiles(M) rows that ws holds
+  // (bn_pooled_tiles enlarges the tile where the tile rule of MP alone would give more)
+  bn_bwd_pooled_reduce_kernel<<<p.tiles, 256, 0, st>>>(dpool, idx, y, mean, invstd, gamma, beta, ws, N, H, W, C, p.OH, p.OW, p.tile_rows);
   MLA_CHECK_LAUNCH("bn_bwd_pooled_reduce_kernel");
-  if (int rc = bn_bwd_finalize(ws, nt, M, C, dgamma, dbeta, st)) return rc;
+  if (int rc = bn_bwd_finalize(ws, p.tiles, p.M, C, dgamma, dbeta, st)) return rc;
   if (!dy) return MLA_OK;            // reduction half only: the consumer of dy forms it itself (mla_conv2d_stem_wgrad_split_bnpool)
-  const size_t nq = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);     // one thread per 2x2 pixel quad and 4 channels
-  bn_bwd_pooled_apply_kernel<<<ew_grid(nq), 256, 0, st>>>(dpool, idx, y, mean, invstd, gamma, beta, dgamma, dbeta, dy, N, H, W, C, OH, OW);
+  bn_bwd_pooled_apply_kernel<<<p.grid, 256, 0, st>>>(dpool, idx, y, mean, invstd, gamma, beta, dgamma, dbeta, dy, N, H, W, C, p.OH, p.OW);
   MLA_CHECK_LAUNCH("bn_bwd_pooled_apply_kernel");
   return MLA_OK;
 }

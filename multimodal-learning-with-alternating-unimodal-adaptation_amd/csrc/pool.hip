@@ -6,6 +6,7 @@
 //   video -> frames         x.permute(0,2,1,3,4).contiguous().view(B*T,C,H,W) (backbone.py:144-147),
 //                           fused with the NCHW->NHWC change of layout
 #include "common.h"
+#include "pool_args.h"
 
 // idx = kh*3+kw of the FIRST maximum in row-major window order (ATen: `val > maxval || isnan(val)`).
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
@@ -148,59 +149,52 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
   }
 }
 
-static int ew_grid(size_t n) {
-  size_t b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
-}
-
+// The checks, output sizes and grids are the host half, pool_args.h.
 extern "C" int mla_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
-  MLA_REQUIRE(x && y && idx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "mla_maxpool3x3s2_fwd: bad argument");
-  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
-  maxpool_fwd_kernel<<<ew_grid((size_t)N * OH * OW * (C / 4)), 256, 0, (hipStream_t)stream>>>(x, y, idx, N, H, W, C, OH, OW);
+  PoolPlan p;
+  MLA_TRY(maxpool_fwd_plan(x, y, idx, N, H, W, C, &p));
+  maxpool_fwd_kernel<<<p.grid, POOL_THREADS, 0, (hipStream_t)stream>>>(x, y, idx, N, H, W, C, p.OH, p.OW);
   MLA_CHECK_LAUNCH("maxpool_fwd_kernel");
   return MLA_OK;
 }
 
 extern "C" int mla_maxpool3x3s2_bwd(const float* dy, const uint8_t* idx, const float* relu_src, float* dx, int N, int H,
                                     int W, int C, void* stream) {
-  MLA_REQUIRE(dy && idx && dx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "mla_maxpool3x3s2_bwd: bad argument");
-  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
-  maxpool_bwd_kernel<<<ew_grid((size_t)N * H * W * (C / 4)), 256, 0, (hipStream_t)stream>>>(dy, idx, relu_src, dx, N, H, W, C, OH, OW);
+  PoolPlan p;
+  MLA_TRY(maxpool_bwd_plan(dy, idx, dx, N, H, W, C, &p));
+  maxpool_bwd_kernel<<<p.grid, POOL_THREADS, 0, (hipStream_t)stream>>>(dy, idx, relu_src, dx, N, H, W, C, p.OH, p.OW);
   MLA_CHECK_LAUNCH("maxpool_bwd_kernel");
   return MLA_OK;
 }
 
 extern "C" int mla_avgpool_fwd(const float* x, float* y, int NB, int P, int C, void* stream) {
-  MLA_REQUIRE(x && y && NB > 0 && P > 0 && C > 0 && C % 4 == 0, "mla_avgpool_fwd: bad argument");
-  const int c4n = C / 4;
-  int cgpb = 256;
-  while (cgpb > 1 && c4n % cgpb != 0) cgpb >>= 1;     // largest power of two <= 256 dividing C/4 (C=768 -> 64)
-  MLA_REQUIRE(cgpb >= 4, "mla_avgpool_fwd: C=%d unsupported", C);
-  dim3 grid(NB, c4n / cgpb);
-  avgpool_fwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(x, y, P, C, cgpb);
+  AvgPlan p;
+  MLA_TRY(avgpool_fwd_plan(x, y, NB, P, C, &p));
+  avgpool_fwd_kernel<<<dim3(p.grid_x, p.grid_y), POOL_THREADS, 0, (hipStream_t)stream>>>(x, y, P, C, p.cgpb);
   MLA_CHECK_LAUNCH("avgpool_fwd_kernel");
   return MLA_OK;
 }
 
 extern "C" int mla_avgpool_bwd(const float* dy, const float* relu_src, float* dx, int NB, int P, int C, void* stream) {
-  MLA_REQUIRE(dy && dx && NB > 0 && P > 0 && C > 0 && C % 4 == 0, "mla_avgpool_bwd: bad argument");
-  const size_t n4 = (size_t)NB * P * (C / 4);
-  avgpool_bwd_kernel<<<ew_grid(n4), 256, 0, (hipStream_t)stream>>>(dy, relu_src, dx, n4, P, C / 4);
+  PoolPlan p;
+  MLA_TRY(avgpool_bwd_plan(dy, dx, NB, P, C, &p));
+  avgpool_bwd_kernel<<<p.grid, POOL_THREADS, 0, (hipStream_t)stream>>>(dy, relu_src, dx, p.units, P, C / 4);
   MLA_CHECK_LAUNCH("avgpool_bwd_kernel");
   return MLA_OK;
 }
 
 extern "C" int mla_video_to_nhwc(const float* src, float* dst, int B, int C, int T, int H, int W, void* stream) {
-  MLA_REQUIRE(src && dst && B > 0 && C > 0 && C <= 8 && T > 0 && H > 0 && W > 0, "mla_video_to_nhwc: bad argument");
-  video_to_nhwc_kernel<<<ew_grid((size_t)B * T * H * W), 256, 0, (hipStream_t)stream>>>(src, dst, B, C, T, H, W);
+  PoolPlan p;
+  MLA_TRY(video_to_nhwc_plan(src, dst, B, C, T, H, W, &p));
+  video_to_nhwc_kernel<<<p.grid, POOL_THREADS, 0, (hipStream_t)stream>>>(src, dst, B, C, T, H, W);
   MLA_CHECK_LAUNCH("video_to_nhwc_kernel");
   return MLA_OK;
 }
 
 static int transpose_launch(const float* src, float* dst, int batch, int R, int S, hipStream_t st) {
-  MLA_REQUIRE(src && dst && batch > 0 && batch < 65536 && R > 0 && S > 0, "transpose: bad argument");
-  MLA_REQUIRE(cdiv(R, 32) < 65536, "transpose: too many rows");
-  transpose_kernel<<<dim3(cdiv(S, 32), cdiv(R, 32), batch), 256, 0, st>>>(src, dst, R, S);
+  TransposePlan p;
+  MLA_TRY(transpose_plan(src, dst, batch, R, S, &p));
+  transpose_kernel<<<dim3(p.gx, p.gy, p.gz), POOL_THREADS, 0, st>>>(src, dst, R, S);
   MLA_CHECK_LAUNCH("transpose_kernel");
   return MLA_OK;
 }

@@ -96,24 +96,39 @@ def conv_out(n: int, k: int, s: int, p: int) -> int:
     return (n + 2 * p - k) // s + 1
 
 
+def _want(who: str, **named) -> None:
+    """name=(tensor or None, shape): refuse a tensor that is not of its shape before any pointer of it reaches a kernel -- the
+    C entry points take sizes from the input alone and would write a smaller buffer out of bounds."""
+    for name, (t, shape) in named.items():
+        if t is not None and tuple(t.shape) != tuple(shape):
+            raise MLAHipError(f"{who}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+
+
+def _dims(who: str, name: str, t: torch.Tensor, n: int) -> Tuple[int, ...]:
+    if t.dim() != n:
+        raise MLAHipError(f"{who}: {name} has shape {tuple(t.shape)}, expected {n} dimensions")
+    return tuple(t.shape)
+
+
 # ---- layout -------------------------------------------------------------------------------------
 def video_to_nhwc(src: torch.Tensor, dst: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
-    B, C, T, H, W = src.shape
+    B, C, T, H, W = _dims("video_to_nhwc", "src", src, 5)
     if dst is None:
         dst = torch.empty((B * T, H, W, C), device=src.device, dtype=torch.float32)
+    _want("video_to_nhwc", dst=(dst, (B * T, H, W, C)))
     _call("mla_video_to_nhwc", _p(src), _p(dst), B, C, T, H, W, stream or cur_stream())
     return dst
 
 
 def nchw_to_nhwc(src: torch.Tensor, stream: Optional[int] = None) -> torch.Tensor:
-    N, C, H, W = src.shape
+    N, C, H, W = _dims("nchw_to_nhwc", "src", src, 4)
     dst = torch.empty((N, H, W, C), device=src.device, dtype=torch.float32)
     _call("mla_nchw_to_nhwc", _p(src), _p(dst), N, C, H, W, stream or cur_stream())
     return dst
 
 
 def nhwc_to_nchw(src: torch.Tensor, stream: Optional[int] = None) -> torch.Tensor:
-    N, H, W, C = src.shape
+    N, H, W, C = _dims("nhwc_to_nchw", "src", src, 4)
     dst = torch.empty((N, C, H, W), device=src.device, dtype=torch.float32)
     _call("mla_nhwc_to_nchw", _p(src), _p(dst), N, C, H, W, stream or cur_stream())
     return dst
@@ -485,7 +500,10 @@ def bn_bwd(dout, x, mean, invstd, gamma, dx, dgamma, dbeta, ws, M: int, C: int, 
 
 def bn_relu_maxpool_fwd(y, mean, invstd, gamma, beta, out, idx, stream: Optional[int] = None) -> None:
     """maxpool3x3s2(relu(bn(y))) without materialising the ReLU output (stem, backbone.py:150-152)."""
-    N, H, W, C = y.shape
+    N, H, W, C = _dims("bn_relu_maxpool_fwd", "y", y, 4)
+    pooled = (N, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), C)
+    _want("bn_relu_maxpool_fwd", mean=(mean, (C,)), invstd=(invstd, (C,)), gamma=(gamma, (C,)), beta=(beta, (C,)), out=(out, pooled),
+          idx=(idx, pooled))
     t0 = _begin()
     _call("mla_bn_relu_maxpool_fwd", _p(y), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(out), _p(idx, torch.uint8), N, H, W, C,
           stream or cur_stream())
@@ -496,7 +514,13 @@ def bn_relu_maxpool_fwd(y, mean, invstd, gamma, beta, out, idx, stream: Optional
 def bn_bwd_pooled(dpool, idx, y, mean, invstd, gamma, beta, dy, dgamma, dbeta, ws, stream: Optional[int] = None) -> None:
     """BatchNorm backward fed by the pooled gradient (max-pool scatter + ReLU mask recomputed on the fly).  dy = None: the
     reduction half alone (dgamma, dbeta), for conv2d_stem_wgrad_split_bnpool."""
-    N, H, W, C = y.shape
+    N, H, W, C = _dims("bn_bwd_pooled", "y", y, 4)
+    pooled = (N, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), C)
+    _want("bn_bwd_pooled", dpool=(dpool, pooled), idx=(idx, pooled), mean=(mean, (C,)), invstd=(invstd, (C,)), gamma=(gamma, (C,)),
+          beta=(beta, (C,)), dy=(dy, (N, H, W, C)), dgamma=(dgamma, (C,)), dbeta=(dbeta, (C,)))
+    need = bn_bwd_ws_elems(N * H * W, C) if 0 < N * H * W < 2 ** 31 else 0      # (sizes out of range: the entry point refuses them)
+    if ws is not None and ws.numel() < need:
+        raise MLAHipError(f"bn_bwd_pooled: ws has {ws.numel()} elements, bn_bwd_ws_elems({N * H * W}, {C}) = {need}")
     t0 = _begin()
     _call("mla_bn_bwd_pooled", _p(dpool), _p(idx, torch.uint8), _p(y), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(dy), _p(dgamma), _p(dbeta),
           _p(ws), N, H, W, C, stream or cur_stream())
@@ -518,20 +542,35 @@ def bn_bwd_from_partial(dout, x, mean, invstd, gamma, dx, dgamma, dbeta, partial
 
 # ---- pooling ------------------------------------------------------------------------------------
 def maxpool_fwd(x: torch.Tensor, y: torch.Tensor, idx: torch.Tensor, stream: Optional[int] = None) -> None:
-    N, H, W, C = x.shape
+    N, H, W, C = _dims("maxpool_fwd", "x", x, 4)
+    pooled = (N, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), C)
+    _want("maxpool_fwd", y=(y, pooled), idx=(idx, pooled))
     _call("mla_maxpool3x3s2_fwd", _p(x), _p(y), _p(idx, torch.uint8), N, H, W, C, stream or cur_stream())
 
 
 def maxpool_bwd(dy, idx, dx, x_shape, relu_src=None, stream: Optional[int] = None) -> None:
+    if len(x_shape) != 4:
+        raise MLAHipError(f"maxpool_bwd: x_shape {tuple(x_shape)} must be (N, H, W, C)")
     N, H, W, C = x_shape
+    pooled = (N, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), C)
+    _want("maxpool_bwd", dy=(dy, pooled), idx=(idx, pooled), dx=(dx, x_shape), relu_src=(relu_src, x_shape))
     _call("mla_maxpool3x3s2_bwd", _p(dy), _p(idx, torch.uint8), _p(relu_src), _p(dx), N, H, W, C, stream or cur_stream())
 
 
+def _want_numel(who: str, **named) -> None:
+    """name=(tensor or None, element count): the average pool takes [NB][P][C] activations in whatever shape holds them."""
+    for name, (t, n) in named.items():
+        if t is not None and t.numel() != n:
+            raise MLAHipError(f"{who}: {name} has {t.numel()} elements (shape {tuple(t.shape)}), expected {n}")
+
+
 def avgpool_fwd(x, y, NB: int, P: int, C: int, stream: Optional[int] = None) -> None:
+    _want_numel("avgpool_fwd", x=(x, NB * P * C), y=(y, NB * C))
     _call("mla_avgpool_fwd", _p(x), _p(y), NB, P, C, stream or cur_stream())
 
 
 def avgpool_bwd(dy, dx, NB: int, P: int, C: int, relu_src=None, stream: Optional[int] = None) -> None:
+    _want_numel("avgpool_bwd", dy=(dy, NB * C), dx=(dx, NB * P * C), relu_src=(relu_src, NB * P * C))
     _call("mla_avgpool_bwd", _p(dy), _p(relu_src), _p(dx), NB, P, C, stream or cur_stream())
 
 
