@@ -740,6 +740,48 @@ int mla_eval_fuse(const float* out0, const float* out1, const float* out2, const
 int mla_eval_head(const float* x0, const float* x1, const float* x2, const float* W, const float* b, const int64_t* labels,
                   const uint8_t* present, int* counts, float* logits_out, float* fused_out, float* weights_out, int* pred_out,
                   int M, int B, int D, int C, int mode, float alpha0, float alpha1, float alpha2, void* stream);
+/* ---- evaluation metrics beyond accuracy: score store, average precision, confusion counts ---------------------------
+ * valid() forms prediction = softmax(out), pred_a, pred_v (main.py:653-657) and keeps only their arg-max; the store keeps them.
+ * A store of `cap` rows and H = 1 + M heads (fused first, then each modality; 1 <= H <= 4, C <= 128) is three caller-owned buffers:
+ *   scores  fp32 (H, C, cap), CLASS-major: scores[h][c][n] = softmax(logits_h[n])[c] = e / s of the two-slot softmax every head uses
+ *   pred    int32 (H, cap): arg-max of the LOGITS, first maximum (the evaluators' rule; not the arg-max of the rounded probabilities)
+ *   labels  int32 (cap): the label as given (a value outside int32 is stored as -1)
+ * The row count lives with the caller: no device counter, no synchronisation.
+ *
+ * mla_scores_append writes rows pos .. pos + B - 1 from the H logit matrices (B, C) of one batch and its int64 labels, in one launch.
+ * weights (nullable): H - 1 floats on the device -- what mla_eval_fuse has just written, or the fixed alphas.  Then l0 must be null
+ * and head 0 is formed as sum_m weights[m] l_{1+m}, modalities in order from +0.0: the expression and the order of mla_eval_fuse,
+ * whose fused logits are never materialised, so the stored pred[0] is its fused arg-max.
+ * MLA_ERR_INVALID_ARG, nothing launched, the store untouched: H outside [1, 4]; C <= 0 or C > 128; B <= 0; cap <= 0 or cap > 2^26;
+ * pos < 0 or pos + B > cap; a null pointer among labels, the three buffers and the matrices the call reads; weights together with
+ * l0 or with H == 1; a float / int32 buffer off a 4-byte or labels off an 8-byte boundary.
+ *
+ * mla_average_precision: ap[h][c] (fp64 (H, C)) and npos[c] (int32 (C)) over the first N rows, in two launches and without a sort.
+ * For a class with P positives sklearn's average_precision_score, sum over distinct thresholds of (R_n - R_{n-1}) P_n, equals
+ * (1 / P) sum over positives p of TP(>= s_p) / CNT(>= s_p): the k positives of a tie group each contribute the precision at the
+ * end of their group and together its recall step k / P.  Labels are single-label, so row r owns one term, in its own class c:
+ *   terms     ws[h][r] = ge ? (double)tp / (double)ge : 0.0, ge = #{n < N: scores[h][c][n] >= s}, tp = those of them with
+ *             labels[n] == c, s = scores[h][c][r] (integer counts)
+ *   finalize  lane l of one wave adds the ws[h][n] of its rows n = l, l + 64, ... with labels[n] == c in increasing n from +0.0, the
+ *             64 lane sums are added by the xor butterfly (offsets 32, 16, .., 1), the sum is divided by npos[c]
+ * That order is the definition: a restatement that follows it reproduces ap bit for bit.  ws: mla_metrics_ws_bytes(cap, H) bytes
+ * (fp64 (H, cap)), holds the terms afterwards.
+ * Policies: a NaN score is >= nothing and nothing is >= it, so a NaN-scored positive has ge = 0 and the term 0.0; a label outside
+ * [0, C) makes its row a positive of no class and a negative of every class (term 0.0); a class with npos == 0 gets ap = NaN
+ * (sklearn warns and answers 0.0 there); rows >= N of the store are never read.
+ *
+ * mla_confusion_count: conf[h][true][predicted] += 1 (int32 (H, C, C), accumulated: the caller zeroes it) over the first N rows,
+ * integer atomics, one launch.  A row whose label lies outside [0, C) is skipped for every head, as mla_eval_fuse counts such a
+ * row nowhere, not in its samples-per-class counter either; so is a prediction outside [0, C).
+ * Both refuse (MLA_ERR_INVALID_ARG, nothing launched): H outside [1, 4]; C <= 0 or C > 128; cap <= 0 or cap > 2^26; N <= 0 or
+ * N > cap; a null pointer; a float / int32 buffer off a 4-byte or a double buffer off an 8-byte boundary. */
+int mla_scores_append(const float* l0, const float* l1, const float* l2, const float* l3, const float* weights,
+                      const int64_t* labels, float* scores, int* pred, int* labels_out, int H, int B, int C, int pos, int cap,
+                      void* stream);
+size_t mla_metrics_ws_bytes(int cap, int H);
+int mla_average_precision(const float* scores, const int* labels, int N, int cap, int H, int C, double* ap, int* npos,
+                          double* ws, void* stream);
+int mla_confusion_count(const int* pred, const int* labels, int N, int cap, int H, int C, int* conf, void* stream);
 /* invstd = 1/sqrt(var + eps) (eval-mode BatchNorm on running statistics) */
 int mla_bn_invstd(const float* var, float* invstd, int n, float eps, void* stream);
 

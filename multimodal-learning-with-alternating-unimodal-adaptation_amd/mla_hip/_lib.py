@@ -122,6 +122,10 @@ PROTOTYPES = {
     "mla_head_logits": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "mla_eval_fuse": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _P]),
     "mla_eval_head": (_I, [_P] * 12 + [_I] * 5 + [_F, _F, _F, _P]),
+    "mla_scores_append": (_I, [_P] * 9 + [_I] * 5 + [_P]),
+    "mla_metrics_ws_bytes": (_Z, [_I, _I]),
+    "mla_average_precision": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "mla_confusion_count": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "mla_bn_invstd": (_I, [_P, _P, _I, _F, _P]),
     "mla_linear_fwd": (_I, [_P] * 6 + [_I] * 8 + [_P]),
     "mla_linear_dgrad": (_I, [_P] * 6 + [_I] * 8 + [_P]),

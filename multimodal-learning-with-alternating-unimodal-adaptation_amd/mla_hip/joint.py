@@ -32,6 +32,7 @@ import torch
 from . import ops
 from ._lib import MLAHipError
 from .dist import Comm
+from .metrics import MetricsMixin
 from .module import is_attached_fusion
 from .modulation import OGM
 from .trainer import StreamTrainer
@@ -152,16 +153,20 @@ class JointTrainer(StreamTrainer):
         return self.losses
 
 
-class JointEvaluator:
+class JointEvaluator(MetricsMixin):
     """`valid()` of the joint model (main.py:539-619, 653-679): eval-mode encoders, out = fc_out(cat(...)) and the half /
     third-head logits out_m, arg-max predictions (first maximum, like np.argmax) and per-class counters kept on the device.
     Data parallel: every rank all-gathers out / out_m / labels of all ranks in rank order and counts the global batch, as
     `Evaluator` does.
 
     The counters come from the existing fusion / accuracy kernel (mla_eval_fuse) fed with (out, out_a, out_v) and the fixed
-    weights (1, 0, 0): its fused prediction is then exactly arg-max(out); with three modalities a second call counts out_t."""
+    weights (1, 0, 0): its fused prediction is then exactly arg-max(out); with three modalities a second call counts out_t.
 
-    def __init__(self, model, comm: Optional[Comm] = None):
+    metrics=True, capacity=len(test_set): every update() also appends softmax(out) and softmax(out_m), their arg-max and the labels
+    to a device store (mla_hip.metrics: average_precision(), mean_average_precision(), confusion(), f1()); film / gated fusion
+    stores `out` alone, the reference defines no out_a there.  Not with an active `comm`."""
+
+    def __init__(self, model, comm: Optional[Comm] = None, metrics: bool = False, capacity: Optional[int] = None):
         self.fusion = _attached(_joint_fusion(model), comm)
         self.model = model
         self.comm = comm if comm is not None else Comm()
@@ -172,11 +177,14 @@ class JointEvaluator:
         self.counts = torch.zeros(self.C * 5, device=dev, dtype=torch.int32)       # [num, argmax(out), out, out_a, out_v]
         self.counts_t = torch.zeros(self.C * 4, device=dev, dtype=torch.int32)     # [num, out_t, out_t, out_t]
         self.weights = torch.zeros(3, device=dev, dtype=torch.float32)
+        heads = 1 + self.M if self.fusion is None or self.fusion.per_modality else 1
+        self._metrics_init(metrics, capacity, heads, self.C, dev, self.comm)
         model.eval()                                                                # main.py:519
 
     def reset(self) -> None:
         self.counts.zero_()
         self.counts_t.zero_()
+        self._metrics_reset()
 
     def update(self, *batch):
         """update(spec, image, label) | update(token, padding_mask, image, label) | update(token, pm, image, spec, label).
@@ -188,6 +196,8 @@ class JointEvaluator:
         else:
             out, out_m = self.head.concat_logits(list(feats), slot="eval")
         outs = [out] + [out_m[k] if out_m is not None else out for k in range(self.M)]
+        if self._store is not None:
+            self._metrics_append(outs[:self._store.H], label)
         if self.comm.active:
             outs = [self.comm.allgather_rows(o) for o in outs]
             label = self.comm.allgather_rows(label.contiguous())

@@ -1052,6 +1052,58 @@ def eval_head(feats, W, b, labels, counts, logits_out, *, mode: int, alphas, pre
           stream or cur_stream())
 
 
+def _store_shape(who: str, scores, pred, labels):
+    """(H, C, cap) of a score store (see include/mla_hip.h, mla_scores_append); pred may be None."""
+    if scores.dim() != 3 or (pred is not None and tuple(pred.shape) != (scores.shape[0], scores.shape[2])) \
+            or tuple(labels.shape) != (scores.shape[2],):
+        raise MLAHipError(f"{who}: expected scores (H, C, cap), pred (H, cap) and labels (cap), got {tuple(scores.shape)}, "
+                          f"{None if pred is None else tuple(pred.shape)} and {tuple(labels.shape)}")
+    return tuple(scores.shape)
+
+
+def scores_append(logits, labels, scores, pred, store_labels, pos: int, weights=None, stream: Optional[int] = None):
+    """Rows pos .. pos + B - 1 of a score store from one batch, in one launch: class-major softmax scores (H, C, cap), the arg-max
+    of the logits (H, cap) and the labels (cap).  logits: the H (B, C) matrices, fused first; with `weights` (a device vector of
+    H - 1 floats, what eval_fuse wrote) logits[0] is None and head 0 is formed as eval_fuse forms it."""
+    H, C, cap = _store_shape("scores_append", scores, pred, store_labels)
+    if len(logits) != H or H > 4 or any(t is not None and (t.dim() != 2 or t.shape[1] != C) for t in logits):
+        raise MLAHipError(f"scores_append: expected {H} (B, {C}) logit matrices for a store of {H} heads (at most 4), got "
+                          f"{[None if t is None else tuple(t.shape) for t in logits]}")
+    B = labels.shape[0]
+    if any(t is not None and t.shape[0] != B for t in logits) or (weights is not None and weights.numel() < H - 1):
+        raise MLAHipError(f"scores_append: {B} labels for logits {[None if t is None else tuple(t.shape) for t in logits]}, weights "
+                          f"{None if weights is None else tuple(weights.shape)}")
+    lp = [_p(t) for t in logits] + [None] * (4 - H)
+    _call("mla_scores_append", lp[0], lp[1], lp[2], lp[3], _p(weights), _p(labels, torch.int64), _p(scores), _p(pred, torch.int32),
+          _p(store_labels, torch.int32), H, B, C, int(pos), cap, stream or cur_stream())
+
+
+def metrics_ws_bytes(cap: int, H: int) -> int:
+    return int(_lib.load().mla_metrics_ws_bytes(cap, H))
+
+
+def average_precision(scores, labels, N: int, ap, npos, ws, stream: Optional[int] = None):
+    """ap float64 (H, C) and npos int32 (C) over the first N rows of scores (H, C, cap) / labels int32 (cap); ws: float64 (H, cap),
+    holds the per-row terms afterwards.  See include/mla_hip.h, mla_average_precision."""
+    H, C, cap = _store_shape("average_precision", scores, None, labels)
+    if tuple(ap.shape) != (H, C) or tuple(npos.shape) != (C,) or ws.numel() * 8 < metrics_ws_bytes(cap, H):
+        raise MLAHipError(f"average_precision: ap {tuple(ap.shape)} / npos {tuple(npos.shape)} / ws {tuple(ws.shape)} do not fit "
+                          f"scores {tuple(scores.shape)}")
+    _call("mla_average_precision", _p(scores), _p(labels, torch.int32), int(N), cap, H, C, _p(ap, torch.float64), _p(npos, torch.int32),
+          _p(ws, torch.float64), stream or cur_stream())
+
+
+def confusion_count(pred, labels, N: int, conf, stream: Optional[int] = None):
+    """conf int32 (H, C, C) [true][predicted], accumulated, over the first N rows of pred int32 (H, cap) / labels int32 (cap)."""
+    if pred.dim() != 2 or tuple(labels.shape) != (pred.shape[1],) or conf.dim() != 3 or conf.shape[0] != pred.shape[0] \
+            or conf.shape[1] != conf.shape[2]:
+        raise MLAHipError(f"confusion_count: expected pred (H, cap), labels (cap) and conf (H, C, C), got {tuple(pred.shape)}, "
+                          f"{tuple(labels.shape)} and {tuple(conf.shape)}")
+    H, cap = pred.shape
+    _call("mla_confusion_count", _p(pred, torch.int32), _p(labels, torch.int32), int(N), cap, H, conf.shape[1], _p(conf, torch.int32),
+          stream or cur_stream())
+
+
 def bn_invstd(var, invstd, eps: float = BN_EPS, stream: Optional[int] = None):
     _call("mla_bn_invstd", _p(var), _p(invstd), var.numel(), eps, stream or cur_stream())
 

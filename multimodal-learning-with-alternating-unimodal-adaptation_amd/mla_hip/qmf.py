@@ -24,6 +24,7 @@ import torch
 from . import ops
 from ._lib import MLAHipError
 from .dist import Comm
+from .metrics import MetricsMixin
 from .model import SharedHead
 from .module import is_attached_fusion
 from .trainer import StreamTrainer
@@ -148,11 +149,13 @@ class QMFTrainer(StreamTrainer):
         return self.losses
 
 
-class QMFEvaluator:
+class QMFEvaluator(MetricsMixin):
     """`valid()` under QMF (main.py:576-586, 653-679): eval-mode encoders, out = sum_m conf_m out_m, arg-max counters of `out`
-    and of every out_m, kept on the device by the fusion / accuracy kernel the way JointEvaluator counts."""
+    and of every out_m, kept on the device by the fusion / accuracy kernel the way JointEvaluator counts.
+    metrics=True, capacity=len(test_set): every update() also appends softmax(out) and softmax(out_m), their arg-max and the labels
+    to a device store (mla_hip.metrics: average_precision(), mean_average_precision(), confusion(), f1())."""
 
-    def __init__(self, model):
+    def __init__(self, model, metrics: bool = False, capacity: Optional[int] = None):
         if model.qmf_heads is None:
             raise MLAHipError("QMFEvaluator needs a model with attached QMF heads (attach_qmf_heads / QMFTrainer)")
         self.model, self.heads = model, model.qmf_heads
@@ -162,11 +165,13 @@ class QMFEvaluator:
         self.counts_t = torch.zeros(self.C * 4, device=dev, dtype=torch.int32)     # [num, out_t, out_t, out_t]
         self.weights = torch.zeros(3, device=dev, dtype=torch.float32)
         self._bufs: dict = {}
+        self._metrics_init(metrics, capacity, 1 + self.M, self.C, dev)
         model.eval()                                                                # main.py:519
 
     def reset(self) -> None:
         self.counts.zero_()
         self.counts_t.zero_()
+        self._metrics_reset()
 
     def update(self, *batch):
         """update(spec, image, label) | update(token, padding_mask, image, label) | update(token, pm, image, spec, label).
@@ -180,6 +185,7 @@ class QMFEvaluator:
         z, out, conf = self._bufs[B]
         Ws, bs = _weights(self.heads)
         ops.qmf_head_fwd(list(feats), Ws, bs, z, out, conf)
+        self._metrics_append([out] + [z[m] for m in range(self.M)], label)
         ops.eval_fuse([out, z[0], z[1]], label, self.counts, self.weights, False, [1.0, 0.0, 0.0])
         if self.M == 3:
             ops.eval_fuse([z[2], z[2]], label, self.counts_t, self.weights, False, [1.0, 0.0])

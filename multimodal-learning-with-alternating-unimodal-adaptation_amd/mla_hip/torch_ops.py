@@ -402,6 +402,30 @@ def eval_head(feats, W, b, labels, counts, mode, alphas, present=None):
     return logits, fused, weights, pred
 
 
+@_op("average_precision(Tensor scores, Tensor labels) -> Tensor")
+def average_precision(scores, labels):
+    """Average precision per head and class of one's own scores, class-major fp32 (H, C, N) or (C, N), against integer labels
+    (N): float64 (H, C) resp. (C), NaN where a class has no positive (include/mla_hip.h, mla_average_precision)."""
+    s = (scores if scores.dim() == 3 else scores.unsqueeze(0)).contiguous()
+    H, C, N = s.shape
+    lab = labels.clamp(-1, C).to(torch.int32).contiguous()          # every label outside [0, C) is no class, at any width
+    ap = torch.empty((H, C), device=s.device, dtype=torch.float64)
+    npos = torch.empty(C, device=s.device, dtype=torch.int32)
+    ws = torch.empty((H, N), device=s.device, dtype=torch.float64)
+    ops.average_precision(s, lab, N, ap, npos, ws)
+    return ap if scores.dim() == 3 else ap[0]
+
+
+@_op("confusion_count(Tensor pred, Tensor labels, int C) -> Tensor")
+def confusion_count(pred, labels, C):
+    """Confusion counts of one's own predictions, integer (H, N) or (N), against integer labels (N): int32 (H, C, C) resp. (C, C),
+    [true][predicted]; rows whose label or prediction lies outside [0, C) are skipped."""
+    p = (pred if pred.dim() == 2 else pred.unsqueeze(0)).to(torch.int32).contiguous()
+    conf = torch.zeros((p.shape[0], C, C), device=p.device, dtype=torch.int32)
+    ops.confusion_count(p, labels.clamp(-1, C).to(torch.int32).contiguous(), p.shape[1], conf)
+    return conf if pred.dim() == 2 else conf[0]
+
+
 @_op("gather_rows2(Tensor T0, Tensor T1, Tensor labels, Tensor idx) -> (Tensor, Tensor, Tensor, Tensor)")
 def gather_rows2(T0, T1, labels, idx):
     """(out0 (B, D), out1 (B, D), label (B), idx (B, 1)): rows `idx` of two device-resident feature tables and their labels."""

@@ -25,6 +25,7 @@ from .streams import distinct_streams
 
 from . import ops
 from .dist import Comm
+from .metrics import MetricsMixin
 from .module import is_attached_fusion
 from .optim import FusedAdam, FusedSGD
 from .plugin import GSPlugin
@@ -324,7 +325,7 @@ def present_in_encoder_order(model, present, B: int) -> torch.Tensor:
     return have[:, cols].to(torch.uint8).contiguous()
 
 
-class Evaluator:
+class Evaluator(MetricsMixin):
     """`valid()` of the reference under --gs_flag (main.py:486-679): eval-mode encoders, shared head applied to every
     modality, fixed (av_alpha | a/v/t_alpha) or entropy-gated (--dynamic, main.py:65-106) fusion, per-class accuracy
     counters -- kept on the device (one fusion/arg-max kernel per batch instead of the per-sample .cpu() loop of
@@ -336,7 +337,8 @@ class Evaluator:
     evaluating the concatenated batch."""
 
     def __init__(self, model, dynamic: bool = False, av_alpha: float = 0.5, a_alpha: float = 0.35, v_alpha: float = 0.25,
-                 t_alpha: float = 0.4, comm: Optional[Comm] = None, dynamic_mode: str = "batch", gate_absent: bool = False):
+                 t_alpha: float = 0.4, comm: Optional[Comm] = None, dynamic_mode: str = "batch", gate_absent: bool = False,
+                 metrics: bool = False, capacity: Optional[int] = None):
         """dynamic_mode (with dynamic=True): "batch", the published rule above, or "sample": every sample is gated by the entropy of
         its OWN class distribution (the reference's commented-out softmax(dim=1)), one weight vector per sample.
         gate_absent (models whose update takes present=, i.e. Modal3Classifier): a modality a sample does not have is left out of
@@ -345,7 +347,10 @@ class Evaluator:
         the fusion kernel; independent of the batch a sample arrives in, so under data parallel each rank counts its own rows, no
         all-gather, and result() / per_class() sum the counters over the ranks.  That path sets `sample_weights` (B, M), `pred`
         (B, 1 + M: fused arg-max, then each modality's) and `fused` (B, C) of the last batch, in reused buffers; `weights` stays
-        the batch-level vector of the default path."""
+        the batch-level vector of the default path.
+        metrics=True, capacity=len(test_set): every update() also appends the batch's class scores (softmax of the fused and of each
+        modality's logits), arg-max predictions and labels to a device store, one more launch per batch; average_precision(),
+        mean_average_precision(), confusion() and f1() are formed from it (mla_hip.metrics).  Not with an active `comm`."""
         check_eval_mode(model, dynamic, dynamic_mode, gate_absent)
         self.model = model
         self.comm = comm if comm is not None else Comm()
@@ -359,10 +364,14 @@ class Evaluator:
         self.counts = torch.zeros(self.C * (2 + self.M), device=model.device, dtype=torch.int32)
         self.weights = torch.zeros(3, device=model.device, dtype=torch.float32)
         self._sample: dict = {}
+        self._metrics_init(metrics, capacity, 1 + self.M, self.C, model.device, self.comm)
+        # the batch-level path never materialises the fused logits: the store forms them from the weights the fusion kernel used
+        self._fixed_weights = torch.tensor(self.alphas, device=model.device, dtype=torch.float32) if self._store is not None else None
         model.eval()                                                                                   # main.py:519
 
     def reset(self) -> None:
         self.counts.zero_()
+        self._metrics_reset()
 
     def _sample_bufs(self, B: int) -> dict:
         if B not in self._sample:
@@ -385,7 +394,13 @@ class Evaluator:
                       mode=1 if self.dynamic else 0, alphas=self.alphas, present=have, fused_out=buf["fused"],
                       weights_out=buf["weights"], pred_out=buf["pred"])
         self.sample_weights, self.pred, self.fused = buf["weights"], buf["pred"], buf["fused"]
-        return [buf["logits"][m] for m in range(self.M)]
+        outs = [buf["logits"][m] for m in range(self.M)]
+        if self._store is not None:
+            at = self._store.n
+            self._metrics_append([buf["fused"]] + outs, label)
+            if self.gate_absent:                     # a row the kernel counted nowhere (pred -1) is stored as a row without a class
+                self._store.labels[at:at + B].masked_fill_(buf["pred"][:, 0] < 0, -1)
+        return outs
 
     def update(self, *batch, present=None):
         """update(spec, image, label) | update(token, padding_mask, image, label) | update(token, pm, image, spec, label, present=None).
@@ -402,6 +417,8 @@ class Evaluator:
             ops.eval_fuse(g_outs, g_label, self.counts, self.weights, self.dynamic, self.alphas)
         else:
             ops.eval_fuse(outs, label, self.counts, self.weights, self.dynamic, self.alphas)
+        if self._store is not None:
+            self._metrics_append([None] + outs, label, self.weights if self.dynamic else self._fixed_weights)
         return outs
 
     def _global_counts(self) -> torch.Tensor:
