@@ -392,6 +392,19 @@ int mla_colsum(const float* X, float* r, int B, int D, float scale, void* stream
  * Pl [D][D] and G [C][D] are updated in place.  ws: mla_gs_ws_elems(D, C) floats. */
 size_t mla_gs_ws_elems(int D, int C);
 int mla_gs_project(float* Pl, const float* r, float* G, int D, int C, float alpha, float* ws, void* stream);
+/* gs_mode="owm": the same step with the scalar denominator of the recursive-least-squares / OWM rule the published one was taken
+ * from.  Only utils/utils.py:36-40 change; the skipped first call, alpha, r = mean(X, 0), update before projection, grad <- grad Pl^T
+ * and the exp_count accounting stay the reference's:
+ *     k  = Pl r^T                        (D)
+ *     s  = alpha + r . k                 (scalar; >= alpha when Pl is PSD)
+ *     Pl <- Pl - k k^T / s               (no renormalisation)
+ *     G  <- G Pl^T                       (with the updated Pl)
+ * fp32 in, out and accumulate.  Every sum is taken in mla_gs_project's lane / stride order and there are no atomics: two calls on the
+ * same inputs give the same bits.  The element update is Pl[i][j] - (k_i * k_j) / s, symmetric in (i, j): a Pl that starts symmetric
+ * stays symmetric bit for bit.  Two launches and no copy.  Any D, C > 0 with D <= 8192 (a row of Pl is kept in LDS); ws:
+ * mla_gs_owm_ws_elems(D, C) = D + C * D floats, overlapping none of Pl, r and G. */
+size_t mla_gs_owm_ws_elems(int D, int C);
+int mla_gs_project_owm(float* Pl, const float* r, float* G, int D, int C, float alpha, float* ws, void* stream);
 
 /* ---- head-only modality phase on stored features (models/basic_model.py:278-319 CLIPClassifier; main.py:432-442) ----
  * One call = one phase: out = fc_out(X) (main.py:432), loss = CE(out, labels) (:434), the head gradients of loss.backward() (:435),
@@ -407,6 +420,11 @@ size_t mla_feature_ws_elems(int B, int D, int C);
 int mla_feature_phase(const float* X, const int64_t* labels, float* W, float* b, float* buf, float* Pl, float* logits,
                       float* loss, float* ws, int B, int D, int C, float inv_batch, int project, double alpha, float lr,
                       float momentum, float wd, int first, void* stream);
+/* The same phase with mla_gs_project_owm's rule in place of the literal one, in fp32: same arguments, workspace and limits.  3 kernel
+ * launches when projecting (r and k in the gradient launch, then s, the row update, the projection and SGD in one), 2 otherwise. */
+int mla_feature_phase_owm(const float* X, const int64_t* labels, float* W, float* b, float* buf, float* Pl, float* logits,
+                          float* loss, float* ws, int B, int D, int C, float inv_batch, int project, double alpha, float lr,
+                          float momentum, float wd, int first, void* stream);
 /* The batch feed of such a model (dataset/dataset.py:864-872 CLIPDataset.__getitem__) from device-resident tables: row idx[b] of
  * T0 and T1 (N, D) -> out0 / out1 (B, D), labels[idx[b]] -> out_label (B), idx[b] -> out_idx (B, 1), one launch; 16-byte row
  * accesses when D % 4 == 0 and the tables are 16-byte aligned, scalar otherwise.  The kernel clamps an index to [0, N) and never

@@ -7,7 +7,7 @@
 #define FEATURE_KROWS 8         // rows of Pl one workgroup of the gradient launch forms k for
 
 // Workspace (floats): dlogits (B, C) | rowloss (B) | pad to 16 bytes | fp64 r (D), k (D), rowsq (D) | G (C, D), the raw head gradient
-// of a projecting phase
+// of a projecting phase.  mla_feature_phase_owm keeps fp32 r (D), k (D) at the head of the fp64 region and the rest of it unused.
 struct FeaturePlan {
   size_t dlogits, rowloss, f64, G, total;            // offsets into ws (floats; f64: the 3 D doubles, 16-byte aligned), and its size
   int dchunks;                                       // ceil(D / 256): column blocks of the weight gradient
@@ -21,17 +21,18 @@ static inline size_t feature_ws_elems(int B, int D, int C) {
   return (((size_t)B * C + (size_t)B + 3) & ~(size_t)3) + 6 * (size_t)D + (size_t)C * D;
 }
 
-static inline int feature_phase_plan(const void* X, const void* labels, const void* W, const void* b, const void* buf,
-                                     const void* Pl, const void* logits, const void* loss, const void* ws, int B, int D, int C,
-                                     int project, FeaturePlan* out) {
-  MLA_REQUIRE(X && labels && W && b && buf && logits && loss && ws && (!project || Pl), "mla_feature_phase: null pointer");
-  MLA_TRY(head_check_shape("mla_feature_phase", B, D, C));
-  MLA_REQUIRE(D <= FEATURE_MAXD, "mla_feature_phase: need D <= %d (got %d)", FEATURE_MAXD, D);
+// `who`: the entry point the messages name (mla_feature_phase, or mla_feature_phase_owm: the same arguments, workspace and plan)
+static inline int feature_phase_plan_for(const char* who, const void* X, const void* labels, const void* W, const void* b,
+                                         const void* buf, const void* Pl, const void* logits, const void* loss, const void* ws, int B,
+                                         int D, int C, int project, FeaturePlan* out) {
+  MLA_REQUIRE(X && labels && W && b && buf && logits && loss && ws && (!project || Pl), "%s: null pointer", who);
+  MLA_TRY(head_check_shape(who, B, D, C));
+  MLA_REQUIRE(D <= FEATURE_MAXD, "%s: need D <= %d (got %d)", who, FEATURE_MAXD, D);
   // the flat bases as the allocator hands them out; b = W + C*D and its momentum only need float alignment (C*D is arbitrary)
   MLA_REQUIRE(!(((uintptr_t)X | (uintptr_t)W | (uintptr_t)buf | (uintptr_t)Pl | (uintptr_t)ws | (uintptr_t)logits) & 15),
-              "mla_feature_phase: buffers must be 16-byte aligned");
+              "%s: buffers must be 16-byte aligned", who);
   MLA_REQUIRE(!(((uintptr_t)b | (uintptr_t)loss) & 3) && !((uintptr_t)labels & 7),
-              "mla_feature_phase: bias / loss must be 4-byte and labels 8-byte aligned");
+              "%s: bias / loss must be 4-byte and labels 8-byte aligned", who);
   out->dlogits = 0;
   out->rowloss = (size_t)B * C;
   out->f64 = (out->rowloss + (size_t)B + 3) & ~(size_t)3;
@@ -42,6 +43,12 @@ static inline int feature_phase_plan(const void* X, const void* labels, const vo
   out->k_blocks = project ? (D + FEATURE_KROWS - 1) / FEATURE_KROWS : 0;
   out->lds_bytes = (size_t)D * sizeof(float);
   return MLA_OK;
+}
+
+static inline int feature_phase_plan(const void* X, const void* labels, const void* W, const void* b, const void* buf,
+                                     const void* Pl, const void* logits, const void* loss, const void* ws, int B, int D, int C,
+                                     int project, FeaturePlan* out) {
+  return feature_phase_plan_for("mla_feature_phase", X, labels, W, b, buf, Pl, logits, loss, ws, B, D, C, project, out);
 }
 
 // vec: 1 when rows move as 16-byte accesses (D % 4 == 0 and every table / output 16-byte aligned), else the scalar path

@@ -57,6 +57,14 @@ int main() {
       EXPECT(p.lds_bytes == (size_t)D * 4 && 2 * p.lds_bytes <= 32768);
     }
   EXPECT(feature_ws_elems(0, 4, 2) == 0 && feature_ws_elems(2, 4, -1) == 0);
+  // mla_feature_phase_owm: the same checks and plan under its own name
+  const char* owm = "mla_feature_phase_owm";
+  REFUSED(feature_phase_plan_for(owm, X, lab, W, W + 8, m, nullptr, lg, loss, ws, 2, 4, 2, 1, &p), "mla_feature_phase_owm: null pointer");
+  REFUSED(feature_phase_plan_for(owm, X, lab, W, W + 8, m, Pl, lg, loss, ws, 2, 0, 2, 1, &p), "mla_feature_phase_owm: need B, D, C > 0");
+  REFUSED(feature_phase_plan_for(owm, X, lab, W, W + 8, m, Pl, lg, loss, ws, 2, FEATURE_MAXD + 1, 2, 1, &p),
+          "mla_feature_phase_owm: need D <= 4096 (got 4097)");
+  REFUSED(feature_phase_plan_for(owm, X, lab, W, W + 8, m, Pl + 3, lg, loss, ws, 2, 4, 2, 1, &p), "mla_feature_phase_owm: buffers must be");
+  EXPECT(feature_phase_plan_for(owm, X, lab, W, W + 8, m, Pl, lg, loss, ws, 7, 257, 2, 1, &p) == MLA_OK && p.total == feature_ws_elems(7, 257, 2));
 
   // gather: null pointers, sizes, alignment, and the vector / scalar choice
   int64_t *idx = ibuf[1], *ol = ibuf[2], *oi = ibuf[3];

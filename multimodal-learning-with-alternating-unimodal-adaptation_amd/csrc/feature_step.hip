@@ -15,6 +15,8 @@
 // in order, as head_dw_block does): logits and loss are the chain's bit for bit.  The projection is the literal utils/utils.py:34-41
 // in the chain's lane / stride order, but r, k, the denominator, the norm and the projected sums are carried in fp64 and every stored value is rounded once: with features
 // of both signs some denominators come within a few hundred ulp of zero, where an fp32 r or k decides the answer.
+// mla_feature_phase_owm is the same phase with the scalar-denominator rule of gs_owm.hip in fp32: launches 1 and 2 (r and k in fp32),
+// no rowsq launch, and feat_finish_owm_kernel in place of 4 -- 3 launches when it projects.
 // Also here: mla_gather_rows2, the batch feed of such a model from device-resident feature tables (dataset/dataset.py:864-872).
 #include "head_common.h"
 #include "feature_args.h"
@@ -64,6 +66,7 @@ struct FeatGradArgs {
   float *W, *b, *bufW, *bufb;     // updated in place
   float *G, *loss;                // out
   double *r, *k;                  // out (projecting)
+  float *r32, *k32;               // out (projecting, the scalar-denominator rule: fp32)
   int B, D, C, dchunks, grad_blocks, project, first;
   float inv_batch, lr, momentum, wd;
 };
@@ -71,12 +74,36 @@ struct FeatGradArgs {
 // ---- 2. blocks [0, grad_blocks): dW[c][d] = sum_rows dl[row][c] X[row][d] (rows in order, as head_dw_block); the d-chunk-0 block
 // of class c also db[c] and the bias SGD, the one of class 0 the loss.  Blocks past them (projecting): r = mean(X, 0) into LDS in
 // fp64 (every block its own copy, rows in order; block 0 of them publishes it), then k_i = Pl[i] . r for FEATURE_KROWS rows of Pl
-// (one wave per row, lanes striding the columns, fp64 accumulators).
+// (one wave per row, lanes striding the columns, fp64 accumulators).  OWM (mla_feature_phase_owm): the same blocks in fp32, r as
+// colsum_kernel forms it (rows in order, times 1 / B) and k as gs_owm_k_kernel does; everything else is the same text.
+template <bool OWM>
 __global__ __launch_bounds__(256) void feat_grad_kernel(const FeatGradArgs a) {
   extern __shared__ __attribute__((aligned(16))) double r_s[];
   const int B = a.B, D = a.D, C = a.C;
   if ((int)blockIdx.x >= a.grad_blocks) {
     const int kb = blockIdx.x - a.grad_blocks;
+    if constexpr (OWM) {
+      float* r32_s = reinterpret_cast<float*>(r_s);
+      const float inv_b = 1.f / (float)B;
+      for (int d = threadIdx.x; d < D; d += 256) {
+        float s = 0.f;
+        for (int i = 0; i < B; ++i) s += a.X[(size_t)i * D + d];
+        s = s * inv_b;
+        r32_s[d] = s;
+        if (kb == 0) a.r32[d] = s;
+      }
+      __syncthreads();
+      const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+      for (int q = wave; q < FEATURE_KROWS; q += 4) {
+        const int i = kb * FEATURE_KROWS + q;
+        if (i >= D) break;
+        float s = 0.f;
+        for (int j = lane; j < D; j += 64) s += a.Pl[(size_t)i * D + j] * r32_s[j];
+        s = wave_sum(s);
+        if (lane == 0) a.k32[i] = s;
+      }
+      return;
+    }
     for (int d = threadIdx.x; d < D; d += 256) {
       double s = 0.0;
       for (int i = 0; i < B; ++i) s += (double)a.X[(size_t)i * D + d];
@@ -167,13 +194,48 @@ __global__ __launch_bounds__(64 * FEAT_WAVES) void feat_finish_kernel(float* __r
   }
 }
 
+// ---- 3 + 4 of the scalar-denominator rule (mla_feature_phase_owm; gs_owm.hip states the rule): one workgroup per row i of Pl.  Every
+// wave forms s = alpha + r . k in the same lane / stride order (the same bits in every wave and workgroup); the workgroup updates row i
+// as Pl[i][j] - (k_i * k_j) / s (symmetric in (i, j)), stores it and keeps it in LDS; wave w then forms column i of G Pl^T for the
+// classes c = w, w + FEAT_WAVES, ... and its lane 0 applies SGD to W[c][i].  fp32 throughout: s >= alpha is well away from zero.
+__global__ __launch_bounds__(64 * FEAT_WAVES) void feat_finish_owm_kernel(float* __restrict__ Pl, const float* __restrict__ r,
+                                                               const float* __restrict__ k, const float* __restrict__ G,
+                                                               float* __restrict__ W, float* __restrict__ bufW, int D, int C,
+                                                               float alpha, float lr, float momentum, float wd, int first) {
+  extern __shared__ __attribute__((aligned(16))) float row_s[];
+  const int i = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float t = 0.f;
+  for (int j = lane; j < D; j += 64) t += r[j] * k[j];
+  const float s = alpha + wave_sum(t);
+  const float ki = k[i];
+  for (int j = threadIdx.x; j < D; j += 64 * FEAT_WAVES) {
+    const float v = Pl[(size_t)i * D + j] - (ki * k[j]) / s;
+    Pl[(size_t)i * D + j] = v;
+    row_s[j] = v;
+  }
+  __syncthreads();
+  for (int c = wave; c < C; c += FEAT_WAVES) {
+    float g = 0.f;
+    for (int j = lane; j < D; j += 64) g += G[(size_t)c * D + j] * row_s[j];
+    g = wave_sum(g);
+    if (lane == 0) {
+      const size_t e = (size_t)c * D + i;
+      sgd_elem(W + e, bufW + e, g, lr, momentum, wd, first);
+    }
+  }
+}
+
 extern "C" size_t mla_feature_ws_elems(int B, int D, int C) { return feature_ws_elems(B, D, C); }
 
-extern "C" int mla_feature_phase(const float* X, const int64_t* labels, float* W, float* b, float* buf, float* Pl, float* logits,
-                                 float* loss, float* ws, int B, int D, int C, float inv_batch, int project, double alpha, float lr,
-                                 float momentum, float wd, int first, void* stream) {
+// Both entry points: launches 1 and 2, then -- when the projection fires -- the literal rule's rowsq and finish launches in fp64
+// (OWM false: r | k | rowsq, D doubles each, in the workspace's fp64 region) or the scalar rule's one finish launch in fp32 (OWM
+// true: r | k, D floats each, at the head of that region).
+template <bool OWM>
+static int feature_phase_run(const char* who, const float* X, const int64_t* labels, float* W, float* b, float* buf, float* Pl,
+                             float* logits, float* loss, float* ws, int B, int D, int C, float inv_batch, int project, double alpha,
+                             float lr, float momentum, float wd, int first, void* stream) {
   FeaturePlan p;
-  const int rc = feature_phase_plan(X, labels, W, b, buf, Pl, logits, loss, ws, B, D, C, project, &p);
+  const int rc = feature_phase_plan_for(who, X, labels, W, b, buf, Pl, logits, loss, ws, B, D, C, project, &p);
   if (rc != MLA_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   feat_fwd_kernel<<<B, 64 * FEAT_WAVES, 0, st>>>(X, W, b, labels, logits, ws + p.rowloss, ws + p.dlogits, D, C, inv_batch);
@@ -181,19 +243,42 @@ extern "C" int mla_feature_phase(const float* X, const int64_t* labels, float* W
   FeatGradArgs a;
   a.X = X; a.dlogits = ws + p.dlogits; a.rowloss = ws + p.rowloss; a.Pl = Pl;
   a.W = W; a.b = b; a.bufW = buf; a.bufb = buf + (size_t)C * D;
-  double* w64 = reinterpret_cast<double*>(ws + p.f64);   // r | k | rowsq, D doubles each
-  a.G = ws + p.G; a.r = w64; a.k = w64 + D; a.loss = loss;
+  double* w64 = reinterpret_cast<double*>(ws + p.f64);
+  float* w32 = ws + p.f64;
+  a.G = ws + p.G; a.loss = loss;
+  a.r = OWM ? nullptr : w64; a.k = OWM ? nullptr : w64 + D;
+  a.r32 = OWM ? w32 : nullptr; a.k32 = OWM ? w32 + D : nullptr;
   a.B = B; a.D = D; a.C = C; a.dchunks = p.dchunks; a.grad_blocks = p.grad_blocks; a.project = project ? 1 : 0; a.first = first ? 1 : 0;
   a.inv_batch = inv_batch; a.lr = lr; a.momentum = momentum; a.wd = wd;
-  feat_grad_kernel<<<p.grad_blocks + p.k_blocks, 256, project ? 2 * p.lds_bytes : 0, st>>>(a);
+  feat_grad_kernel<OWM><<<p.grad_blocks + p.k_blocks, 256, project ? (OWM ? 1 : 2) * p.lds_bytes : 0, st>>>(a);
   MLA_CHECK_LAUNCH("feat_grad_kernel");
   if (!project) return MLA_OK;
-  feat_rowsq_kernel<<<cdiv(D, 4), 256, 0, st>>>(Pl, w64, w64 + D, w64 + 2 * (size_t)D, D, alpha);
-  MLA_CHECK_LAUNCH("feat_rowsq_kernel");
-  feat_finish_kernel<<<D, 64 * FEAT_WAVES, p.lds_bytes, st>>>(Pl, w64, w64 + D, w64 + 2 * (size_t)D, ws + p.G, W, buf, D, C, alpha, lr, momentum,
-                                                              wd, first ? 1 : 0);
-  MLA_CHECK_LAUNCH("feat_finish_kernel");
+  if constexpr (OWM) {
+    feat_finish_owm_kernel<<<D, 64 * FEAT_WAVES, p.lds_bytes, st>>>(Pl, w32, w32 + D, ws + p.G, W, buf, D, C, (float)alpha, lr, momentum, wd,
+                                                                    first ? 1 : 0);
+    MLA_CHECK_LAUNCH("feat_finish_owm_kernel");
+  } else {
+    feat_rowsq_kernel<<<cdiv(D, 4), 256, 0, st>>>(Pl, w64, w64 + D, w64 + 2 * (size_t)D, D, alpha);
+    MLA_CHECK_LAUNCH("feat_rowsq_kernel");
+    feat_finish_kernel<<<D, 64 * FEAT_WAVES, p.lds_bytes, st>>>(Pl, w64, w64 + D, w64 + 2 * (size_t)D, ws + p.G, W, buf, D, C, alpha, lr, momentum,
+                                                                wd, first ? 1 : 0);
+    MLA_CHECK_LAUNCH("feat_finish_kernel");
+  }
   return MLA_OK;
+}
+
+extern "C" int mla_feature_phase(const float* X, const int64_t* labels, float* W, float* b, float* buf, float* Pl, float* logits,
+                                 float* loss, float* ws, int B, int D, int C, float inv_batch, int project, double alpha, float lr,
+                                 float momentum, float wd, int first, void* stream) {
+  return feature_phase_run<false>("mla_feature_phase", X, labels, W, b, buf, Pl, logits, loss, ws, B, D, C, inv_batch, project, alpha, lr,
+                                  momentum, wd, first, stream);
+}
+
+extern "C" int mla_feature_phase_owm(const float* X, const int64_t* labels, float* W, float* b, float* buf, float* Pl, float* logits,
+                                     float* loss, float* ws, int B, int D, int C, float inv_batch, int project, double alpha, float lr,
+                                     float momentum, float wd, int first, void* stream) {
+  return feature_phase_run<true>("mla_feature_phase_owm", X, labels, W, b, buf, Pl, logits, loss, ws, B, D, C, inv_batch, project, alpha,
+                                 lr, momentum, wd, first, stream);
 }
 
 // ---- batch feed from device-resident tables: one workgroup per batch row ---------------------------------------------------------

@@ -113,6 +113,9 @@ PROTOTYPES = {
     "mla_colsum": (_I, [_P, _P, _I, _I, _F, _P]),
     "mla_gs_ws_elems": (_Z, [_I, _I]),
     "mla_gs_project": (_I, [_P, _P, _P, _I, _I, _F, _P, _P]),
+    "mla_gs_owm_ws_elems": (_Z, [_I, _I]),
+    "mla_gs_project_owm": (_I, [_P, _P, _P, _I, _I, _F, _P, _P]),
+    "mla_feature_phase_owm": (_I, [_P] * 9 + [_I, _I, _I, _F, _I, ctypes.c_double, _F, _F, _F, _I, _P]),
     "mla_feature_ws_elems": (_Z, [_I, _I, _I]),
     "mla_feature_phase": (_I, [_P] * 9 + [_I, _I, _I, _F, _I, ctypes.c_double, _F, _F, _F, _I, _P]),
     "mla_gather_index_check": (_I, [_P, _I, _I]),

@@ -3,7 +3,7 @@
 There is no encoder: `forward(token, visual)` squeezes two (B, 1, D) feature tensors (dataset/dataset.py:864-872 stores one
 (1, 512) array per sample and modality) and hands them to `fusion_module`.  The only parameters are
 `fusion_module.fc_out.weight` / `.bias`.  Under --gs_flag the training step (main.py:428-454) is two head phases and nothing
-else -- `MLATrainer` runs each as one `mla_feature_phase` call (csrc/feature_step.hip); with gs_flag false the model goes
+else -- `MLATrainer` runs each as one `mla_feature_phase` call (csrc/feature_step.hip; `mla_feature_phase_owm` under gs_mode="owm"); with gs_flag false the model goes
 through `JointTrainer` / `JointEvaluator` on the concatenated-head kernels like the other classifiers.
 """
 from __future__ import annotations

@@ -812,6 +812,20 @@ def gs_project(Pl, r, G, alpha: float, ws, stream: Optional[int] = None) -> None
     _call("mla_gs_project", _p(Pl), _p(r), _p(G), D, C, alpha, _p(ws), stream or cur_stream())
 
 
+def gs_owm_ws_elems(D: int, C: int) -> int:
+    return int(_lib.load().mla_gs_owm_ws_elems(D, C))
+
+
+def gs_project_owm(Pl, r, G, alpha: float, ws, stream: Optional[int] = None) -> None:
+    """gs_mode="owm": k = Pl r, s = alpha + r . k, Pl <- Pl - k k^T / s, G <- G Pl^T, in place (include/mla_hip.h, mla_gs_project_owm)."""
+    D = Pl.shape[0]
+    C = G.shape[0]
+    if tuple(Pl.shape) != (D, D) or r.numel() != D or G.dim() != 2 or G.shape[1] != D or ws.numel() < gs_owm_ws_elems(D, C):
+        raise MLAHipError(f"gs_project_owm: Pl {tuple(Pl.shape)} / r {tuple(r.shape)} / G {tuple(G.shape)} / workspace {ws.numel()} "
+                          f"do not match D={D}, C={C}")
+    _call("mla_gs_project_owm", _p(Pl), _p(r), _p(G), D, C, alpha, _p(ws), stream or cur_stream())
+
+
 def sgd_step(p, g, buf, lr: float, momentum: float, wd: float, first: bool, stream: Optional[int] = None) -> None:
     _call("mla_sgd_step", _p(p), _p(g), _p(buf), p.numel(), lr, momentum, wd, int(first), stream or cur_stream())
 
@@ -821,9 +835,10 @@ def feature_ws_elems(B: int, D: int, C: int) -> int:
 
 
 def feature_phase(X, labels, W, b, buf, Pl, logits, loss, ws, inv_batch: float, project: bool, alpha: float, lr: float,
-                  momentum: float, wd: float, first: bool, stream: Optional[int] = None) -> None:
+                  momentum: float, wd: float, first: bool, stream: Optional[int] = None, owm: bool = False) -> None:
     """One head-only modality phase (main.py:432-442) on stored features, in place: logits / loss out; W (C, D), b (C), the
-    momentum buffer `buf` over [W | b] and, when `project`, Pl (D, D) updated (see include/mla_hip.h, mla_feature_phase)."""
+    momentum buffer `buf` over [W | b] and, when `project`, Pl (D, D) updated (see include/mla_hip.h, mla_feature_phase).
+    owm: the projection is the scalar-denominator rule of gs_project_owm (mla_feature_phase_owm)."""
     if X.dim() != 2 or W.dim() != 2 or W.shape[1] != X.shape[1]:
         raise MLAHipError(f"feature_phase: X {tuple(X.shape)} {X.dtype} does not match the head weight {tuple(W.shape)}")
     B, D = X.shape
@@ -833,7 +848,7 @@ def feature_phase(X, labels, W, b, buf, Pl, logits, loss, ws, inv_batch: float, 
         raise MLAHipError(f"feature_phase: labels {tuple(labels.shape)} / bias {tuple(b.shape)} / momentum {tuple(buf.shape)} / logits "
                           f"{tuple(logits.shape)} / Pl {None if Pl is None else tuple(Pl.shape)} / workspace {ws.numel()} do not match "
                           f"B={B}, D={D}, C={C}")
-    _call("mla_feature_phase", _p(X), _p(labels, torch.int64), _p(W), _p(b), _p(buf), _p(Pl), _p(logits), _p(loss), _p(ws), B, D, C,
+    _call("mla_feature_phase_owm" if owm else "mla_feature_phase", _p(X), _p(labels, torch.int64), _p(W), _p(b), _p(buf), _p(Pl), _p(logits), _p(loss), _p(ws), B, D, C,
           inv_batch, int(bool(project)), alpha, lr, momentum, wd, int(bool(first)), stream or cur_stream())
 
 

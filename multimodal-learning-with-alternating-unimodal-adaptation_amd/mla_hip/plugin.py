@@ -4,11 +4,14 @@ Same surface as the reference: attributes `Pl` (D,D) and `exp_count`, method
 `before_update(model, before_batch_input, batch_index, len_dataloader, train_exp_counter)` which
 mutates the head's weight gradient and `Pl` in place.
 
-Two parity modes:
+Two parity modes and the rule as the method describes it (Q2):
   * "as_published": the reference compares parameter names with "module.weight" while it is
     handed the bare nn.Linear (names "weight"/"bias"), so the body never runs -> no-op;
   * "as_intended" (default): executes utils/utils.py:34-41 literally -- element-wise DxD
     denominator `alpha + k r`, Frobenius renormalisation (Q2) -- on the HIP kernels.
+  * "owm": the rule the published one was taken from -- the scalar denominator `alpha + r k` of recursive least squares / OWM
+    and no renormalisation (k = Pl r, s = alpha + r . k, Pl <- Pl - k k^T / s); everything around utils/utils.py:36-40 stays the
+    reference's.  Pl stays symmetric with eigenvalues in (0, 1], and s >= alpha never comes near zero.
 D is taken from the head (512 ResNet, 768 M3AE/CAV-MAE) instead of the hard-wired eye(512) (Q3);
 the update is graph-free (Q4).
 """
@@ -24,10 +27,10 @@ from . import ops
 
 class GSPlugin:
     def __init__(self, gs_flag: bool = True, dim: int = 512, device="cuda", mode: Optional[str] = None):
-        """`GSPlugin()` as at main.py:819.  mode: "as_intended" (default; $MLA_GS_MODE overrides) or "as_published"."""
+        """`GSPlugin()` as at main.py:819.  mode: "as_intended" (default; $MLA_GS_MODE overrides), "as_published" or "owm"."""
         mode = mode or os.environ.get("MLA_GS_MODE", "as_intended")
-        if mode not in ("as_intended", "as_published"):
-            raise ValueError("mode must be 'as_intended' or 'as_published'")
+        if mode not in ("as_intended", "as_published", "owm"):
+            raise ValueError("mode must be 'as_intended', 'as_published' or 'owm'")
         self.mode = mode
         self.device = torch.device(device)
         self.Pl = torch.eye(dim, device=self.device, dtype=torch.float32)       # utils/utils.py:20
@@ -71,8 +74,10 @@ class GSPlugin:
         C, D = G.shape
         if D != self.Pl.shape[0]:
             self._resize(D)
-        if self._ws is None or self._ws.numel() < ops.gs_ws_elems(D, C):
-            self._ws = torch.empty(ops.gs_ws_elems(D, C), device=self.device, dtype=torch.float32)
+        owm = self.mode == "owm"
+        ws_elems = ops.gs_owm_ws_elems(D, C) if owm else ops.gs_ws_elems(D, C)
+        if self._ws is None or self._ws.numel() < ws_elems:
+            self._ws = torch.empty(ws_elems, device=self.device, dtype=torch.float32)
         if r_mean is None:
             X = before_batch_input.detach()                                     # graph-free (Q4)
             comm = getattr(model, "comm", None)
@@ -82,7 +87,8 @@ class GSPlugin:
             else:
                 ops.colsum(X.contiguous(), self._r, 1.0 / X.shape[0])           # r = mean(X, 0)      :34
             r_mean = self._r
-        ops.gs_project(self.Pl, r_mean, G, self.alpha(batch_index, len_dataloader), self._ws)   # :35-41
+        project = ops.gs_project_owm if owm else ops.gs_project
+        project(self.Pl, r_mean, G, self.alpha(batch_index, len_dataloader), self._ws)          # :35-41
         self._fired = True
         if write_back is not None:
             write_back.grad.data.copy_(G)                                       # w.grad.data = ...   :41

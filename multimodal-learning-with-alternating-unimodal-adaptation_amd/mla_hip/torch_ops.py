@@ -371,6 +371,16 @@ def gs_project(Pl, X, G, alpha):
     ops.gs_project(Pl, r, G, alpha, _f32(ops.gs_ws_elems(D, C), X))
 
 
+@_op("gs_project_owm(Tensor(a!) Pl, Tensor X, Tensor(b!) G, float alpha) -> ()")
+def gs_project_owm(Pl, X, G, alpha):
+    """GSPlugin(mode="owm").before_update body on the batch features X (B, D): k = Pl r, s = alpha + r . k, Pl <- Pl - k k^T / s,
+    G <- G Pl^T with r = mean(X, 0); Pl and G updated in place."""
+    D, C = Pl.shape[0], G.shape[0]
+    r = _f32(D, X)
+    ops.colsum(X, r, 1.0 / X.shape[0])
+    ops.gs_project_owm(Pl, r, G, alpha, _f32(ops.gs_owm_ws_elems(D, C), X))
+
+
 @_op("sgd_step(Tensor(a!) p, Tensor? g, Tensor(b!) buf, float lr, float momentum, float weight_decay, bool first) -> ()")
 def sgd_step(p, g, buf, lr, momentum, weight_decay, first):
     ops.sgd_step(p, g, buf, lr, momentum, weight_decay, first)

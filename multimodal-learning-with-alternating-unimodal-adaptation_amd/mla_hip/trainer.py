@@ -127,6 +127,8 @@ class MLATrainer(StreamTrainer):
         CLIPClassifier (stored features: train_step(token_feat, image_feat, label, batch_step, len_dataloader)).  The calling
         stream carries head forward/backward, the packed head exchange, GSPlugin and the head's SGD; the next modality only
         needs the updated head, so the last modality's backward overlaps the next step's first forward.
+        gs_mode: GSPlugin's mode -- "as_intended" (the literal utils/utils.py:34-41), "as_published" (never fires) or "owm" (the
+        scalar-denominator rule without renormalisation; the fused feature phase then runs mla_feature_phase_owm).
         optimizer="adam" (main.py:736-747): torch.optim.Adam semantics with `betas`, `eps`, `weight_decay`; `lr` a float, a mapping
         {"audio" | ...: lr, "head": lr}, or per-parameter `param_groups` such as `cav_param_groups(model, lr)`; `momentum` is unused."""
         adam = dict(betas=betas, eps=eps, param_groups=param_groups) if optimizer == "adam" else None
@@ -160,13 +162,14 @@ class MLATrainer(StreamTrainer):
             f32 = dict(device=feat.device, dtype=torch.float32)
             self._fbufs[(B, name)] = (torch.empty((B, C), **f32), torch.empty(1, **f32), torch.empty(ops.feature_ws_elems(B, D, C), **f32))
         logits, loss, ws = self._fbufs[(B, name)]
-        fires = gs.mode == "as_intended" and gs.exp_count != 0                                # utils/utils.py:29-32 (Q1, Q5)
+        fires = gs.mode != "as_published" and gs.exp_count != 0                                # utils/utils.py:29-32 (Q1, Q5)
         if fires and gs.Pl.shape[0] != D:
             gs._resize(D)
         lr, mom, wd = opt._hyper("head")
         n = head.weight.numel()
         ops.feature_phase(feat, label, head.flat[:n].view(C, D), head.flat[n:], opt.buf["head"], gs.Pl if fires else None, logits, loss,
-                          ws, inv_batch, fires, gs.alpha(batch_step, len_dataloader), lr, mom, wd, first=not opt.initialized["head"])
+                          ws, inv_batch, fires, gs.alpha(batch_step, len_dataloader), lr, mom, wd, first=not opt.initialized["head"],
+                          owm=gs.mode == "owm")
         opt.initialized["head"] = True
         gs._fired = gs._fired or fires
         gs.exp_count += 1                                                                     # :442
@@ -198,7 +201,7 @@ class MLATrainer(StreamTrainer):
             with torch.cuda.stream(bstream):
                 enc.backward_from_pooled(compact_feature_grad(enc, dX), enc._pa)
                 works = self.comm.allreduce_flat_async(enc.grad)
-        fires = self.gs_plugin.mode == "as_intended" and self.gs_plugin.exp_count != 0
+        fires = self.gs_plugin.mode != "as_published" and self.gs_plugin.exp_count != 0
         r_mean = None
         if self.comm.active:
             ops.colsum(feat, self._colsum, inv_batch)

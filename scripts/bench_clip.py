@@ -2,8 +2,11 @@
 fused phase (mla_feature_phase: 4 launches per projecting phase) and with MLA_FEATURE_FUSED=0 semantics (the general chain: 7
 launches and a copy), batches served by CLIPFeatureBatcher from a synthetic feature directory.  The two trainers alternate in one
 process: warm-up, then three timed windows each of at least a second of steps, every window ended by a device synchronise; the
-figure is the median window, the spread its min .. max.  Also the phase alone (device events around back-to-back calls).  Not the
-headline bench line; numbers go to DESIGN.md section 15 and the README."""
+figure is the median window, the spread its min .. max.  Also the phase alone (device events around back-to-back calls).
+--gs-mode as_intended,owm adds the same two trainers with the scalar-denominator projector (mla_feature_phase_owm: 3 launches per
+projecting phase) to the alternation, as "fused_owm" and "chain_owm".  Not the headline bench line; numbers go to DESIGN.md
+section 15 and the README."""
+import argparse
 import json
 import os
 import sys
@@ -19,6 +22,9 @@ from mla_hip import CLIPClassifier, CLIPFeatureBatcher, MLATrainer  # noqa: E402
 B, D, C = int(os.environ.get("B", "64")), int(os.environ.get("D", "512")), int(os.environ.get("C", "101"))
 N = int(os.environ.get("N", "2048"))
 WINDOW_S, REPEATS = float(os.environ.get("WINDOW_S", "1.0")), 3
+ap = argparse.ArgumentParser()
+ap.add_argument("--gs-mode", default="as_intended", help="comma-separated GSPlugin modes to time: as_intended, owm")
+GS_MODES = ap.parse_args().gs_mode.split(",")
 assert torch.cuda.is_available(), "bench_clip.py measures on the GPU"
 
 
@@ -47,17 +53,18 @@ with tempfile.TemporaryDirectory() as root:
     names, labels = feature_dir(root)
     bt = CLIPFeatureBatcher(names, labels, B, os.path.join(root, "text"), os.path.join(root, "visual"), shuffle=True, seed=0, drop_last=True)
 trainers = {}
-for name, fused in (("fused", True), ("chain", False)):
-    tr = MLATrainer(CLIPClassifier(Args(), seed=1, feat_dim=D), lr=1e-3)
-    tr.fused_feature_phase = fused
-    trainers[name] = tr
+for mode in GS_MODES:
+    for name, fused in (("fused", True), ("chain", False)):
+        tr = MLATrainer(CLIPClassifier(Args(), seed=1, feat_dim=D), lr=1e-3, gs_mode=mode)
+        tr.fused_feature_phase = fused
+        trainers[name if mode == "as_intended" else f"{name}_{mode}"] = tr
 for tr in trainers.values():                                 # warm-up: code objects, buffers, the projection firing
     epoch(tr, bt, 0)
 torch.cuda.synchronize()
 windows = {k: [] for k in trainers}
 e = 1
 for _rep in range(REPEATS):
-    for name, tr in trainers.items():                        # alternate the two in one process
+    for name, tr in trainers.items():                        # alternate them in one process
         steps, t0 = 0, time.perf_counter()
         while True:
             steps += epoch(tr, bt, e)
@@ -67,7 +74,7 @@ for _rep in range(REPEATS):
             if dt >= WINDOW_S:
                 break
         windows[name].append(dt / steps * 1e6)
-result = {"batch": B, "D": D, "C": C, "window_s": WINDOW_S}
+result = {"batch": B, "D": D, "C": C, "window_s": WINDOW_S, "gs_modes": GS_MODES}
 for name, w in windows.items():
     w = sorted(w)
     result[name] = {"us_per_step": w[1], "min": w[0], "max": w[2]}
