@@ -800,6 +800,25 @@ size_t mla_metrics_ws_bytes(int cap, int H);
 int mla_average_precision(const float* scores, const int* labels, int N, int cap, int H, int C, double* ap, int* npos,
                           double* ws, void* stream);
 int mla_confusion_count(const int* pred, const int* labels, int N, int cap, int H, int C, int* conf, void* stream);
+/* ---- fusion-weight search: the fixed-weight fusion of valid() (main.py:647-651) at every point of a grid, in ONE launch ----------
+ * The per-modality logits l_m (B, C) do not depend on the fusion weights, so G candidate weightings are scored from the logits of
+ * one evaluation pass.  grid: fp32 (G, M) on the device, row g = the weights of candidate g.  Tables, int32, accumulated (the caller
+ * zeroes them): tp (G, C) correct per candidate and class, pp (G, C) predictions per candidate and class, num (C, nullable) samples
+ * per class.  Integer atomics only, nothing synchronised; every prediction is a function of its row and its grid row alone.
+ *   rows     a row whose label lies outside [0, C) or that has no present modality is counted nowhere, for any g.  Every other
+ *            row adds 1 to num[label], once per row and not once per grid point.
+ *   present  (nullable, uint8 (B, M); null = all present), the fixed-alpha rule of mla_eval_head (mode 0) with alpha = grid[g]:
+ *            a row that has every modality uses w_m = grid[g][m] as it is; otherwise s = the eligible grid[g][m] added in order
+ *            from +0.0 and w_m = eligible ? grid[g][m] / s : +0.0.  If !(s > 0) the pair (row, g) adds nothing to tp or pp; the
+ *            row stays in num, so it is an error of candidate g.
+ *   fused  = sum_m w_m l_m[c], modalities in order from +0.0: the expression and the order of mla_eval_fuse and mla_eval_head,
+ *            contracted to fused multiply-adds as theirs is.  prediction = the first maximum (v > best from -inf, arg = 0).
+ *            pp[g][prediction] += 1; tp[g][label] += 1 when they agree.
+ * Nothing is indexed with a float: non-finite weights or logits are outside the contract, the prediction stays inside [0, C).
+ * MLA_ERR_INVALID_ARG, nothing launched: M not 2 or 3; a null required pointer (l2 is required when M == 3; present and num may
+ * be null); B, C, G <= 0; C > 128; G > 4096; a float / int32 buffer off a 4-byte or labels off an 8-byte boundary. */
+int mla_fusion_sweep(const float* l0, const float* l1, const float* l2, const int64_t* labels, const uint8_t* present,
+                     const float* grid, int* tp, int* pp, int* num, int M, int B, int C, int G, void* stream);
 /* invstd = 1/sqrt(var + eps) (eval-mode BatchNorm on running statistics) */
 int mla_bn_invstd(const float* var, float* invstd, int n, float eps, void* stream);
 

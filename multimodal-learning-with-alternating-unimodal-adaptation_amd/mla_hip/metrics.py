@@ -62,23 +62,25 @@ class ScoreStore:
         return conf.cpu().numpy().astype("int64")
 
 
+def f1_from_counts(tp, true, predicted, average: str) -> float:
+    """F1 of one head from its per-class counts (C) each -- correct, true samples, predictions -- with the averaging policy
+    f1_from_confusion documents; fp64 from the integers."""
+    if average not in ("macro", "weighted"):
+        raise ValueError(f"f1: average must be 'macro' or 'weighted', got {average!r}")
+    tp, true, predicted = (np.asarray(v, dtype=np.float64) for v in (tp, true, predicted))
+    den = true + predicted
+    f = np.divide(2 * tp, den, out=np.zeros_like(tp), where=den > 0)
+    if average == "macro":
+        seen = den > 0
+        return float(f[seen].mean()) if seen.any() else 0.0
+    return float((f * true).sum() / true.sum()) if true.sum() > 0 else 0.0
+
+
 def f1_from_confusion(conf: np.ndarray, average: str) -> tuple:
     """Per-head F1 from confusion counts (H, C, C) [true][predicted], sklearn's f1_score(average=...) with zero_division=0: a class
     with no true and no predicted sample has F1 0; "macro" averages the classes that occur as a label or as a prediction, "weighted"
     weights each class by its number of true samples."""
-    if average not in ("macro", "weighted"):
-        raise ValueError(f"f1: average must be 'macro' or 'weighted', got {average!r}")
-    out = []
-    for c in np.asarray(conf, dtype=np.float64):
-        tp, true, predicted = np.diag(c), c.sum(axis=1), c.sum(axis=0)
-        den = true + predicted
-        f = np.divide(2 * tp, den, out=np.zeros_like(tp), where=den > 0)
-        if average == "macro":
-            seen = den > 0
-            out.append(float(f[seen].mean()) if seen.any() else 0.0)
-        else:
-            out.append(float((f * true).sum() / true.sum()) if true.sum() > 0 else 0.0)
-    return tuple(out)
+    return tuple(f1_from_counts(np.diag(c), c.sum(axis=1), c.sum(axis=0), average) for c in np.asarray(conf, dtype=np.float64))
 
 
 class MetricsMixin:

@@ -1119,6 +1119,26 @@ def confusion_count(pred, labels, N: int, conf, stream: Optional[int] = None):
           stream or cur_stream())
 
 
+def fusion_sweep(outs, labels, grid, tp, pp, num=None, present=None, stream: Optional[int] = None):
+    """The fixed-weight fusion of one batch at every point of a grid of fusion weights, in one launch (see include/mla_hip.h,
+    mla_fusion_sweep).  outs: M = 2 or 3 (B, C) logit matrices; grid: device fp32 (G, M); tp, pp int32 (G, C) and num int32 (C) or
+    None, accumulated; present: device uint8 (B, M) or None."""
+    M = len(outs)
+    if M < 1 or outs[0].dim() != 2 or grid.dim() != 2:
+        raise MLAHipError(f"fusion_sweep: expected M (B, C) logit matrices and a (G, M) grid, got {M} and {tuple(grid.shape)}")
+    B, C = outs[0].shape
+    G = grid.shape[0]
+    if any(tuple(t.shape) != (B, C) for t in outs) or grid.shape[1] != M:
+        raise MLAHipError(f"fusion_sweep: logits {[tuple(t.shape) for t in outs]} do not match each other or the grid {tuple(grid.shape)}")
+    want = {"labels": (labels, (B,)), "tp": (tp, (G, C)), "pp": (pp, (G, C)), "num": (num, (C,)), "present": (present, (B, M))}
+    for name, (t, shape) in want.items():
+        if t is not None and tuple(t.shape) != shape:
+            raise MLAHipError(f"fusion_sweep: {name} {tuple(t.shape)} should be {shape}")
+    lp = [_p(t) for t in outs[:3]] + [None] * (3 - min(M, 3))
+    _call("mla_fusion_sweep", lp[0], lp[1], lp[2], _p(labels, torch.int64), _p(present, torch.uint8), _p(grid), _p(tp, torch.int32),
+          _p(pp, torch.int32), _p(num, torch.int32), M, B, C, G, stream or cur_stream())
+
+
 def bn_invstd(var, invstd, eps: float = BN_EPS, stream: Optional[int] = None):
     _call("mla_bn_invstd", _p(var), _p(invstd), var.numel(), eps, stream or cur_stream())
 

@@ -436,6 +436,14 @@ def confusion_count(pred, labels, C):
     return conf if pred.dim() == 2 else conf[0]
 
 
+@_op("fusion_sweep(Tensor logits, Tensor labels, Tensor grid, Tensor(a!) tp, Tensor(b!) pp, Tensor(c!)? num=None, "
+     "Tensor? present=None) -> ()")
+def fusion_sweep(logits, labels, grid, tp, pp, num=None, present=None):
+    """The fixed-weight fusion of the per-modality logits (M, B, C) at every row of grid (G, M), in one launch: int32 tp (G, C), pp
+    (G, C) and num (C) accumulated in place (include/mla_hip.h, mla_fusion_sweep)."""
+    ops.fusion_sweep([logits[m] for m in range(logits.shape[0])], labels, grid, tp, pp, num=num, present=present)
+
+
 @_op("gather_rows2(Tensor T0, Tensor T1, Tensor labels, Tensor idx) -> (Tensor, Tensor, Tensor, Tensor)")
 def gather_rows2(T0, T1, labels, idx):
     """(out0 (B, D), out1 (B, D), label (B), idx (B, 1)): rows `idx` of two device-resident feature tables and their labels."""

@@ -31,6 +31,7 @@ from .optim import FusedAdam, FusedSGD
 from .plugin import GSPlugin
 from ._lib import MLAHipError
 from .rows import check_present, compact_feature_grad
+from .sweep import FusionSweep, SweepResult
 
 
 class StreamTrainer:
@@ -341,7 +342,7 @@ class Evaluator(MetricsMixin):
 
     def __init__(self, model, dynamic: bool = False, av_alpha: float = 0.5, a_alpha: float = 0.35, v_alpha: float = 0.25,
                  t_alpha: float = 0.4, comm: Optional[Comm] = None, dynamic_mode: str = "batch", gate_absent: bool = False,
-                 metrics: bool = False, capacity: Optional[int] = None):
+                 metrics: bool = False, capacity: Optional[int] = None, sweep=None):
         """dynamic_mode (with dynamic=True): "batch", the published rule above, or "sample": every sample is gated by the entropy of
         its OWN class distribution (the reference's commented-out softmax(dim=1)), one weight vector per sample.
         gate_absent (models whose update takes present=, i.e. Modal3Classifier): a modality a sample does not have is left out of
@@ -353,7 +354,12 @@ class Evaluator(MetricsMixin):
         the batch-level vector of the default path.
         metrics=True, capacity=len(test_set): every update() also appends the batch's class scores (softmax of the fused and of each
         modality's logits), arg-max predictions and labels to a device store, one more launch per batch; average_precision(),
-        mean_average_precision(), confusion() and f1() are formed from it (mla_hip.metrics).  Not with an active `comm`."""
+        mean_average_precision(), confusion() and f1() are formed from it (mla_hip.metrics).  Not with an active `comm`.
+        sweep=grid (a host (G, M) tensor of finite, non-negative fusion weights, e.g. fusion_grid(M, steps)): every update() also
+        scores the FIXED-weight fusion of the batch at every grid row, one more launch per batch on the logits the update holds
+        anyway; sweep_result() answers the accuracy / F1 surface (mla_hip.sweep).  Whatever the evaluator's own mode: with
+        dynamic=True it tells whether any fixed weighting beats the gating.  With gate_absent the sweep leaves out what the
+        evaluator's fusion leaves out.  Not with an active `comm`."""
         check_eval_mode(model, dynamic, dynamic_mode, gate_absent)
         self.model = model
         self.comm = comm if comm is not None else Comm()
@@ -370,11 +376,19 @@ class Evaluator(MetricsMixin):
         self._metrics_init(metrics, capacity, 1 + self.M, self.C, model.device, self.comm)
         # the batch-level path never materialises the fused logits: the store forms them from the weights the fusion kernel used
         self._fixed_weights = torch.tensor(self.alphas, device=model.device, dtype=torch.float32) if self._store is not None else None
+        self._sweep = None
+        if sweep is not None:
+            if self.comm.active:
+                raise NotImplementedError("Evaluator: sweep= counts each rank's own rows; summing the tables across ranks is not "
+                                          "implemented -- run the fusion-weight search in one process")
+            self._sweep = FusionSweep(sweep, self.M, self.C, model.device)
         model.eval()                                                                                   # main.py:519
 
     def reset(self) -> None:
         self.counts.zero_()
         self._metrics_reset()
+        if self._sweep is not None:
+            self._sweep.reset()
 
     def _sample_bufs(self, B: int) -> dict:
         if B not in self._sample:
@@ -403,6 +417,8 @@ class Evaluator(MetricsMixin):
             self._metrics_append([buf["fused"]] + outs, label)
             if self.gate_absent:                     # a row the kernel counted nowhere (pred -1) is stored as a row without a class
                 self._store.labels[at:at + B].masked_fill_(buf["pred"][:, 0] < 0, -1)
+        if self._sweep is not None:
+            self._sweep.update(outs, label, have)
         return outs
 
     def update(self, *batch, present=None):
@@ -422,6 +438,8 @@ class Evaluator(MetricsMixin):
             ops.eval_fuse(outs, label, self.counts, self.weights, self.dynamic, self.alphas)
         if self._store is not None:
             self._metrics_append([None] + outs, label, self.weights if self.dynamic else self._fixed_weights)
+        if self._sweep is not None:
+            self._sweep.update(outs, label)
         return outs
 
     def _global_counts(self) -> torch.Tensor:
@@ -443,3 +461,9 @@ class Evaluator(MetricsMixin):
         """The counters as a host int64 array (2 + M, C): samples per class, fused-correct per class, then each modality's
         correct per class (the acc / num lists of main.py:659-676; one host sync)."""
         return self._global_counts().cpu().numpy().astype("int64")
+
+    def sweep_result(self) -> SweepResult:
+        """The tables of sweep=grid as a SweepResult: weights, tp, pp, num, acc, counted, f1(average), best(metric) (one host sync)."""
+        if self._sweep is None:
+            raise MLAHipError("Evaluator: constructed with sweep=None; pass sweep=fusion_grid(M, steps) or a (G, M) tensor of weights")
+        return self._sweep.result()
