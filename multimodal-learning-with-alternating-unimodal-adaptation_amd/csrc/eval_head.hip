@@ -1,30 +1,119 @@
-// mla_eval_head: the evaluation of one batch from features to counters in ONE launch (main.py:636-676 with the gating of
-// main.py:65-106 applied to each sample's own class distribution, the form the reference's commented-out softmax(dim=1) and
-// the method describe; head_gs_sgd.hip's eval_fuse_kernel keeps the published batch-axis form).
-//
+// Evaluation path (main.py:486-679 `valid`, gs_flag branch 622-651), two forms from the same features to the same counter layout:
+//   the published chain   M mla_head_logits launches + one mla_eval_fuse: fixed or entropy-gated fusion (main.py:65-106; SURVEY Q9:
+//                         the "entropy" is taken over softmax(dim=0), i.e. over the BATCH axis, and summed over the whole tensor ->
+//                         one scalar weight per modality per batch), arg-max and the per-class counters of main.py:659-676 -- on
+//                         the device, one workgroup, instead of a per-sample .cpu() loop;
+//   mla_eval_head         one batch from features to counters in ONE launch, with the gating of main.py:65-106 applied to each
+//                         sample's own class distribution, the form the reference's commented-out softmax(dim=1) and the method
+//                         describe.
+// The arg-max, fusion and bad-row rules of both are eval_common.h's.
+#include "eval_args.h"
+
+// ---- the published chain -------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void head_logits_kernel(const float* __restrict__ X, const float* __restrict__ W,
+                                                           const float* __restrict__ bias, float* __restrict__ logits, int B,
+                                                           int D, int C) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= B) return;
+  const float* x = X + (size_t)row * D;
+  for (int c = 0; c < C; ++c) {
+    const float s = head_row_dot(x, W + (size_t)c * D, D, lane);
+    if (lane == 0) logits[(size_t)row * C + c] = s + bias[c];
+  }
+}
+
+extern "C" int mla_head_logits(const float* X, const float* W, const float* b, float* logits, int B, int D, int C, void* stream) {
+  MLA_REQUIRE(X && W && b && logits && B > 0 && D > 0 && C > 0, "mla_head_logits: bad argument");
+  head_logits_kernel<<<cdiv(B, 4), 256, 0, (hipStream_t)stream>>>(X, W, b, logits, B, D, C);
+  MLA_CHECK_LAUNCH("head_logits_kernel");
+  return MLA_OK;
+}
+
+// counts layout (int32, accumulated across calls): [0..C) num per class, then for k = 0 (fused), 1..M (modalities):
+// [C*(1+k) .. C*(2+k)) correct per class.  weights_out[M]: the fusion weights used for this batch.
+__global__ __launch_bounds__(256) void eval_fuse_kernel(const EvalFuseArgs a, const int64_t* __restrict__ labels,
+                                                         int* __restrict__ counts, float* __restrict__ weights_out) {
+  __shared__ float ent[MLA_HEAD_MAXM];
+  __shared__ float wgt[MLA_HEAD_MAXM];
+  __shared__ float colpart[256];
+  const int tid = threadIdx.x;
+  if (a.dynamic) {
+    // entropy_m = - sum_{rows, cols} p log p, p = softmax over ROWS (dim=0) of out_m   (main.py:65-70)
+    for (int m = 0; m < a.M; ++m) {
+      float acc = 0.f;
+      for (int c = tid; c < a.C; c += 256) {           // one column per thread
+        float mx = -INFINITY;
+        for (int r = 0; r < a.B; ++r) mx = fmaxf(mx, a.out[m][(size_t)r * a.C + c]);
+        float s = 0.f;
+        for (int r = 0; r < a.B; ++r) s += expf(a.out[m][(size_t)r * a.C + c] - mx);
+        const float ls = logf(s);
+        for (int r = 0; r < a.B; ++r) {
+          const float lp = a.out[m][(size_t)r * a.C + c] - mx - ls;   // log softmax
+          acc -= expf(lp) * lp;
+        }
+      }
+      colpart[tid] = acc;
+      __syncthreads();
+      if (tid == 0) {
+        float e = 0.f;
+        for (int k = 0; k < 256; ++k) e += colpart[k];
+        ent[m] = e;
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {                                    // main.py:72-106
+      float mx = ent[0];
+      for (int m = 1; m < a.M; ++m) mx = fmaxf(mx, ent[m]);
+      float sum = 0.f;
+      for (int m = 0; m < a.M; ++m) {
+        wgt[m] = expf(mx - ent[m]);
+        sum += wgt[m];
+      }
+      for (int m = 0; m < a.M; ++m) wgt[m] /= sum;
+    }
+  } else if (tid < a.M) {
+    wgt[tid] = a.alpha[tid];                           // main.py:647-651
+  }
+  __syncthreads();
+  if (tid < a.M && weights_out) weights_out[tid] = wgt[tid];
+  __syncthreads();                                     // a bad label's NaN (below, any wave) lands after thread 0's weights_out[0]
+  for (int r = tid; r < a.B; r += 256) {               // one sample per thread
+    const long lab_raw = (long)labels[r];
+    if (eval_bad_label(lab_raw, a.C)) {                // poison the weights instead
+      if (weights_out) weights_out[0] = NAN;
+      continue;
+    }
+    const int lab = (int)lab_raw;
+    const size_t at = (size_t)r * a.C;
+    atomicAdd(&counts[lab], 1);
+    const int arg = eval_scan_first_max(a.C, [&](int c) { return eval_fused_slot(a.M, wgt, [&](int m) { return a.out[m][at + c]; }); });
+    if (arg == lab) atomicAdd(&counts[a.C * 1 + lab], 1);
+    for (int m = 0; m < a.M; ++m)
+      if (eval_scan_first_max(a.C, [&](int c) { return a.out[m][at + c]; }) == lab) atomicAdd(&counts[a.C * (2 + m) + lab], 1);
+  }
+}
+
+extern "C" int mla_eval_fuse(const float* out0, const float* out1, const float* out2, const int64_t* labels, int* counts,
+                             float* weights_out, int M, int B, int C, int dynamic, float alpha0, float alpha1, float alpha2,
+                             void* stream) {
+  EvalFuseArgs a;
+  a.out[0] = out0; a.out[1] = out1; a.out[2] = out2;
+  a.alpha[0] = alpha0; a.alpha[1] = alpha1; a.alpha[2] = alpha2;
+  a.M = M; a.B = B; a.C = C; a.dynamic = dynamic;
+  EvalPlan p;
+  MLA_TRY(eval_fuse_plan(&a, labels, counts, &p));
+  eval_fuse_kernel<<<p.blocks, p.threads, 0, (hipStream_t)stream>>>(a, labels, counts, weights_out);
+  MLA_CHECK_LAUNCH("eval_fuse_kernel");
+  return MLA_OK;
+}
+
+// ---- mla_eval_head ---------------------------------------------------------------------------------------------------------------
 // One wave per (row, modality), EVAL_ROWS rows per workgroup.  A wave forms its modality's logits with head_row_dot + bias --
 // the sum and the order of head_logits_kernel, so logits_out[m] equals mla_head_logits bit for bit -- keeps them in LDS, and
 // takes the row's softmax, entropy and first maximum.  After one barrier the row's first wave gates, fuses, takes the fused
 // arg-max and increments the counters.  Every float written is a function of its row alone: the only atomics are the integer
 // counters, nothing is exchanged between workgroups, and the result does not depend on the batch a row arrives in.
-#include "eval_args.h"
-
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// First slot that holds the row maximum mx (numpy.argmax), a lane holding the slots lane and lane + 64.  A row in which no slot
-// equals mx (non-finite logits, outside the contract) answers 0: always inside [0, C).
-__device__ __forceinline__ int first_max2(float v0, float v1, float mx, int C, int lane) {
-  int i = INT_MAX;
-  if (lane + 64 < C && v1 == mx) i = lane + 64;
-  if (lane < C && v0 == mx) i = lane;
-  i = wave_min_i(i);
-  return i < C ? i : 0;
-}
-
 __global__ __launch_bounds__(64 * MLA_HEAD_MAXM * EVAL_ROWS) void eval_head_kernel(const EvalHeadArgs a) {
   __shared__ float lg[EVAL_ROWS][MLA_HEAD_MAXM][MLA_HEAD_MAXC];      // 3 KB
   __shared__ float ent[EVAL_ROWS][MLA_HEAD_MAXM];
@@ -56,7 +145,7 @@ __global__ __launch_bounds__(64 * MLA_HEAD_MAXM * EVAL_ROWS) void eval_head_kern
       const float t1 = sm.e1 != 0.f ? (sm.e1 / sm.s) * ((sm.l1 - sm.mx) - sm.logs) : 0.f;
       h = 0.f - wave_sum(t0 + t1);
     }
-    const int am = first_max2(sm.l0, sm.l1, sm.mx, C, lane);
+    const int am = eval_first_max2(sm.l0, sm.l1, sm.mx, C, lane);
     if (lane == 0) {
       ent[rl][m] = h;
       arg[rl][m] = am;
@@ -65,7 +154,9 @@ __global__ __launch_bounds__(64 * MLA_HEAD_MAXM * EVAL_ROWS) void eval_head_kern
   __syncthreads();
   if (!live || m != 0) return;
 
-  // the row's first wave; every lane computes the (wave-uniform) weights
+  // The row's first wave; every lane computes the (wave-uniform) weights.
+  // eval_present_mask / eval_fixed_weights / eval_fused_slot written out: called, they cost this kernel 4.7 %.
+  // Only the cross-kernel tests (tests/test_sweep_gpu.py against mla_fusion_sweep) tie the mode-0 copy to eval_fixed_weights.
   const long lab = (long)a.labels[row];
   bool el[MLA_HEAD_MAXM];
   int n_el = 0;
@@ -74,7 +165,7 @@ __global__ __launch_bounds__(64 * MLA_HEAD_MAXM * EVAL_ROWS) void eval_head_kern
     el[k] = k < M && (!a.present || a.present[(size_t)row * M + k] != 0);
     n_el += el[k] ? 1 : 0;
   }
-  bool bad = lab < 0 || lab >= C || n_el == 0;
+  bool bad = eval_bad_label(lab, C) || n_el == 0;
   float w[MLA_HEAD_MAXM] = {0.f, 0.f, 0.f};
   if (a.mode == 1) {                                                  // main.py:72-106 on this row, over the eligible modalities
     float hmax = -INFINITY;
@@ -91,7 +182,7 @@ __global__ __launch_bounds__(64 * MLA_HEAD_MAXM * EVAL_ROWS) void eval_head_kern
     const float s = (float)sum;
 #pragma unroll
     for (int k = 0; k < MLA_HEAD_MAXM; ++k) w[k] = el[k] ? g[k] / s : 0.f;
-  } else if (n_el == M) {                                             // main.py:647-651
+  } else if (n_el == M) {                                             // eval_fixed_weights: main.py:647-651
 #pragma unroll
     for (int k = 0; k < MLA_HEAD_MAXM; ++k) w[k] = k < M ? a.alpha[k] : 0.f;
   } else {
@@ -105,7 +196,7 @@ __global__ __launch_bounds__(64 * MLA_HEAD_MAXM * EVAL_ROWS) void eval_head_kern
   }
   if (bad) w[0] = w[1] = w[2] = NAN;
 
-  float v0 = 0.f, v1 = 0.f;                                           // fused = sum_m w_m l_m, modalities in order
+  float v0 = 0.f, v1 = 0.f;                                           // eval_fused_slot, both slots in one pass over the modalities
 #pragma unroll
   for (int k = 0; k < MLA_HEAD_MAXM; ++k)
     if (k < M) {
@@ -117,7 +208,7 @@ __global__ __launch_bounds__(64 * MLA_HEAD_MAXM * EVAL_ROWS) void eval_head_kern
     if (lane + 64 < C) a.fused_out[(size_t)row * C + lane + 64] = v1;
   }
   const float mx = wave_max(fmaxf(lane < C ? v0 : -INFINITY, lane + 64 < C ? v1 : -INFINITY));
-  const int af = first_max2(v0, v1, mx, C, lane);
+  const int af = eval_first_max2(v0, v1, mx, C, lane);
   if (lane != 0) return;
   if (a.weights_out) {
 #pragma unroll
@@ -131,7 +222,7 @@ __global__ __launch_bounds__(64 * MLA_HEAD_MAXM * EVAL_ROWS) void eval_head_kern
     for (int k = 0; k < MLA_HEAD_MAXM; ++k)
       if (k < M) p[1 + k] = bad ? -1 : arg[rl][k];
   }
-  if (bad) return;                                                    // counted nowhere; the counters are never indexed with it
+  if (bad) return;
   const int l = (int)lab;
   atomicAdd(&a.counts[l], 1);
   if (af == l) atomicAdd(&a.counts[C + l], 1);
@@ -151,8 +242,7 @@ extern "C" int mla_eval_head(const float* x0, const float* x1, const float* x2, 
   a.alpha[0] = alpha0; a.alpha[1] = alpha1; a.alpha[2] = alpha2;
   a.M = M; a.B = B; a.D = D; a.C = C; a.mode = mode;
   EvalPlan p;
-  const int rc = eval_head_plan(&a, &p);
-  if (rc != MLA_OK) return rc;
+  MLA_TRY(eval_head_plan(&a, &p));
   eval_head_kernel<<<p.blocks, p.threads, 0, (hipStream_t)stream>>>(a);
   MLA_CHECK_LAUNCH("eval_head_kernel");
   return MLA_OK;

@@ -1,4 +1,5 @@
-// Stand-alone host check of mla_eval_head's argument validation and launch plan (eval_args.h) with util.cpp's error reporting.
+// Stand-alone host check of mla_eval_head's and mla_eval_fuse's argument validation and launch plans (eval_args.h) with util.cpp's
+// error reporting.
 // No GPU, no HIP: `make host-check` builds it with -fsanitize=address,undefined and runs it.
 #include <initializer_list>
 #include "eval_args.h"
@@ -110,5 +111,32 @@ int main() {
       EXPECT((long)p.blocks * EVAL_ROWS >= B && (long)(p.blocks - 1) * EVAL_ROWS < B);
     }
   EXPECT(sizeof(float) * EVAL_ROWS * MLA_HEAD_MAXM * MLA_HEAD_MAXC <= 6144);
+
+  // mla_eval_fuse: one message for every refusal; out[2] is required with three modalities only; one workgroup of 256 threads
+  EvalFuseArgs fuse;
+  memset(&fuse, 0, sizeof(fuse));
+  fuse.out[0] = buf[0]; fuse.out[1] = buf[1]; fuse.out[2] = buf[2];
+  fuse.M = 3; fuse.B = 2; fuse.C = 2;
+  EXPECT(eval_fuse_plan(&fuse, lab, ibuf[0], &p) == MLA_OK && p.threads == 256 && p.blocks == 1);
+  for (int f = 0; f < 3; ++f) {
+    EvalFuseArgs a = fuse;
+    a.out[f] = nullptr;
+    REFUSED(eval_fuse_plan(&a, lab, ibuf[0], &p), "mla_eval_fuse: bad argument");
+    a.M = 2;
+    EXPECT((eval_fuse_plan(&a, lab, ibuf[0], &p) == MLA_OK) == (f == 2));
+  }
+  REFUSED(eval_fuse_plan(&fuse, nullptr, ibuf[0], &p), "mla_eval_fuse: bad argument");
+  REFUSED(eval_fuse_plan(&fuse, lab, nullptr, &p), "mla_eval_fuse: bad argument");
+  for (int M : {-1, 0, 1, 4}) {
+    EvalFuseArgs a = fuse;
+    a.M = M;
+    REFUSED(eval_fuse_plan(&a, lab, ibuf[0], &p), "mla_eval_fuse: bad argument");
+  }
+  for (int z = 0; z < 2; ++z)
+    for (int v : {0, -1}) {
+      EvalFuseArgs a = fuse;
+      (z == 0 ? a.B : a.C) = v;
+      REFUSED(eval_fuse_plan(&a, lab, ibuf[0], &p), "mla_eval_fuse: bad argument");
+    }
   return host_check_done("eval");
 }

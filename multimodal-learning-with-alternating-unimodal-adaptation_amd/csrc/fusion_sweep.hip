@@ -4,9 +4,9 @@
 //
 // One lane per grid point, its M weights in registers; a workgroup owns SWEEP_LANES grid points (blockIdx.y) and walks row tiles of
 // SWEEP_ROWS rows (blockIdx.x, striding).  A tile's logits, labels and eligibility masks are staged in LDS once; every lane then
-// reads the same address (a broadcast, no bank conflict).  The class scan is the `v > best` loop of eval_fuse_kernel
-// (head_gs_sgd.hip) with its fused sum written as it is written there and in eval_head_kernel (eval_head.hip), so a grid point that
-// equals an evaluator's alphas predicts what that evaluator predicts, bit for bit.  No cross-lane operation, integer atomics only.
+// reads the same address (a broadcast, no bank conflict).  The class scan, the fused sum and the renormalisation over what a row has
+// are eval_common.h's, the ones eval_fuse_kernel and eval_head_kernel (eval_head.hip) call, so a grid point that equals an
+// evaluator's alphas predicts what that evaluator predicts, bit for bit.  No cross-lane operation, integer atomics only.
 #include "sweep_args.h"
 
 __global__ __launch_bounds__(SWEEP_LANES) void fusion_sweep_kernel(const SweepArgs a, const long row_tiles) {
@@ -16,7 +16,6 @@ __global__ __launch_bounds__(SWEEP_LANES) void fusion_sweep_kernel(const SweepAr
   const int tid = threadIdx.x, M = a.M, C = a.C;
   const int g = blockIdx.y * SWEEP_LANES + tid;
   const bool live = g < a.G;                                          // dead lanes stage and keep the barriers company
-  const int full = (1 << M) - 1;
   float al[MLA_HEAD_MAXM] = {0.f, 0.f, 0.f};
 #pragma unroll
   for (int k = 0; k < MLA_HEAD_MAXM; ++k)
@@ -38,11 +37,8 @@ __global__ __launch_bounds__(SWEEP_LANES) void fusion_sweep_kernel(const SweepAr
     if (tid < rows) {
       const size_t row = (size_t)r0 + tid;
       const long lab_raw = (long)a.labels[row];
-      int e = 0;
-#pragma unroll
-      for (int k = 0; k < MLA_HEAD_MAXM; ++k)
-        if (k < M && (!a.present || a.present[row * M + k] != 0)) e |= 1 << k;
-      const bool bad = lab_raw < 0 || lab_raw >= C || e == 0;
+      const int e = eval_present_mask(a.present, row, M);
+      const bool bad = eval_bad_label(lab_raw, C) || e == 0;
       lab[tid] = bad ? -1 : (int)lab_raw;
       elig[tid] = e;
       if (!bad && a.num && blockIdx.y == 0) atomicAdd(&a.num[(int)lab_raw], 1);                // once per row, not per grid point
@@ -52,28 +48,9 @@ __global__ __launch_bounds__(SWEEP_LANES) void fusion_sweep_kernel(const SweepAr
       for (int rl = 0; rl < rows; ++rl) {
         const int l = lab[rl], e = elig[rl];
         if (l < 0) continue;                                          // never index the tables with a bad label
-        float w[MLA_HEAD_MAXM] = {0.f, 0.f, 0.f};
-        if (e == full) {                                              // main.py:647-651
-#pragma unroll
-          for (int k = 0; k < MLA_HEAD_MAXM; ++k) w[k] = k < M ? al[k] : 0.f;
-        } else {                                                      // eval_head_kernel, mode 0: renormalise over what the row has
-          float s = 0.f;
-#pragma unroll
-          for (int k = 0; k < MLA_HEAD_MAXM; ++k)
-            if ((e >> k) & 1) s += al[k];
-          if (!(s > 0.f)) continue;                                   // what is left carries no share: the pair adds nothing
-#pragma unroll
-          for (int k = 0; k < MLA_HEAD_MAXM; ++k) w[k] = ((e >> k) & 1) ? al[k] / s : 0.f;
-        }
-        float best = -INFINITY;
-        int arg = 0;
-        for (int c = 0; c < C; ++c) {                                 // first maximum, like np.argmax
-          float v = 0.f;                                              // fused = sum_m w_m l_m, modalities in order
-#pragma unroll
-          for (int k = 0; k < MLA_HEAD_MAXM; ++k)
-            if (k < M) v += w[k] * lg[rl][k][c];
-          if (v > best) { best = v; arg = c; }
-        }
+        float w[MLA_HEAD_MAXM];
+        if (!eval_fixed_weights(al, e, M, w)) continue;               // what is left carries no share: the pair adds nothing
+        const int arg = eval_scan_first_max(C, [&](int c) { return eval_fused_slot(M, w, [&](int k) { return lg[rl][k][c]; }); });
         atomicAdd(&pp[arg], 1);
         if (arg == l) atomicAdd(&tp[l], 1);
       }

@@ -13,24 +13,9 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-__device__ __forceinline__ int wave_first_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// First slot that holds the row maximum (numpy.argmax; eval_head.hip's first_max2, and what eval_fuse_kernel's `v > best` scan
-// answers): NaN slots never win, a row without a winner answers 0.
-__device__ __forceinline__ int metrics_first_max(float v0, float v1, float mx, int C, int lane) {
-  int i = INT_MAX;
-  if (lane + 64 < C && v1 == mx) i = lane + 64;
-  if (lane < C && v0 == mx) i = lane;
-  i = wave_first_i(i);
-  return i < C ? i : 0;
-}
 
 // One wave per (row, head).  Head 0 of a store whose fused logits were never materialised is formed here from the modality rows and
-// the weight vector mla_eval_fuse wrote, with the expression and the order of eval_fuse_kernel's arg-max loop.
+// the weight vector mla_eval_fuse wrote: eval_fused_slot's sum (eval_common.h), the row eval_fuse_kernel took its arg-max of.
 __global__ __launch_bounds__(64 * METRICS_WAVES) void scores_append_kernel(const ScoresAppendArgs a) {
   __shared__ float fl[METRICS_WAVES][MLA_HEAD_MAXC];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -45,7 +30,7 @@ __global__ __launch_bounds__(64 * METRICS_WAVES) void scores_append_kernel(const
     for (int k = 0; k < 2; ++k) {
       const int c = lane + 64 * k;
       if (c < C) {
-        float v = 0.f;
+        float v = 0.f;             // eval_fused_slot written out: called, the append row came out slower
 #pragma unroll
         for (int m = 0; m < MLA_HEAD_MAXM; ++m)
           if (m < M) v += a.weights[m] * a.logits[1 + m][(size_t)r * C + c];
@@ -57,7 +42,7 @@ __global__ __launch_bounds__(64 * METRICS_WAVES) void scores_append_kernel(const
     row = (h == 0 ? a.logits[0] : h == 1 ? a.logits[1] : h == 2 ? a.logits[2] : a.logits[3]) + (size_t)r * C;
   }
   const Softmax2 sm = head_softmax2(row, C, lane);
-  const int am = metrics_first_max(sm.l0, sm.l1, sm.mx, C, lane);
+  const int am = eval_first_max2(sm.l0, sm.l1, sm.mx, C, lane);
   const size_t at = (size_t)a.pos + r;
   float* col = a.scores + (size_t)h * C * a.cap + at;
   if (lane < C) col[(size_t)lane * a.cap] = sm.e0 / sm.s;

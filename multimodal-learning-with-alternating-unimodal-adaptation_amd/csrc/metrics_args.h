@@ -2,7 +2,7 @@
 // mla_average_precision and mla_confusion_count.  Plain C++ with no HIP in it, so metrics_host_check.cpp builds it with the host
 // sanitizers.
 #pragma once
-#include "head_common.h"
+#include "eval_common.h"
 
 #define METRICS_MAXH 4                  // heads of a store: the fused one, then up to MLA_HEAD_MAXM modalities
 #define METRICS_MAXCAP (1 << 26)        // rows of a store: H * cap waves and every (h, row) index stay far inside an int
@@ -61,6 +61,7 @@ static inline int scores_append_plan(const ScoresAppendArgs* a, MetricsPlan* out
               (long)a->pos + a->B - 1, a->cap);
   MLA_REQUIRE(!a->weights || (a->H >= 2 && !a->logits[0]),
               "%s: with a weight vector head 0 is formed from the H - 1 >= 1 modality matrices: pass no fused matrix (H = %d)", who, a->H);
+  // no eval_check_modalities: the store has H = 1 .. 4 heads, and which logits[] are required depends on `weights`, not on M alone
   uintptr_t words = (uintptr_t)a->weights | (uintptr_t)a->scores | (uintptr_t)a->pred | (uintptr_t)a->labels_out;
   bool have = a->labels && a->scores && a->pred && a->labels_out;
   for (int h = a->weights ? 1 : 0; h < a->H; ++h) {
@@ -68,7 +69,7 @@ static inline int scores_append_plan(const ScoresAppendArgs* a, MetricsPlan* out
     words |= (uintptr_t)a->logits[h];
   }
   MLA_REQUIRE(have, "%s: null pointer", who);
-  MLA_REQUIRE(!(words & 3) && !((uintptr_t)a->labels & 7), "%s: float / int32 buffers must be 4-byte and labels 8-byte aligned", who);
+  MLA_TRY(eval_check_aligned(who, words, a->labels));
   out->threads = 64 * METRICS_WAVES;
   out->blocks = metrics_wave_blocks((long)a->B * a->H);          // one wave per (row, head)
   out->blocks2 = 0;

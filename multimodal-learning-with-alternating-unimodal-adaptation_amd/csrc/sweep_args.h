@@ -1,7 +1,7 @@
 // Host half of mla_fusion_sweep (fusion_sweep.hip): argument checks and the launch plan.  Plain C++ with no HIP in it, so
 // sweep_host_check.cpp builds it with the host sanitizers.
 #pragma once
-#include "head_common.h"
+#include "eval_common.h"
 
 #define SWEEP_MAXG 4096                 // grid points of one call: a three-modality lattice at step 1/80 has 3 321
 #define SWEEP_LANES 256                 // one lane per grid point: a workgroup owns a tile of SWEEP_LANES grid points ...
@@ -28,13 +28,11 @@ struct SweepPlan {
 
 static inline int fusion_sweep_plan(const SweepArgs* a, SweepPlan* out) {
   const char* who = "mla_fusion_sweep";
-  MLA_REQUIRE(a->M == 2 || a->M == 3, "%s: need M = 2 or 3 (got %d)", who, a->M);            // first: M says which l[] are required
-  MLA_REQUIRE(a->l[0] && a->l[1] && (a->M != 3 || a->l[2]) && a->labels && a->grid && a->tp && a->pp, "%s: null pointer", who);
+  MLA_TRY(eval_check_modalities(who, a->M, a->l, a->labels && a->grid && a->tp && a->pp));
   MLA_TRY(head_check_shape(who, a->B, 1, a->C));
   MLA_REQUIRE(a->G > 0 && a->G <= SWEEP_MAXG, "%s: need 0 < G <= %d grid points (got %d)", who, SWEEP_MAXG, a->G);
-  uintptr_t words = (uintptr_t)a->grid | (uintptr_t)a->tp | (uintptr_t)a->pp | (uintptr_t)a->num;
-  for (int m = 0; m < a->M; ++m) words |= (uintptr_t)a->l[m];
-  MLA_REQUIRE(!(words & 3) && !((uintptr_t)a->labels & 7), "%s: float / int32 buffers must be 4-byte and labels 8-byte aligned", who);
+  const uintptr_t words = (uintptr_t)a->grid | (uintptr_t)a->tp | (uintptr_t)a->pp | (uintptr_t)a->num | eval_or_ptrs(a->l, a->M);
+  MLA_TRY(eval_check_aligned(who, words, a->labels));
   out->threads = SWEEP_LANES;
   out->row_tiles = ((long)a->B + SWEEP_ROWS - 1) / SWEEP_ROWS;
   out->blocks_x = (int)(out->row_tiles < SWEEP_MAX_ROW_BLOCKS ? out->row_tiles : SWEEP_MAX_ROW_BLOCKS);

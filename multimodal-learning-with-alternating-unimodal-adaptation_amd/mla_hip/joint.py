@@ -29,35 +29,13 @@ from typing import Optional
 
 import torch
 
-from . import ops
-from ._lib import MLAHipError
 from .dist import Comm
-from .metrics import MetricsMixin
-from .module import is_attached_fusion
+from .evaluators import JointEvaluator  # noqa: F401  (its old home)
+from .module import _attached, _joint_fusion
 from .modulation import OGM
 from .trainer import StreamTrainer
 
 MODULATIONS = ("Normal", "OGM", "OGM_GE")
-
-
-def _joint_fusion(model):
-    fusion = model.fusion_module
-    if not getattr(fusion, "joint", False):
-        raise MLAHipError("the joint step needs a classifier built with gs_flag false (ConcatFusion on cat(a, v[, t]))")
-    return fusion
-
-
-def _attached(fusion, comm: Optional[Comm], modulation: str = "Normal"):
-    """The attached sum / film / gated fusion module (mla_hip.fusion) of a joint model, or None for concat fusion."""
-    if not is_attached_fusion(fusion):
-        return None
-    if comm is not None and comm.world > 1:
-        raise NotImplementedError("data-parallel training / evaluation (comm.world > 1) with an attached sum / film / gated fusion is "
-                                  "not implemented")
-    if modulation != "Normal" and not fusion.per_modality:
-        raise NotImplementedError(f"--modulation {modulation} with --fusion_method {fusion.method}: the reference defines no per-modality "
-                                  "logits out_a / out_v for film / gated fusion (main.py:291-302), so OGM / OGM-GE have no coefficients")
-    return fusion
 
 
 class JointTrainer(StreamTrainer):
@@ -151,68 +129,3 @@ class JointTrainer(StreamTrainer):
         opt.step_group("head")
         opt.drop_grads()
         return self.losses
-
-
-class JointEvaluator(MetricsMixin):
-    """`valid()` of the joint model (main.py:539-619, 653-679): eval-mode encoders, out = fc_out(cat(...)) and the half /
-    third-head logits out_m, arg-max predictions (first maximum, like np.argmax) and per-class counters kept on the device.
-    Data parallel: every rank all-gathers out / out_m / labels of all ranks in rank order and counts the global batch, as
-    `Evaluator` does.
-
-    The counters come from the existing fusion / accuracy kernel (mla_eval_fuse) fed with (out, out_a, out_v) and the fixed
-    weights (1, 0, 0): its fused prediction is then exactly arg-max(out); with three modalities a second call counts out_t.
-
-    metrics=True, capacity=len(test_set): every update() also appends softmax(out) and softmax(out_m), their arg-max and the labels
-    to a device store (mla_hip.metrics: average_precision(), mean_average_precision(), confusion(), f1()); film / gated fusion
-    stores `out` alone, the reference defines no out_a there.  Not with an active `comm`."""
-
-    def __init__(self, model, comm: Optional[Comm] = None, metrics: bool = False, capacity: Optional[int] = None):
-        self.fusion = _attached(_joint_fusion(model), comm)
-        self.model = model
-        self.comm = comm if comm is not None else Comm()
-        self.head = self.fusion if self.fusion is not None else model.fusion_module.fc_out
-        self.M = len(model.mla_encoders())
-        self.C = self.head.out_features
-        dev = model.device
-        self.counts = torch.zeros(self.C * 5, device=dev, dtype=torch.int32)       # [num, argmax(out), out, out_a, out_v]
-        self.counts_t = torch.zeros(self.C * 4, device=dev, dtype=torch.int32)     # [num, out_t, out_t, out_t]
-        self.weights = torch.zeros(3, device=dev, dtype=torch.float32)
-        heads = 1 + self.M if self.fusion is None or self.fusion.per_modality else 1
-        self._metrics_init(metrics, capacity, heads, self.C, dev, self.comm)
-        model.eval()                                                                # main.py:519
-
-    def reset(self) -> None:
-        self.counts.zero_()
-        self.counts_t.zero_()
-        self._metrics_reset()
-
-    def update(self, *batch):
-        """update(spec, image, label) | update(token, padding_mask, image, label) | update(token, pm, image, spec, label).
-        Returns (out, out_m) of the local batch."""
-        *inputs, label = batch
-        feats = self.model.forward_raw(*inputs)
-        if self.fusion is not None:                           # sum: out_m with HALF the bias (main.py:610-614); film / gated: none
-            out, out_m = self.fusion.logits(list(feats), bias_scale=0.5, slot="eval")
-        else:
-            out, out_m = self.head.concat_logits(list(feats), slot="eval")
-        outs = [out] + [out_m[k] if out_m is not None else out for k in range(self.M)]
-        if self._store is not None:
-            self._metrics_append(outs[:self._store.H], label)
-        if self.comm.active:
-            outs = [self.comm.allgather_rows(o) for o in outs]
-            label = self.comm.allgather_rows(label.contiguous())
-        ops.eval_fuse(outs[:3], label, self.counts, self.weights, False, [1.0, 0.0, 0.0])
-        if self.M == 3:
-            ops.eval_fuse([outs[3], outs[3]], label, self.counts_t, self.weights, False, [1.0, 0.0])
-        return out, out_m
-
-    def result(self):
-        """(acc, acc_a, acc_v[, acc_t]) = sum(acc) / sum(num) (main.py:677-679; one host sync)."""
-        c = self.counts.view(5, self.C).sum(dim=1).cpu().tolist()
-        num = max(c[0], 1)
-        if self.fusion is not None and not self.fusion.per_modality:
-            return (c[1] / num,)                              # film / gated: the reference defines no out_a / out_v
-        res = [c[1] / num, c[3] / num, c[4] / num]
-        if self.M == 3:
-            res.append(self.counts_t.view(4, self.C).sum(dim=1)[1].item() / num)
-        return tuple(res)

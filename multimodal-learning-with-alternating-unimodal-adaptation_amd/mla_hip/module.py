@@ -57,6 +57,26 @@ def is_attached_fusion(fusion) -> bool:
     return bool(getattr(fusion, "attached_fusion", False))
 
 
+def _joint_fusion(model):
+    fusion = model.fusion_module
+    if not getattr(fusion, "joint", False):
+        raise MLAHipError("the joint step needs a classifier built with gs_flag false (ConcatFusion on cat(a, v[, t]))")
+    return fusion
+
+
+def _attached(fusion, comm, modulation: str = "Normal"):
+    """The attached sum / film / gated fusion module (mla_hip.fusion) of a joint model, or None for concat fusion."""
+    if not is_attached_fusion(fusion):
+        return None
+    if comm is not None and comm.world > 1:
+        raise NotImplementedError("data-parallel training / evaluation (comm.world > 1) with an attached sum / film / gated fusion is "
+                                  "not implemented")
+    if modulation != "Normal" and not fusion.per_modality:
+        raise NotImplementedError(f"--modulation {modulation} with --fusion_method {fusion.method}: the reference defines no per-modality "
+                                  "logits out_a / out_v for film / gated fusion (main.py:291-302), so OGM / OGM-GE have no coefficients")
+    return fusion
+
+
 def _bare_init(self) -> None:
     nn.Module.__init__(self)
 

@@ -1031,13 +1031,18 @@ def head_logits(X, W, b, logits, stream: Optional[int] = None):
     _call("mla_head_logits", _p(X), _p(W), _p(b), _p(logits), B, D, W.shape[0], stream or cur_stream())
 
 
+def _padded(tensors, n: int, alphas=()):
+    """What a C entry point with n pointer slots and three alpha slots takes: the tensors' pointers, then None up to n (a list longer
+    than n is cut: the entry point refuses its count); the alphas as floats, then 0.0 up to three."""
+    return ([_p(t) for t in tensors] + [None] * n)[:n], ([float(v) for v in alphas] + [0.0] * 3)[:3]
+
+
 def eval_fuse(outs, labels, counts, weights_out, dynamic: bool, alphas, stream: Optional[int] = None):
     M = len(outs)
     B, C = outs[0].shape
-    o = [_p(t) for t in outs] + [None] * (3 - M)
-    al = list(alphas) + [0.0] * (3 - len(alphas))
-    _call("mla_eval_fuse", o[0], o[1], o[2], _p(labels, torch.int64), _p(counts, torch.int32), _p(weights_out), M, B, C, int(dynamic), al[0], al[1],
-          al[2], stream or cur_stream())
+    o, al = _padded(outs, 3, alphas)
+    _call("mla_eval_fuse", *o, _p(labels, torch.int64), _p(counts, torch.int32), _p(weights_out), M, B, C, int(dynamic), *al,
+          stream or cur_stream())
 
 
 def eval_head(feats, W, b, labels, counts, logits_out, *, mode: int, alphas, present=None, fused_out=None, weights_out=None,
@@ -1054,17 +1059,11 @@ def eval_head(feats, W, b, labels, counts, logits_out, *, mode: int, alphas, pre
     if any(tuple(f.shape) != (B, D) for f in feats) or W.shape[1] != D or tuple(b.shape) != (C,):
         raise MLAHipError(f"eval_head: features {[tuple(f.shape) for f in feats]} / bias {tuple(b.shape)} do not match the head weight "
                           f"{tuple(W.shape)}")
-    want = {"labels": (labels, (B,)), "counts": (counts, (C * (2 + M),)), "logits_out": (logits_out, (M, B, C)),
-            "present": (present, (B, M)), "fused_out": (fused_out, (B, C)), "weights_out": (weights_out, (B, M)),
-            "pred_out": (pred_out, (B, 1 + M))}
-    for name, (t, shape) in want.items():
-        if t is not None and tuple(t.shape) != shape:
-            raise MLAHipError(f"eval_head: {name} {tuple(t.shape)} should be {shape}")
-    x = [_p(f) for f in feats[:3]] + [None] * (3 - min(M, 3))
-    al = [float(v) for v in alphas] + [0.0] * 3
-    _call("mla_eval_head", x[0], x[1], x[2], _p(W), _p(b), _p(labels, torch.int64), _p(present, torch.uint8), _p(counts, torch.int32),
-          _p(logits_out), _p(fused_out), _p(weights_out), _p(pred_out, torch.int32), M, B, D, C, int(mode), al[0], al[1], al[2],
-          stream or cur_stream())
+    _want("eval_head", labels=(labels, (B,)), counts=(counts, (C * (2 + M),)), logits_out=(logits_out, (M, B, C)),
+          present=(present, (B, M)), fused_out=(fused_out, (B, C)), weights_out=(weights_out, (B, M)), pred_out=(pred_out, (B, 1 + M)))
+    x, al = _padded(feats, 3, alphas)
+    _call("mla_eval_head", *x, _p(W), _p(b), _p(labels, torch.int64), _p(present, torch.uint8), _p(counts, torch.int32),
+          _p(logits_out), _p(fused_out), _p(weights_out), _p(pred_out, torch.int32), M, B, D, C, int(mode), *al, stream or cur_stream())
 
 
 def _store_shape(who: str, scores, pred, labels):
@@ -1088,8 +1087,7 @@ def scores_append(logits, labels, scores, pred, store_labels, pos: int, weights=
     if any(t is not None and t.shape[0] != B for t in logits) or (weights is not None and weights.numel() < H - 1):
         raise MLAHipError(f"scores_append: {B} labels for logits {[None if t is None else tuple(t.shape) for t in logits]}, weights "
                           f"{None if weights is None else tuple(weights.shape)}")
-    lp = [_p(t) for t in logits] + [None] * (4 - H)
-    _call("mla_scores_append", lp[0], lp[1], lp[2], lp[3], _p(weights), _p(labels, torch.int64), _p(scores), _p(pred, torch.int32),
+    _call("mla_scores_append", *_padded(logits, 4)[0], _p(weights), _p(labels, torch.int64), _p(scores), _p(pred, torch.int32),
           _p(store_labels, torch.int32), H, B, C, int(pos), cap, stream or cur_stream())
 
 
@@ -1130,12 +1128,8 @@ def fusion_sweep(outs, labels, grid, tp, pp, num=None, present=None, stream: Opt
     G = grid.shape[0]
     if any(tuple(t.shape) != (B, C) for t in outs) or grid.shape[1] != M:
         raise MLAHipError(f"fusion_sweep: logits {[tuple(t.shape) for t in outs]} do not match each other or the grid {tuple(grid.shape)}")
-    want = {"labels": (labels, (B,)), "tp": (tp, (G, C)), "pp": (pp, (G, C)), "num": (num, (C,)), "present": (present, (B, M))}
-    for name, (t, shape) in want.items():
-        if t is not None and tuple(t.shape) != shape:
-            raise MLAHipError(f"fusion_sweep: {name} {tuple(t.shape)} should be {shape}")
-    lp = [_p(t) for t in outs[:3]] + [None] * (3 - min(M, 3))
-    _call("mla_fusion_sweep", lp[0], lp[1], lp[2], _p(labels, torch.int64), _p(present, torch.uint8), _p(grid), _p(tp, torch.int32),
+    _want("fusion_sweep", labels=(labels, (B,)), tp=(tp, (G, C)), pp=(pp, (G, C)), num=(num, (C,)), present=(present, (B, M)))
+    _call("mla_fusion_sweep", *_padded(outs, 3)[0], _p(labels, torch.int64), _p(present, torch.uint8), _p(grid), _p(tp, torch.int32),
           _p(pp, torch.int32), _p(num, torch.int32), M, B, C, G, stream or cur_stream())
 
 

@@ -24,7 +24,7 @@ import torch
 from . import ops
 from ._lib import MLAHipError
 from .dist import Comm
-from .metrics import MetricsMixin
+from .evaluators import QMFEvaluator  # noqa: F401  (its old home)
 from .model import SharedHead
 from .module import is_attached_fusion
 from .trainer import StreamTrainer
@@ -147,55 +147,3 @@ class QMFTrainer(StreamTrainer):
             opt.step_group(name)
         opt.drop_grads()
         return self.losses
-
-
-class QMFEvaluator(MetricsMixin):
-    """`valid()` under QMF (main.py:576-586, 653-679): eval-mode encoders, out = sum_m conf_m out_m, arg-max counters of `out`
-    and of every out_m, kept on the device by the fusion / accuracy kernel the way JointEvaluator counts.
-    metrics=True, capacity=len(test_set): every update() also appends softmax(out) and softmax(out_m), their arg-max and the labels
-    to a device store (mla_hip.metrics: average_precision(), mean_average_precision(), confusion(), f1())."""
-
-    def __init__(self, model, metrics: bool = False, capacity: Optional[int] = None):
-        if model.qmf_heads is None:
-            raise MLAHipError("QMFEvaluator needs a model with attached QMF heads (attach_qmf_heads / QMFTrainer)")
-        self.model, self.heads = model, model.qmf_heads
-        self.M, self.C = len(self.heads), self.heads[0].out_features
-        dev = model.device
-        self.counts = torch.zeros(self.C * 5, device=dev, dtype=torch.int32)       # [num, argmax(out), out, out_a, out_v]
-        self.counts_t = torch.zeros(self.C * 4, device=dev, dtype=torch.int32)     # [num, out_t, out_t, out_t]
-        self.weights = torch.zeros(3, device=dev, dtype=torch.float32)
-        self._bufs: dict = {}
-        self._metrics_init(metrics, capacity, 1 + self.M, self.C, dev)
-        model.eval()                                                                # main.py:519
-
-    def reset(self) -> None:
-        self.counts.zero_()
-        self.counts_t.zero_()
-        self._metrics_reset()
-
-    def update(self, *batch):
-        """update(spec, image, label) | update(token, padding_mask, image, label) | update(token, pm, image, spec, label).
-        Returns (out, out_m (M, B, C))."""
-        *inputs, label = batch
-        feats = self.model.forward_raw(*inputs)
-        B = label.shape[0]
-        if B not in self._bufs:
-            f32 = dict(device=self.model.device, dtype=torch.float32)
-            self._bufs[B] = (torch.empty((self.M, B, self.C), **f32), torch.empty((B, self.C), **f32), torch.empty((self.M, B), **f32))
-        z, out, conf = self._bufs[B]
-        Ws, bs = _weights(self.heads)
-        ops.qmf_head_fwd(list(feats), Ws, bs, z, out, conf)
-        self._metrics_append([out] + [z[m] for m in range(self.M)], label)
-        ops.eval_fuse([out, z[0], z[1]], label, self.counts, self.weights, False, [1.0, 0.0, 0.0])
-        if self.M == 3:
-            ops.eval_fuse([z[2], z[2]], label, self.counts_t, self.weights, False, [1.0, 0.0])
-        return out, z
-
-    def result(self):
-        """(acc, acc_a, acc_v[, acc_t]) = sum(acc) / sum(num) (main.py:677-679; one host sync)."""
-        c = self.counts.view(5, self.C).sum(dim=1).cpu().tolist()
-        num = max(c[0], 1)
-        res = [c[1] / num, c[3] / num, c[4] / num]
-        if self.M == 3:
-            res.append(self.counts_t.view(4, self.C).sum(dim=1)[1].item() / num)
-        return tuple(res)

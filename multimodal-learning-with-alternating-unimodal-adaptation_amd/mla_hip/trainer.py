@@ -15,7 +15,6 @@ audio step), Q8 (av_alpha fixed at 0.55 in the reported loss).
 from __future__ import annotations
 
 import contextlib
-import inspect
 import os
 from typing import Optional
 
@@ -25,13 +24,11 @@ from .streams import distinct_streams
 
 from . import ops
 from .dist import Comm
-from .metrics import MetricsMixin
+from .evaluators import PRESENT_COLUMNS, Evaluator, check_eval_mode, present_in_encoder_order, takes_present  # noqa: F401  (their old home)
 from .module import is_attached_fusion
 from .optim import FusedAdam, FusedSGD
 from .plugin import GSPlugin
-from ._lib import MLAHipError
-from .rows import check_present, compact_feature_grad
-from .sweep import FusionSweep, SweepResult
+from .rows import compact_feature_grad
 
 
 class StreamTrainer:
@@ -297,173 +294,3 @@ class MLATrainer(StreamTrainer):
         torch.add(self.losses["loss_" + t0] * self.av_alpha, self.losses["loss_" + t1], alpha=1 - self.av_alpha,
                   out=self.losses["loss"])                                                    # main.py:472 (Q8)
         return self.losses
-
-
-PRESENT_COLUMNS = ("a", "v", "t")       # the columns of a `present` matrix: (audio, image, text), Modal3Batcher.present / Modal3Classifier._calls
-
-
-def takes_present(model) -> bool:
-    """Whether the model's forward takes present= (Modal3Classifier): asked of `_calls`, which forward_raw hands its options to."""
-    fn = getattr(model, "_calls", None) or model.forward_raw
-    return "present" in inspect.signature(fn).parameters
-
-
-def check_eval_mode(model, dynamic: bool, dynamic_mode: str, gate_absent: bool) -> None:
-    """Evaluator's argument rules, before anything is allocated."""
-    if dynamic_mode not in ("batch", "sample"):
-        raise ValueError(f"Evaluator: dynamic_mode must be 'batch' (the published batch-level gating) or 'sample' (per-sample "
-                         f"gating), got {dynamic_mode!r}")
-    if gate_absent and not takes_present(model):
-        raise MLAHipError(f"Evaluator: gate_absent needs a model whose forward takes present= (Modal3Classifier); "
-                          f"{type(model).__name__} has no missing-modality masks")
-    if gate_absent and dynamic and dynamic_mode != "sample":
-        raise ValueError("Evaluator: gate_absent leaves a modality out of single samples' fusion; with dynamic=True that needs "
-                         "dynamic_mode='sample' (the batch-level gating has one weight per modality for the whole batch)")
-
-
-def present_in_encoder_order(model, present, B: int) -> torch.Tensor:
-    """The user's host (B, 3) `present` matrix, columns PRESENT_COLUMNS, as uint8 (B, M) with one column per mla_encoders() entry
-    in that order -- the pairing Modal3Classifier._calls makes between the columns and its encoders."""
-    have = check_present(present, B, len(PRESENT_COLUMNS))
-    cols = [PRESENT_COLUMNS.index(tag) for tag, _g, _e in model.mla_encoders()]
-    return have[:, cols].to(torch.uint8).contiguous()
-
-
-class Evaluator(MetricsMixin):
-    """`valid()` of the reference under --gs_flag (main.py:486-679): eval-mode encoders, shared head applied to every
-    modality, fixed (av_alpha | a/v/t_alpha) or entropy-gated (--dynamic, main.py:65-106) fusion, per-class accuracy
-    counters -- kept on the device (one fusion/arg-max kernel per batch instead of the per-sample .cpu() loop of
-    main.py:659-676).  Data parallel: the dynamic weights are ONE scalar per modality computed over the whole
-    batch (softmax over dim 0), so they depend on the batch composition; the reference evaluates the global batch on GPU 0
-    (DataParallel gathers the features, main.py:624-639).  With an active `comm` every rank all-gathers the (B_local, C)
-    logits and labels of all ranks (rank order = the order DataParallel scatters / gathers in) on the head communicator
-    and runs the fusion kernel on the global batch: every rank holds the same counters and weights as a single process
-    evaluating the concatenated batch."""
-
-    def __init__(self, model, dynamic: bool = False, av_alpha: float = 0.5, a_alpha: float = 0.35, v_alpha: float = 0.25,
-                 t_alpha: float = 0.4, comm: Optional[Comm] = None, dynamic_mode: str = "batch", gate_absent: bool = False,
-                 metrics: bool = False, capacity: Optional[int] = None, sweep=None):
-        """dynamic_mode (with dynamic=True): "batch", the published rule above, or "sample": every sample is gated by the entropy of
-        its OWN class distribution (the reference's commented-out softmax(dim=1)), one weight vector per sample.
-        gate_absent (models whose update takes present=, i.e. Modal3Classifier): a modality a sample does not have is left out of
-        that sample's fusion, weight +0.0, and the others are renormalised -- with the fixed alphas or with dynamic_mode="sample".
-        Either one takes the per-sample path: features to counters in ONE launch (ops.eval_head) instead of M head launches and
-        the fusion kernel; independent of the batch a sample arrives in, so under data parallel each rank counts its own rows, no
-        all-gather, and result() / per_class() sum the counters over the ranks.  That path sets `sample_weights` (B, M), `pred`
-        (B, 1 + M: fused arg-max, then each modality's) and `fused` (B, C) of the last batch, in reused buffers; `weights` stays
-        the batch-level vector of the default path.
-        metrics=True, capacity=len(test_set): every update() also appends the batch's class scores (softmax of the fused and of each
-        modality's logits), arg-max predictions and labels to a device store, one more launch per batch; average_precision(),
-        mean_average_precision(), confusion() and f1() are formed from it (mla_hip.metrics).  Not with an active `comm`.
-        sweep=grid (a host (G, M) tensor of finite, non-negative fusion weights, e.g. fusion_grid(M, steps)): every update() also
-        scores the FIXED-weight fusion of the batch at every grid row, one more launch per batch on the logits the update holds
-        anyway; sweep_result() answers the accuracy / F1 surface (mla_hip.sweep).  Whatever the evaluator's own mode: with
-        dynamic=True it tells whether any fixed weighting beats the gating.  With gate_absent the sweep leaves out what the
-        evaluator's fusion leaves out.  Not with an active `comm`."""
-        check_eval_mode(model, dynamic, dynamic_mode, gate_absent)
-        self.model = model
-        self.comm = comm if comm is not None else Comm()
-        self.head = model.fusion_module.fc_out
-        self.M = len(model.mla_encoders())
-        self.C = self.head.out_features
-        self.dynamic = dynamic
-        self.dynamic_mode, self.gate_absent = dynamic_mode, bool(gate_absent)
-        self.per_sample = bool(gate_absent) or (bool(dynamic) and dynamic_mode == "sample")
-        self.alphas = [av_alpha, 1.0 - av_alpha] if self.M == 2 else [a_alpha, v_alpha, t_alpha]      # main.py:647-651
-        self.counts = torch.zeros(self.C * (2 + self.M), device=model.device, dtype=torch.int32)
-        self.weights = torch.zeros(3, device=model.device, dtype=torch.float32)
-        self._sample: dict = {}
-        self._metrics_init(metrics, capacity, 1 + self.M, self.C, model.device, self.comm)
-        # the batch-level path never materialises the fused logits: the store forms them from the weights the fusion kernel used
-        self._fixed_weights = torch.tensor(self.alphas, device=model.device, dtype=torch.float32) if self._store is not None else None
-        self._sweep = None
-        if sweep is not None:
-            if self.comm.active:
-                raise NotImplementedError("Evaluator: sweep= counts each rank's own rows; summing the tables across ranks is not "
-                                          "implemented -- run the fusion-weight search in one process")
-            self._sweep = FusionSweep(sweep, self.M, self.C, model.device)
-        model.eval()                                                                                   # main.py:519
-
-    def reset(self) -> None:
-        self.counts.zero_()
-        self._metrics_reset()
-        if self._sweep is not None:
-            self._sweep.reset()
-
-    def _sample_bufs(self, B: int) -> dict:
-        if B not in self._sample:
-            dev, M, C = self.model.device, self.M, self.C
-            self._sample[B] = {"logits": torch.empty((M, B, C), device=dev, dtype=torch.float32),
-                               "fused": torch.empty((B, C), device=dev, dtype=torch.float32),
-                               "weights": torch.empty((B, M), device=dev, dtype=torch.float32),
-                               "pred": torch.empty((B, 1 + M), device=dev, dtype=torch.int32),
-                               "present": torch.empty((B, M), device=dev, dtype=torch.uint8)}
-        return self._sample[B]
-
-    def _update_per_sample(self, feats, label, present):
-        B = label.shape[0]
-        buf = self._sample_bufs(B)
-        have = None
-        if self.gate_absent and present is not None:
-            buf["present"].copy_(present_in_encoder_order(self.model, present, B))
-            have = buf["present"]
-        ops.eval_head(list(feats), self.head.weight.detach(), self.head.bias.detach(), label, self.counts, buf["logits"],
-                      mode=1 if self.dynamic else 0, alphas=self.alphas, present=have, fused_out=buf["fused"],
-                      weights_out=buf["weights"], pred_out=buf["pred"])
-        self.sample_weights, self.pred, self.fused = buf["weights"], buf["pred"], buf["fused"]
-        outs = [buf["logits"][m] for m in range(self.M)]
-        if self._store is not None:
-            at = self._store.n
-            self._metrics_append([buf["fused"]] + outs, label)
-            if self.gate_absent:                     # a row the kernel counted nowhere (pred -1) is stored as a row without a class
-                self._store.labels[at:at + B].masked_fill_(buf["pred"][:, 0] < 0, -1)
-        if self._sweep is not None:
-            self._sweep.update(outs, label, have)
-        return outs
-
-    def update(self, *batch, present=None):
-        """update(spec, image, label) | update(token, padding_mask, image, label) | update(token, pm, image, spec, label, present=None).
-        present (Modal3Classifier only): host bool / uint8 (B, 3) as in MLATrainer.train_step; with gate_absent it also takes the
-        absent modalities out of each sample's fusion.  Returns the per-modality logits."""
-        *inputs, label = batch
-        feats = self.model.forward_raw(*inputs, **({} if present is None else {"present": present}))
-        if self.per_sample:
-            return self._update_per_sample(feats, label, present)
-        outs = [self.head.logits(f, slot="eval_" + str(k)) for k, f in enumerate(feats)]
-        if self.comm.active:                                         # global batch (Q9): (world * B_local, C) in rank order
-            g_outs = [self.comm.allgather_rows(o) for o in outs]
-            g_label = self.comm.allgather_rows(label.contiguous())
-            ops.eval_fuse(g_outs, g_label, self.counts, self.weights, self.dynamic, self.alphas)
-        else:
-            ops.eval_fuse(outs, label, self.counts, self.weights, self.dynamic, self.alphas)
-        if self._store is not None:
-            self._metrics_append([None] + outs, label, self.weights if self.dynamic else self._fixed_weights)
-        if self._sweep is not None:
-            self._sweep.update(outs, label)
-        return outs
-
-    def _global_counts(self) -> torch.Tensor:
-        """The counters of all ranks as (2 + M, C).  The batch-level path evaluates the global batch on every rank already; the
-        per-sample path sums a COPY over the ranks on the head communicator, the local counters stay local."""
-        c = self.counts
-        if self.per_sample and self.comm.active:
-            c = c.clone()
-            self.comm.allreduce_small(c)
-        return c.view(2 + self.M, self.C)
-
-    def result(self):
-        """(acc, acc_a, acc_v[, acc_t]) = sum(acc)/sum(num) as in main.py:677-679 (one host sync)."""
-        c = self._global_counts().sum(dim=1).cpu().tolist()
-        num = max(c[0], 1)
-        return tuple(x / num for x in c[1:])
-
-    def per_class(self):
-        """The counters as a host int64 array (2 + M, C): samples per class, fused-correct per class, then each modality's
-        correct per class (the acc / num lists of main.py:659-676; one host sync)."""
-        return self._global_counts().cpu().numpy().astype("int64")
-
-    def sweep_result(self) -> SweepResult:
-        """The tables of sweep=grid as a SweepResult: weights, tp, pp, num, acc, counted, f1(average), best(metric) (one host sync)."""
-        if self._sweep is None:
-            raise MLAHipError("Evaluator: constructed with sweep=None; pass sweep=fusion_grid(M, steps) or a (G, M) tensor of weights")
-        return self._sweep.result()

@@ -8,53 +8,17 @@ Not the headline bench line; numbers go to DESIGN.md section 9, the README and I
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-learning-with-alternating-unimodal-adaptation_amd"))
 import torch  # noqa: E402
 from mla_hip import CLIPClassifier, Evaluator, ops  # noqa: E402
+from _windows import WINDOW_S, summary, verdict, windows  # noqa: E402
 
 SHAPES = [(2, 64, 512, 101), (2, 64, 512, 6), (2, 64, 768, 101), (3, 32, 768, 4)]            # (M, B, D, C)
-WINDOW_S, REPEATS = float(os.environ.get("WINDOW_S", "0.5")), 3
 N_TABLE = int(os.environ.get("N", "22714"))                                                  # Food-101 test samples
 assert torch.cuda.is_available(), "bench_eval.py measures on the GPU"
 f32 = dict(device="cuda", dtype=torch.float32)
-
-
-def windows(forms):
-    """forms: name -> (callable running one unit of work, units per call).  -> name -> sorted us per unit of the REPEATS windows."""
-    for fn, units in forms.values():                         # warm-up: code objects, buffers
-        for _ in range(max(1, 20 // units)):
-            fn()
-    torch.cuda.synchronize()
-    out = {k: [] for k in forms}
-    for _rep in range(REPEATS):
-        for name, (fn, units) in forms.items():              # alternate the forms in one process
-            n, t0 = 0, time.perf_counter()
-            while True:
-                inner = max(1, 50 // units)
-                for _ in range(inner):
-                    fn()
-                n += inner * units
-                torch.cuda.synchronize()                     # the window ends on finished work
-                dt = time.perf_counter() - t0
-                if dt >= WINDOW_S:
-                    break
-            out[name].append(dt / n * 1e6)
-    return {k: sorted(v) for k, v in out.items()}
-
-
-def summary(w):
-    return {"us": w[1], "min": w[0], "max": w[2], "spread": (w[2] - w[0]) / w[1]}
-
-
-def verdict(chain, fused):
-    """The fused call against the chain, judged by the chain's own spread."""
-    gap = (fused["us"] - chain["us"]) / chain["us"]
-    if abs(gap) <= chain["spread"]:
-        return f"inside the chain's spread ({gap:+.1%} vs {chain['spread']:.1%})"
-    return f"{'slower' if gap > 0 else 'faster'} beyond the chain's spread ({gap:+.1%} vs {chain['spread']:.1%})"
 
 
 result = {"window_s": WINDOW_S, "shapes": [], "clip_loop": {}}
@@ -79,7 +43,7 @@ for M, B, D, C in SHAPES:
 
     w = windows({"chain": (chain, 1), "eval_head": (one, 1)})
     row = {"M": M, "B": B, "D": D, "C": C, "chain": summary(w["chain"]), "eval_head": summary(w["eval_head"])}
-    row["verdict"] = verdict(row["chain"], row["eval_head"])
+    row["verdict"] = verdict(row["chain"], row["eval_head"], what="the chain's spread")
     result["shapes"].append(row)
     print(f"M={M} B={B} D={D} C={C}: chain ({M + 1} launches) {row['chain']['us']:.1f} us (spread {row['chain']['spread']:.1%}), "
           f"eval_head (1 launch) {row['eval_head']['us']:.1f} us (spread {row['eval_head']['spread']:.1%}): {row['verdict']}")
@@ -111,7 +75,7 @@ w = windows({k: (loop(ev), len(batches)) for k, ev in evs.items()})
 for k, ev in evs.items():
     result["clip_loop"][k] = dict(summary(w[k]), acc=ev.result()[0])
 result["clip_loop"]["batches"], result["clip_loop"]["N"] = len(batches), N_TABLE
-result["clip_loop"]["verdict"] = verdict(result["clip_loop"]["chain"], result["clip_loop"]["eval_head"])
+result["clip_loop"]["verdict"] = verdict(result["clip_loop"]["chain"], result["clip_loop"]["eval_head"], what="the chain's spread")
 for k in evs:
     r = result["clip_loop"][k]
     print(f"CLIP valid loop ({k}): N={N_TABLE} B={B} D={D} C={C}: {r['us']:.1f} us/batch (spread {r['spread']:.1%}), "

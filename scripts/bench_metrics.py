@@ -7,60 +7,23 @@ without metrics=True.  Not the headline bench line; numbers go to DESIGN.md sect
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-learning-with-alternating-unimodal-adaptation_amd"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from mla_hip import CLIPClassifier, Evaluator, ScoreStore  # noqa: E402
+from _windows import WINDOW_S, summary, verdict, windows  # noqa: E402
 
 try:
     from sklearn.metrics import average_precision_score
 except ImportError:
     average_precision_score = None
 
-WINDOW_S, REPEATS = float(os.environ.get("WINDOW_S", "0.5")), 3
 SETS = [("CREMA-D test", 744, 6), ("Food-101 test", int(os.environ.get("N", "22716")), 101)]     # (name, N, C)
 M, B = 2, 64
 assert torch.cuda.is_available(), "bench_metrics.py measures on the GPU"
 f32 = dict(device="cuda", dtype=torch.float32)
-
-
-def windows(forms):
-    """forms: name -> (callable running one unit of work, units per call[, calls between two looks at the clock: 1 for a call that
-    takes milliseconds and ends in a host sync of its own]).  -> name -> sorted us per unit of the REPEATS windows."""
-    forms = {k: (v[0], v[1], v[2] if len(v) > 2 else max(1, 50 // v[1])) for k, v in forms.items()}
-    for fn, units, inner in forms.values():                  # warm-up: code objects, buffers
-        for _ in range(min(inner, max(1, 20 // units))):
-            fn()
-    torch.cuda.synchronize()
-    out = {k: [] for k in forms}
-    for _rep in range(REPEATS):
-        for name, (fn, units, inner) in forms.items():       # alternate the forms in one process
-            n, t0 = 0, time.perf_counter()
-            while True:
-                for _ in range(inner):
-                    fn()
-                n += inner * units
-                torch.cuda.synchronize()                     # the window ends on finished work
-                dt = time.perf_counter() - t0
-                if dt >= WINDOW_S:
-                    break
-            out[name].append(dt / n * 1e6)
-    return {k: sorted(v) for k, v in out.items()}
-
-
-def summary(w):
-    return {"us": w[1], "min": w[0], "max": w[2], "spread": (w[2] - w[0]) / w[1]}
-
-
-def verdict(base, new):
-    """`new` against `base`, judged by base's own spread."""
-    gap = (new["us"] - base["us"]) / base["us"]
-    if abs(gap) <= base["spread"]:
-        return f"inside the spread ({gap:+.1%} vs {base['spread']:.1%})"
-    return f"{'slower' if gap > 0 else 'faster'} beyond the spread ({gap:+.1%} vs {base['spread']:.1%})"
 
 
 def host_ap(probs, labels, C):

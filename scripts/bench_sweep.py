@@ -8,52 +8,15 @@ to DESIGN.md section 9 and profiles/."""
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-learning-with-alternating-unimodal-adaptation_amd"))
 import torch  # noqa: E402
 from mla_hip import CLIPClassifier, Evaluator, fusion_grid, ops  # noqa: E402
+from _windows import WINDOW_S, summary, verdict, windows  # noqa: E402
 
-WINDOW_S, REPEATS = float(os.environ.get("WINDOW_S", "0.5")), 3
 SHAPES = [(2, 64, 6, 100), (2, 64, 101, 100), (3, 32, 4, 20), (3, 32, 4, 80)]       # (M, B, C, steps): G = 101, 101, 231, 3 321
 assert torch.cuda.is_available(), "bench_sweep.py measures on the GPU"
-
-
-def windows(forms):
-    """forms: name -> (callable running one unit of work, units per call[, calls between two looks at the clock]).
-    -> name -> sorted us per unit of the REPEATS windows."""
-    forms = {k: (v[0], v[1], v[2] if len(v) > 2 else 1) for k, v in forms.items()}
-    for fn, _units, _inner in forms.values():                # warm-up: code objects, buffers
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    out = {k: [] for k in forms}
-    for _rep in range(REPEATS):
-        for name, (fn, units, inner) in forms.items():       # alternate the forms in one process
-            n, t0 = 0, time.perf_counter()
-            while True:
-                for _ in range(inner):
-                    fn()
-                n += inner * units
-                torch.cuda.synchronize()                     # the window ends on finished work
-                dt = time.perf_counter() - t0
-                if dt >= WINDOW_S:
-                    break
-            out[name].append(dt / n * 1e6)
-    return {k: sorted(v) for k, v in out.items()}
-
-
-def summary(w):
-    return {"us": w[1], "min": w[0], "max": w[2], "spread": (w[2] - w[0]) / w[1]}
-
-
-def verdict(base, new):
-    """`new` against `base`, judged by the larger of the two spreads."""
-    gap, spread = (new["us"] - base["us"]) / base["us"], max(base["spread"], new["spread"])
-    if abs(gap) <= spread:
-        return f"inside the spread ({gap:+.1%} vs {spread:.1%})"
-    return f"{'slower' if gap > 0 else 'faster'} beyond the spread ({gap:+.1%} vs {spread:.1%})"
 
 
 result = {"window_s": WINDOW_S, "shapes": [], "clip_loop": {}}
@@ -80,9 +43,9 @@ for M, B, C, steps in SHAPES:
     one_launch()
     g_fuse_launches()
     same = bool(torch.equal(tp, counts[:, C:2 * C]))         # the fused-correct counters of the G launches are the sweep's tp
-    w = windows({"sweep": (one_launch, 1, 50), "g_fuse": (g_fuse_launches, 1)})       # back-to-back launches on both sides
+    w = windows({"sweep": (one_launch, 1, 50), "g_fuse": (g_fuse_launches, 1, 1)}, warmup=3)       # back-to-back launches on both sides
     row = {"M": M, "B": B, "C": C, "G": G, "sweep": summary(w["sweep"]), "g_fuse": summary(w["g_fuse"]), "same_counts": same}
-    row["verdict"] = verdict(row["g_fuse"], row["sweep"])
+    row["verdict"] = verdict(row["g_fuse"], row["sweep"], both=True)
     result["shapes"].append(row)
     print(f"(M, B, C, G) = ({M}, {B}, {C}, {G}): one sweep launch {row['sweep']['us']:.1f} us (spread {row['sweep']['spread']:.1%}) vs "
           f"{G} eval_fuse launches {row['g_fuse']['us']:.1f} us (spread {row['g_fuse']['spread']:.1%}): {row['verdict']}; "
@@ -115,14 +78,14 @@ def loop(ev):
     return run
 
 
-w = windows({k: (loop(ev), len(table)) for k, ev in evs.items()})
+w = windows({k: (loop(ev), len(table), 1) for k, ev in evs.items()}, warmup=3)
 for k, ev in evs.items():
     result["clip_loop"][k] = dict(summary(w[k]), acc=ev.result()[0])
     r = result["clip_loop"][k]
     print(f"CLIP valid loop ({k}): N={N_TABLE} B={B} D={D} C={C} G={grid.shape[0]}: {r['us']:.1f} us/batch (spread {r['spread']:.1%}), "
           f"{r['us'] * len(table) / 1e3:.2f} ms per pass")
 for k in ("chain", "eval_head"):
-    result["clip_loop"][k + "_verdict"] = verdict(result["clip_loop"][k], result["clip_loop"][k + "+sweep"])
+    result["clip_loop"][k + "_verdict"] = verdict(result["clip_loop"][k], result["clip_loop"][k + "+sweep"], both=True)
     print(f"CLIP valid loop, {k} with sweep= against without:", result["clip_loop"][k + "_verdict"])
 s = evs["chain+sweep"].sweep_result()
 at = 55                                                      # grid row 55 = (0.55, 1.0 - 0.55): the evaluator's own alphas

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 machine code of the head-family translation units at two commits.
 
-    python scripts/head_isa.py [--parent REV] [--out profiles/head_common_isa.json]
+    python scripts/head_isa.py [--parent REV] [--units UNIT ...] [--out profiles/head_common_isa.json]
 
 Both trees (REV from `git archive`, and the working tree) are compiled with the Makefile's CXXFLAGS plus
 `--cuda-device-only -S -Rpass-analysis=kernel-resource-usage`.  For every __global__ symbol the instruction lines (comments,
@@ -62,14 +62,15 @@ def kernels_of(csrc, unit, tmp):
     return out
 
 
-def tree_kernels(csrc):
+def tree_kernels(csrc, units):
     with tempfile.TemporaryDirectory() as tmp:
-        return {u: kernels_of(csrc, u, tmp) for u in UNITS}
+        return {u: kernels_of(csrc, u, tmp) for u in units}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", default="HEAD")
+    ap.add_argument("--units", nargs="+", default=UNITS, help="translation units (csrc/<unit>.hip); default: the head family")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "head_common_isa.json"))
     ap.add_argument("--digests", nargs=2, metavar=("PARENT.json", "HERE.json"),
                     help="{case: {buffer: sha256}} of the GPU outputs of the entry points whose kernels differ, at the parent's build "
@@ -79,12 +80,17 @@ def main():
     with tempfile.TemporaryDirectory() as old:
         tar = subprocess.run(["git", "archive", a.parent, PKG + "/csrc", "include"], cwd=ROOT, check=True, capture_output=True).stdout
         tarfile.open(fileobj=io.BytesIO(tar)).extractall(old)
-        before = tree_kernels(os.path.join(old, PKG, "csrc"))
-    after = tree_kernels(os.path.join(ROOT, PKG, "csrc"))
+        before = tree_kernels(os.path.join(old, PKG, "csrc"), a.units)
+    after = tree_kernels(os.path.join(ROOT, PKG, "csrc"), a.units)
     rev = subprocess.run(["git", "rev-parse", "--short", a.parent], cwd=ROOT, check=True, capture_output=True, text=True).stdout.strip()
     report = {"parent": rev, "flags": "Makefile CXXFLAGS + --cuda-device-only -S -Rpass-analysis=kernel-resource-usage", "units": {}}
     bad = 0
-    for u in UNITS:
+    for u in a.units:                                 # a kernel that moved to another unit is compared there, under its new unit
+        for k in [k for k in before[u] if k not in after[u]]:
+            for v in a.units:
+                if k in after[v] and k not in before[v]:
+                    before[v][k] = dict(before[u].pop(k), moved_from=u)
+    for u in a.units:
         rows = report["units"][u] = {}
         for k in sorted(set(before[u]) | set(after[u])):
             b, n = before[u].get(k), after[u].get(k)
@@ -95,6 +101,8 @@ def main():
             same = b["stream"] == n["stream"]
             row = {"instructions_parent": b["n"], "instructions_here": n["n"], "identical": same,
                    "sha256_here": hashlib.sha256("\n".join(n["stream"]).encode()).hexdigest()[:16]}
+            if "moved_from" in b:
+                row["moved_from"] = b["moved_from"]
             for f in ("vgprs", "sgprs", "lds", "scratch"):
                 row[f] = n.get(f) if b.get(f) == n.get(f) else {"parent": b.get(f), "here": n.get(f)}
             if not same:

@@ -1,5 +1,5 @@
 """Inputs and fp64 / exact models for the step-tail kernels: OGM / OGM-GE modulation and coefficients (csrc/modulation.hip), SGD,
-scale_by_device_scalar, colsum, bn_invstd, the GS projection and the evaluation fusion (csrc/head_gs_sgd.hip).
+scale_by_device_scalar, colsum, bn_invstd, the GS projection (csrc/head_gs_sgd.hip) and the evaluation fusion (csrc/eval_head.hip).
 
 Everything here is numpy / CPU torch.  tests/test_tail_cpu.py proves that the inputs meet the conditions the tolerances rest on and that
 the models agree with oracle/mla_oracle.py; tests/test_tail_gpu.py holds the kernels to the models.  Where a result is exactly
