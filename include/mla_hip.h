@@ -819,6 +819,51 @@ int mla_confusion_count(const int* pred, const int* labels, int N, int cap, int 
  * be null); B, C, G <= 0; C > 128; G > 4096; a float / int32 buffer off a 4-byte or labels off an 8-byte boundary. */
 int mla_fusion_sweep(const float* l0, const float* l1, const float* l2, const int64_t* labels, const uint8_t* present,
                      const float* grid, int* tp, int* pp, int* num, int M, int B, int C, int G, void* stream);
+/* ---- gate search: the gated fusion family w_m ~ a_m exp(-beta H_m), a gate = (a_0 .. a_{M-1}, beta) ------------------------------
+ * a: a non-negative prior per modality; beta: an inverse temperature on the per-sample entropies.  beta = 0 is the (normalised)
+ * fixed-weight fusion, a = 1 and beta = 1 the gating of mla_eval_head mode 1.  The rule, per batch row, E the eligible modalities
+ * (present, or all):
+ *   H_k    the entropy exactly as mla_eval_head forms it in mode 1: the two-slot softmax of the row (maximum, e = expf(l - mx),
+ *          s = the wave sum of e, logs = logf(s)), t = e != 0 ? (e / s) * ((l - mx) - logs) : 0 per slot, H = 0 - wave_sum(t0 + t1)
+ *   hmax = max_{k in E} H_k (fmaxf from -inf, k ascending)
+ * and for a gate (a, beta):
+ *   x_k  = beta * (hmax - H_k)                          fp32
+ *   g_k  = k in E ? a_k * expf(x_k) : +0.0              fp32
+ *   sum  = sum_k (double) g_k, k = 0, 1, 2 in that order
+ *   s    = (float) sum
+ *   the (row, gate) pair is left out unless s > 0
+ *   w_k  = k in E ? g_k / s : +0.0
+ *   fused = sum_m w_m l_m[c], modalities in order from +0.0, the expression of mla_eval_fuse / mla_eval_head / mla_fusion_sweep
+ *   prediction = the first maximum
+ * Two identities hold bit for bit: a = 1, beta = 1 gives the weights of mla_eval_head mode 1 (both multiplications by 1 are exact);
+ * beta = 0 with (float) sum_k (double) a_k == 1.0f over E gives w_k = a_k, the weights of the fixed fusion (expf(0) = 1, a / 1 is
+ * exact).
+ * Contract on a gate: every entry finite, 0 <= a_k <= 1024, 0 <= beta <= 16.  hmax - H_k <= ln 128, so x_k <= 16 ln 128 = 77.6 <
+ * 88.7 = ln FLT_MAX, and 1024 e^77.6 = 5e36 < FLT_MAX: neither g_k nor the three-term sum can overflow.  mla_eval_head_gated checks
+ * its gate; a device grid is the caller's to validate before upload: one that breaks the contract may give meaningless counts,
+ * never an out-of-range index (the scan answers inside [0, C)).
+ *
+ * mla_gate_sweep: every gate of grid (fp32 (G, M + 1) on the device, row g = a_0 .. a_{M-1}, beta) scored on one batch's logits in
+ * ONE launch.  Tables and policies are mla_fusion_sweep's: int32, accumulated; tp[g][class] and pp[g][class] per gate, num[class]
+ * (nullable) once per counted row; integer atomics only.  A row whose label lies outside [0, C) or that has no present modality is
+ * counted nowhere; a left-out pair adds nothing to tp / pp and its row stays in num, an error of gate g.  ent_out (nullable, fp32
+ * (B, M)) receives H of every row and modality, the rows counted nowhere and the absent modalities included.
+ * MLA_ERR_INVALID_ARG, nothing launched: M not 2 or 3; a null required pointer (l2 is required when M == 3; present, num and ent_out
+ * may be null); B, C, G <= 0; C > 128; G > 4096; a float / int32 buffer off a 4-byte or labels off an 8-byte boundary.
+ * mla_gate_sweep_tile(rows): the batch rows a workgroup stages at a time, 1 (the default), 2 or 4; any other value only queries.
+ * Answers the tile in force.  The tables do not depend on it; it exists to be measured.
+ *
+ * mla_eval_head_gated: mla_eval_head with the gate (prior0 .. prior2, beta) in place of mode / alphas: the same arguments, outputs,
+ * counter layout and bad-row policy; logits_out equals mla_head_logits bit for bit.  A pair the rule leaves out (!(s > 0)) is a bad
+ * row: NaN weights_out and fused_out rows, pred_out row -1, counted nowhere.  With the same gate it predicts, on every row, what
+ * that gate's row of mla_gate_sweep predicts.  Refuses what mla_eval_head refuses (there is no mode) and a gate outside the
+ * contract (prior2 is not read when M == 2). */
+int mla_gate_sweep(const float* l0, const float* l1, const float* l2, const int64_t* labels, const uint8_t* present,
+                   const float* grid, int* tp, int* pp, int* num, float* ent_out, int M, int B, int C, int G, void* stream);
+int mla_gate_sweep_tile(int rows);
+int mla_eval_head_gated(const float* x0, const float* x1, const float* x2, const float* W, const float* b, const int64_t* labels,
+                        const uint8_t* present, int* counts, float* logits_out, float* fused_out, float* weights_out, int* pred_out,
+                        int M, int B, int D, int C, float prior0, float prior1, float prior2, float beta, void* stream);
 /* invstd = 1/sqrt(var + eps) (eval-mode BatchNorm on running statistics) */
 int mla_bn_invstd(const float* var, float* invstd, int n, float eps, void* stream);
 

@@ -29,5 +29,6 @@ from .joint import JointEvaluator, JointTrainer  # noqa: F401
 from .qmf import QMFEvaluator, QMFHistory, QMFTrainer, attach_qmf_heads  # noqa: F401
 from .metrics import ScoreStore  # noqa: F401
 from .sweep import FusionSweep, SweepResult, fusion_grid  # noqa: F401
+from .gate import GateSweep, GateSweepResult, gate_grid  # noqa: F401
 from .fusion import FiLM, GatedFusion, SumFusion, attach_fusion  # noqa: F401
 from . import torch_ops  # noqa: F401,E402  registers torch.ops.mla_hip.* (dispatch key CUDA; no other implementation)

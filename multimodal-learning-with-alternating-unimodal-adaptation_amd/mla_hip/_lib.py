@@ -130,6 +130,9 @@ PROTOTYPES = {
     "mla_average_precision": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "mla_confusion_count": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "mla_fusion_sweep": (_I, [_P] * 9 + [_I] * 4 + [_P]),
+    "mla_gate_sweep": (_I, [_P] * 10 + [_I] * 4 + [_P]),
+    "mla_gate_sweep_tile": (_I, [_I]),
+    "mla_eval_head_gated": (_I, [_P] * 12 + [_I] * 4 + [_F, _F, _F, _F, _P]),
     "mla_bn_invstd":(_I, [_P, _P, _I, _F, _P]),
     "mla_linear_fwd": (_I, [_P] * 6 + [_I] * 8 + [_P]),
     "mla_linear_dgrad": (_I, [_P] * 6 + [_I] * 8 + [_P]),

@@ -1,8 +1,9 @@
 """The evaluators: `valid()` of the reference for the MLA model (Evaluator), the joint model (JointEvaluator) and QMF (QMFEvaluator),
 with their per-class counters kept on the device.  All three take metrics= / capacity= (mla_hip.metrics); Evaluator also takes sweep=
-(mla_hip.sweep).  `HeadCounts` is the counting of a fused output and its per-modality logits the joint and the QMF evaluator share.
+(mla_hip.sweep) and gate_sweep= / gate_prior= / gate_beta= (mla_hip.gate).  `HeadCounts` is the counting of a fused output and its
+per-modality logits the joint and the QMF evaluator share.
 
-Orchestration only: every arithmetic step is a libmla_hip.so kernel (csrc/eval_head.hip, metrics.hip, fusion_sweep.hip).
+Orchestration only: every arithmetic step is a libmla_hip.so kernel (csrc/eval_head.hip, metrics.hip, fusion_sweep.hip, gate_sweep.hip).
 """
 from __future__ import annotations
 
@@ -14,6 +15,7 @@ import torch
 from . import ops
 from ._lib import MLAHipError
 from .dist import Comm
+from .gate import GateSweep, GateSweepResult, check_gate
 from .metrics import MetricsMixin
 from .module import _attached, _joint_fusion
 from .rows import check_present
@@ -63,7 +65,8 @@ class Evaluator(MetricsMixin):
 
     def __init__(self, model, dynamic: bool = False, av_alpha: float = 0.5, a_alpha: float = 0.35, v_alpha: float = 0.25,
                  t_alpha: float = 0.4, comm: Optional[Comm] = None, dynamic_mode: str = "batch", gate_absent: bool = False,
-                 metrics: bool = False, capacity: Optional[int] = None, sweep=None):
+                 metrics: bool = False, capacity: Optional[int] = None, sweep=None, gate_sweep=None, gate_prior=None,
+                 gate_beta=None):
         """dynamic_mode (with dynamic=True): "batch", the published rule above, or "sample": every sample is gated by the entropy of
         its OWN class distribution (the reference's commented-out softmax(dim=1)), one weight vector per sample.
         gate_absent (models whose update takes present=, i.e. Modal3Classifier): a modality a sample does not have is left out of
@@ -80,8 +83,17 @@ class Evaluator(MetricsMixin):
         scores the FIXED-weight fusion of the batch at every grid row, one more launch per batch on the logits the update holds
         anyway; sweep_result() answers the accuracy / F1 surface (mla_hip.sweep).  Whatever the evaluator's own mode: with
         dynamic=True it tells whether any fixed weighting beats the gating.  With gate_absent the sweep leaves out what the
-        evaluator's fusion leaves out.  Not with an active `comm`."""
+        evaluator's fusion leaves out.  Not with an active `comm`.
+        gate_sweep=grid (a host (G, M + 1) tensor of gates (a_0 .. a_{M-1}, beta), e.g. gate_grid(M, betas, steps)): every update()
+        also scores the gated fusion w_m ~ a_m exp(-beta H_m) of the batch at every gate, one more launch per batch on the same
+        logits; gate_sweep_result() answers the surface (mla_hip.gate).  Whatever the evaluator's own mode, under the masks its own
+        fusion took (gate_absent + present=).  Not with an active `comm`.
+        gate_prior (M floats) / gate_beta (with dynamic=True, dynamic_mode="sample"): the per-sample path gates with that gate
+        (ops.eval_head_gated) instead of a = 1, beta = 1; giving one alone leaves the other at 1.  Search it on a validation split."""
         check_eval_mode(model, dynamic, dynamic_mode, gate_absent)
+        if (gate_prior is not None or gate_beta is not None) and not (dynamic and dynamic_mode == "sample"):
+            raise ValueError("Evaluator: gate_prior / gate_beta shape the per-sample entropy gating; they need dynamic=True, "
+                             "dynamic_mode='sample'")
         self.model = model
         self.comm = comm if comm is not None else Comm()
         self.head = model.fusion_module.fc_out
@@ -103,6 +115,13 @@ class Evaluator(MetricsMixin):
                 raise NotImplementedError("Evaluator: sweep= counts each rank's own rows; summing the tables across ranks is not "
                                           "implemented -- run the fusion-weight search in one process")
             self._sweep = FusionSweep(sweep, self.M, self.C, model.device)
+        self._gate = None if gate_prior is None and gate_beta is None else check_gate(gate_prior, gate_beta, self.M)
+        self._gate_sweep = None
+        if gate_sweep is not None:
+            if self.comm.active:
+                raise NotImplementedError("Evaluator: gate_sweep= counts each rank's own rows; summing the tables across ranks is "
+                                          "not implemented -- run the gate search in one process")
+            self._gate_sweep = GateSweep(gate_sweep, self.M, self.C, model.device)
         model.eval()                                                                                   # main.py:519
 
     def reset(self) -> None:
@@ -110,6 +129,8 @@ class Evaluator(MetricsMixin):
         self._metrics_reset()
         if self._sweep is not None:
             self._sweep.reset()
+        if self._gate_sweep is not None:
+            self._gate_sweep.reset()
 
     def _sample_bufs(self, B: int) -> dict:
         if B not in self._sample:
@@ -128,9 +149,14 @@ class Evaluator(MetricsMixin):
         if self.gate_absent and present is not None:
             buf["present"].copy_(present_in_encoder_order(self.model, present, B))
             have = buf["present"]
-        ops.eval_head(list(feats), self.head.weight.detach(), self.head.bias.detach(), label, self.counts, buf["logits"],
-                      mode=1 if self.dynamic else 0, alphas=self.alphas, present=have, fused_out=buf["fused"],
-                      weights_out=buf["weights"], pred_out=buf["pred"])
+        if self._gate is not None:
+            ops.eval_head_gated(list(feats), self.head.weight.detach(), self.head.bias.detach(), label, self.counts, buf["logits"],
+                                prior=self._gate[0], beta=self._gate[1], present=have, fused_out=buf["fused"],
+                                weights_out=buf["weights"], pred_out=buf["pred"])
+        else:
+            ops.eval_head(list(feats), self.head.weight.detach(), self.head.bias.detach(), label, self.counts, buf["logits"],
+                          mode=1 if self.dynamic else 0, alphas=self.alphas, present=have, fused_out=buf["fused"],
+                          weights_out=buf["weights"], pred_out=buf["pred"])
         self.sample_weights, self.pred, self.fused = buf["weights"], buf["pred"], buf["fused"]
         outs = [buf["logits"][m] for m in range(self.M)]
         if self._store is not None:
@@ -140,6 +166,8 @@ class Evaluator(MetricsMixin):
                 self._store.labels[at:at + B].masked_fill_(buf["pred"][:, 0] < 0, -1)
         if self._sweep is not None:
             self._sweep.update(outs, label, have)
+        if self._gate_sweep is not None:
+            self._gate_sweep.update(outs, label, have)
         return outs
 
     def update(self, *batch, present=None):
@@ -161,6 +189,8 @@ class Evaluator(MetricsMixin):
             self._metrics_append([None] + outs, label, self.weights if self.dynamic else self._fixed_weights)
         if self._sweep is not None:
             self._sweep.update(outs, label)
+        if self._gate_sweep is not None:
+            self._gate_sweep.update(outs, label)
         return outs
 
     def _global_counts(self) -> torch.Tensor:
@@ -188,6 +218,14 @@ class Evaluator(MetricsMixin):
         if self._sweep is None:
             raise MLAHipError("Evaluator: constructed with sweep=None; pass sweep=fusion_grid(M, steps) or a (G, M) tensor of weights")
         return self._sweep.result()
+
+    def gate_sweep_result(self) -> GateSweepResult:
+        """The tables of gate_sweep=grid as a GateSweepResult: priors, beta, tp, pp, num, acc, counted, f1(average), best(metric) (one
+        host sync)."""
+        if self._gate_sweep is None:
+            raise MLAHipError("Evaluator: constructed with gate_sweep=None; pass gate_sweep=gate_grid(M, betas, steps) or a (G, M + 1) "
+                              "tensor of gates")
+        return self._gate_sweep.result()
 
 
 class HeadCounts:

@@ -1133,6 +1133,49 @@ def fusion_sweep(outs, labels, grid, tp, pp, num=None, present=None, stream: Opt
           _p(pp, torch.int32), _p(num, torch.int32), M, B, C, G, stream or cur_stream())
 
 
+def gate_sweep(outs, labels, grid, tp, pp, num=None, present=None, ent_out=None, stream: Optional[int] = None):
+    """The gated fusion w_m ~ a_m exp(-beta H_m) of one batch at every gate of a grid, in one launch (see include/mla_hip.h,
+    mla_gate_sweep).  outs: M = 2 or 3 (B, C) logit matrices; grid: device fp32 (G, M + 1), row = (a_0 .. a_{M-1}, beta), inside the
+    contract on a gate (mla_hip.gate.check_gate_grid); tp, pp int32 (G, C) and num int32 (C) or None, accumulated; present: device
+    uint8 (B, M) or None; ent_out: fp32 (B, M) or None, receives the entropies."""
+    M = len(outs)
+    if M < 1 or outs[0].dim() != 2 or grid.dim() != 2:
+        raise MLAHipError(f"gate_sweep: expected M (B, C) logit matrices and a (G, M + 1) grid, got {M} and {tuple(grid.shape)}")
+    B, C = outs[0].shape
+    G = grid.shape[0]
+    if any(tuple(t.shape) != (B, C) for t in outs) or grid.shape[1] != M + 1:
+        raise MLAHipError(f"gate_sweep: logits {[tuple(t.shape) for t in outs]} do not match each other or the grid {tuple(grid.shape)}")
+    _want("gate_sweep", labels=(labels, (B,)), tp=(tp, (G, C)), pp=(pp, (G, C)), num=(num, (C,)), present=(present, (B, M)),
+          ent_out=(ent_out, (B, M)))
+    _call("mla_gate_sweep", *_padded(outs, 3)[0], _p(labels, torch.int64), _p(present, torch.uint8), _p(grid), _p(tp, torch.int32),
+          _p(pp, torch.int32), _p(num, torch.int32), _p(ent_out), M, B, C, G, stream or cur_stream())
+
+
+def gate_sweep_tile(rows: int = -1) -> int:
+    """The batch rows a gate_sweep workgroup stages at a time: 1, 2 or 4 sets it, anything else queries (scripts/bench_gate_sweep.py)."""
+    return int(_lib.load().mla_gate_sweep_tile(int(rows)))
+
+
+def eval_head_gated(feats, W, b, labels, counts, logits_out, *, prior, beta: float, present=None, fused_out=None, weights_out=None,
+                    pred_out=None, stream: Optional[int] = None):
+    """ops.eval_head under the gate (prior (M floats), beta): w_m ~ prior_m exp(-beta H_m) per row (see include/mla_hip.h,
+    mla_eval_head_gated).  Every other argument is eval_head's."""
+    M = len(feats)
+    if M < 1 or feats[0].dim() != 2 or W.dim() != 2 or len(prior) != M:
+        raise MLAHipError(f"eval_head_gated: expected M (B, D) feature matrices, a (C, D) head weight and M priors, got {M}, "
+                          f"{tuple(W.shape)} and {len(prior)}")
+    B, D = feats[0].shape
+    C = W.shape[0]
+    if any(tuple(f.shape) != (B, D) for f in feats) or W.shape[1] != D or tuple(b.shape) != (C,):
+        raise MLAHipError(f"eval_head_gated: features {[tuple(f.shape) for f in feats]} / bias {tuple(b.shape)} do not match the head "
+                          f"weight {tuple(W.shape)}")
+    _want("eval_head_gated", labels=(labels, (B,)), counts=(counts, (C * (2 + M),)), logits_out=(logits_out, (M, B, C)),
+          present=(present, (B, M)), fused_out=(fused_out, (B, C)), weights_out=(weights_out, (B, M)), pred_out=(pred_out, (B, 1 + M)))
+    x, pr = _padded(feats, 3, prior)
+    _call("mla_eval_head_gated", *x, _p(W), _p(b), _p(labels, torch.int64), _p(present, torch.uint8), _p(counts, torch.int32),
+          _p(logits_out), _p(fused_out), _p(weights_out), _p(pred_out, torch.int32), M, B, D, C, *pr, float(beta), stream or cur_stream())
+
+
 def bn_invstd(var, invstd, eps: float = BN_EPS, stream: Optional[int] = None):
     _call("mla_bn_invstd", _p(var), _p(invstd), var.numel(), eps, stream or cur_stream())
 

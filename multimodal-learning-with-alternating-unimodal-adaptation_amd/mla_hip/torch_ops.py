@@ -444,6 +444,27 @@ def fusion_sweep(logits, labels, grid, tp, pp, num=None, present=None):
     ops.fusion_sweep([logits[m] for m in range(logits.shape[0])], labels, grid, tp, pp, num=num, present=present)
 
 
+@_op("gate_sweep(Tensor logits, Tensor labels, Tensor grid, Tensor(a!) tp, Tensor(b!) pp, Tensor(c!)? num=None, "
+     "Tensor? present=None, Tensor(d!)? ent_out=None) -> ()")
+def gate_sweep(logits, labels, grid, tp, pp, num=None, present=None, ent_out=None):
+    """The gated fusion w_m ~ a_m exp(-beta H_m) of the per-modality logits (M, B, C) at every gate of grid (G, M + 1), in one
+    launch: int32 tp (G, C), pp (G, C) and num (C) accumulated in place, ent_out (B, M) written (include/mla_hip.h, mla_gate_sweep)."""
+    ops.gate_sweep([logits[m] for m in range(logits.shape[0])], labels, grid, tp, pp, num=num, present=present, ent_out=ent_out)
+
+
+@_op("eval_head_gated(Tensor[] feats, Tensor W, Tensor b, Tensor labels, Tensor(a!) counts, float[] prior, float beta, "
+     "Tensor? present=None) -> (Tensor, Tensor, Tensor, Tensor)")
+def eval_head_gated(feats, W, b, labels, counts, prior, beta, present=None):
+    """eval_head under the gate (prior, beta): (logits (M, B, C), fused (B, C), weights (B, M), pred int32 (B, 1 + M)); `counts`
+    accumulated in place (include/mla_hip.h, mla_eval_head_gated)."""
+    M, B, C = len(feats), feats[0].shape[0], W.shape[0]
+    logits, fused, weights = _f32((M, B, C), W), _f32((B, C), W), _f32((B, M), W)
+    pred = torch.empty((B, 1 + M), device=W.device, dtype=torch.int32)
+    ops.eval_head_gated(list(feats), W, b, labels, counts, logits, prior=list(prior), beta=beta, present=present, fused_out=fused,
+                        weights_out=weights, pred_out=pred)
+    return logits, fused, weights, pred
+
+
 @_op("gather_rows2(Tensor T0, Tensor T1, Tensor labels, Tensor idx) -> (Tensor, Tensor, Tensor, Tensor)")
 def gather_rows2(T0, T1, labels, idx):
     """(out0 (B, D), out1 (B, D), label (B), idx (B, 1)): rows `idx` of two device-resident feature tables and their labels."""
